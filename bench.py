@@ -1,21 +1,28 @@
 #!/usr/bin/env python3
 """Headline benchmark: fine-tune images/sec, ViT-B/16 + CaRA rank 16 @224, bs 64 per GPU.
 
-One "step" = the reference's train step (/root/reference/image_classification/vit_cp.py:45-50):
+One "step" = the reference's train step (image_classification/vit_cp.py:45-50):
 forward, mean cross-entropy, backward into the 12 CP tensors + head, (N > 1: one RCCL all-reduce
 of the flat gradient buffer), AdamW.  Synthetic data and random-init weights of the named
 architecture; inputs are resident in HBM before the timed region.  Train mode: DropPath 0.1 (per-rank
 random streams), factored adapters WITHOUT the reference's Dropout(0.1) on the materialised dW (that
 mode is ``--weight-dropout exact``, informational).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints ONE JSON line from rank 0 (metric, value,
+unit, ms_per_step, dtype, config, ...).  ``--dump-outputs DIR`` writes what the caller of the timed step holds
+after its last step -- the loss, every trainable parameter after AdamW and its gradient -- as float32
+``DIR/<name>.npy`` (rank 0); the inputs are seeded, so two builds can be compared output for output.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>`` as a CHILD process
 (before anything touches the GPU) and exits with its code; under torchrun it reads RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* itself.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+``--full`` adds what the headline figure does not need: the bracketed steps and legs behind the objects below, the
+forward-only rate (``config.forward_only_*``), ``precision_matched`` (the same step on the IEEE-half build) and
+``informational`` (exact weight dropout, rank 64, order 2).  With ``--full`` the line carries these extra objects:
 ``roofline``      the dominant kernel by measured time share (picked from a bracketed warm-up step), timed with
                   HIP events on the compute stream INSIDE the timed region;
 ``roofline_top``  the three kernel sites with the largest time share (name, algorithmic GFLOP, avg us, fraction
@@ -298,6 +305,21 @@ def read_sites(lib, names):
     return out
 
 
+def dump_outputs(path, loss, model):
+    """What the caller of the timed step holds after its last step: the loss and, for every trainable parameter, its value
+    after AdamW and its gradient (``p.grad``, a view of the flat gradient buffer), one float32 ``<name>.npy`` each (about 1 MB
+    at the headline shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.reshape(1)}
+    for n, p in model.named_parameters():
+        if p.requires_grad:
+            arrays["param." + n] = p
+            arrays["grad." + n] = p.grad
+    for n, t in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -305,13 +327,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch")
     ap.add_argument("--rank", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-info-legs", action="store_true", help="skip the informational exact-dropout / rank-64 legs behind the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: site brackets and roofline objects, the forward-only "
+                         "rate, the precision-matched region, the informational legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss, the trainable parameters and their gradients after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-info-legs", action="store_true", help="with --full: skip the informational exact-dropout / rank-64 legs behind the timed region")
     ap.add_argument("--graph", action="store_true",
                     help="N = 1: capture the whole step (forward, cross-entropy, backward, AdamW) once per synthetic batch into a hipGraph and "
                          "replay it in the timed loop (cara_vit_forward / _backward only enqueue: DESIGN.md section 1); eager is the default")
-    ap.add_argument("--no-precision-matched", action="store_true", help="skip the second timed region (precision = 'fp16': the 1e-3 build)")
-    ap.add_argument("--all-sites", action="store_true", help="diagnostic: roofline_top lists every bracketed MFMA site, not the top three")
+    ap.add_argument("--no-precision-matched", action="store_true", help="with --full: skip the second timed region (precision = 'fp16': the 1e-3 build)")
+    ap.add_argument("--all-sites", action="store_true", help="diagnostic, with --full: roofline_top lists every bracketed MFMA site, not the top three")
     ap.add_argument("--weight-dropout", default="off", choices=["off", "exact"],
                     help="exact = the reference's train-mode Dropout(0.1) on the materialised adapters (merged weights + "
                          "dense dW gradients); informational, the reported metric uses the factored default")
@@ -320,6 +347,11 @@ def main():
     ap.add_argument("--model", default="vit_base_patch16_224_in21k",
                     help="vit_large_patch16_384 runs BASELINE.json configs[4] (use --batch 32); informational only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.all_sites and not args.full:
+        ap.error("--all-sites reports the roofline objects of --full: pass both")
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -419,10 +451,10 @@ def main():
     factored = args.weight_dropout == "off"
     for _ in range(max(args.warmup - 1, 0)):
         step()
-    # last warm-up step with every site bracketed: which site has the largest time share?  (the exact mode runs
+    # --full: last warm-up step with every site bracketed: which site has the largest time share?  (the exact mode runs
     # its linears through other entry points; its GEMM sites then hold several kernels and are not reported)
     dominant = "fc2_bwd"
-    if factored and args.warmup > 0:
+    if full and factored and args.warmup > 0:
         _lib.check(lib.cara_profile_sites(C.c_ulonglong(all_mask), 1), "cara_profile_sites")
         step()
         torch.cuda.synchronize()
@@ -440,7 +472,8 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    _lib.check(lib.cara_profile_sites(C.c_ulonglong(1 << SITES.index(dominant)) if (factored and not use_graph) else C.c_ulonglong(0), PROFILE_EVERY),
+    bracket_timed = full and factored and not use_graph   # (a plain run times the step without site brackets)
+    _lib.check(lib.cara_profile_sites(C.c_ulonglong(1 << SITES.index(dominant)) if bracket_timed else C.c_ulonglong(0), PROFILE_EVERY),
                "cara_profile_sites")
     # one event per step boundary (a record between two kernels of a stream idles the chip ~3 us: 0.03 % of a step):
     # ms_per_step_median next to the mean that `value` is computed from
@@ -457,18 +490,20 @@ def main():
         dist.barrier()
     wall = time.perf_counter() - t0
     ev_ms = e0.elapsed_time(e1)
-    dom = read_sites(lib, [dominant]).get(dominant) if (factored and not use_graph) else None
+    dom = read_sites(lib, [dominant]).get(dominant) if bracket_timed else None
     graphs_live = list(graphs)
     graphs.clear()           # everything behind the timed region runs eager (site brackets, the fp16 region, the informational legs)
     t = torch.tensor([wall], device="cpu" if (world > 1 and rehearsal) else dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = t.item()
+    if args.dump_outputs and rank == 0:   # before anything else runs a step
+        dump_outputs(args.dump_outputs, loss, model)
 
-    # after the timed region, rank 0's own clock: (i) three steps with every site bracketed on every block ->
+    # --full, after the timed region, rank 0's own clock: (i) three steps with every site bracketed on every block ->
     # roofline_top / roofline_hbm; (ii) the forward-only rate (SURVEY 8d asks for it next to the train rate)
     post, fwd_ms = {}, None
-    if rank == 0 or world > 1:   # (every rank runs the bracketed steps: they contain the all-reduce)
+    if full and (rank == 0 or world > 1):   # (every rank runs the bracketed steps: they contain the all-reduce)
         if factored:
             _lib.check(lib.cara_profile_sites(C.c_ulonglong(all_mask), 1), "cara_profile_sites")
             for _ in range(3):
@@ -478,7 +513,7 @@ def main():
             if use_graph:            # the dominant site's launch time: from these bracketed eager steps (a replayed graph carries no brackets)
                 dom = post.get(dominant)
     lib.cara_profile_sites(C.c_ulonglong(0), 1)
-    if rank == 0:
+    if full and rank == 0:
         model.eval()
         with torch.no_grad():
             for _ in range(3):
@@ -498,7 +533,7 @@ def main():
     # tests run), timed under the same protocol as the headline region -- barrier + synchronize on both sides, max over ranks --
     # with the dominant site bracketed in THAT library.  Every rank runs it (it contains the all-reduce).
     pm = None
-    if factored and args.precision == "bf16" and not args.no_precision_matched:
+    if full and factored and args.precision == "bf16" and not args.no_precision_matched:
         try:
             lib16 = _lib.lib("fp16")
             eng.precision = "fp16"
@@ -536,7 +571,7 @@ def main():
     # informational legs (rank 0, N = 1, the headline configuration only; never the headline number): the reference's
     # train-mode arithmetic (exact weight-space dropout) and BASELINE.json configs[3] (rank 64), 2 warm-ups + 5 steps each
     info = {}
-    if rank == 0 and world == 1 and factored and not large and args.batch == 64 and args.rank == 16 and not args.no_info_legs:
+    if full and rank == 0 and world == 1 and factored and not large and args.batch == 64 and args.rank == 16 and not args.no_info_legs:
         def timed_steps(fn, warm=2, n=5):
             for _ in range(warm):
                 fn()
@@ -589,7 +624,35 @@ def main():
     if rank == 0:
         ms_step = wall * 1e3 / args.steps
         ips = world * args.batch * args.steps / wall
+        ex_fwd, ex_step = executed_gflop(gf, args.batch, dim, args.rank, heads, tokens, 24 if large else 12)
+        out = {
+            "metric": ("fine-tune images/sec ViT-L/16+CaRA r=16 @384, bs=32/GPU (BASELINE.json configs[4], informational)" if large
+                       else "fine-tune images/sec ViT-B/16+CaRA r=16 @224, bs=64/GPU, 1/2/4/8 MI355X"),
+            "value": round(ips, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3), "ms_per_step_median": round(statistics.median(step_ms), 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.precision, "data": "synthetic",
+            "config": {"workload": (f"ViT-L/16 + CaRA rank={args.rank}, synthetic 384x384, bs={args.batch}/GPU, bf16 "
+                                    "(BASELINE.json configs[4], informational); fwd + CE + bwd + AdamW, drop-path 0.1, factored adapters"
+                                    if large else
+                                    f"ViT-B/16 + CaRA rank={args.rank}, synthetic 224x224, bs={args.batch}/GPU, bf16 "
+                                    "(BASELINE.json configs[1]); fwd + CE + bwd + AdamW, drop-path 0.1, "
+                                    + ("factored adapters, no weight-space dropout" if factored else
+                                       "EXACT weight-space dropout 0.1 (merged weights, dense dW; informational)")),
+                       "global_batch": world * args.batch, "parallelism": f"dp{world}",
+                       "batches": f"{NB} seeded synthetic batches per rank, resident in HBM before the timed region, fed in turn",
+                       "launch": ("hipGraph replay: the whole step captured once per resident batch" if use_graph else "eager"),
+                       "ranks_in_allreduce": ranks_seen, "backend": ("gloo-rehearsal" if rehearsal else "rccl") if world > 1 else "none",
+                       "step_algorithmic_gflop": round(gf["step"] * args.batch, 1),
+                       "step_tflops_per_gpu": round(gf["step"] * args.batch / ms_step, 1),
+                       "step_frac_of_mfma_peak": round(gf["step"] * args.batch / ms_step / PEAK_BF16_TFLOPS, 4),
+                       "gpu_event_ms_per_step": round(ev_ms / args.steps, 3), "loss": float(loss),
+                       # the same fraction over what the device EXECUTES (executed_gflop: the cls-row shortcut of the last block
+                       # and block 0's skipped qkv dX taken out of the numerator): hardware utilisation, not algorithmic throughput
+                       "step_executed_gflop": round(ex_step, 1),
+                       "step_frac_of_mfma_peak_executed": round(ex_step / ms_step / PEAK_BF16_TFLOPS, 4)},
+        }
 
+    if rank == 0 and full:
         def entry(n, v, per_step):
             kind, amount = work[n]
             us = v["avg_ms"] * 1e3
@@ -607,7 +670,12 @@ def main():
                 d.update(algorithmic_mb=round(amount / 1e6, 1), achieved_gbs=round(amount / us / 1e3, 1),
                          frac_of_hbm_peak=round(amount / us / 1e3 / PEAK_HBM_GBS, 4))
             return d
-        ex_fwd, ex_step = executed_gflop(gf, args.batch, dim, args.rank, heads, tokens, 24 if large else 12)
+        out["config"].update({
+            "forward_only_ms": round(fwd_ms, 3),
+            "forward_only_images_per_sec_per_gpu": round(args.batch / fwd_ms * 1e3, 1),
+            "forward_frac_of_mfma_peak": round(gf["fwd"] * args.batch / fwd_ms / PEAK_BF16_TFLOPS, 4),
+            "forward_executed_gflop": round(ex_fwd, 1),
+            "forward_frac_of_mfma_peak_executed": round(ex_fwd / fwd_ms / PEAK_BF16_TFLOPS, 4)})
         per_step = {n: v["brackets"] // 3 for n, v in post.items()}
         ranked = sorted((n for n in post if work[n][0] == "mfma"), key=lambda n: -post[n]["avg_ms"] * per_step[n])
         top = [entry(n, post[n], per_step[n]) for n in (ranked if args.all_sites else ranked[:3])]
@@ -632,46 +700,15 @@ def main():
                            "kernel_source_sha16_at_measurement": meta.get("kernel_source_sha16"),
                            "kernel_source_sha16_now": kernel_source_sha16(),
                            "stale": meta.get("kernel_source_sha16") != kernel_source_sha16()}
-        out = {
-            "metric": ("fine-tune images/sec ViT-L/16+CaRA r=16 @384, bs=32/GPU (BASELINE.json configs[4], informational)" if large
-                       else "fine-tune images/sec ViT-B/16+CaRA r=16 @224, bs=64/GPU, 1/2/4/8 MI355X"),
-            "value": round(ips, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3), "ms_per_step_median": round(statistics.median(step_ms), 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": (f"ViT-L/16 + CaRA rank={args.rank}, synthetic 384x384, bs={args.batch}/GPU, bf16 "
-                                    "(BASELINE.json configs[4], informational); fwd + CE + bwd + AdamW, drop-path 0.1, factored adapters"
-                                    if large else
-                                    f"ViT-B/16 + CaRA rank={args.rank}, synthetic 224x224, bs={args.batch}/GPU, bf16 "
-                                    "(BASELINE.json configs[1]); fwd + CE + bwd + AdamW, drop-path 0.1, "
-                                    + ("factored adapters, no weight-space dropout" if factored else
-                                       "EXACT weight-space dropout 0.1 (merged weights, dense dW; informational)")),
-                       "global_batch": world * args.batch, "parallelism": f"dp{world}",
-                       "batches": f"{NB} seeded synthetic batches per rank, resident in HBM before the timed region, fed in turn",
-                       "launch": ("hipGraph replay: the whole step captured once per resident batch" if use_graph else "eager"),
-                       "ranks_in_allreduce": ranks_seen, "backend": ("gloo-rehearsal" if rehearsal else "rccl") if world > 1 else "none",
-                       "step_algorithmic_gflop": round(gf["step"] * args.batch, 1),
-                       "step_tflops_per_gpu": round(gf["step"] * args.batch / ms_step, 1),
-                       "step_frac_of_mfma_peak": round(gf["step"] * args.batch / ms_step / PEAK_BF16_TFLOPS, 4),
-                       "gpu_event_ms_per_step": round(ev_ms / args.steps, 3), "loss": float(loss),
-                       "forward_only_ms": round(fwd_ms, 3),
-                       "forward_only_images_per_sec_per_gpu": round(args.batch / fwd_ms * 1e3, 1),
-                       "forward_frac_of_mfma_peak": round(gf["fwd"] * args.batch / fwd_ms / PEAK_BF16_TFLOPS, 4),
-                       # the same two fractions over what the device EXECUTES (executed_gflop: the cls-row shortcut of the last block
-                       # and block 0's skipped qkv dX taken out of the numerator): hardware utilisation, not algorithmic throughput
-                       "step_executed_gflop": round(ex_step, 1),
-                       "step_frac_of_mfma_peak_executed": round(ex_step / ms_step / PEAK_BF16_TFLOPS, 4),
-                       "forward_executed_gflop": round(ex_fwd, 1),
-                       "forward_frac_of_mfma_peak_executed": round(ex_fwd / fwd_ms / PEAK_BF16_TFLOPS, 4)},
-            "roofline": {"bound": "mfma", "achieved": round(ach, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": f"{SITE_KERNEL[dominant]}; site {dominant}: the largest time share of the step among the "
-                                   f"bracketed sites; M={M}",
-                         "algorithmic_gflop_per_launch": round(fl / 1e9, 2),
-                         "avg_launch_ms": round(dom["avg_ms"], 4) if dom else None, "launches_timed": dom["brackets"] if dom else 0,
-                         "event_marker_ms_subtracted": round(dom["marker_ms"], 4) if dom else None},
-            "roofline_top": top,
-            "roofline_hbm": hbm,
-        }
+        out["roofline"] = {"bound": "mfma", "achieved": round(ach, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                           "frac": round(ach / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                           "kernel": f"{SITE_KERNEL[dominant]}; site {dominant}: the largest time share of the step among the "
+                                     f"bracketed sites; M={M}",
+                           "algorithmic_gflop_per_launch": round(fl / 1e9, 2),
+                           "avg_launch_ms": round(dom["avg_ms"], 4) if dom else None, "launches_timed": dom["brackets"] if dom else 0,
+                           "event_marker_ms_subtracted": round(dom["marker_ms"], 4) if dom else None}
+        out["roofline_top"] = top
+        out["roofline_hbm"] = hbm
         if args.all_sites:   # every site was bracketed: the step's sites against the sum of their OWN binding roofs
             rows = top + hbm
             t_sites = sum(r["avg_launch_us"] * r["launches_per_step"] for r in rows)
@@ -718,6 +755,7 @@ def main():
             out["informational"] = info
         if world == 1 and not args.no_cpu_baseline and not large:
             out["cpu_baseline"] = cpu_baseline(scale)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -901,7 +901,7 @@ def test_bench_self_launches_for_more_than_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["CARA_BENCH_REHEARSAL"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--full"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -909,6 +909,31 @@ def test_bench_self_launches_for_more_than_one_gpu():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["ranks_in_allreduce"] == 2 and d["config"]["global_batch"] == 16
     assert d["roofline"]["launches_timed"] > 0 and len(d["roofline_top"]) == 3 and d["roofline_hbm"]
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(tmp_path):
+    """`python bench.py` without --full: the contract's keys and none of the --full objects; --dump-outputs writes the loss and
+    every trainable parameter with its gradient after the last timed step, float32, and the loss is the one the line reports."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                          "--dump-outputs", str(tmp_path)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "bf16"
+    assert not {"roofline", "roofline_top", "precision_matched", "informational", "cpu_baseline"} & set(d)
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and loss[0] == np.float32(d["config"]["loss"])
+    for n in ("CP_A2", "CP_P2", "CP_bias2", "head.weight", "head.bias"):
+        p, g = np.load(tmp_path / f"param.{n}.npy"), np.load(tmp_path / f"grad.{n}.npy")
+        assert p.dtype == g.dtype == np.float32 and p.shape == g.shape and np.isfinite(p).all() and np.isfinite(g).all(), n
+        assert np.abs(g).max() > 0, n
 
 
 def test_bench_two_ranks_rehearsal(tmp_path):
@@ -922,7 +947,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CARA_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"]
+           "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -4,22 +4,23 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
+out=${CARA_OUT:-bench_out}   # where the runs' files go
+mkdir -p $out
 i=0
 for envs in "$1" "$2"; do
   i=$((i+1))
-  ( export $envs; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/abk_$i -- python3 bench.py --no-cpu-baseline --no-info-legs --steps 10 --warmup 3 > gpurun_out/abk_$i.log 2>&1 ) || exit 1
-  cp "$(find gpurun_out/abk_$i -name '*kernel_stats.csv' | head -1)" gpurun_out/abk_$i.csv
-  rm -rf gpurun_out/abk_$i
+  ( export $envs; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/abk_$i -- python3 bench.py --full --no-cpu-baseline --no-info-legs --steps 10 --warmup 3 > $out/abk_$i.log 2>&1 ) || exit 1
+  cp "$(find $out/abk_$i -name '*kernel_stats.csv' | head -1)" $out/abk_$i.csv
+  rm -rf $out/abk_$i
 done
-python3 - <<'PY'
-import csv
+OUT=$out python3 - <<'PY'
+import csv, os
 def load(f):
     d = {}
     for r in csv.DictReader(open(f)):
         d[r["Name"]] = (int(r["Calls"]), float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e3)
     return d
-a, b = load("gpurun_out/abk_1.csv"), load("gpurun_out/abk_2.csv")
+a, b = load(os.environ["OUT"] + "/abk_1.csv"), load(os.environ["OUT"] + "/abk_2.csv")
 names = sorted(set(a) | set(b), key=lambda n: -(a.get(n, (0, 0, 0))[1] + b.get(n, (0, 0, 0))[1]))
 print(f"{'kernel':70s} {'calls':>6s} {'A avg us':>9s} {'B avg us':>9s} {'A tot ms':>9s} {'B tot ms':>9s}")
 for n in names[:22]:

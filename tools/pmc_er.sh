@@ -3,9 +3,10 @@
 # where the riders' 28 us go.  Usage (GPU box): bash tools/pmc_er.sh
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out/pmc_er
+out=${CARA_OUT:-bench_out}   # where the runs' files go
+mkdir -p $out/pmc_er
 run() { tag=$1; n=$2; shift 2
-  timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" -d gpurun_out/pmc_er/${tag}_$n --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-info-legs > gpurun_out/pmc_er/${tag}_$n.log 2>&1 || echo "pass $tag $n failed"
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" -d $out/pmc_er/${tag}_$n --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-info-legs > $out/pmc_er/${tag}_$n.log 2>&1 || echo "pass $tag $n failed"
 }
 for tag in on off; do
   if [ $tag = off ]; then export CARA_EPI_RIDERS=0; else export CARA_EPI_RIDERS=1; fi   # (the default is 0 since r04: the 'on' arm must say so)
@@ -16,11 +17,11 @@ for tag in on off; do
   run $tag p5 WRITE_SIZE
   run $tag p6 TCP_PENDING_STALL_CYCLES TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TA_BUSY_avr TCP_TA_DATA_STALL_CYCLES
 done
-python3 - <<'PY'
-import collections, csv, glob
+OUT=$out python3 - <<'PY'
+import collections, csv, glob, os
 for tag in ("on", "off"):
     acc = collections.defaultdict(lambda: collections.defaultdict(lambda: [0.0, 0]))
-    for f in glob.glob(f"gpurun_out/pmc_er/{tag}_*/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"{os.environ['OUT']}/pmc_er/{tag}_*/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             a = acc[r["Kernel_Name"]][r["Counter_Name"]]
             a[0] += float(r["Counter_Value"]); a[1] += 1
@@ -33,4 +34,4 @@ for tag in ("on", "off"):
         for c in sorted(cs):
             print(f"      {c:34s} {cs[c][0] / cs[c][1]:16.0f}")
 PY
-rm -rf gpurun_out/pmc_er/*/*/*kernel_trace.csv gpurun_out/pmc_er/*/*/*agent_info.csv
+rm -rf $out/pmc_er/*/*/*kernel_trace.csv $out/pmc_er/*/*/*agent_info.csv
