@@ -1,7 +1,8 @@
 // Fused attention forward / backward for the ViT token counts (head dim 64) on gfx950: N <= 224 (ViT-B/16
 // @224: 197 tokens) on the register-resident path described below, N <= 608 (ViT-L/16 @384: 577 tokens) on
 // the same kernels with the whole K/V (or Q/dO) of a head still in LDS (152 KiB, one workgroup per CU) and a
-// forward that sweeps the key tiles twice (max + sum, then P.V) instead of holding the score rows.
+// forward that sweeps the key tiles twice (max + sum, then P.V) instead of holding the score rows; any N above that (ViT-B/16
+// @448: 785 tokens, @512: 1 025) on the streamed kernels near the end of this file, which hold 64-row tiles of K/V (Q/dO) in LDS.
 // Reference semantics: /root/reference/src/cara/cara.py:43-48
 //     attn = softmax((q @ k^T) * scale); x = (attn @ v).transpose(1, 2).reshape(B, N, C)
 // with q, k, v the three [B,H,N,64] views of the qkv activation laid out exactly as cara.py:39
@@ -1747,6 +1748,526 @@ __global__ __launch_bounds__(256) void attn_cls_bwd_kernel(const bf16* __restric
     dqkv[row0 * ld + h * HD + lane] = (bf16)(((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) * scale);
 }
 
+// ------------------------------------------------------------------------------------------
+// Streamed kernels: any N > 608 (and 224 < N <= 608 behind CARA_ATTN_STREAM=1).  The resident kernels above keep a head's whole
+// K / V (forward, dQ) or Q / dO (dK/dV) image in LDS, which ends at 608 rows of the 160 KiB.  Here a workgroup of four waves owns
+// 128 query rows (forward, dQ) or 128 keys (dK/dV) of one head -- grid = (B H, ceil(N / 128)) -- and the OTHER operand passes
+// through LDS in tiles of 64 rows (two of the 32-row blocks the fragment offsets of row_ofs / tr_ofs address), double-buffered:
+// while a tile is computed on, every thread holds its 2 x 16 bytes of each matrix of the next tile in registers (global loads
+// issued before the arithmetic, written to the other buffer behind it), one __syncthreads per tile.  Plain loads and stores, no
+// LDS-DMA: nothing is in flight when the workgroup ends.  LDS: 32 KiB (forward, dQ), 33 KiB (dK/dV) -- the register budget
+// (two workgroups per CU at up to 256 VGPRs, more where a kernel needs fewer), not the LDS, decides the residency.
+//
+// Softmax of the forward: the EXACT TWO-SWEEP form of attn_fwd_long_kernel, not an online softmax.  Sweep 1 streams the K tiles for
+// the row maxima, sweep 2 streams K and V for exp, the row sum and P.V.  It costs the second stream of K (L2 hits: the 64 keys x
+// 128 B of a tile are shared by every workgroup of the head) and a second Q K^T (a third more MFMA work), and it buys: the rounding points, the key
+// order and the summation order of the resident kernel exactly (the two paths can be compared bit for bit at 577 tokens, which
+// is what the A/B behind CARA_ATTN_STREAM is for), and no rescale of the output accumulators -- 32 more vector instructions per
+// key block beside the MFMAs, where this code base measured every extra vector instruction (docs/findings/r05.md 7c-7d).
+// The backward kernels recompute P from the LSE as the resident ones do: same bodies per 32 x 32 block, same rounding points.
+// No atomics, every output element written by exactly one lane; a wave whose 32 rows lie beyond N still stages and keeps the
+// barriers, and stores nothing.  Ragged tails: rows >= N of a tile are copies of row N - 1 (finite) and masked as above.
+// N is bounded by the index arithmetic alone: N <= 2^20 (grid.y = N / 128 <= 65 535 with room) and B N < 2^31 (row indices are int).
+// ------------------------------------------------------------------------------------------
+constexpr int ST_WAVES = 4;              // 128 query rows (keys) per workgroup
+constexpr int ST_TILE = 64;              // rows of a streamed tile
+constexpr int ST_IMG = ST_TILE * 128;    // one tile of one matrix: 8 KiB
+constexpr int NMAX_STREAM = 1 << 20;
+
+// a thread's share of a 64-row tile: row tid >> 2, the two 16-byte chunks 2 (tid & 3) and 2 (tid & 3) + 1
+struct TilePiece {
+  uint4 a, b;
+};
+__device__ __forceinline__ TilePiece tile_load(const bf16* __restrict__ src, int ld, int N, int row0, int tid) {
+  const int n = row0 + (tid >> 2);
+  const bf16* p = src + (size_t)(n < N ? n : N - 1) * ld + (tid & 3) * 16;
+  TilePiece t;
+  t.a = *reinterpret_cast<const uint4*>(p);
+  t.b = *reinterpret_cast<const uint4*>(p + 8);
+  return t;
+}
+__device__ __forceinline__ void tile_store(char* img, const TilePiece& t, int tid) {
+  const int r = tid >> 2, c = (tid & 3) * 2;
+  *reinterpret_cast<uint4*>(img + swz128(r, c)) = t.a;
+  *reinterpret_cast<uint4*>(img + swz128(r, c + 1)) = t.b;
+}
+
+__global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_fwd_stream_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+                                                                           float* __restrict__ lse, int N, int H, float scale) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * ST_IMG];   // [buffer][K | V]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, head = bh - b * H;
+  const int ld = 3 * H * HD;
+  const bf16* qb = qkv + (size_t)b * N * ld + head * HD;
+  const bf16* kb = qb + H * HD;
+  const bf16* vb = qb + 2 * H * HD;
+  const int ql = lane & 31, h = lane >> 5;
+  const int q0 = (blockIdx.y * ST_WAVES + wave) * 32;
+  const bool active = q0 < N;   // (wave-uniform)
+  const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
+  bf16x8 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qb + (size_t)qrow * ld + ks * 16 + h * 8);
+  const int nkt = (N + 31) >> 5, ntile = (N + ST_TILE - 1) / ST_TILE;
+  const float c2 = scale * 1.4426950408889634f;
+  const RowOfs ro = row_ofs(lane);
+  const TrOfs to = tr_ofs(lane);
+  const int last_keys = N - (nkt - 1) * 32;   // valid keys of the last 32-key block (only that block needs a mask)
+
+  auto score_block = [&](const char* kblk, int kt) {
+    f32x16 t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const bf16x8 a = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
+      t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], t, 0, 0, 0);
+    }
+    if (kt == nkt - 1) {   // S^T: row = key, column = query
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t[r] = crow(r, h) < last_keys ? t[r] : -3.0e38f;
+    }
+    return t;
+  };
+
+  float mx = -3.0e38f, mxc = 0.f, sum = 0.f;
+  f32x16 o[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+  // ONE stream of 2 ntile steps: steps 0 .. ntile - 1 are sweep 1 (K only), the rest sweep 2 (K and V); the first tile of sweep 2
+  // is fetched under the last tile of sweep 1
+  TilePiece kp = tile_load(kb, ld, N, 0, tid), vp = kp;
+  tile_store(smem, kp, tid);
+  __syncthreads();
+  for (int s = 0; s < 2 * ntile; ++s) {
+    const bool sweep2 = s >= ntile;
+    const int t = sweep2 ? s - ntile : s;
+    const int s1 = s + 1;
+    const bool more = s1 < 2 * ntile, v1 = s1 >= ntile;
+    const int t1 = v1 ? s1 - ntile : s1;
+    if (more) {
+      kp = tile_load(kb, ld, N, t1 * ST_TILE, tid);
+      if (v1) vp = tile_load(vb, ld, N, t1 * ST_TILE, tid);
+    }
+    const char* Ks = smem + (s & 1) * 2 * ST_IMG;
+    const char* Vs = Ks + ST_IMG;
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int kt = 2 * t + j;
+        if (kt < nkt) {
+          f32x16 tl = score_block(Ks + j * 4096, kt);
+          if (!sweep2) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, tl[r]);
+          } else {
+            // P = exp(S - max) (masked keys give exp(-huge) = 0), sum and P.V together
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              tl[r] = __builtin_amdgcn_exp2f(tl[r] * c2 - mxc);   // <= 0: raw v_exp_f32, no denormal fix-up code
+              sum += tl[r];
+            }
+            const char* vb_ = Vs + j * 4096;
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+              const bf16x8 pa = pack8(tl, st);
+#pragma unroll
+              for (int dt = 0; dt < 2; ++dt) {
+                const bf16x8 vf = tr_frag_at(vb_, to.lo[st][dt], to.hi[st][dt]);
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, vf, o[dt], 0, 0, 0);
+              }
+            }
+          }
+        }
+      }
+    }
+    if (s == ntile - 1) {
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      mxc = mx * c2;
+    }
+    if (more) {
+      char* nK = smem + (s1 & 1) * 2 * ST_IMG;
+      tile_store(nK, kp, tid);
+      if (v1) tile_store(nK + ST_IMG, vp, tid);
+    }
+    __syncthreads();   // the next tile is complete; everybody is through with this one (its buffer is rewritten a step later)
+  }
+  if (!active) return;
+  sum += __shfl_xor(sum, 32, 64);
+  const float inv = 1.0f / sum;
+  bf16* ob = out + (size_t)b * N * (H * HD) + head * HD;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int qq = crow(r, h);
+    const float iv = __shfl(inv, qq, 64);
+    if (q0 + qq < N) {
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) ob[(size_t)(q0 + qq) * (H * HD) + dt * 32 + ql] = (bf16)(o[dt][r] * iv);
+    }
+  }
+  if (h == 0 && q0 + ql < N) lse[(size_t)bh * N + q0 + ql] = mx * scale + __logf(sum);
+}
+
+// dK, dV of 128 keys per workgroup (wave = 32 keys, key on the lane, dK^T / dV^T in accumulators as in attn_bwd_dkv_kernel);
+// Q, dO, the LSE and delta = rowsum(dO . O) of the head pass through LDS in tiles of 64 queries.  delta of a tile's rows is formed
+// by the four threads that stage the row (their O and dO chunks are in registers then), summed over the quad.
+constexpr int ST_DKV_BUF = 2 * ST_IMG + 2 * ST_TILE * 4;   // Q | dO | lse (log2 units) | delta
+
+__global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dkv_stream_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
+                                                                               const bf16* __restrict__ dout, const float* __restrict__ lse,
+                                                                               bf16* __restrict__ dqkv, int N, int H, float scale) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * ST_DKV_BUF];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, head = bh - b * H;
+  const int ld = 3 * H * HD, ldo = H * HD;
+  const bf16* qb = qkv + (size_t)b * N * ld + head * HD;
+  const bf16* kb = qb + H * HD;
+  const bf16* vb = qb + 2 * H * HD;
+  const bf16* ob = out + (size_t)b * N * ldo + head * HD;
+  const bf16* dob = dout + (size_t)b * N * ldo + head * HD;
+  const float* lseb = lse + (size_t)bh * N;
+  const int kl = lane & 31, h = lane >> 5;
+  const float c2 = scale * 1.4426950408889634f;
+  const int key0 = (blockIdx.y * ST_WAVES + wave) * 32;
+  const bool active = key0 < N;   // (wave-uniform)
+  const int key = key0 + kl;
+  const int keyc = key < N ? key : N - 1;
+  const bool kvalid = key < N;
+  // B operands with the key on the lane: K[key][16ks + 8h + j], V likewise
+  bf16x8 kf[4], vf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    kf[ks] = *reinterpret_cast<const bf16x8*>(kb + (size_t)keyc * ld + ks * 16 + h * 8);
+    vf[ks] = *reinterpret_cast<const bf16x8*>(vb + (size_t)keyc * ld + ks * 16 + h * 8);
+  }
+  f32x16 dkt[2], dvt[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dkt[dt][r] = 0.f; dvt[dt][r] = 0.f; }
+  const int nqt = (N + 31) >> 5, ntile = (N + ST_TILE - 1) / ST_TILE;
+  const RowOfs ro = row_ofs(lane);
+  const TrOfs to = tr_ofs(lane);
+  const int last_q = N - (nqt - 1) * 32;   // valid queries of the last 32-row block (rows beyond are clamped duplicates)
+
+  TilePiece qp, dop, op;
+  float lv;
+  auto fetch = [&](int t) {
+    qp = tile_load(qb, ld, N, t * ST_TILE, tid);
+    dop = tile_load(dob, ldo, N, t * ST_TILE, tid);
+    op = tile_load(ob, ldo, N, t * ST_TILE, tid);
+    const int n = t * ST_TILE + (tid >> 2);
+    lv = lseb[n < N ? n : N - 1];
+  };
+  auto put = [&](int buf) {   // (called by all 256 threads: the quad sums are shuffles)
+    char* Qs = smem + buf * ST_DKV_BUF;
+    tile_store(Qs, qp, tid);
+    tile_store(Qs + ST_IMG, dop, tid);
+    float dl = 0.f;
+    {
+      const bf16x8 a0 = __builtin_bit_cast(bf16x8, op.a), a1 = __builtin_bit_cast(bf16x8, op.b);
+      const bf16x8 g0 = __builtin_bit_cast(bf16x8, dop.a), g1 = __builtin_bit_cast(bf16x8, dop.b);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dl += (float)a0[j] * (float)g0[j];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dl += (float)a1[j] * (float)g1[j];
+    }
+    dl += __shfl_xor(dl, 1, 64);
+    dl += __shfl_xor(dl, 2, 64);
+    if ((tid & 3) == 0) {
+      float* lse_s = reinterpret_cast<float*>(Qs + 2 * ST_IMG);
+      lse_s[tid >> 2] = lv * 1.4426950408889634f;
+      lse_s[ST_TILE + (tid >> 2)] = dl;
+    }
+  };
+  fetch(0);
+  put(0);
+  __syncthreads();
+  for (int t = 0; t < ntile; ++t) {
+    const bool more = t + 1 < ntile;
+    if (more) fetch(t + 1);
+    const char* Qs = smem + (t & 1) * ST_DKV_BUF;
+    const char* dOs = Qs + ST_IMG;
+    const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * ST_IMG);
+    const float* del_s = lse_s + ST_TILE;
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int qt = 2 * t + j;
+        if (qt < nqt) {
+          const char* qblk = Qs + j * 4096;
+          const char* dblk = dOs + j * 4096;
+          f32x16 sacc, pacc;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; pacc[r] = 0.f; }
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) {
+            const bf16x8 qa = *reinterpret_cast<const bf16x8*>(qblk + ro.o[ks]);
+            const bf16x8 da = *reinterpret_cast<const bf16x8*>(dblk + ro.o[ks]);
+            sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], pacc, 0, 0, 0);
+          }
+          // layout: column (lane & 31) = key, row = query 32 qt + crow(r, h).  Rows q >= N carry clamped duplicates of row
+          // N - 1: force their P to zero (last block only; an invalid key zeroes the whole lane).
+          f32x16 p, ds;
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {   // registers 4 g4 .. + 3 hold queries 8 g4 + 4 h .. + 3 of the block: one 16-byte LDS read each
+            const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + j * 32 + 8 * g4 + 4 * h);
+            const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_s + j * 32 + 8 * g4 + 4 * h);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int r = 4 * g4 + k;
+              float e = __builtin_amdgcn_exp2f(sacc[r] * c2 - l4[k]);
+              if (qt == nqt - 1) e = crow(r, h) < last_q ? e : 0.f;
+              e = kvalid ? e : 0.f;
+              p[r] = e;
+              ds[r] = e * (pacc[r] - d4[k]);
+            }
+          }
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+            const bf16x8 pb = pack8(p, st), dsb = pack8(ds, st);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+              const bf16x8 doa = tr_frag_at(dblk, to.lo[st][dt], to.hi[st][dt]);
+              const bf16x8 qta = tr_frag_at(qblk, to.lo[st][dt], to.hi[st][dt]);
+              dvt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa, pb, dvt[dt], 0, 0, 0);
+              dkt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qta, dsb, dkt[dt], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+    if (more) put((t + 1) & 1);
+    __syncthreads();   // the next tile is complete; everybody is through with this one
+  }
+  // dK[key][d] = scale * dK^T[d][key]; registers 4g..4g+3 hold d = dt*32 + 8g + 4h + (0..3)
+  if (active && kvalid) {
+    bf16* dk = dqkv + (size_t)(b * N + key) * ld + H * HD + head * HD;
+    bf16* dv = dk + H * HD;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = dt * 32 + 8 * g + 4 * h;
+        bf16x4 a = {(bf16)(dkt[dt][4 * g] * scale), (bf16)(dkt[dt][4 * g + 1] * scale),
+                    (bf16)(dkt[dt][4 * g + 2] * scale), (bf16)(dkt[dt][4 * g + 3] * scale)};
+        bf16x4 c = {(bf16)dvt[dt][4 * g], (bf16)dvt[dt][4 * g + 1], (bf16)dvt[dt][4 * g + 2], (bf16)dvt[dt][4 * g + 3]};
+        *reinterpret_cast<bf16x4*>(dk + d) = a;
+        *reinterpret_cast<bf16x4*>(dv + d) = c;
+      }
+  }
+}
+
+// dQ of 128 queries per workgroup: the streamed forward's shape with the body of attn_bwd_dq_kernel (one sweep, K and V tiles).
+__global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dq_stream_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
+                                                                              const bf16* __restrict__ dout, const float* __restrict__ lse,
+                                                                              bf16* __restrict__ dqkv, int N, int H, float scale) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * ST_IMG];   // [buffer][K | V]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, head = bh - b * H;
+  const int ld = 3 * H * HD, ldo = H * HD;
+  const bf16* qb = qkv + (size_t)b * N * ld + head * HD;
+  const bf16* kb = qb + H * HD;
+  const bf16* vb = qb + 2 * H * HD;
+  const bf16* ob = out + (size_t)b * N * ldo + head * HD;
+  const bf16* dob = dout + (size_t)b * N * ldo + head * HD;
+  const int ql = lane & 31, h = lane >> 5;
+  const int q0 = (blockIdx.y * ST_WAVES + wave) * 32;
+  const bool active = q0 < N;   // (wave-uniform)
+  const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
+  bf16x8 qf[4], dof[4];
+  float dl = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qf[ks] = *reinterpret_cast<const bf16x8*>(qb + (size_t)qrow * ld + ks * 16 + h * 8);
+    dof[ks] = *reinterpret_cast<const bf16x8*>(dob + (size_t)qrow * ldo + ks * 16 + h * 8);
+    const bf16x8 of = *reinterpret_cast<const bf16x8*>(ob + (size_t)qrow * ldo + ks * 16 + h * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dl += (float)of[j] * (float)dof[ks][j];
+  }
+  dl += __shfl_xor(dl, 32, 64);   // delta[q] = sum_d dO[q,d] O[q,d]
+  const float lq = lse[(size_t)bh * N + qrow] * 1.4426950408889634f;
+  const float c2 = scale * 1.4426950408889634f;
+  f32x16 dq[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+  const int nkt = (N + 31) >> 5, ntile = (N + ST_TILE - 1) / ST_TILE;
+  const RowOfs ro = row_ofs(lane);
+  const TrOfs to = tr_ofs(lane);
+  const int last_keys = N - (nkt - 1) * 32;
+
+  TilePiece kp = tile_load(kb, ld, N, 0, tid), vp = tile_load(vb, ld, N, 0, tid);
+  tile_store(smem, kp, tid);
+  tile_store(smem + ST_IMG, vp, tid);
+  __syncthreads();
+  for (int t = 0; t < ntile; ++t) {
+    const bool more = t + 1 < ntile;
+    if (more) {
+      kp = tile_load(kb, ld, N, (t + 1) * ST_TILE, tid);
+      vp = tile_load(vb, ld, N, (t + 1) * ST_TILE, tid);
+    }
+    const char* Ks = smem + (t & 1) * 2 * ST_IMG;
+    const char* Vs = Ks + ST_IMG;
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int kt = 2 * t + j;
+        if (kt < nkt) {
+          const char* kblk = Ks + j * 4096;
+          const char* vblk = Vs + j * 4096;
+          f32x16 sT, dpT;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { sT[r] = 0.f; dpT[r] = 0.f; }
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) {
+            const bf16x8 ka = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
+            const bf16x8 va = *reinterpret_cast<const bf16x8*>(vblk + ro.o[ks]);
+            sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[ks], sT, 0, 0, 0);
+            dpT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[ks], dpT, 0, 0, 0);
+          }
+          // layout: column (lane & 31) = query, row = key 32 kt + crow(r, h); only the last block has keys >= N
+          f32x16 ds;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float e = __builtin_amdgcn_exp2f(sT[r] * c2 - lq);
+            if (kt == nkt - 1) e = crow(r, h) < last_keys ? e : 0.f;
+            ds[r] = e * (dpT[r] - dl);
+          }
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+            const bf16x8 a = pack8(ds, st);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+              const bf16x8 kf = tr_frag_at(kblk, to.lo[st][dt], to.hi[st][dt]);
+              dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, a, dq[dt], 0, 0, 0);   // dQ^T = K^T dS^T: d on the rows
+            }
+          }
+        }
+      }
+    }
+    if (more) {
+      char* nK = smem + ((t + 1) & 1) * 2 * ST_IMG;
+      tile_store(nK, kp, tid);
+      tile_store(nK + ST_IMG, vp, tid);
+    }
+    __syncthreads();   // the next tile is complete; everybody is through with this one
+  }
+  if (!active) return;
+  // dQ^T layout and the half-swapping 16-byte stores: as in attn_bwd_dq_kernel
+  bf16* qrow_out = dqkv + (size_t)(b * N + qrow) * ld + head * HD;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    unsigned w[4][2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const bf16x2 lo = {(bf16)(dq[dt][4 * g] * scale), (bf16)(dq[dt][4 * g + 1] * scale)};
+      const bf16x2 hi = {(bf16)(dq[dt][4 * g + 2] * scale), (bf16)(dq[dt][4 * g + 3] * scale)};
+      w[g][0] = __builtin_bit_cast(unsigned, lo);
+      w[g][1] = __builtin_bit_cast(unsigned, hi);
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(w[g][k], w[g + 2][k], false, false);
+        w[g][k] = sw[0];
+        w[g + 2][k] = sw[1];
+      }
+    if (q0 + ql < N) {
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const uint4 v = {w[g][0], w[g][1], w[g + 2][0], w[g + 2][1]};
+        *reinterpret_cast<uint4*>(qrow_out + dt * 32 + 8 * (g + 2 * h)) = v;
+      }
+    }
+  }
+}
+
+// The cls-query forward without a score row in LDS (any N): sweep 1 streams K for the maximum of the scores, sweep 2 streams K
+// again (recomputing the scores: 128 bytes of K per key, the kernel is bound by HBM latency, not by these dot products) and V
+// for exp, the row sum and P V.  Same rounding points as attn_cls_fwd_kernel; attn_cls_bwd_kernel holds nothing of size N.
+__global__ __launch_bounds__(256) void attn_cls_fwd_stream_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out, float* __restrict__ lse,
+                                                                  const int N, const int H, const float scale) {
+  __shared__ float red[4];
+  __shared__ float part[4][64];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r8 = lane >> 3, c = lane & 7;
+  const int ld = 3 * H * HD;
+  const bf16* base = qkv + (size_t)b * N * ld + h * HD + c * 8;
+  const bf16* kb = base + H * HD;
+  const bf16* vb = kb + H * HD;
+  float q8[8];
+  {
+    const bf16x8 qv = *reinterpret_cast<const bf16x8*>(base);   // the cls row is row 0 of the sample
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q8[j] = (float)qv[j] * scale;
+  }
+  const int nit = (N + 31) / 32;                                // this wave's row groups: rows (it * 4 + wave) * 8 + r8
+  float mx = -3.0e38f;
+  for (int it0 = 0; it0 < nit; it0 += 8) {
+    bf16x8 kv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int n = ((it0 + u) * 4 + wave) * 8 + r8;
+      kv[u] = *reinterpret_cast<const bf16x8*>(kb + (size_t)(n < N ? n : N - 1) * ld);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += q8[j] * (float)kv[u][j];
+      s = row8_sum(s);
+      mx = fmaxf(mx, s);                                        // (a clamped row repeats key N - 1: the maximum is the same)
+    }
+  }
+  mx = block4_reduce(mx, red, true);
+  float sum = 0.f;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  for (int it0 = 0; it0 < nit; it0 += 4) {
+    bf16x8 kk[4], vv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int n = ((it0 + u) * 4 + wave) * 8 + r8;
+      const size_t ro = (size_t)(n < N ? n : N - 1) * ld;
+      kk[u] = *reinterpret_cast<const bf16x8*>(kb + ro);
+      vv[u] = *reinterpret_cast<const bf16x8*>(vb + ro);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int n = ((it0 + u) * 4 + wave) * 8 + r8;
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += q8[j] * (float)kk[u][j];
+      s = row8_sum(s);
+      const float e = n < N ? __expf(s - mx) : 0.f;
+      if (c == 0) sum += e;                                     // (unrounded, as in the MFMA kernels; one lane per row counts it)
+      const float pn = (float)(bf16)e;                          // P as the bf16 operand of P V
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += pn * (float)vv[u][j];
+    }
+  }
+  sum = block4_reduce(sum, red, false);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float t = rows_sum(acc[j]);
+    if (r8 == 0) part[wave][c * 8 + j] = t;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const float o = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) / sum;
+    out[(size_t)b * N * (H * HD) + h * HD + lane] = (bf16)o;
+    if (lane == 0) lse[(size_t)bh * N] = mx + __logf(sum);
+  }
+}
+
 // diagnostic: stage a [N,64] matrix like the kernels do and return every lane's transposed fragment
 __global__ void tr_frag_probe_kernel(const bf16* __restrict__ src, bf16* __restrict__ out, int N, int cbase, int base) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1776,6 +2297,16 @@ static int attn_waves(int N) {
   return N > 128 ? 7 : 4;
 }
 
+// CARA_ATTN_STREAM=1: the streamed kernels also serve 224 < N <= 608 (A/B runs against the resident ones); default 0: they serve
+// N > 608 only, where nothing else exists
+static bool attn_streamed(int N) {
+  static const int force = [] { const char* e = getenv("CARA_ATTN_STREAM"); return e ? atoi(e) : 0; }();
+  return N > NMAX_LONG || (force == 1 && N > NMAX);
+}
+static bool attn_shape_ok(int B, int N, int H) {
+  return B > 0 && H > 0 && N > 0 && N <= NMAX_STREAM && (long long)B * N < (1ll << 31);
+}
+
 constexpr int MAX_LDS = 160 * 1024;
 static void attn_set_lds_limits() {
   static bool done = false;
@@ -1797,9 +2328,15 @@ static void attn_set_lds_limits() {
 }
 
 extern "C" int cara_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream) {
-  if (!qkv || !out || !lse || B <= 0 || H <= 0 || N <= 0 || N > NMAX_LONG) return CARA_E_ARG;
+  if (!qkv || !out || !lse || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
   attn_set_lds_limits();
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (attn_streamed(N)) {
+    hipLaunchKernelGGL(attn_fwd_stream_kernel, dim3(B * H, (N + ST_WAVES * 32 - 1) / (ST_WAVES * 32)), dim3(ST_WAVES * 64), 0, st,
+                       (const bf16*)qkv, (bf16*)out, lse, N, H, scale);
+    CARA_CHECK_LAUNCH();
+    return CARA_OK;
+  }
   const int npad = (N + 31) / 32 * 32, lds = 2 * npad * 128;
   // The two-sweep kernel is also the default for 128 < N <= 224: 123 VGPRs instead of 210 put two 7-wave
   // workgroups on a CU, which more than pays for computing Q K^T twice (same-box 36.9 vs 41.4 us at N = 197).
@@ -1842,9 +2379,19 @@ extern "C" int cara_attention_fwd(const void* qkv, void* out, float* lse, int B,
 
 extern "C" int cara_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                   int B, int N, int H, float scale, void* stream) {
-  if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || H <= 0 || N <= 0 || N > NMAX_LONG) return CARA_E_ARG;
+  if (!qkv || !out || !dout || !lse || !dqkv || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
   attn_set_lds_limits();
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (attn_streamed(N)) {
+    const dim3 grid(B * H, (N + ST_WAVES * 32 - 1) / (ST_WAVES * 32));
+    hipLaunchKernelGGL(attn_bwd_dkv_stream_kernel, grid, dim3(ST_WAVES * 64), 0, st, (const bf16*)qkv, (const bf16*)out,
+                       (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale);
+    CARA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(attn_bwd_dq_stream_kernel, grid, dim3(ST_WAVES * 64), 0, st, (const bf16*)qkv, (const bf16*)out,
+                       (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale);
+    CARA_CHECK_LAUNCH();
+    return CARA_OK;
+  }
   const int npad = (N + 31) / 32 * 32, lds = 2 * npad * 128;
   static const int use_fused = [] { const char* e = getenv("CARA_ATTN_PERSIST"); return e ? atoi(e) : 1; }();
   if (use_fused && N > 128 && N <= NMAX) {
@@ -1875,16 +2422,20 @@ extern "C" int cara_attention_bwd(const void* qkv, const void* out, const void* 
 
 
 extern "C" int cara_attention_cls_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream) {
-  if (!qkv || !out || !lse || B <= 0 || H <= 0 || N <= 0 || N > NMAX_LONG) return CARA_E_ARG;
-  hipLaunchKernelGGL(attn_cls_fwd_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16*)qkv, (bf16*)out, lse, N, H,
-                     scale);
+  if (!qkv || !out || !lse || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
+  if (attn_streamed(N))   // (no score row in LDS)
+    hipLaunchKernelGGL(attn_cls_fwd_stream_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16*)qkv, (bf16*)out,
+                       lse, N, H, scale);
+  else
+    hipLaunchKernelGGL(attn_cls_fwd_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16*)qkv, (bf16*)out, lse, N, H,
+                       scale);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }
 
 extern "C" int cara_attention_cls_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                       int B, int N, int H, float scale, void* stream) {
-  if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || H <= 0 || N <= 0 || N > NMAX_LONG) return CARA_E_ARG;
+  if (!qkv || !out || !dout || !lse || !dqkv || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
   hipLaunchKernelGGL(attn_cls_bwd_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16*)qkv, (const bf16*)out,
                      (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale);
   CARA_CHECK_LAUNCH();

@@ -68,7 +68,9 @@ int env_once(const char* name, int dflt);
 bool save_gelu_grad(const cara_geom* g, const cara_vit_shape* s);
 bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   if (!g || !s || g->depth <= 0 || g->depth > 64 || g->dim % g->heads || g->dim / g->heads != 64) return false;
-  if (!(g->Rp == 32 || g->Rp == 64) || g->rank > g->Rp || s->B <= 0 || s->tokens <= 1 || s->tokens > 608) return false;
+  if (!(g->Rp == 32 || g->Rp == 64) || g->rank > g->Rp || s->B <= 0 || s->tokens <= 1) return false;
+  // (no token limit of the kernels' own: attention streams K / V above 608 tokens; row counts and row indices are int)
+  if (s->tokens > (1 << 20) || (long long)s->B * s->tokens >= (1ll << 31)) return false;
   if (s->img % s->patch || (s->img / s->patch) * (s->img / s->patch) + 1 != s->tokens) return false;
   if ((s->chans * s->patch * s->patch) % 64 || g->dim % 256) return false;
   const size_t D = g->dim, M = (size_t)s->B * s->tokens, Rp = g->Rp;

@@ -204,7 +204,8 @@ class CaraEngine:
             nbytes = self._lib().cara_vit_workspace_bytes(C.byref(geom), C.byref(shape))
             if nbytes == 0:
                 raise CaraError(f"unsupported geometry for the HIP path: {geom.depth=} {geom.dim=} {geom.heads=} "
-                                f"{shape.tokens=} (needs head dim 64, tokens <= 608, dim % 256 == 0)")
+                                f"{shape.tokens=} (needs head dim 64, dim % 256 == 0, chans * patch^2 % 64 == 0, "
+                                f"tokens <= 2^20)")
             if self._slot == 0 and not self.__dict__.get("_keep_ws"):
                 self._ws.clear()  # one live workspace: activations of one step (slots > 0: the two-stream step's second half)
             ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -465,8 +466,8 @@ class CaraEngine:
         model = self._model()
         if not x.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
-        if x.ndim != 3 or x.shape[2] != model.embed_dim or x.shape[1] > 608:
-            raise CaraError("module-level forward expects x of shape [B, N <= 608, embed_dim]")
+        if x.ndim != 3 or x.shape[2] != model.embed_dim or x.shape[1] > 2 ** 20:
+            raise CaraError("module-level forward expects x of shape [B, N <= 2^20, embed_dim]")
         if self.cp_length == 2:
             raise CaraError("with cp_length 2 (dense QKV deltas) call the whole model: the module-level Attention.forward / "
                             "Mlp.forward entries run the factored adapters only")

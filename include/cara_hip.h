@@ -273,8 +273,11 @@ int cara_layernorm_bwd_ex(const void* dy, const float* x, long ldx, const float*
 
 /* ---- attention (cara.py:43-48; softmax(q k^T * scale) v per head) ------------------------- */
 /* qkv bf16 [B*N, 3*H*64] with column k*H*64 + h*64 + d (k = q,k,v): exactly the layout
- * cara.py:39 reshapes.  out bf16 [B*N, H*64]; lse fp32 [B,H,N].  N <= 608, head dim 64 (N <= 224:   *
- * score rows in registers; above: two sweeps over the key tiles, whole K/V of a head in LDS).  */
+ * cara.py:39 reshapes.  out bf16 [B*N, H*64]; lse fp32 [B,H,N].  Head dim 64; N <= 2^20 and      *
+ * B*N < 2^31 (index arithmetic; no limit from LDS).  N <= 224: score rows in registers; N <= 608:  *
+ * two sweeps over the key tiles, whole K/V of a head in LDS; above (and for 224 < N <= 608 with    *
+ * CARA_ATTN_STREAM=1): the same two sweeps with K/V (backward: also Q/dO) streamed through LDS in   *
+ * 64-row tiles.  No atomics on any path: results are bitwise reproducible.                         */
 int cara_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale,
                        void* stream);
 int cara_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
@@ -283,7 +286,7 @@ int cara_attention_bwd(const void* qkv, const void* out, const void* dout, const
  * output reaches the logits (timm's `x[:, 0]` behind the final norm; cara.py:43-48 computes every row).  _fwd writes
  * out[b N + 0, :] and lse[b, h, 0] and leaves the other rows alone; _bwd reads those rows (and dout[b N + 0, :]) and writes
  * ALL of dqkv: dK / dV of every key row, dQ of the cls row, zeros for the dQ of the other rows.  Same rounding points as the
- * full kernels.  N <= 608.                                                                                             */
+ * full kernels.  N as for the full kernels (above 608 tokens _fwd sweeps the keys twice instead of keeping the score row in LDS). */
 int cara_attention_cls_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream);
 int cara_attention_cls_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
                            void* dqkv, int B, int N, int H, float scale, void* stream);
