@@ -1,0 +1,117 @@
+// Scoring a batch of logits on the device (gfx950): what `test()` of image_classification/vit_cp.py:73-82 does with
+// `out.argmax(1) == y` and one `.item()` per batch, as ONE launch per batch that adds into a 40-byte device-resident
+// state -- no host read until the caller wants the totals.
+//
+// state = five 64-bit words (cara_eval_state_bytes):
+//   [0] int64  rows scored            [1] int64  top-1 hits           [2] int64  top-5 hits
+//   [3] double sum of the per-row cross-entropy                       [4] int64  rows whose label is outside [0, classes)
+// A row with a bad label raises word 4 and adds to nothing else.
+//
+// Per row, with v = logits[label]:  rank = #{c : l[c] > v} + #{c < label : l[c] == v}  is the position of the label in a
+// stable descending sort, so  top-1 <=> rank == 0  (ties go to the lowest class index, numpy.argmax's rule) and
+// top-5 <=> rank < 5  (always, with fewer than five classes).  Cross-entropy = m + log(sum exp(l - m)) - v with the
+// log-sum-exp in fp32 (as cara_cross_entropy forms it; the accurate expf / logf here, not the fast intrinsics: the kernel
+// is bound by its loads); rows are summed in fp64.
+//
+// One wave per row: pass 1 the row maximum, pass 2 (the row is in L2 by then: at most 87 KB) the exponentials and the
+// rank, 16-byte loads where the row is 16-byte aligned.  A workgroup of four waves walks rows with a grid stride, adds
+// its waves' partial sums in LDS and issues one atomicAdd per non-zero word.
+#include "common.h"
+
+namespace {
+
+constexpr int EVAL_WAVES = 4;
+
+struct RowAcc {
+  float s;
+  int rank;
+};
+
+__device__ __forceinline__ void row_term(float x, int c, float m, float v, int y, RowAcc& a) {
+  a.s += expf(x - m);
+  a.rank += (x > v || (x == v && c < y)) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const float* __restrict__ logits, int ldl,
+                                                                          const int64_t* __restrict__ labels, int n_valid,
+                                                                          int C, unsigned long long* __restrict__ state) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long n = 0, t1 = 0, t5 = 0, bad = 0;
+  double loss = 0.0;
+  for (int b = blockIdx.x * EVAL_WAVES + wave; b < n_valid; b += gridDim.x * EVAL_WAVES) {
+    const int64_t y64 = labels[b];
+    if (y64 < 0 || y64 >= C) {   // (wave-uniform: one row per wave)
+      ++bad;
+      continue;
+    }
+    const int y = (int)y64;
+    const float* lr = logits + (size_t)b * ldl;
+    const bool vec = ((reinterpret_cast<uintptr_t>(lr) & 15) == 0);
+    const int C4 = vec ? C >> 2 : 0;
+    float m = -3.0e38f;
+    for (int i = lane; i < C4; i += 64) {
+      const float4 q = reinterpret_cast<const float4*>(lr)[i];
+      m = fmaxf(fmaxf(m, q.x), fmaxf(q.y, fmaxf(q.z, q.w)));
+    }
+    for (int c = C4 * 4 + lane; c < C; c += 64) m = fmaxf(m, lr[c]);
+    m = wave_max(m);
+    const float v = lr[y];
+    RowAcc a = {0.f, 0};
+    for (int i = lane; i < C4; i += 64) {
+      const float4 q = reinterpret_cast<const float4*>(lr)[i];
+      row_term(q.x, 4 * i, m, v, y, a);
+      row_term(q.y, 4 * i + 1, m, v, y, a);
+      row_term(q.z, 4 * i + 2, m, v, y, a);
+      row_term(q.w, 4 * i + 3, m, v, y, a);
+    }
+    for (int c = C4 * 4 + lane; c < C; c += 64) row_term(lr[c], c, m, v, y, a);
+    const float s = wave_sum(a.s);
+    int rank = a.rank;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+    const float lse = m + logf(s);
+    ++n;
+    t1 += rank == 0 ? 1 : 0;
+    t5 += rank < 5 ? 1 : 0;
+    loss += (double)lse - (double)v;
+  }
+  // every lane of a wave holds the wave's totals: lane 0 of each wave publishes them, thread 0 adds the four
+  __shared__ unsigned long long sh_i[EVAL_WAVES][4];
+  __shared__ double sh_l[EVAL_WAVES];
+  if (lane == 0) {
+    sh_i[wave][0] = n; sh_i[wave][1] = t1; sh_i[wave][2] = t5; sh_i[wave][3] = bad;
+    sh_l[wave] = loss;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < EVAL_WAVES; ++w) {
+      n += sh_i[w][0]; t1 += sh_i[w][1]; t5 += sh_i[w][2]; bad += sh_i[w][3];
+      loss += sh_l[w];
+    }
+    if (n) {
+      atomicAdd(state + 0, n);
+      atomicAdd(reinterpret_cast<double*>(state + 3), loss);
+    }
+    if (t1) atomicAdd(state + 1, t1);
+    if (t5) atomicAdd(state + 2, t5);
+    if (bad) atomicAdd(state + 4, bad);
+  }
+}
+
+}  // namespace
+
+extern "C" size_t cara_eval_state_bytes(void) { return 5 * sizeof(unsigned long long); }
+
+extern "C" int cara_eval_accumulate(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
+                                    void* state, void* stream) {
+  if (!logits || !labels || !state || B <= 0 || n_valid < 0 || n_valid > B || classes < 1 || ldl < classes) return CARA_E_ARG;
+  if ((reinterpret_cast<uintptr_t>(state) & 7) || (reinterpret_cast<uintptr_t>(logits) & 3)) return CARA_E_ARG;
+  if (n_valid == 0) return CARA_OK;
+  // at most 256 workgroups (one per CU): 1 280 atomics per launch at the worst, every row still read once
+  int grid = (n_valid + EVAL_WAVES - 1) / EVAL_WAVES;
+  grid = grid > 256 ? 256 : grid;
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(grid), dim3(EVAL_WAVES * 64), 0, static_cast<hipStream_t>(stream), logits, ldl,
+                     labels, n_valid, classes, static_cast<unsigned long long*>(state));
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}

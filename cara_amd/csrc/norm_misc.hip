@@ -318,6 +318,33 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
   *reinterpret_cast<bf16x4*>(out + e) = o;
 }
 
+// The same patch rows straight from resident uint8 pixels [B,C,Hi,Wi]: ToTensor + Normalize of vtab.py:92-94 in the fp32
+// operation order of data.normalize_u8 -- u / 255, - mean[c], / std[c], two correctly rounded divisions (no reciprocal
+// multiply: the build has no fast-math flag) -- then the one rounding to the build's 16-bit type that im2col_kernel applies
+// to the fp32 image.  The fp32 image tensor is never written.  Four pixels (one dword) per lane.
+__global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ mean,
+                                                        const float* __restrict__ stdv, bf16* __restrict__ out,
+                                                        int B, int C, int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const int kcols = C * p * p;
+  const long e = idx * 4;
+  const long row = e / kcols;
+  const int col = (int)(e - row * kcols);
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
+  const int gy = pr / gw, gx = pr % gw;
+  const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)b * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
+  const float mu = mean[c], sd = stdv[c];
+  const float v0 = ((float)(u & 255u) / 255.0f - mu) / sd;
+  const float v1 = ((float)((u >> 8) & 255u) / 255.0f - mu) / sd;
+  const float v2 = ((float)((u >> 16) & 255u) / 255.0f - mu) / sd;
+  const float v3 = ((float)(u >> 24) / 255.0f - mu) / sd;
+  bf16x4 o = {(bf16)v0, (bf16)v1, (bf16)v2, (bf16)v3};
+  *reinterpret_cast<bf16x4*>(out + e) = o;
+}
+
 __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__ emb, const float* __restrict__ cls,
                                                        const float* __restrict__ pos, float* __restrict__ x,
                                                        int B, int P, int D, long total4) {
@@ -593,6 +620,17 @@ extern "C" int cara_im2col_patches(const float* img, void* patches, int B, int C
   const long total4 = (long)B * C * Hi * Wi / 4;
   hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      img, (bf16*)patches, B, C, Hi, Wi, p, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_im2col_patches_u8(const unsigned char* pixels, const float* mean, const float* stdv, void* patches, int B, int C,
+                                      int Hi, int Wi, int p, void* stream) {
+  if (!pixels || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi % p || Wi % p || (Wi & 3)) return CARA_E_ARG;
+  if (reinterpret_cast<uintptr_t>(pixels) & 3) return CARA_E_ARG;   // (dword loads: rows are Wi % 4 == 0 bytes apart)
+  const long total4 = (long)B * C * Hi * Wi / 4;
+  hipLaunchKernelGGL(im2col_u8_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     pixels, mean, stdv, (bf16*)patches, B, C, Hi, Wi, p, total4);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }

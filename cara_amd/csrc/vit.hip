@@ -88,8 +88,26 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   w->clsn = c.take((size_t)s->B * D * 2);
   w->meanF = c.take((size_t)s->B * 4);
   w->rstdF = c.take((size_t)s->B * 4);
+  // Everything a forward needs besides the blocks' activations comes first, so that the layout of a forward that no
+  // backward follows (below) is a PREFIX of the training layout: scratch of the few-row split-K products (partial
+  // products, written before they are read) and, for the order-2 tensorisation, the dense QKV deltas and their transposes.
+  w->gemm_scratch = c.take(cara_gemm_scratch_bytes());
+  w->dd = w->ddt = w->dD = w->dd_slabs = w->dd_scratch = 0;
+  if (g->cp_length == 2) {
+    if (s->wd_exact) return false;   // (the dense-delta QKV form and the exact weight-dropout mode are not combined)
+    if (g->dim % 128) return false;  // (its backward's dense x^T dY: 128 x 128 output tiles, cara_gemm_tn_f32)
+    w->dd = c.take((size_t)g->depth * 3 * D * D * 2);
+    w->ddt = c.take((size_t)g->depth * 3 * D * D * 2);
+  }
   w->x_last = c.take(M * D * 4);
-  for (int l = 0; l < g->depth; ++l) {
+  // cara_vit_shape::inference (as cara_vit_forward reads it: never with the exact weight-dropout mode): two activation
+  // sets, which the blocks take in turn -- block l reads the residual stream from set l % 2 and leaves it in the other
+  // set's x_in -- and nothing of the backward: no gradient stream, no dY / G' set, no slabs, no dense gradients.  Being a
+  // prefix of the training layout, the same forward runs on a workspace of either size, whatever a training step left
+  // in it, and every kernel sees the launch it sees on the training layout: different addresses only.
+  const bool inference = s->inference != 0 && !s->wd_exact;
+  const int nsets = inference && g->depth > 2 ? 2 : g->depth;
+  for (int l = 0; l < nsets; ++l) {
     LayerWs& L = w->layer[l];
     L.x_in = c.take(M * D * 4);
     L.x_mid = c.take(M * D * 4);
@@ -105,6 +123,15 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
       L.T[i] = c.take(M * Rp * 2);
       L.Tt[i] = c.take(Rp * ldt * 2);
     }
+  }
+  for (int l = nsets; l < g->depth; ++l) w->layer[l] = w->layer[l - 2];
+  if (inference) {
+    w->dx = w->dXn = w->dAO = w->slabs = w->dclsn = w->gscratch = 0;
+    w->bwd = Ws::Bwd{};
+    w->ldk = (int)((M + 63) / 64 * 64);
+    w->nslab = 1;
+    w->total = c.off;
+    return true;
   }
   w->dx = c.take(M * D * 4);
   w->dXn = c.take(M * D * 2);
@@ -123,7 +150,6 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   w->slabs = 0;
   w->dclsn = c.take((size_t)s->B * D * 2);
   w->gscratch = c.take(cara_factor_grad_scratch_bytes(g));
-  w->gemm_scratch = c.take(cara_gemm_scratch_bytes());   // stream-K partial tiles + flags (workspace is zeroed at allocation)
   const size_t ins[4] = {D, D, D, 4 * D}, outs[4] = {3 * D, D, 4 * D, D};
   for (int i = 0; i < 4; ++i) {
     w->dU[i] = c.take((size_t)g->depth * ins[i] * Rp * 4);
@@ -159,12 +185,7 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
     w->dWd = c.take(dwd);
     w->xscratch = c.take(max_sz(cara_dropout_grad_scratch_bytes((int)(4 * D), (int)D, (int)Rp), cara_colsum_scratch_bytes((int)(4 * D))));
   }
-  w->dd = w->ddt = w->dD = w->dd_slabs = w->dd_scratch = 0;
   if (g->cp_length == 2) {
-    if (s->wd_exact) return false;   // (the dense-delta QKV form and the exact weight-dropout mode are not combined)
-    if (g->dim % 128) return false;  // (its backward's dense x^T dY: 128 x 128 output tiles, cara_gemm_tn_f32)
-    w->dd = c.take((size_t)g->depth * 3 * D * D * 2);
-    w->ddt = c.take((size_t)g->depth * 3 * D * D * 2);
     w->dD = c.take((size_t)g->depth * 3 * D * D * 4);
     w->dd_slabs = c.take((size_t)dw_slabs((int)D, (int)D, (int)M) * D * D * 4);
     w->dd_scratch = c.take(cara_dense_delta_grad_scratch_bytes(g));
@@ -924,11 +945,15 @@ static bool tile_policy(const cara_geom* g, int M, int N, int K, int riders) {
   return g->Rp == 32 && g->rank > 0 && g->rank <= 16 && cara_gemm8_policy(M, N, K, riders);
 }
 
-extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
-                                const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
-                                const float* droppath, void* workspace, float* logits, void* stream) {
+// The forward behind both entries: the image is either fp32 (`images`) or resident uint8 pixels with their per-channel
+// mean / std (`pixels`); everything behind the patch rows is the same.
+static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                            const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
+                            const unsigned char* pixels, const float* mean, const float* stdv,
+                            const float* droppath, void* workspace, float* logits, void* stream) {
   Ws W;
-  if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !images || !workspace || !logits) return CARA_E_ARG;
+  if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !workspace || !logits) return CARA_E_ARG;
+  if (pixels ? (!mean || !stdv) : !images) return CARA_E_ARG;
   char* ws = static_cast<char*>(workspace);
   const int D = g->dim, M = W.M, Rp = g->Rp, B = s->B, N = s->tokens, P = N - 1;
   const float att_scale = 1.0f / sqrtf((float)(D / g->heads));
@@ -939,7 +964,8 @@ extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, con
   if (dense_qkv) TRY(cara_dense_delta_materialize(g, cp, ws + W.dd, ws + W.ddt, stream));
   // patch embedding: Conv2d(k = s = patch) as a GEMM over im2col rows, then cls + pos_embed
   const int kp = s->chans * s->patch * s->patch;
-  TRY(cara_im2col_patches(images, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
+  if (pixels) TRY(cara_im2col_patches_u8(pixels, mean, stdv, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
+  else TRY(cara_im2col_patches(images, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
   cara_gemm_args a = {};
   a.A = ws + W.patches; a.lda = kp; a.B = w->patch_w; a.ldb = kp; a.M = B * P; a.N = D; a.K = kp;
   a.bias = w->patch_b; a.epi = CARA_EPI_F32; a.C = ws + W.emb; a.ldc = D;
@@ -1035,10 +1061,26 @@ extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, con
                            D, s->eps, stream);
 }
 
+extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
+                                const float* droppath, void* workspace, float* logits, void* stream) {
+  return vit_forward_body(g, s, w, cp, head_w, head_b, images, nullptr, nullptr, nullptr, droppath, workspace, logits, stream);
+}
+
+extern "C" int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                   const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                   const float* mean, const float* stdv, const float* droppath, void* workspace, float* logits,
+                                   void* stream) {
+  if (!pixels) return CARA_E_ARG;
+  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, mean, stdv, droppath, workspace, logits, stream);
+}
+
 extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                                  const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,
                                  void* workspace, const cara_cp* grads, float* dhead_w, float* dhead_b, void* stream) {
   Ws W;
+  // a shape that says "inference" describes a workspace without the backward's regions (and a forward that kept nothing)
+  if (s && s->inference != 0 && !s->wd_exact) return CARA_E_ARG;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !dlogits || !workspace || !grads || !dhead_w || !dhead_b) return CARA_E_ARG;
   char* ws = static_cast<char*>(workspace);
   TsPending pending;

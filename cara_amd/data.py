@@ -93,6 +93,17 @@ class ResidentSplit:
             self.pixels[c0:c0 + len(part)].copy_(torch.stack(decoded))
         self.labels = torch.tensor([l for _, l in self.imlist], dtype=torch.int64, device=device)
 
+    @classmethod
+    def from_tensors(cls, pixels: torch.Tensor, labels: torch.Tensor) -> "ResidentSplit":
+        """A split over pixels that are resident already: uint8 [N,3,size,size] and int64 [N] on one device (synthetic
+        splits of tests and tools; nothing is decoded, ``imlist`` holds empty paths)."""
+        if pixels.dtype != torch.uint8 or pixels.ndim != 4 or labels.dtype != torch.int64 or labels.shape != pixels.shape[:1]:
+            raise ValueError("from_tensors takes uint8 [N,C,H,W] pixels and int64 [N] labels")
+        self = cls.__new__(cls)
+        self.root, self.pixels, self.labels = "", pixels.contiguous(), labels.to(pixels.device)
+        self.imlist = [("", int(l)) for l in labels.tolist()]
+        return self
+
     @property
     def images(self) -> torch.Tensor:
         """The whole split normalised, fp32 [N,3,size,size] (materialised: for small splits and tests)."""
@@ -126,14 +137,35 @@ class ResidentSplit:
                 yield normalize_u8(self.pixels[i:i + batch_size]), self.labels[i:i + batch_size]
         return it
 
+    def eval_shard(self, batch_size: int = 256, rank: Optional[int] = None,
+                   world: Optional[int] = None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, int]]:
+        """This rank's part of the split (``dist.eval_shard``: contiguous, file order) as ``(pixels_u8, labels, n_valid)``:
+        the resident uint8 pixels themselves, not normalised -- ``CaraEngine.evaluate`` hands them to the uint8 forward.
+        Every batch has ``batch_size`` rows: the last one of a shard is padded (with copies of its first row and label)
+        and says so in ``n_valid``, so a pass uses one batch shape and one workspace."""
+        rank = D.get_rank() if rank is None else rank
+        world = D.world_size() if world is None else world
+        mine = D.eval_shard(len(self), rank, world, batch_size)
+        for i in range(mine.start, mine.stop, batch_size):
+            j = min(i + batch_size, mine.stop)
+            px, y = self.pixels[i:j], self.labels[i:j]
+            if j - i < batch_size:
+                pad = batch_size - (j - i)
+                px = torch.cat([px, px[:1].expand(pad, -1, -1, -1)])
+                y = torch.cat([y, y[:1].expand(pad)])
+            yield px, y, j - i
+
+
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
-             seed: int = 0, workers: int = 8):
+             seed: int = 0, workers: int = 8, shard_eval: bool = False):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
-    Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders."""
+    Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
+    ``shard_eval = True``: the second value is the test ``ResidentSplit`` itself, the form ``fit(eval_mode="sharded")`` and
+    ``CaraEngine.evaluate`` take (every rank then scores its own part, ``ResidentSplit.eval_shard``)."""
     root = root if root is not None else "./data/vtab-1k/" + name
     tr, te = ("train800val200.txt", "test.txt") if evaluate else ("train800.txt", "val200.txt")
     train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers)
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
-    return train.train_batches(batch_size, seed=seed), test.eval_batches(256)
+    return train.train_batches(batch_size, seed=seed), (test if shard_eval else test.eval_batches(256))

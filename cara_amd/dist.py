@@ -62,6 +62,17 @@ def epoch_shard(n_items: int, epoch: int, rank: int, world: int, per_rank_batch:
     return [mine[i * per_rank_batch:(i + 1) * per_rank_batch] for i in range(nb)]
 
 
+def eval_shard(n_items: int, rank: int, world: int, batch_size: int) -> range:
+    """This rank's part of an evaluation pass over ``n_items`` items in file order: contiguous, disjoint ranges whose
+    union is ``range(n_items)``.  Every rank's range is ``ceil(n_items / world)`` rounded up to whole batches long, so
+    that only the range that holds the end of the split has a short last batch (ranks behind it may get nothing)."""
+    if not (0 <= rank < world) or batch_size <= 0 or n_items < 0:
+        raise ValueError("eval_shard needs 0 <= rank < world, batch_size > 0 and n_items >= 0")
+    per = -(-(-(-n_items // world)) // batch_size) * batch_size
+    start = min(rank * per, n_items)
+    return range(start, min(start + per, n_items))
+
+
 def broadcast_parameters(params: Sequence[torch.Tensor], src: int = 0, group=None) -> None:
     """Make replicas identical once at start-up (afterwards identical gradients + identical
     optimiser state keep them identical; no per-step parameter traffic)."""

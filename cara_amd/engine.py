@@ -455,6 +455,115 @@ class CaraEngine:
             self._apply_gradients(optimizer, group, prescaled=True)
         return self._loss_buf[0]
 
+    # ------------------------------------------------------------------ evaluation on the device
+    def _eval_state(self, model, B, img, dev):
+        """Workspace of the evaluation forwards: sized with cara_vit_shape::inference = 1 (two activation sets, nothing of the
+        backward) and kept in ``_eval_ws``, beside the training workspaces of ``_ws``, which this never touches."""
+        if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
+            self._ingest(model, dev)
+        ews = self.__dict__.setdefault("_eval_ws", {})
+        ncls = model.head.out_features
+        key = (B, img, ncls, str(dev), self._operands())
+        st = ews.get(key)
+        if st is None:
+            pe = model.patch_embed
+            geom = L.Geom(len(model.blocks), model.embed_dim, model.blocks[0].attn.num_heads, self.rank, self.Rp, self.scale,
+                          self.cp_length)
+            patch = pe.proj.kernel_size[0]
+            shape = L.VitShape(B, img, patch, pe.proj.in_channels, (img // patch) ** 2 + 1, ncls, float(model.norm.eps),
+                               0, float(self.weight_dropout_p), 0, 1)
+            nbytes = self._lib().cara_vit_workspace_bytes(C.byref(geom), C.byref(shape))
+            if nbytes == 0:
+                raise CaraError(f"unsupported geometry for the HIP path: {geom.depth=} {geom.dim=} {geom.heads=} {shape.tokens=}")
+            st = {"geom": geom, "shape": shape, "ws": torch.zeros(nbytes, dtype=torch.uint8, device=dev),
+                  "logits": torch.empty(B, ncls, device=dev)}
+            ews[key] = st
+        return st
+
+    def _eval_norm(self, dev):
+        """per-channel mean / std of the reference's Normalize (vtab.py:94) as device fp32 vectors"""
+        got = self.__dict__.get("_eval_meanstd")
+        if got is None or got[0].device != dev:
+            from .data import IMAGENET_MEAN, IMAGENET_STD
+            got = (torch.tensor(IMAGENET_MEAN, device=dev), torch.tensor(IMAGENET_STD, device=dev))
+            self._eval_meanstd = got
+        return got
+
+    def eval_workspace_bytes(self) -> int:
+        """bytes held by the evaluation workspaces (diagnostics: tools/eval_bench.py)"""
+        return sum(st["ws"].numel() for st in self.__dict__.get("_eval_ws", {}).values())
+
+    def _eval_forward(self, model, x, dev):
+        """logits of one evaluation batch: uint8 pixels -> cara_vit_forward_u8, fp32 images -> cara_vit_forward, both on the
+        inference-sized workspace.  The returned tensor is the workspace entry's own: valid until the next batch."""
+        if x.ndim != 4 or x.shape[2] != x.shape[3]:
+            raise CaraError("images must be [B, C, H, H]")
+        st = self._eval_state(model, x.shape[0], x.shape[2], dev)
+        cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
+        cps = self._cp_ptrs([t.detach().contiguous() for t in cp])
+        hw, hb = model.head.weight.detach().contiguous(), model.head.bias.detach().contiguous()
+        lib, args = self._lib(), (C.byref(st["geom"]), C.byref(st["shape"]), C.byref(self._ingested[1]), C.byref(cps), ptr(hw), ptr(hb))
+        if x.dtype == torch.uint8:
+            if st["shape"].chans != 3:
+                raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
+            mean, std = self._eval_norm(dev)
+            check(lib.cara_vit_forward_u8(*args, ptr(x.contiguous()), ptr(mean), ptr(std), None, ptr(st["ws"]), ptr(st["logits"]),
+                                          stream(dev)), "cara_vit_forward_u8")
+        else:
+            check(lib.cara_vit_forward(*args, ptr(x.contiguous().float()), None, ptr(st["ws"]), ptr(st["logits"]), stream(dev)),
+                  "cara_vit_forward")
+        return st["logits"]
+
+    def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None) -> dict:
+        """Top-1 / top-5 accuracy and mean cross-entropy of a whole split, on the device and sharded over the ranks of
+        ``group``: ``test()`` of vit_cp.py:73-82 without its host read per batch.  -> ``dict(top1, top5, loss, n)``, the
+        same on every rank; ``n`` is the number of images scored by all ranks together.
+
+        ``split_or_batches``: a ``data.ResidentSplit`` (this rank's ``eval_shard(batch_size)`` is taken), or an iterable --
+        or a callable returning one -- of ``(pixels_u8, labels, n_valid)`` / ``(images_fp32, labels)`` batches that are this
+        rank's part already.  Each batch is one forward on an inference-sized workspace held beside the training workspace
+        and one ``cara_eval_accumulate`` launch into a 40-byte device state; nothing is read back inside the loop.  Then
+        one SUM all-reduce of the state and one read-back.  Like the reference's ``test()`` it leaves the model in eval mode.
+        ``debug_hook(logits, labels, n_valid)`` (tests) sees every batch's logits; they are overwritten by the next batch."""
+        from . import dist as cdist
+        model = self._model()
+        model.eval()
+        if not hasattr(model.head, "weight"):
+            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+        if self.precision not in ("bf16", "fp16"):
+            raise CaraError(f"precision must be 'bf16' or 'fp16', not {self.precision!r}")
+        if self.precision == "fp16" and self.cp_length == 2:
+            raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
+        dev = model.head.weight.device
+        if dev.type != "cuda":
+            raise CaraError("cara_amd runs on the GPU only: move the model to a ROCm device (there is no CPU fallback)")
+        if hasattr(split_or_batches, "eval_shard"):
+            batches = split_or_batches.eval_shard(batch_size, cdist.get_rank(group), cdist.world_size(group))
+        else:
+            batches = split_or_batches() if callable(split_or_batches) else split_or_batches
+        lib = self._lib()
+        with torch.no_grad(), torch.cuda.device(dev):
+            state = torch.zeros(int(lib.cara_eval_state_bytes()) // 8, dtype=torch.int64, device=dev)
+            for item in batches:
+                x, y = item[0], item[1]
+                n_valid = int(item[2]) if len(item) > 2 else y.shape[0]
+                if x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]:
+                    raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
+                logits = self._eval_forward(model, x, dev)
+                check(lib.cara_eval_accumulate(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
+                                               logits.shape[1], ptr(state), stream(dev)), "cara_eval_accumulate")
+                if debug_hook is not None:
+                    debug_hook(logits, y, n_valid)
+            # the five words as fp64 (counts are exact up to 2^53): ONE collective carries integers and the loss sum alike
+            vec = state.to(torch.float64)
+            vec[3] = state.view(torch.float64)[3]
+            cdist.allreduce_sum_(vec, group)
+            n, t1, t5, loss, bad = vec.tolist()   # the pass's only host read
+        if bad:
+            raise CaraError(f"evaluate: {int(bad)} label(s) outside [0, {model.head.out_features})")
+        d = max(n, 1.0)
+        return {"top1": t1 / d, "top5": t5 / d, "loss": loss / d, "n": int(n)}
+
     # module-level entries (cara.cp_attn / cara.cp_mlp): the reference's patched forwards
     def _weights(self, model, dev):
         if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:

@@ -150,7 +150,7 @@ class GraphedTrainStep:
 def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[Callable[[], Iterable]] = None,
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
         on_eval: Optional[Callable[[int, float], None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
-        graph: bool = False):
+        graph: bool = False, eval_mode: str = "reference"):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -164,7 +164,13 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     Single process: the masks come from torch's global generators, exactly as in the reference, unless a ``seed`` is
     passed explicitly.
     ``graph = True``: the step is replayed from a hipGraph (``GraphedTrainStep``; the host then issues one launch per step
-    instead of ~600: for boxes where several ranks share few cores).  Eager is the default: the step is GPU-bound."""
+    instead of ~600: for boxes where several ranks share few cores).  Eager is the default: the step is GPU-bound.
+    ``eval_mode = "sharded"``: ``test_batches`` is a ``data.ResidentSplit`` (or a callable returning batches in the form of
+    its ``eval_shard``) and the evaluation epochs run ``CaraEngine.evaluate`` on it -- every rank scores its own part of
+    the split on the device and all of them get the global top-1 accuracy.  ``"reference"`` (default): ``evaluate`` below
+    over ``test_batches()``, on every rank."""
+    if eval_mode not in ("reference", "sharded"):
+        raise CaraError(f"eval_mode must be 'reference' or 'sharded', not {eval_mode!r}")
     from . import dist as cdist
     model.train()
     params = trainable_parameters(model)
@@ -194,7 +200,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
             if epoch >= 50:
                 sched = None
             if test_batches is not None:
-                acc = evaluate(model, test_batches())
+                if eval_mode == "sharded":
+                    acc = eng.evaluate(test_batches, group=group)["top1"]
+                else:
+                    acc = evaluate(model, test_batches())
                 if acc > best and save_best is not None and cdist.get_rank(group) == 0:
                     import os
                     old = save_best.get("path")

@@ -295,6 +295,12 @@ int cara_attention_cls_bwd(const void* qkv, const void* out, const void* dout, c
 /* patches bf16 [B*gh*gw, C*p*p] <- images fp32 [B,C,Hi,Wi]  (Conv2d k=s=p as a GEMM operand)  */
 int cara_im2col_patches(const float* img, void* patches, int B, int C, int Hi, int Wi, int p,
                         void* stream);
+/* The same patch rows straight from uint8 pixels [B,C,Hi,Wi] (a resident data split): ToTensor + Normalize of
+ * vtab.py:92-94 per element in fp32, in this order -- u / 255, - mean[c], / std[c], both divisions correctly rounded --
+ * then the one rounding to the build's 16-bit type.  mean / std: device fp32 [C].  pixels 4-byte aligned.  The fp32
+ * image is never written; the rows are bitwise those of cara_im2col_patches on the fp32 image so computed.          */
+int cara_im2col_patches_u8(const unsigned char* pixels, const float* mean, const float* std, void* patches,
+                           int B, int C, int Hi, int Wi, int p, void* stream);
 /* x fp32 [B,1+P,D]: row 0 = cls + pos[0]; row 1+i = emb[b*P+i] + pos[1+i]                      */
 int cara_assemble_tokens(const float* emb, const float* cls, const float* pos, float* x, int B,
                          int P, int D, void* stream);
@@ -310,6 +316,18 @@ int cara_cross_entropy(const float* logits, const int64_t* labels, float* loss, 
  * UNSCALED mean loss.                                                                                                  */
 int cara_cross_entropy_ex(const float* logits, const int64_t* labels, float* loss, float* dlogits,
                           int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream);
+/* Scoring on the device (test() of vit_cp.py:73-82 without its per-batch host read): for the first n_valid <= B rows of
+ * logits fp32 [B,classes] (row stride ldl floats) and labels int64 [B], ADD into `state`, five 64-bit words
+ * (cara_eval_state_bytes() = 40 bytes, 8-byte aligned, zeroed by the caller before the first batch):
+ *   [0] int64 rows scored   [1] int64 top-1 hits   [2] int64 top-5 hits   [3] double sum of the per-row cross-entropy
+ *   [4] int64 rows whose label lies outside [0, classes): such a row raises this word and adds to nothing else.
+ * Top-1 ties go to the lowest class index (numpy.argmax); top-5 = the label is among the first five of a stable
+ * descending sort (always, with fewer than five classes).  Log-sum-exp in fp32 per row, rows summed in fp64.  Any B,
+ * any class count; one launch, a handful of atomicAdd per workgroup (the integer words are exact in any order; the loss
+ * word is an fp64 sum whose order is not fixed).                                                                    */
+size_t cara_eval_state_bytes(void);
+int cara_eval_accumulate(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
+                         void* state, void* stream);
 /* bf16 <-> fp32 helpers (weight ingest)                                                        */
 int cara_f32_to_bf16(const float* src, void* dst, size_t n, void* stream);
 int cara_transpose_bf16(const void* src, void* dst, int rows, int cols, void* stream);
@@ -481,7 +499,11 @@ typedef struct {
   unsigned wd_seed;
   /* 1: no backward will follow this forward (eval / no_grad).  The forward then skips what only the backward
    * reads -- the bf16 pre-activation of fc1 (77 MB per block at bs 64), T^T of the adapter products -- and
-   * cara_vit_backward on that workspace is an error until a forward with inference = 0 has run.            */
+   * cara_vit_backward on that workspace is an error until a forward with inference = 0 has run.
+   * cara_vit_workspace_bytes sees the flag too (without wd_exact): two activation sets, which the blocks take in turn,
+   * and none of the backward's regions -- a prefix of the training layout, so a forward with inference = 1 runs on a
+   * workspace of either size with the same launches and the same logits, bit for bit.  cara_vit_backward with
+   * inference = 1 returns CARA_E_ARG.                                                                       */
   int inference;
   /* Loss scaling (the IEEE-half operand build; both NULL otherwise).  cara_vit_backward is linear in dlogits: a caller that
    * scaled dlogits by S = *loss_scale (device float) gets every gradient it writes multiplied by 1/S here, in the kernels
@@ -500,6 +522,12 @@ size_t cara_vit_workspace_bytes(const cara_geom* g, const cara_vit_shape* s);
 int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                      const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
                      const float* droppath, void* workspace, float* logits, void* stream);
+/* cara_vit_forward with the image given as uint8 pixels [B,chans,img,img] and the per-channel mean / std (device fp32
+ * [chans]) of the reference's Normalize: the patch rows come from cara_im2col_patches_u8, every later stage is shared.  */
+int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                        const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                        const float* mean, const float* std, const float* droppath, void* workspace, float* logits,
+                        void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,

@@ -1,0 +1,34 @@
+"""Child process of test_two_ranks_on_one_gpu_return_the_same_dict: rank `argv[1]` of `argv[2]`, every rank on cuda:0 over gloo.
+Scores its shard of a 700-image synthetic split with CaraEngine.evaluate and writes the returned dict (plus the number of batches
+every rank ran) to `argv[3]`.<rank>.json."""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import torch.distributed as dist  # noqa: E402
+
+
+def main():
+    rank, world, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.cuda.set_device(0)
+    from cara_amd.data import ResidentSplit
+    from tests.test_eval_gpu import _model, _pixels
+    m = _model(2)
+    px, labels = _pixels(700, seed=9)
+    split = ResidentSplit.from_tensors(px.cuda(), labels.cuda())
+    batches = []
+    res = m._cara_engine.evaluate(split, 256, debug_hook=lambda lg, lb, nv: batches.append(nv))
+    counts = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(counts, torch.tensor([len(batches)]))
+    res["batches"] = [int(c) for c in counts]
+    with open(f"{out}.{rank}.json", "w") as fh:
+        json.dump(res, fh)
+    dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

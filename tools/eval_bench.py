@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Time one evaluation pass over a synthetic resident split (uint8 noise, ViT-B/16 + CaRA rank 16) through
+
+  (a) recipe.evaluate(model, split.eval_batches(B)())   -- the reference loop: normalise on the device, model(x), argmax,
+      one .item() per batch, the training-sized workspace of the engine;
+  (b) engine.evaluate(split, B)                         -- the uint8 forward on an inference-sized workspace, the counting
+      kernel after every batch, one host read per pass;
+
+and print seconds per pass (median, min, max over --passes after one warm-up each), images/s and the workspace bytes of
+both.  Standalone: not part of bench.py.  --only a|b runs one leg (the leg (a) of an older build: CARA_LIB_PATH)."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=10_000)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--passes", type=int, default=5)
+    ap.add_argument("--classes", type=int, default=100)
+    ap.add_argument("--rank", type=int, default=16)
+    ap.add_argument("--depth", type=int, default=12)
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"])
+    ap.add_argument("--only", default="ab", choices=["a", "b", "ab"])
+    args = ap.parse_args()
+    from cara_amd import cara, create_model, recipe
+    from cara_amd.data import ResidentSplit
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = create_model("vit_base_patch16_224_in21k", depth=args.depth, num_classes=args.classes, drop_path_rate=0.1)
+    m = cara({"model": m, "rank": args.rank, "scale": 0.1, "l_mu": 1.5, "l_std": 0.1, "precision": args.precision}).to(dev).eval()
+    eng = m._cara_engine
+    g = torch.Generator(device=dev).manual_seed(1)
+    px = torch.randint(0, 256, (args.images, 3, 224, 224), generator=g, dtype=torch.uint8, device=dev)
+    y = torch.randint(0, args.classes, (args.images,), generator=g, device=dev)
+    split = ResidentSplit.from_tensors(px, y)
+
+    def timed(fn):
+        fn()   # warm-up: workspaces allocated, weights ingested
+        torch.cuda.synchronize(dev)
+        out = []
+        for _ in range(args.passes):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            out.append(time.perf_counter() - t0)
+        return out
+
+    res = {"images": args.images, "batch": args.batch, "passes": args.passes, "precision": args.precision, "depth": args.depth}
+
+    def report(name, ts, ws_bytes, acc):
+        med = statistics.median(ts)
+        res[name] = {"seconds": [round(t, 4) for t in ts], "median_s": round(med, 4), "min_s": round(min(ts), 4),
+                     "max_s": round(max(ts), 4), "spread_pct": round(100 * (max(ts) - min(ts)) / med, 2),
+                     "images_per_s": round(args.images / med, 1), "workspace_bytes": int(ws_bytes), "top1": acc}
+
+    if "a" in args.only:
+        acc = [0.0]
+        ts = timed(lambda: acc.__setitem__(0, recipe.evaluate(m, split.eval_batches(args.batch)())))
+        # (the reference loop leaves the workspace of its LAST batch shape alive; the full-batch one is the larger)
+        peak = max(st["ws"].numel() for st in eng._ws.values())
+        full = int(eng._lib().cara_vit_workspace_bytes(*[C.byref(v) for v in _shape(eng, m, args.batch)]))
+        report("reference_loop", ts, max(peak, full), acc[0])
+        eng._ws.clear()
+        torch.cuda.empty_cache()
+    if "b" in args.only:
+        out = [None]
+        ts = timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch)))
+        report("engine_evaluate", ts, eng.eval_workspace_bytes(), out[0]["top1"])
+        res["engine_evaluate"].update(top5=out[0]["top5"], loss=out[0]["loss"], n=out[0]["n"])
+    print(json.dumps(res))
+
+
+def _shape(eng, m, B):
+    """(geom, shape) of the engine's training-sized workspace at batch B: what model(x) allocates for a full batch"""
+    from cara_amd import _lib as L
+    pe = m.patch_embed
+    patch = pe.proj.kernel_size[0]
+    geom = L.Geom(len(m.blocks), m.embed_dim, m.blocks[0].attn.num_heads, eng.rank, eng.Rp, eng.scale, eng.cp_length)
+    shape = L.VitShape(B, 224, patch, 3, (224 // patch) ** 2 + 1, m.head.out_features, float(m.norm.eps), 0, 0.1, 0, 0)
+    return geom, shape
+
+
+if __name__ == "__main__":
+    main()
