@@ -1,28 +1,32 @@
-// Fused attention forward / backward for the ViT token counts (head dim 64) on gfx950: N <= 224 (ViT-B/16
-// @224: 197 tokens) on the register-resident path described below, N <= 608 (ViT-L/16 @384: 577 tokens) on
-// the same kernels with the whole K/V (or Q/dO) of a head still in LDS (152 KiB, one workgroup per CU) and a
-// forward that sweeps the key tiles twice (max + sum, then P.V) instead of holding the score rows; any N above that (ViT-B/16
-// @448: 785 tokens, @512: 1 025) on the streamed kernels near the end of this file, which hold 64-row tiles of K/V (Q/dO) in LDS.
+// Fused attention forward / backward (head dim 64) on gfx950, any token count.  Four paths by N -- attn_path() at the end of this
+// file is the dispatch, and the table above it names the kernels:
+//   N <= 128        short:    K / V of a head in LDS, a wave's whole score row block in registers; two-kernel backward
+//   129 .. 224      headline (ViT-B/16 @224: 197 tokens): persistent kernels, one 7-wave workgroup per CU walking the (batch,
+//                   head) pairs, the next head's images arriving by LDS-DMA: attn_fwd_p2_kernel and ONE backward kernel,
+//                   attn_bwd_fused_kernel, which runs the dK/dV and the dQ sweep on the same LDS images
+//   225 .. 608      long (ViT-L/16 @384: 577 tokens): the whole K / V (or Q / dO) of a head still in LDS (152 KiB, one workgroup
+//                   per CU), a forward that sweeps the key tiles twice (max, then sum + P.V) instead of holding the score rows;
+//                   two-kernel backward
+//   > 608           streamed (ViT-B/16 @448: 785 tokens, @512: 1 025): the same block steps with K / V (Q / dO) passing through
+//                   LDS in 64-row tiles
 // Reference semantics: /root/reference/src/cara/cara.py:43-48
 //     attn = softmax((q @ k^T) * scale); x = (attn @ v).transpose(1, 2).reshape(B, N, C)
 // with q, k, v the three [B,H,N,64] views of the qkv activation laid out exactly as cara.py:39
 // reshapes it ([B*N, 3*H*64], column k*H*64 + h*64 + d).  attn_drop has p = 0 in the reference
 // configuration (timm attn_drop_rate = 0), so no dropout on the probabilities.
 //
-// Forward: the whole K/V of one head sits in LDS (28 KiB + 33 KiB), each wave owns 32 query rows
-// and, because N is small, the whole score row block in registers (7 tiles of 32x32): exact
-// two-pass softmax, no online rescaling.  Scores are computed TRANSPOSED (S^T = K Q^T) with
-// v_mfma_f32_32x32x16_bf16 so that a query's row lives in ONE lane (max / sum = in-lane reduction
-// + one cross-half shuffle) and the probability accumulators are already the A operand of P.V
-// (no LDS round trip).  K and V sit in LDS as plain row-major (swizzled) images; the P.V B fragments
-// (keys on the k axis) come out of the V image with the transposing LDS read ds_read_b64_tr_b16.
+// Forward, all paths: each wave owns 32 query rows; exact two-pass softmax, no online rescaling.  Scores are computed TRANSPOSED
+// (S^T = K Q^T) with v_mfma_f32_32x32x16_bf16 so that a query's row lives in ONE lane (max / sum = in-lane reduction + one
+// cross-half shuffle) and the probability accumulators are already the A operand of P.V (no LDS round trip).  K and V sit in
+// LDS as plain row-major (swizzled) images; the P.V B fragments (keys on the k axis) come out of the V image with the transposing
+// LDS read ds_read_b64_tr_b16.
 //
-// Backward: two kernels, both recomputing P from Q, K and the forward's LSE.  (1) dK/dV: a
-// workgroup of 7 waves per (batch, head); wave w owns keys 32w..32w+31 and keeps dK^T, dV^T in
-// accumulators while sweeping the query tiles; S and dP are computed with the key on the lane, so
-// P and dS feed dV^T += dO^T P and dK^T += Q^T dS straight from the accumulators.  (2) dQ: the
-// forward's structure (wave = 32 queries, query on the lane): dS^T feeds dQ += dS K from the
-// accumulators.  No atomics, no cross-wave sums: results are bitwise reproducible.
+// Backward, all paths, recomputes P from Q, K and the forward's LSE in two sweeps.  (1) dK/dV: wave w owns 32 keys and keeps dK^T,
+// dV^T in accumulators while sweeping the query tiles; S and dP are computed with the key on the lane, so P and dS feed
+// dV^T += dO^T P and dK^T += Q^T dS straight from the accumulators.  (2) dQ: the forward's structure (wave = 32 queries, query on
+// the lane): dS^T feeds dQ += dS K from the accumulators.  Two kernels on the short, long and streamed paths, two phases of one
+// kernel on the headline path.  No atomics, no cross-wave sums: results are bitwise reproducible.
+// The per-block steps that the long and the streamed kernels share are written once (fwd_*_block, dkv_block, dq_block, ...).
 #include <stdlib.h>
 
 #include "common.h"
@@ -140,13 +144,74 @@ __device__ __forceinline__ void stage_rows_swz(const bf16* __restrict__ src, int
 }
 
 // ------------------------------------------------------------------------------------------
+// Block steps of the two-sweep forward, written once: attn_fwd_long_kernel (K / V of the head resident in LDS) and
+// attn_fwd_stream_kernel (K / V passing through in 64-row tiles) differ in how a 32-key block gets into LDS, not in what is done
+// with it.  That the two give the same bits at 577 tokens rests on these being the same code.
+// ------------------------------------------------------------------------------------------
+// S^T = K Q^T of one 32-key block (row = key crow(r, h) of the block, column = the lane's query).  `last`: the block holds the
+// head's last keys, of which `last_keys` are real; the padded ones (copies of key N - 1) get -huge, so that their exp is 0.
+__device__ __forceinline__ f32x16 fwd_score_block(const char* kblk, const bf16x8 (&qf)[4], const RowOfs& ro, const bool last,
+                                                  const int last_keys, const int h) {
+  f32x16 t;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) t[r] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], t, 0, 0, 0);
+  }
+  if (last) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = crow(r, h) < last_keys ? t[r] : -3.0e38f;
+  }
+  return t;
+}
+// second sweep: P = exp(S - max) (masked keys give exp(-huge) = 0), the row sum and O += P V of the block
+__device__ __forceinline__ void fwd_pv_block(f32x16 t, const char* vblk, const TrOfs& to, const float c2, const float mxc, float& sum,
+                                             f32x16 (&o)[2]) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    t[r] = __builtin_amdgcn_exp2f(t[r] * c2 - mxc);   // <= 0: raw v_exp_f32, no denormal fix-up code
+    sum += t[r];
+  }
+#pragma unroll
+  for (int st = 0; st < 2; ++st) {
+    const bf16x8 pa = pack8(t, st);
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      const bf16x8 vf = tr_frag_at(vblk, to.lo[st][dt], to.hi[st][dt]);
+      o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, vf, o[dt], 0, 0, 0);
+    }
+  }
+}
+// Normalise and store the wave's 32 output rows and their log-sum-exp.  O layout: column (lane & 31) = d, row = query
+// q0 + crow(r, h); `sum` is the row sum of the lane's query q0 + (lane & 31), so 1/sum of a row sits in lane crow(r, h).
+// ob: the head's columns of the output (row stride H * 64); bh = b * H + head indexes the LSE rows.
+__device__ __forceinline__ void fwd_store_rows(const f32x16 (&o)[2], const float mx, const float sum, bf16* ob, float* lse, const int bh,
+                                               const int q0, const int N, const int H, const float scale, const int ql, const int h) {
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int qq = crow(r, h);
+    const float iv = __shfl(inv, qq, 64);
+    if (q0 + qq < N) {
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) ob[(size_t)(q0 + qq) * (H * HD) + dt * 32 + ql] = (bf16)(o[dt][r] * iv);
+    }
+  }
+  if (h == 0 && q0 + ql < N) lse[(size_t)bh * N + q0 + ql] = mx * scale + __logf(sum);
+}
+
+// ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
 // LDS: K and V, both as swizzled row-major images of npad rows
 
-template <int NW>  // waves per workgroup: 7 covers N <= 224 with ONE staging of K/V per head
-__global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
-                                                              float* __restrict__ lse, int N, int H, float scale, int npad) {
+// N <= 128: four waves, one workgroup per head, the score rows of a wave in registers (the tile loops are unrolled to the seven
+// tiles the registers hold; tiles beyond nkt are skipped at run time)
+constexpr int FWD_WAVES = 4;
+__global__ __launch_bounds__(FWD_WAVES * 64, 2) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+                                                                     float* __restrict__ lse, int N, int H, float scale, int npad) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
   char* Vs = smem + npad * 128;
@@ -157,11 +222,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16* __rest
   const bf16* kb = qb + H * HD;
   const bf16* vb = qb + 2 * H * HD;
 
-  stage_rows_swz(kb, ld, N, Ks, tid, NW * 64, npad);
-  stage_rows_swz(vb, ld, N, Vs, tid, NW * 64, npad);
+  stage_rows_swz(kb, ld, N, Ks, tid, FWD_WAVES * 64, npad);
+  stage_rows_swz(vb, ld, N, Vs, tid, FWD_WAVES * 64, npad);
   __syncthreads();
 
-  const int q0 = (blockIdx.y * NW + wave) * 32;
+  const int q0 = (blockIdx.y * FWD_WAVES + wave) * 32;
   if (q0 >= N) return;
   const int ql = lane & 31, h = lane >> 5;
   const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
@@ -245,9 +310,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16* __rest
 // registers, so the key tiles are swept twice -- pass 1 recomputes S^T tile by tile for the row maxima and
 // the sums of exp, pass 2 recomputes it again and feeds P straight into P.V.  Still the exact softmax of
 // the short kernel (no running rescale); QK^T is 1/3 of the work, so the second sweep costs about a third.
-template <int NW>
-__global__ __launch_bounds__(NW * 64, 2) void attn_fwd_long_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
-                                                                   float* __restrict__ lse, int N, int H, float scale, int npad) {
+constexpr int LONG_WAVES = 7;
+__global__ __launch_bounds__(LONG_WAVES * 64, 2) void attn_fwd_long_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+                                                                           float* __restrict__ lse, int N, int H, float scale, int npad) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
   char* Vs = smem + npad * 128;
@@ -257,8 +322,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_long_kernel(const bf16* _
   const bf16* qb = qkv + (size_t)b * N * ld + head * HD;
   const bf16* kb = qb + H * HD;
   const bf16* vb = qb + 2 * H * HD;
-  stage_rows_swz(kb, ld, N, Ks, tid, NW * 64, npad);
-  stage_rows_swz(vb, ld, N, Vs, tid, NW * 64, npad);
+  stage_rows_swz(kb, ld, N, Ks, tid, LONG_WAVES * 64, npad);
+  stage_rows_swz(vb, ld, N, Vs, tid, LONG_WAVES * 64, npad);
   __syncthreads();
 
   const int ql = lane & 31, h = lane >> 5;
@@ -267,80 +332,40 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_long_kernel(const bf16* _
   const RowOfs ro = row_ofs(lane);
   const TrOfs to = tr_ofs(lane);
   const int last_keys = N - (nkt - 1) * 32;   // valid keys of the last tile (only that tile needs a mask)
-  // r05: the workgroup walks the query groups of its head (group = NW x 32 queries; gridDim.y = 1 since r05) instead of one group
+  // r05: the workgroup walks the query groups of its head (group = 7 x 32 queries; gridDim.y = 1 since r05) instead of one group
   // per workgroup: K / V are staged ONCE per head -- at 577 tokens three workgroups per head each staged all 148 KB, six rounds of
   // workgroups on the chip, 56 % of the wave-cycles waiting (profiles/r05_pmc_attn.txt).  No barrier inside the loop.
   for (int qg = blockIdx.y;; qg += gridDim.y) {
-  const int q0 = (qg * NW + wave) * 32;
-  if (q0 >= N) break;
-  const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
-  bf16x8 qf[4];
+    const int q0 = (qg * LONG_WAVES + wave) * 32;
+    if (q0 >= N) break;
+    const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
+    bf16x8 qf[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qb + (size_t)qrow * ld + ks * 16 + h * 8);
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qb + (size_t)qrow * ld + ks * 16 + h * 8);
 
-  auto score_tile = [&](int kt) {
-    f32x16 t;
+    // (a local name for the shared step, not a second body.  It is a lambda on purpose: with fwd_score_block called directly from
+    // the two loops hipcc forms the twelve LDS addresses of a tile pair inside the pass-2 loop instead of once in front of it --
+    // 80 vector instructions per two tiles against 68, 115 against 106 us at 577 tokens, docs/findings/attention_refactor.md)
+    auto score_tile = [&](int kt) { return fwd_score_block(Ks + kt * 4096, qf, ro, kt == nkt - 1, last_keys, h); };
+    // pass 1: row maximum
+    float mx = -3.0e38f;
+    for (int kt = 0; kt < nkt; ++kt) {
+      const f32x16 t = score_tile(kt);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.f;
-    const char* kb_ = Ks + kt * 4096;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 a = *reinterpret_cast<const bf16x8*>(kb_ + ro.o[ks]);
-      t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], t, 0, 0, 0);
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, t[r]);
     }
-    if (kt == nkt - 1) {   // S^T: row = key, column = query
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mxc = mx * c2;
+    float sum = 0.f;
+    f32x16 o[2];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) t[r] = crow(r, h) < last_keys ? t[r] : -3.0e38f;
-    }
-    return t;
-  };
-  // pass 1: row maximum, then (with the maximum known) the sum of exponentials, in the key order of pass 2
-  float mx = -3.0e38f;
-  for (int kt = 0; kt < nkt; ++kt) {
-    const f32x16 t = score_tile(kt);
+    for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, t[r]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float mxc = mx * c2;
-  float sum = 0.f;
-  f32x16 o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-  // pass 2: P = exp(S - max) (masked keys give exp(-huge) = 0), sum and P.V together
-  for (int kt = 0; kt < nkt; ++kt) {
-    f32x16 t = score_tile(kt);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      t[r] = __builtin_amdgcn_exp2f(t[r] * c2 - mxc);   // <= 0: raw v_exp_f32, no denormal fix-up code
-      sum += t[r];
-    }
-    const char* vb_ = Vs + kt * 4096;
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      const bf16x8 pa = pack8(t, st);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const bf16x8 vf = tr_frag_at(vb_, to.lo[st][dt], to.hi[st][dt]);
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, vf, o[dt], 0, 0, 0);
-      }
-    }
-  }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-  bf16* ob = out + (size_t)b * N * (H * HD) + head * HD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int qq = crow(r, h);
-    const float iv = __shfl(inv, qq, 64);
-    if (q0 + qq < N) {
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) ob[(size_t)(q0 + qq) * (H * HD) + dt * 32 + ql] = (bf16)(o[dt][r] * iv);
-    }
-  }
-  if (h == 0 && q0 + ql < N) lse[(size_t)bh * N + q0 + ql] = mx * scale + __logf(sum);
+      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    // pass 2: exp, sum and P.V together
+    for (int kt = 0; kt < nkt; ++kt) fwd_pv_block(score_tile(kt), Vs + kt * 4096, to, c2, mxc, sum, o);
+    sum += __shfl_xor(sum, 32, 64);
+    fwd_store_rows(o, mx, sum, out + (size_t)b * N * (H * HD) + head * HD, lse, bh, q0, N, H, scale, ql, h);
   }
 }
 
@@ -382,232 +407,12 @@ extern "C" int cara_debug_attn_stamps(void* buf) {
 #else
 #define ATTN_STAMP(i)
 #endif
-__global__ __launch_bounds__(PF_WAVES * 64, 1) void attn_fwd_persist_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
-                                                                            float* __restrict__ lse, int N, int H, int BH, float scale) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NPAD = 224, IMG = NPAD * 128;       // one K or V image
-  char* Qs = smem + 4 * IMG;                         // wave-private Q images behind the two (K, V) pairs
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ld = 3 * H * HD;
-  const int ql = lane & 31, h = lane >> 5;
-  const int q0 = wave * 32;
-  const int nkt = (N + 31) >> 5;
-  const float c2 = scale * 1.4426950408889634f;
-  const RowOfs ro = row_ofs(lane);
-  const TrOfs to = tr_ofs(lane);
-  const int last_keys = N - (nkt - 1) * 32;
-  char* myQ = Qs + wave * 4096;
-
-  // per-lane 32-bit byte offsets of the DMA pieces (head-independent; the head's base pointer is wave-uniform, so a
-  // piece is "SGPR base + VGPR offset" with no 64-bit vector arithmetic).  K and V of one head: 2 x 28 pieces of 8 rows,
-  // wave w takes pieces w, w + 7, ... (8 per wave); Q: the wave's own 32 rows = 4 pieces.
-  unsigned kvoff[8], kvdst[8], qoff[4];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int q = wave + t * PF_WAVES;              // 0..55: < 28 -> K, else V
-    const bool isv = q >= 28;
-    const int piece = isv ? q - 28 : q;
-    const int row = piece * 8 + (lane >> 3);
-    const int rr = row < N ? row : N - 1;
-    const int c = (lane & 7) ^ swzk(row);
-    kvoff[t] = (unsigned)rr * (unsigned)(ld * 2) + (unsigned)(c * 16) + (unsigned)((isv ? 2 : 1) * H * HD * 2);
-    kvdst[t] = (unsigned)((isv ? IMG : 0) + piece * 1024);   // wave-uniform
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int row = t * 8 + (lane >> 3);
-    int gr = q0 + row;
-    gr = gr < N ? gr : N - 1;
-    const int c = (lane & 7) ^ swzk(row);
-    qoff[t] = (unsigned)gr * (unsigned)(ld * 2) + (unsigned)(c * 16);
-  }
-  auto lds_of = [](const char* p) { return __builtin_amdgcn_readfirstlane((unsigned)(size_t)p); };   // LDS byte address
-  auto head_base = [&](int bh) {
-    const int b = bh / H, hd = bh - b * H;
-    return reinterpret_cast<const char*>(qkv + (size_t)b * N * ld + hd * HD);   // wave-uniform
-  };
-  auto stage_kv = [&](int bh, int buf) {
-    const char* base = head_base(bh);
-    char* img = smem + buf * 2 * IMG;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) glds16_hidden(base, kvoff[t], lds_of(img) + __builtin_amdgcn_readfirstlane(kvdst[t]));
-  };
-  auto stage_q = [&](int bh) {
-    const char* base = head_base(bh);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) glds16_hidden(base, qoff[t], lds_of(myQ) + t * 1024);
-  };
-
-  int bh = blockIdx.x;
-  if (bh >= BH) return;
-  stage_kv(bh, 0);
-  stage_q(bh);
-  int cur = 0;
-#ifdef CARA_ATTN_STAMPS
-  int slot = -1;
-#endif
-  for (; bh < BH; bh += gridDim.x) {
-    const int nxt = bh + gridDim.x;
-#ifdef CARA_ATTN_STAMPS
-    ++slot;
-#endif
-    ATTN_STAMP(0);
-    // ONE barrier per head: behind it every wave's pieces of this head's K, V and Q have landed (they were issued during the
-    // previous head -- everything this wave has outstanding, its output stores included, is old by now) AND every wave is
-    // through with the previous head, whose K / V images the next head's pieces may therefore overwrite.  Those pieces are
-    // handed out over the key tiles of the S^T loop below: issued between two barriers, as they used to be, the 56 pieces
-    // of a head held all seven waves for 1.6 us while the CU's load path accepted them (time stamps, tools/attn_stamps.py).
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    ATTN_STAMP(1);
-    const char* Ks = smem + cur * 2 * IMG;
-    const char* Vs = Ks + IMG;
-    const int b = bh / H, head = bh - b * H;
-
-    bf16x8 qf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(myQ + ro.o[ks]);
-    // S^T = K Q^T, the K fragments of tile kt + 1 requested before the MFMAs of tile kt (one wave or two per SIMD: nothing
-    // else hides the LDS latency)
-    f32x16 s[7];
-    bf16x8 ka[2][4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) ka[0][ks] = *reinterpret_cast<const bf16x8*>(Ks + ro.o[ks]);
-    const char* nbase = head_base(nxt < BH ? nxt : bh);
-    const unsigned nimg = lds_of(smem + (cur ^ 1) * 2 * IMG);
-#pragma unroll
-    for (int kt = 0; kt < 7; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-      if (nxt < BH && (kt & 1) == 0)   // the next head's K / V: pieces 0-3 behind the even tiles here, 4-7 in the P V loop
-        glds16_hidden(nbase, kvoff[kt >> 1], nimg + __builtin_amdgcn_readfirstlane(kvdst[kt >> 1]));
-      if (kt < nkt) {
-        if (kt + 1 < nkt) {
-          const char* kb_ = Ks + (kt + 1) * 4096;
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) ka[(kt + 1) & 1][ks] = *reinterpret_cast<const bf16x8*>(kb_ + ro.o[ks]);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[kt & 1][ks], qf[ks], s[kt], 0, 0, 0);
-      }
-    }
-    ATTN_STAMP(2);
-    // the Q fragments are in registers: the wave's Q image may take the next head's rows
-    if (nxt < BH) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      stage_q(nxt);
-    }
-    // S^T layout: column (lane & 31) = query, row = key kt*32 + crow(r, h); only the last key tile needs a mask
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int kt = 0; kt < 7; ++kt) {
-      if (kt < nkt) {
-        if (kt == nkt - 1) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s[kt][r] = crow(r, h) < last_keys ? s[kt][r] : -3.0e38f;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    ATTN_STAMP(3);
-    const float mxc = mx * c2;
-    float sum = 0.f;
-    f32x16 o[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 7; ++kt) {
-      if (kt < nkt) {
-        // the four V fragments of this key tile are requested first: the exponentials below cover their latency
-        const char* vb_ = Vs + kt * 4096;
-        if (nxt < BH && (kt & 1) == 0)
-          glds16_hidden(nbase, kvoff[4 + (kt >> 1)], nimg + __builtin_amdgcn_readfirstlane(kvdst[4 + (kt >> 1)]));
-        bf16x8 vf[2][2];
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) vf[st][dt] = tr_frag_at(vb_, to.lo[st][dt], to.hi[st][dt]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[kt][r] = __builtin_amdgcn_exp2f(s[kt][r] * c2 - mxc);   // <= 0: raw v_exp_f32 (masked keys: exp(-huge) = 0)
-          sum += s[kt][r];
-        }
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-          const bf16x8 pa = pack8(s[kt], st);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt)
-            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[st][dt], pa, o[dt], 0, 0, 0);   // O^T = V^T P^T: d on the rows
-        }
-      }
-    }
-    if (nxt < BH) {
-#pragma unroll
-      for (int kt = 0; kt < 7; kt += 2)   // (the pieces of tiles this N does not have)
-        if (kt >= nkt) glds16_hidden(nbase, kvoff[4 + (kt >> 1)], nimg + __builtin_amdgcn_readfirstlane(kvdst[4 + (kt >> 1)]));
-    }
-    sum += __shfl_xor(sum, 32, 64);
-    ATTN_STAMP(4);
-    const float inv = 1.0f / sum;
-    // O^T layout: column (lane & 31) = QUERY, register r of lane half h = d = 32 dt + 8 (r >> 2) + 4 h + (r & 3): a lane
-    // holds its query's row in runs of four d, and 1 / sum of that query is the lane's own.  Lane halves swap runs
-    // (v_permlane32_swap) so that each lane ends up with two runs of EIGHT consecutive d per dt: four 16-byte stores per
-    // lane and head instead of 32 two-byte ones (the store tail was 21 % of the kernel).
-    bf16* ob = out + (size_t)b * N * (H * HD) + head * HD;
-#ifdef CARA_ABLATE_ATTN_STORES
-    if (q0 < N && inv == 123.f) {
-#else
-    if (q0 < N) {
-#endif
-      bf16* orow = ob + (size_t)(q0 + ql < N ? q0 + ql : N - 1) * (H * HD);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        unsigned w[4][2];   // run g = r >> 2 of this lane: d = 32 dt + 8 g + 4 h .. + 3, as two packed dwords
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const bf16x2 lo = {(bf16)(o[dt][4 * g] * inv), (bf16)(o[dt][4 * g + 1] * inv)};
-          const bf16x2 hi = {(bf16)(o[dt][4 * g + 2] * inv), (bf16)(o[dt][4 * g + 3] * inv)};
-          w[g][0] = __builtin_bit_cast(unsigned, lo);
-          w[g][1] = __builtin_bit_cast(unsigned, hi);
-        }
-        // after the swaps: half 0 holds d-groups 0 and 1 complete (its own first halves + half 1's second halves),
-        // half 1 holds d-groups 2 and 3
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(w[g][k], w[g + 2][k], false, false);
-            w[g][k] = sw[0];
-            w[g + 2][k] = sw[1];
-          }
-        if (q0 + ql < N) {
-#pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            // half 0: w[g] = own run (d 8g..8g+3), w[g+2] = half 1's run (d 8g+4..8g+7); half 1: w[g] = half 0's run of
-            // group g+2 (d 8(g+2)..+3), w[g+2] = own (d 8(g+2)+4..+7)
-            const uint4 v = {w[g][0], w[g][1], w[g + 2][0], w[g + 2][1]};
-            *reinterpret_cast<uint4*>(orow + dt * 32 + 8 * (g + 2 * h)) = v;
-          }
-        }
-      }
-      if (h == 0 && q0 + ql < N) lse[(size_t)bh * N + q0 + ql] = mx * scale + __logf(sum);
-    }
-    ATTN_STAMP(5);
-    cur ^= 1;
-  }
-}
-
 // ------------------------------------------------------------------------------------------
-// Round 5: the persistent forward, SPECIALISED on the number of key tiles and written as an explicit schedule.
-// The kernel above serves any 128 < N <= 224 with one body: every tile is conditional (`kt < nkt`), so the compiler keeps the
-// accumulators' zero fill (112 v_mov per head and wave), selects every score against "is this the last tile" (112 v_cndmask), and
-// emits the three phases -- 28 MFMAs, then 112 maxima, then exponentials + 28 MFMAs -- one after the other: 779 vector
-// instructions per head and wave where ~470 are needed, the matrix pipe busy 13 % of the time (profiles/r04_pmc_attn.txt).
+// The kernel: SPECIALISED on the number of key tiles and written as an explicit schedule.  One body for any tile count makes
+// every tile conditional (`kt < nkt`): the compiler then keeps the accumulators' zero fill (112 v_mov per head and wave), selects
+// every score against "is this the last tile" (112 v_cndmask), and emits the three phases -- 28 MFMAs, then 112 maxima, then
+// exponentials + 28 MFMAs -- one after the other: 779 vector instructions per head and wave where ~470 are needed, the matrix
+// pipe busy 13 % of the time (profiles/r04_pmc_attn.txt; that round-3 body is in the history before this file lost it).
 // Here  * NKT is a template parameter: no per-tile conditions, the first MFMA of a chain takes a literal zero accumulator;
 //       * the padded keys of the last tile are masked through that tile's accumulator SEED (-1e30 in their rows: they are
 //         duplicates of key N - 1, finite, so their exponential is exactly 0): no select anywhere;
@@ -615,9 +420,8 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void attn_fwd_persist_kernel(cons
 //         kt + 1 are issued between the MFMAs of tile kt (an in-order wave that issues four MFMAs back to back waits 3 x 24
 //         cycles for the pipe; two such waves per SIMD wait for each other too).  Every "MFMA | vector chunk" boundary is a
 //         scheduling barrier: the order below is the order in the binary;
-//       * K fragments are requested two tiles ahead.
-// Same operand layouts, rounding points and LDS images as attn_fwd_persist_kernel (its results are bitwise equal where the
-// summation order of the row sum allows: four partial sums here).
+//       * K fragments are requested two tiles ahead;
+//       * the row sum is kept in four partial sums.
 // ------------------------------------------------------------------------------------------
 #define SB() __builtin_amdgcn_sched_barrier(0)
 
@@ -723,9 +527,6 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void attn_fwd_p2_kernel(const bf1
 #ifdef CARA_ATTN_STAMPS
   int slot = -1;
 #endif
-#ifdef CARA_ATTN_PRIO   // (A/B build: static priority for the second-dispatched waves)
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   for (; bh < BH; bh += gridDim.x) {
     const int nxt = bh + gridDim.x;
     const bool has_nxt = nxt < BH;
@@ -733,7 +534,11 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void attn_fwd_p2_kernel(const bf1
     ++slot;
 #endif
     ATTN_STAMP(0);
-    // ONE barrier per head (see attn_fwd_persist_kernel): this head's K, V, Q have landed, the previous head is done with
+    // ONE barrier per head: behind it every wave's pieces of this head's K, V and Q have landed (they were issued during the
+    // previous head -- everything this wave has outstanding, its output stores included, is old by now) AND every wave is
+    // through with the previous head, whose K / V images the next head's pieces may therefore overwrite.  Those pieces are
+    // handed out over the key tiles of the loops below: issued between two barriers, the 56 pieces of a head held all seven
+    // waves for 1.6 us while the CU's load path accepted them (time stamps, tools/attn_stamps.py).
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     SB();
     ATTN_STAMP(1);
@@ -888,13 +693,170 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void attn_fwd_p2_kernel(const bf1
 }
 
 // ------------------------------------------------------------------------------------------
+// Block steps of the two-kernel backward, written once for the resident pair (attn_bwd_dkv_kernel, attn_bwd_dq_kernel: the other
+// operand of the head whole in LDS) and the streamed pair (attn_bwd_dkv_stream_kernel, attn_bwd_dq_stream_kernel: 64-row tiles).
+// Both recompute P from Q, K and the forward's LSE.
+// ------------------------------------------------------------------------------------------
+// dK/dV, one block of 32 queries against the wave's 32 keys (key on the lane, kf / vf = the lane's K / V row): S = Q K^T and
+// dP = dO V^T from the row-major Q / dO blocks, then dV^T += dO^T P and dK^T += Q^T dS with P / dS straight from the accumulators.
+// Layout: column (lane & 31) = key, row = query crow(r, h) of the block.  lse_blk (log2 units) / del_blk: the block's 32 row
+// constants in LDS.  Rows q >= N carry clamped duplicates of row N - 1: their P is forced to zero (`last`: the block holds the
+// head's last queries, `last_q` of them real); an invalid key zeroes the whole lane.
+__device__ __forceinline__ void dkv_block(const char* qblk, const char* dblk, const float* lse_blk, const float* del_blk,
+                                          const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], const RowOfs& ro, const TrOfs& to, const float c2,
+                                          const bool last, const int last_q, const bool kvalid, const int h, f32x16 (&dkt)[2],
+                                          f32x16 (&dvt)[2]) {
+  f32x16 sacc, pacc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; pacc[r] = 0.f; }
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const bf16x8 qa = *reinterpret_cast<const bf16x8*>(qblk + ro.o[ks]);
+    const bf16x8 da = *reinterpret_cast<const bf16x8*>(dblk + ro.o[ks]);
+    sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
+    pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], pacc, 0, 0, 0);
+  }
+  f32x16 p, ds;
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {   // registers 4*g4 .. +3 hold queries 8*g4 + 4h .. +3 of the block: one 16-byte LDS read each
+    const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_blk + 8 * g4 + 4 * h);
+    const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_blk + 8 * g4 + 4 * h);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int r = 4 * g4 + k;
+      float e = __builtin_amdgcn_exp2f(sacc[r] * c2 - l4[k]);
+      if (last) e = crow(r, h) < last_q ? e : 0.f;
+      e = kvalid ? e : 0.f;
+      p[r] = e;
+      ds[r] = e * (pacc[r] - d4[k]);
+    }
+  }
+#pragma unroll
+  for (int st = 0; st < 2; ++st) {
+    const bf16x8 pb = pack8(p, st), dsb = pack8(ds, st);
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      const bf16x8 doa = tr_frag_at(dblk, to.lo[st][dt], to.hi[st][dt]);
+      const bf16x8 qta = tr_frag_at(qblk, to.lo[st][dt], to.hi[st][dt]);
+      dvt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa, pb, dvt[dt], 0, 0, 0);
+      dkt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qta, dsb, dkt[dt], 0, 0, 0);
+    }
+  }
+}
+// dK[key][d] = scale * dK^T[d][key], dV likewise unscaled; registers 4g..4g+3 hold d = dt*32 + 8g + 4h + (0..3).  dk: the lane's
+// key row of the dK columns of dqkv (dV sits hd = H * 64 elements further on).
+__device__ __forceinline__ void dkv_store(const f32x16 (&dkt)[2], const f32x16 (&dvt)[2], bf16* dk, const int hd, const float scale,
+                                          const int h) {
+  bf16* dv = dk + hd;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = dt * 32 + 8 * g + 4 * h;
+      bf16x4 a = {(bf16)(dkt[dt][4 * g] * scale), (bf16)(dkt[dt][4 * g + 1] * scale),
+                  (bf16)(dkt[dt][4 * g + 2] * scale), (bf16)(dkt[dt][4 * g + 3] * scale)};
+      bf16x4 c = {(bf16)dvt[dt][4 * g], (bf16)dvt[dt][4 * g + 1], (bf16)dvt[dt][4 * g + 2], (bf16)dvt[dt][4 * g + 3]};
+      *reinterpret_cast<bf16x4*>(dk + d) = a;
+      *reinterpret_cast<bf16x4*>(dv + d) = c;
+    }
+}
+
+// dQ: what a wave keeps of its 32 queries (query on the lane): the Q and dO rows as B fragments, delta[q] = sum_d dO[q,d] O[q,d]
+// and the LSE in log2 units
+struct DqRows {
+  bf16x8 qf[4], dof[4];
+  float dl, lq;
+};
+// qrow / orow / dorow: the lane's (clamped) query row of Q, O and dO; lse_q: its LSE
+__device__ __forceinline__ DqRows dq_rows(const bf16* qrow, const bf16* orow, const bf16* dorow, const float lse_q, const int h) {
+  DqRows w;
+  w.dl = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    w.qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + ks * 16 + h * 8);
+    w.dof[ks] = *reinterpret_cast<const bf16x8*>(dorow + ks * 16 + h * 8);
+    const bf16x8 of = *reinterpret_cast<const bf16x8*>(orow + ks * 16 + h * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w.dl += (float)of[j] * (float)w.dof[ks][j];
+  }
+  w.dl += __shfl_xor(w.dl, 32, 64);
+  w.lq = lse_q * 1.4426950408889634f;
+  return w;
+}
+// One block of 32 keys: S^T = K Q^T and dP^T = V dO^T (key on the accumulator row, query on the lane, so LSE and delta are
+// lane-local scalars), dS^T formed in registers and fed as the operand of dQ^T += K^T dS^T (K fragments by the transposing read
+// of the same block): no LDS round trip.  `last`: the block holds the head's last keys, `last_keys` of them real.
+__device__ __forceinline__ void dq_block(const char* kblk, const char* vblk, const DqRows& w, const RowOfs& ro, const TrOfs& to,
+                                         const float c2, const bool last, const int last_keys, const int h, f32x16 (&dq)[2]) {
+  f32x16 sT, dpT;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { sT[r] = 0.f; dpT[r] = 0.f; }
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const bf16x8 ka = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
+    const bf16x8 va = *reinterpret_cast<const bf16x8*>(vblk + ro.o[ks]);
+    sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, w.qf[ks], sT, 0, 0, 0);
+    dpT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, w.dof[ks], dpT, 0, 0, 0);
+  }
+  f32x16 ds;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float e = __builtin_amdgcn_exp2f(sT[r] * c2 - w.lq);
+    if (last) e = crow(r, h) < last_keys ? e : 0.f;
+    ds[r] = e * (dpT[r] - w.dl);
+  }
+#pragma unroll
+  for (int st = 0; st < 2; ++st) {
+    const bf16x8 a = pack8(ds, st);
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      const bf16x8 kf = tr_frag_at(kblk, to.lo[st][dt], to.hi[st][dt]);
+      dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, a, dq[dt], 0, 0, 0);   // dQ^T = K^T dS^T: d on the rows
+    }
+  }
+}
+// dQ^T layout: column (lane & 31) = QUERY, register r of lane half h = d = 32 dt + 8 (r >> 2) + 4 h + (r & 3): a lane holds its
+// query's row in runs of four d.  The lane halves swap runs (v_permlane32_swap) so that every lane ends up with two runs of EIGHT
+// consecutive d per dt: four 16-byte stores per lane instead of 32 two-byte ones.  All 64 lanes take part in the swaps; `valid`
+// lanes store.  qrow_out: the lane's query row of the dQ columns of dqkv.
+__device__ __forceinline__ void dq_store(const f32x16 (&dq)[2], bf16* qrow_out, const float scale, const bool valid, const int h) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    unsigned w[4][2];   // run g = r >> 2 of this lane: d = 32 dt + 8 g + 4 h .. + 3, as two packed dwords
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const bf16x2 lo = {(bf16)(dq[dt][4 * g] * scale), (bf16)(dq[dt][4 * g + 1] * scale)};
+      const bf16x2 hi = {(bf16)(dq[dt][4 * g + 2] * scale), (bf16)(dq[dt][4 * g + 3] * scale)};
+      w[g][0] = __builtin_bit_cast(unsigned, lo);
+      w[g][1] = __builtin_bit_cast(unsigned, hi);
+    }
+    // after the swaps: half 0 holds d-groups 0 and 1 complete (its own first halves + half 1's second halves), half 1 holds 2 and 3
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(w[g][k], w[g + 2][k], false, false);
+        w[g][k] = sw[0];
+        w[g + 2][k] = sw[1];
+      }
+    if (valid) {
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const uint4 v = {w[g][0], w[g][1], w[g + 2][0], w[g + 2][1]};
+        *reinterpret_cast<uint4*>(qrow_out + dt * 32 + 8 * (g + 2 * h)) = v;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // backward, kernel 1: dK, dV.  One workgroup of 7 waves per (batch, head); wave w owns keys
 // 32w..32w+31 and keeps dK^T, dV^T in accumulators while sweeping the query tiles.  Q and dO are
 // staged in LDS once, row-major: plain ds_read_b128 rows feed S = Q K^T and dP = dO V^T, and the
 // transposing read ds_read_b64_tr_b16 of the same images feeds dV^T += dO^T P and dK^T += Q^T dS
 // (whose B operands are the P / dS accumulators).
 // ------------------------------------------------------------------------------------------
-constexpr int BWD_WAVES = 7;   // keys per workgroup = 7 * 32; blockIdx.y walks the key groups when N > 224
+constexpr int BWD_WAVES = 7;   // keys per group = 7 * 32; the workgroup walks the key groups of its head when N > 224
 __host__ __device__ constexpr int dkv_lds_bytes(int npad) { return 2 * npad * 128 + 2 * npad * 4; }
 
 __global__ __launch_bounds__(448, 2) void attn_bwd_dkv_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
@@ -935,87 +897,31 @@ __global__ __launch_bounds__(448, 2) void attn_bwd_dkv_kernel(const bf16* __rest
   const float c2 = scale * 1.4426950408889634f;
   // r05: the workgroup walks the key groups of its head (gridDim.y = 1): Q / dO / delta are staged once per head, not once per group
   for (int kg = blockIdx.y;; kg += gridDim.y) {
-  const int key0 = (kg * BWD_WAVES + wave) * 32;
-  if (key0 >= N) break;
-  const int key = key0 + kl;
-  const int keyc = key < N ? key : N - 1;
-  const bool kvalid = key < N;
-  // B operands with the key on the lane: K[key][16ks + 8h + j], V likewise
-  bf16x8 kf[4], vf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    kf[ks] = *reinterpret_cast<const bf16x8*>(kb + (size_t)keyc * ld + ks * 16 + h * 8);
-    vf[ks] = *reinterpret_cast<const bf16x8*>(vb + (size_t)keyc * ld + ks * 16 + h * 8);
-  }
-  f32x16 dkt[2], dvt[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dkt[dt][r] = 0.f; dvt[dt][r] = 0.f; }
-
-  const int nqt = npad >> 5;
-  const RowOfs ro = row_ofs(lane);
-  const TrOfs to = tr_ofs(lane);
-  const int last_q = N - (nqt - 1) * 32;   // valid queries of the last tile (rows beyond are clamped duplicates)
-  for (int qt = 0; qt < nqt; ++qt) {
-    const int q0 = qt * 32;
-    const char* qblk = Qs + qt * 4096;
-    const char* dblk = dOs + qt * 4096;
-    f32x16 sacc, pacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; pacc[r] = 0.f; }
+    const int key0 = (kg * BWD_WAVES + wave) * 32;
+    if (key0 >= N) break;
+    const int key = key0 + kl;
+    const int keyc = key < N ? key : N - 1;
+    const bool kvalid = key < N;
+    // B operands with the key on the lane: K[key][16ks + 8h + j], V likewise
+    bf16x8 kf[4], vf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 qa = *reinterpret_cast<const bf16x8*>(qblk + ro.o[ks]);
-      const bf16x8 da = *reinterpret_cast<const bf16x8*>(dblk + ro.o[ks]);
-      sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
-      pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], pacc, 0, 0, 0);
+      kf[ks] = *reinterpret_cast<const bf16x8*>(kb + (size_t)keyc * ld + ks * 16 + h * 8);
+      vf[ks] = *reinterpret_cast<const bf16x8*>(vb + (size_t)keyc * ld + ks * 16 + h * 8);
     }
-    // layout: column (lane & 31) = key, row = query q0 + crow(r, h).  Rows q >= N carry clamped
-    // duplicates of row N-1: force their P to zero (last query tile only; an invalid key zeroes the whole lane).
-    f32x16 p, ds;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {   // registers 4*g4 .. +3 hold queries q0 + 8*g4 + 4h .. +3: one 16-byte LDS read each
-      const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + q0 + 8 * g4 + 4 * h);
-      const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_s + q0 + 8 * g4 + 4 * h);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int r = 4 * g4 + k;
-        float e = __builtin_amdgcn_exp2f(sacc[r] * c2 - l4[k]);
-        if (qt == nqt - 1) e = crow(r, h) < last_q ? e : 0.f;
-        e = kvalid ? e : 0.f;
-        p[r] = e;
-        ds[r] = e * (pacc[r] - d4[k]);
-      }
-    }
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      const bf16x8 pb = pack8(p, st), dsb = pack8(ds, st);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const bf16x8 doa = tr_frag_at(dblk, to.lo[st][dt], to.hi[st][dt]);
-        const bf16x8 qta = tr_frag_at(qblk, to.lo[st][dt], to.hi[st][dt]);
-        dvt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa, pb, dvt[dt], 0, 0, 0);
-        dkt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qta, dsb, dkt[dt], 0, 0, 0);
-      }
-    }
-  }
-  // dK[key][d] = scale * dK^T[d][key]; registers 4g..4g+3 hold d = dt*32 + 8g + 4h + (0..3)
-  if (kvalid) {
-    bf16* dk = dqkv + (size_t)(b * N + key) * ld + H * HD + head * HD;
-    bf16* dv = dk + H * HD;
+    f32x16 dkt[2], dvt[2];
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = dt * 32 + 8 * g + 4 * h;
-        bf16x4 a = {(bf16)(dkt[dt][4 * g] * scale), (bf16)(dkt[dt][4 * g + 1] * scale),
-                    (bf16)(dkt[dt][4 * g + 2] * scale), (bf16)(dkt[dt][4 * g + 3] * scale)};
-        bf16x4 c = {(bf16)dvt[dt][4 * g], (bf16)dvt[dt][4 * g + 1], (bf16)dvt[dt][4 * g + 2], (bf16)dvt[dt][4 * g + 3]};
-        *reinterpret_cast<bf16x4*>(dk + d) = a;
-        *reinterpret_cast<bf16x4*>(dv + d) = c;
-      }
-  }
+      for (int r = 0; r < 16; ++r) { dkt[dt][r] = 0.f; dvt[dt][r] = 0.f; }
+
+    const int nqt = npad >> 5;
+    const RowOfs ro = row_ofs(lane);
+    const TrOfs to = tr_ofs(lane);
+    const int last_q = N - (nqt - 1) * 32;   // valid queries of the last tile (rows beyond are clamped duplicates)
+    for (int qt = 0; qt < nqt; ++qt)
+      dkv_block(Qs + qt * 4096, dOs + qt * 4096, lse_s + qt * 32, del_s + qt * 32, kf, vf, ro, to, c2, qt == nqt - 1, last_q, kvalid, h, dkt, dvt);
+    if (kvalid) dkv_store(dkt, dvt, dqkv + (size_t)(b * N + key) * ld + H * HD + head * HD, H * HD, scale, h);
   }
 }
 
@@ -1049,93 +955,23 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const bf16* __r
   const int ql = lane & 31, h = lane >> 5;
   // r05: the workgroup walks the query groups of its head (gridDim.y = 1): K / V are staged once per head
   for (int qg = blockIdx.y;; qg += gridDim.y) {
-  const int q0 = (qg * NW + wave) * 32;
-  if (q0 >= N) break;
-  const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
-  bf16x8 qf[4], dof[4];
-  float dl = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    qf[ks] = *reinterpret_cast<const bf16x8*>(qb + (size_t)qrow * ld + ks * 16 + h * 8);
-    dof[ks] = *reinterpret_cast<const bf16x8*>(dob + (size_t)qrow * ldo + ks * 16 + h * 8);
-    const bf16x8 of = *reinterpret_cast<const bf16x8*>(ob + (size_t)qrow * ldo + ks * 16 + h * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dl += (float)of[j] * (float)dof[ks][j];
-  }
-  dl += __shfl_xor(dl, 32, 64);   // delta[q] = sum_d dO[q,d] O[q,d]
-  const float lq = lse[(size_t)bh * N + qrow] * 1.4426950408889634f;
-  const float c2 = scale * 1.4426950408889634f;
+    const int q0 = (qg * NW + wave) * 32;
+    if (q0 >= N) break;
+    const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
+    const DqRows w = dq_rows(qb + (size_t)qrow * ld, ob + (size_t)qrow * ldo, dob + (size_t)qrow * ldo, lse[(size_t)bh * N + qrow], h);
+    const float c2 = scale * 1.4426950408889634f;
 
-  f32x16 dq[2];
+    f32x16 dq[2];
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
-  const int nkt = npad >> 5;
-  const RowOfs ro = row_ofs(lane);
-  const TrOfs to = tr_ofs(lane);
-  const int last_keys = N - (nkt - 1) * 32;
-  for (int kt = 0; kt < nkt; ++kt) {
-    const char* kblk = Ks + kt * 4096;
-    const char* vblk = Vs + kt * 4096;
-    f32x16 sT, dpT;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { sT[r] = 0.f; dpT[r] = 0.f; }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 ka = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
-      const bf16x8 va = *reinterpret_cast<const bf16x8*>(vblk + ro.o[ks]);
-      sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[ks], sT, 0, 0, 0);
-      dpT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[ks], dpT, 0, 0, 0);
-    }
-    // layout: column (lane & 31) = query, row = key kt*32 + crow(r, h); only the last tile has keys >= N
-    f32x16 ds;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float e = __builtin_amdgcn_exp2f(sT[r] * c2 - lq);
-      if (kt == nkt - 1) e = crow(r, h) < last_keys ? e : 0.f;
-      ds[r] = e * (dpT[r] - dl);
-    }
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      const bf16x8 a = pack8(ds, st);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const bf16x8 kf = tr_frag_at(kblk, to.lo[st][dt], to.hi[st][dt]);
-        dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, a, dq[dt], 0, 0, 0);   // dQ^T = K^T dS^T: d on the rows
-      }
-    }
-  }
-  // dQ^T layout: column (lane & 31) = QUERY, register r of lane half h = d = 32 dt + 8 (r >> 2) + 4 h + (r & 3).  As in the
-  // forward: the lane halves swap runs of four d (v_permlane32_swap) and every lane stores two runs of eight consecutive
-  // d per dt -- four 16-byte stores per lane instead of 32 two-byte ones.
-  bf16* qrow_out = dqkv + (size_t)(b * N + qrow) * ld + head * HD;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt) {
-    unsigned w[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const bf16x2 lo = {(bf16)(dq[dt][4 * g] * scale), (bf16)(dq[dt][4 * g + 1] * scale)};
-      const bf16x2 hi = {(bf16)(dq[dt][4 * g + 2] * scale), (bf16)(dq[dt][4 * g + 3] * scale)};
-      w[g][0] = __builtin_bit_cast(unsigned, lo);
-      w[g][1] = __builtin_bit_cast(unsigned, hi);
-    }
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(w[g][k], w[g + 2][k], false, false);
-        w[g][k] = sw[0];
-        w[g + 2][k] = sw[1];
-      }
-    if (q0 + ql < N) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const uint4 v = {w[g][0], w[g][1], w[g + 2][0], w[g + 2][1]};
-        *reinterpret_cast<uint4*>(qrow_out + dt * 32 + 8 * (g + 2 * h)) = v;
-      }
-    }
-  }
+      for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+    const int nkt = npad >> 5;
+    const RowOfs ro = row_ofs(lane);
+    const TrOfs to = tr_ofs(lane);
+    const int last_keys = N - (nkt - 1) * 32;   // only the last tile has keys >= N
+    for (int kt = 0; kt < nkt; ++kt) dq_block(Ks + kt * 4096, Vs + kt * 4096, w, ro, to, c2, kt == nkt - 1, last_keys, h, dq);
+    dq_store(dq, dqkv + (size_t)(b * N + qrow) * ld + head * HD, scale, q0 + ql < N, h);
   }
 }
 
@@ -1148,8 +984,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const bf16* __r
 //   phase A reads Q, dO (images) + its keys' K, V rows (registers);   meanwhile K, V of THIS head land in their images
 //   phase B reads K, V (images) + its queries' Q, dO rows (registers); meanwhile Q, dO, O of the NEXT head land
 // delta = rowsum(dO . O) is formed from the O and dO images (2 threads per row) before phase A.  Every wait for a DMA
-// piece is a vmcnt(0) placed just before a phase's stores are issued, when everything outstanding is old; four
-// barriers per head.  LDS: five [224][64] images + lse + delta = 145 KiB.  The arithmetic of the two phases is that
+// piece is a vmcnt(0) placed just before a phase's stores are issued, when everything outstanding is old; two
+// barriers per head (T1, T3).  LDS: five [224][64] images + lse + delta = 145 KiB.  The arithmetic of the two phases is that
 // of attn_bwd_dkv_kernel / attn_bwd_dq_kernel<7> (same operand layouts and rounding points; delta is summed in another
 // order, so results agree to fp32 rounding of that one scalar per row, not bitwise).  Deterministic: no atomics.
 // ------------------------------------------------------------------------------------------
@@ -1158,7 +994,6 @@ __device__ __forceinline__ void glds4_hidden(const char* base, unsigned voff, un
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory", "m0");
 }
 
-template <bool TWO_BARRIERS>
 __global__ __launch_bounds__(448, 1) void attn_bwd_fused_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
                                                                 const bf16* __restrict__ dout, const float* __restrict__ lse,
                                                                 bf16* __restrict__ dqkv, int N, int H, int BH, float scale) {
@@ -1216,16 +1051,10 @@ __global__ __launch_bounds__(448, 1) void attn_bwd_fused_kernel(const bf16* __re
   }
   auto dma_lse = [&](int bh_) {
     const char* base = reinterpret_cast<const char*>(lse + (size_t)bh_ * N);
-    if constexpr (TWO_BARRIERS) {
-      // piece w by wave w (w < 4): the wave that scales entries 64 w .. 64 w + 63 in the delta step is the wave whose own wait covers them
+    // piece w by wave w (w < 4): the wave that scales entries 64 w .. 64 w + 63 in the delta step is the wave whose own wait covers them
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (wave == t && t * 64 < NPAD) glds4_hidden(base, off_lse[t], lds_of(reinterpret_cast<const char*>(lse_s)) + (unsigned)(t * 256));
-    } else if (wave == 0) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (t * 64 < NPAD) glds4_hidden(base, off_lse[t], lds_of(reinterpret_cast<const char*>(lse_s)) + (unsigned)(t * 256));
-    }
+    for (int t = 0; t < 4; ++t)
+      if (wave == t && t * 64 < NPAD) glds4_hidden(base, off_lse[t], lds_of(reinterpret_cast<const char*>(lse_s)) + (unsigned)(t * 256));
   };
   {
     const char* qb = qkv_base(bh);
@@ -1251,9 +1080,6 @@ __global__ __launch_bounds__(448, 1) void attn_bwd_fused_kernel(const bf16* __re
     g_attn_stamp_buf[((size_t)blockIdx.x * 4 + 3) * 8 + 1] = __builtin_amdgcn_s_memrealtime();
   }
 #endif
-#ifdef CARA_ATTN_PRIO   // (A/B build: static priority for the second-dispatched waves, cdna_hip_programming.md T5 static form)
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   for (; bh < BH; bh += gridDim.x) {
     const int nxt = bh + gridDim.x;
     const int b = bh / H, head = bh - b * H;
@@ -1263,16 +1089,15 @@ __global__ __launch_bounds__(448, 1) void attn_bwd_fused_kernel(const bf16* __re
     ATTN_STAMP(0);
     // T0: every wave is through with phase B of the previous head (K, V images free) and has seen its own pieces of this
     // head's Q, dO, O images land
-    // TWO_BARRIERS (r05): no barrier here.  Each wave forms delta for the rows of ITS OWN DMA pieces (pieces w, w + 7, w + 14, w + 21 of
+    // No barrier here (r05).  Each wave forms delta for the rows of ITS OWN DMA pieces (pieces w, w + 7, w + 14, w + 21 of
     // the O / dO images: 32 rows, two lanes per row) and scales the 64 entries of its own LSE piece: everything it reads has landed
     // behind its own wait at the end of the previous head's dQ sweep; nobody still reads lse_s / del_s of the previous head (their
     // last reads sit in front of its T3).  T1 below then publishes delta / lse AND stands for "every wave's pieces have landed, every
     // wave is through with the previous head".
-    if constexpr (TWO_BARRIERS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // delta[row] = sum_d dO[row][d] O[row][d] from the images, two threads per row (4 chunks of 8 each); lse in log2 units
     {
-      const int row = TWO_BARRIERS ? (wave + 7 * (lane >> 4)) * 8 + ((lane >> 1) & 7) : tid >> 1, half = tid & 1;
+      const int row = (wave + 7 * (lane >> 4)) * 8 + ((lane >> 1) & 7), half = tid & 1;
       float dl = 0.f;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -1359,12 +1184,11 @@ __global__ __launch_bounds__(448, 1) void attn_bwd_fused_kernel(const bf16* __re
     ATTN_STAMP(2);
     // T2: this wave's pieces of K, V have landed (they are old by now); then every wave's
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // TWO_BARRIERS: no barrier here either -- the staging below is this wave's own 4 KiB of the O image (read by everybody in the
+    // No barrier here either -- the staging below is this wave's own 4 KiB of the O image (read by everybody in the
     // delta step only, a barrier ago), the row reads behind it are of the Q / dO images; T3 then also stands for "every wave's K / V
     // pieces have landed" (each wave passed the wait above first).  A wave that is through with its sweep stores while the others
     // still sweep instead of waiting for them twice.
-    if constexpr (TWO_BARRIERS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     ATTN_STAMP(3);
     // dK, dV of this wave's 32 keys leave as WHOLE 128-byte rows: the accumulators hold them transposed (key on the lane, a
@@ -1764,7 +1588,8 @@ __global__ __launch_bounds__(256) void attn_cls_bwd_kernel(const bf16* __restric
 // order and the summation order of the resident kernel exactly (the two paths can be compared bit for bit at 577 tokens, which
 // is what the A/B behind CARA_ATTN_STREAM is for), and no rescale of the output accumulators -- 32 more vector instructions per
 // key block beside the MFMAs, where this code base measured every extra vector instruction (docs/findings/r05.md 7c-7d).
-// The backward kernels recompute P from the LSE as the resident ones do: same bodies per 32 x 32 block, same rounding points.
+// The backward kernels recompute P from the LSE as the resident ones do: the same block steps (dkv_block, dq_block), called on a tile's
+// two 32-row blocks instead of on an image's.
 // No atomics, every output element written by exactly one lane; a wave whose 32 rows lie beyond N still stages and keeps the
 // barriers, and stores nothing.  Ragged tails: rows >= N of a tile are copies of row N - 1 (finite) and masked as above.
 // N is bounded by the index arithmetic alone: N <= 2^20 (grid.y = N / 128 <= 65 535 with room) and B N < 2^31 (row indices are int).
@@ -1814,22 +1639,6 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_fwd_stream_kernel(const
   const TrOfs to = tr_ofs(lane);
   const int last_keys = N - (nkt - 1) * 32;   // valid keys of the last 32-key block (only that block needs a mask)
 
-  auto score_block = [&](const char* kblk, int kt) {
-    f32x16 t;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 a = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
-      t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], t, 0, 0, 0);
-    }
-    if (kt == nkt - 1) {   // S^T: row = key, column = query
-#pragma unroll
-      for (int r = 0; r < 16; ++r) t[r] = crow(r, h) < last_keys ? t[r] : -3.0e38f;
-    }
-    return t;
-  };
-
   float mx = -3.0e38f, mxc = 0.f, sum = 0.f;
   f32x16 o[2];
 #pragma unroll
@@ -1858,27 +1667,12 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_fwd_stream_kernel(const
       for (int j = 0; j < 2; ++j) {
         const int kt = 2 * t + j;
         if (kt < nkt) {
-          f32x16 tl = score_block(Ks + j * 4096, kt);
+          const f32x16 tl = fwd_score_block(Ks + j * 4096, qf, ro, kt == nkt - 1, last_keys, h);
           if (!sweep2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) mx = fmaxf(mx, tl[r]);
           } else {
-            // P = exp(S - max) (masked keys give exp(-huge) = 0), sum and P.V together
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              tl[r] = __builtin_amdgcn_exp2f(tl[r] * c2 - mxc);   // <= 0: raw v_exp_f32, no denormal fix-up code
-              sum += tl[r];
-            }
-            const char* vb_ = Vs + j * 4096;
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-              const bf16x8 pa = pack8(tl, st);
-#pragma unroll
-              for (int dt = 0; dt < 2; ++dt) {
-                const bf16x8 vf = tr_frag_at(vb_, to.lo[st][dt], to.hi[st][dt]);
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, vf, o[dt], 0, 0, 0);
-              }
-            }
+            fwd_pv_block(tl, Vs + j * 4096, to, c2, mxc, sum, o);
           }
         }
       }
@@ -1896,18 +1690,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_fwd_stream_kernel(const
   }
   if (!active) return;
   sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-  bf16* ob = out + (size_t)b * N * (H * HD) + head * HD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int qq = crow(r, h);
-    const float iv = __shfl(inv, qq, 64);
-    if (q0 + qq < N) {
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) ob[(size_t)(q0 + qq) * (H * HD) + dt * 32 + ql] = (bf16)(o[dt][r] * iv);
-    }
-  }
-  if (h == 0 && q0 + ql < N) lse[(size_t)bh * N + q0 + ql] = mx * scale + __logf(sum);
+  fwd_store_rows(o, mx, sum, out + (size_t)b * N * (H * HD) + head * HD, lse, bh, q0, N, H, scale, ql, h);
 }
 
 // dK, dV of 128 keys per workgroup (wave = 32 keys, key on the lane, dK^T / dV^T in accumulators as in attn_bwd_dkv_kernel);
@@ -1996,72 +1779,18 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dkv_stream_kernel(c
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int qt = 2 * t + j;
-        if (qt < nqt) {
-          const char* qblk = Qs + j * 4096;
-          const char* dblk = dOs + j * 4096;
-          f32x16 sacc, pacc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; pacc[r] = 0.f; }
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const bf16x8 qa = *reinterpret_cast<const bf16x8*>(qblk + ro.o[ks]);
-            const bf16x8 da = *reinterpret_cast<const bf16x8*>(dblk + ro.o[ks]);
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], sacc, 0, 0, 0);
-            pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], pacc, 0, 0, 0);
-          }
-          // layout: column (lane & 31) = key, row = query 32 qt + crow(r, h).  Rows q >= N carry clamped duplicates of row
-          // N - 1: force their P to zero (last block only; an invalid key zeroes the whole lane).
-          f32x16 p, ds;
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {   // registers 4 g4 .. + 3 hold queries 8 g4 + 4 h .. + 3 of the block: one 16-byte LDS read each
-            const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + j * 32 + 8 * g4 + 4 * h);
-            const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_s + j * 32 + 8 * g4 + 4 * h);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const int r = 4 * g4 + k;
-              float e = __builtin_amdgcn_exp2f(sacc[r] * c2 - l4[k]);
-              if (qt == nqt - 1) e = crow(r, h) < last_q ? e : 0.f;
-              e = kvalid ? e : 0.f;
-              p[r] = e;
-              ds[r] = e * (pacc[r] - d4[k]);
-            }
-          }
-#pragma unroll
-          for (int st = 0; st < 2; ++st) {
-            const bf16x8 pb = pack8(p, st), dsb = pack8(ds, st);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-              const bf16x8 doa = tr_frag_at(dblk, to.lo[st][dt], to.hi[st][dt]);
-              const bf16x8 qta = tr_frag_at(qblk, to.lo[st][dt], to.hi[st][dt]);
-              dvt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa, pb, dvt[dt], 0, 0, 0);
-              dkt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qta, dsb, dkt[dt], 0, 0, 0);
-            }
-          }
-        }
+        if (qt < nqt)
+          dkv_block(Qs + j * 4096, dOs + j * 4096, lse_s + j * 32, del_s + j * 32, kf, vf, ro, to, c2, qt == nqt - 1, last_q, kvalid, h,
+                    dkt, dvt);
       }
     }
     if (more) put((t + 1) & 1);
     __syncthreads();   // the next tile is complete; everybody is through with this one
   }
-  // dK[key][d] = scale * dK^T[d][key]; registers 4g..4g+3 hold d = dt*32 + 8g + 4h + (0..3)
-  if (active && kvalid) {
-    bf16* dk = dqkv + (size_t)(b * N + key) * ld + H * HD + head * HD;
-    bf16* dv = dk + H * HD;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = dt * 32 + 8 * g + 4 * h;
-        bf16x4 a = {(bf16)(dkt[dt][4 * g] * scale), (bf16)(dkt[dt][4 * g + 1] * scale),
-                    (bf16)(dkt[dt][4 * g + 2] * scale), (bf16)(dkt[dt][4 * g + 3] * scale)};
-        bf16x4 c = {(bf16)dvt[dt][4 * g], (bf16)dvt[dt][4 * g + 1], (bf16)dvt[dt][4 * g + 2], (bf16)dvt[dt][4 * g + 3]};
-        *reinterpret_cast<bf16x4*>(dk + d) = a;
-        *reinterpret_cast<bf16x4*>(dv + d) = c;
-      }
-  }
+  if (active && kvalid) dkv_store(dkt, dvt, dqkv + (size_t)(b * N + key) * ld + H * HD + head * HD, H * HD, scale, h);
 }
 
-// dQ of 128 queries per workgroup: the streamed forward's shape with the body of attn_bwd_dq_kernel (one sweep, K and V tiles).
+// dQ of 128 queries per workgroup: the streamed forward's shape around the block step of attn_bwd_dq_kernel (one sweep, K and V tiles).
 __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dq_stream_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
                                                                               const bf16* __restrict__ dout, const float* __restrict__ lse,
                                                                               bf16* __restrict__ dqkv, int N, int H, float scale) {
@@ -2078,18 +1807,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dq_stream_kernel(co
   const int q0 = (blockIdx.y * ST_WAVES + wave) * 32;
   const bool active = q0 < N;   // (wave-uniform)
   const int qrow = (q0 + ql) < N ? (q0 + ql) : N - 1;
-  bf16x8 qf[4], dof[4];
-  float dl = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    qf[ks] = *reinterpret_cast<const bf16x8*>(qb + (size_t)qrow * ld + ks * 16 + h * 8);
-    dof[ks] = *reinterpret_cast<const bf16x8*>(dob + (size_t)qrow * ldo + ks * 16 + h * 8);
-    const bf16x8 of = *reinterpret_cast<const bf16x8*>(ob + (size_t)qrow * ldo + ks * 16 + h * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dl += (float)of[j] * (float)dof[ks][j];
-  }
-  dl += __shfl_xor(dl, 32, 64);   // delta[q] = sum_d dO[q,d] O[q,d]
-  const float lq = lse[(size_t)bh * N + qrow] * 1.4426950408889634f;
+  const DqRows w = dq_rows(qb + (size_t)qrow * ld, ob + (size_t)qrow * ldo, dob + (size_t)qrow * ldo, lse[(size_t)bh * N + qrow], h);
   const float c2 = scale * 1.4426950408889634f;
   f32x16 dq[2];
 #pragma unroll
@@ -2117,37 +1835,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dq_stream_kernel(co
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int kt = 2 * t + j;
-        if (kt < nkt) {
-          const char* kblk = Ks + j * 4096;
-          const char* vblk = Vs + j * 4096;
-          f32x16 sT, dpT;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { sT[r] = 0.f; dpT[r] = 0.f; }
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const bf16x8 ka = *reinterpret_cast<const bf16x8*>(kblk + ro.o[ks]);
-            const bf16x8 va = *reinterpret_cast<const bf16x8*>(vblk + ro.o[ks]);
-            sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[ks], sT, 0, 0, 0);
-            dpT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[ks], dpT, 0, 0, 0);
-          }
-          // layout: column (lane & 31) = query, row = key 32 kt + crow(r, h); only the last block has keys >= N
-          f32x16 ds;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float e = __builtin_amdgcn_exp2f(sT[r] * c2 - lq);
-            if (kt == nkt - 1) e = crow(r, h) < last_keys ? e : 0.f;
-            ds[r] = e * (dpT[r] - dl);
-          }
-#pragma unroll
-          for (int st = 0; st < 2; ++st) {
-            const bf16x8 a = pack8(ds, st);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-              const bf16x8 kf = tr_frag_at(kblk, to.lo[st][dt], to.hi[st][dt]);
-              dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, a, dq[dt], 0, 0, 0);   // dQ^T = K^T dS^T: d on the rows
-            }
-          }
-        }
+        if (kt < nkt) dq_block(Ks + j * 4096, Vs + j * 4096, w, ro, to, c2, kt == nkt - 1, last_keys, h, dq);
       }
     }
     if (more) {
@@ -2158,34 +1846,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void attn_bwd_dq_stream_kernel(co
     __syncthreads();   // the next tile is complete; everybody is through with this one
   }
   if (!active) return;
-  // dQ^T layout and the half-swapping 16-byte stores: as in attn_bwd_dq_kernel
-  bf16* qrow_out = dqkv + (size_t)(b * N + qrow) * ld + head * HD;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt) {
-    unsigned w[4][2];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const bf16x2 lo = {(bf16)(dq[dt][4 * g] * scale), (bf16)(dq[dt][4 * g + 1] * scale)};
-      const bf16x2 hi = {(bf16)(dq[dt][4 * g + 2] * scale), (bf16)(dq[dt][4 * g + 3] * scale)};
-      w[g][0] = __builtin_bit_cast(unsigned, lo);
-      w[g][1] = __builtin_bit_cast(unsigned, hi);
-    }
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(w[g][k], w[g + 2][k], false, false);
-        w[g][k] = sw[0];
-        w[g + 2][k] = sw[1];
-      }
-    if (q0 + ql < N) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const uint4 v = {w[g][0], w[g][1], w[g + 2][0], w[g + 2][1]};
-        *reinterpret_cast<uint4*>(qrow_out + dt * 32 + 8 * (g + 2 * h)) = v;
-      }
-    }
-  }
+  dq_store(dq, dqkv + (size_t)(b * N + qrow) * ld + head * HD, scale, q0 + ql < N, h);
 }
 
 // The cls-query forward without a score row in LDS (any N): sweep 1 streams K for the maximum of the scores, sweep 2 streams K
@@ -2286,22 +1947,19 @@ extern "C" int cara_debug_tr_frag(const void* src, void* out, int N, int cbase, 
   return CARA_OK;
 }
 
-// CARA_ATTN_WAVES=4 selects the 4-wave workgroups (two per head at N = 197) for A/B measurements
-static int attn_waves(int N) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("CARA_ATTN_WAVES");
-    forced = e ? atoi(e) : 0;
-  }
-  if (forced == 4 || forced == 7) return forced;
-  return N > 128 ? 7 : 4;
-}
-
-// CARA_ATTN_STREAM=1: the streamed kernels also serve 224 < N <= 608 (A/B runs against the resident ones); default 0: they serve
-// N > 608 only, where nothing else exists
-static bool attn_streamed(int N) {
-  static const int force = [] { const char* e = getenv("CARA_ATTN_STREAM"); return e ? atoi(e) : 0; }();
-  return N > NMAX_LONG || (force == 1 && N > NMAX);
+// Which kernels serve a token count.  This is the whole dispatch: every entry point below switches on it.
+//   N <= 128      SHORT     attn_fwd_kernel (4 waves)      attn_bwd_dkv_kernel + attn_bwd_dq_kernel<4>
+//   129 .. 224    HEADLINE  attn_fwd_p2_kernel<5 / 6 / 7>  attn_bwd_fused_kernel
+//   225 .. 608    LONG      attn_fwd_long_kernel           attn_bwd_dkv_kernel + attn_bwd_dq_kernel<7>
+//   > 608         STREAMED  attn_fwd_stream_kernel         attn_bwd_dkv_stream_kernel + attn_bwd_dq_stream_kernel
+// CARA_ATTN_STREAM=1 sends 225 .. 608 to the streamed kernels too (A/B runs and tests against the resident ones).
+// The cls pair: attn_cls_fwd_stream_kernel on STREAMED, attn_cls_fwd_kernel otherwise; attn_cls_bwd_kernel for every N.
+enum class AttnPath { SHORT, HEADLINE, LONG, STREAMED };
+static AttnPath attn_path(int N) {
+  static const int force_stream = [] { const char* e = getenv("CARA_ATTN_STREAM"); return e ? atoi(e) : 0; }();
+  if (N > NMAX_LONG || (force_stream == 1 && N > NMAX)) return AttnPath::STREAMED;
+  if (N > NMAX) return AttnPath::LONG;
+  return N > 128 ? AttnPath::HEADLINE : AttnPath::SHORT;
 }
 static bool attn_shape_ok(int B, int N, int H) {
   return B > 0 && H > 0 && N > 0 && N <= NMAX_STREAM && (long long)B * N < (1ll << 31);
@@ -2312,118 +1970,89 @@ static void attn_set_lds_limits() {
   static bool done = false;
   if (done) return;
   const hipFuncAttribute at = hipFuncAttributeMaxDynamicSharedMemorySize;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<4>), at, MAX_LDS);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<7>), at, MAX_LDS);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<7>), at, MAX_LDS);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_persist_kernel), at, MAX_LDS);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel), at, MAX_LDS);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel), at, MAX_LDS);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_p2_kernel<5>), at, MAX_LDS);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_p2_kernel<6>), at, MAX_LDS);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_p2_kernel<7>), at, MAX_LDS);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel), at, MAX_LDS);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel<false>), at, MAX_LDS);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel<true>), at, MAX_LDS);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel), at, MAX_LDS);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel<4>), at, MAX_LDS);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel<7>), at, MAX_LDS);
   done = true;
 }
 
-extern "C" int cara_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream) {
-  if (!qkv || !out || !lse || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
+extern "C" int cara_attention_fwd(const void* qkv_, void* out_, float* lse, int B, int N, int H, float scale, void* stream) {
+  if (!qkv_ || !out_ || !lse || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
   attn_set_lds_limits();
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (attn_streamed(N)) {
-    hipLaunchKernelGGL(attn_fwd_stream_kernel, dim3(B * H, (N + ST_WAVES * 32 - 1) / (ST_WAVES * 32)), dim3(ST_WAVES * 64), 0, st,
-                       (const bf16*)qkv, (bf16*)out, lse, N, H, scale);
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
+  const bf16* qkv = static_cast<const bf16*>(qkv_);
+  bf16* out = static_cast<bf16*>(out_);
+  const int BH = B * H, npad = (N + 31) / 32 * 32, lds = 2 * npad * 128;
+  switch (attn_path(N)) {
+    case AttnPath::SHORT:
+      hipLaunchKernelGGL(attn_fwd_kernel, dim3(BH, (N + 127) / 128), dim3(FWD_WAVES * 64), lds, st, qkv, out, lse, N, H, scale, npad);
+      break;
+    case AttnPath::HEADLINE: {
+      // one workgroup per CU walks the (batch, head) pairs: K / V of the next pair stream in while this one computes
+      const int grid = BH < 256 ? BH : 256, nkt = npad / 32;
+      const size_t plds = 4 * 224 * 128 + PF_WAVES * 4096;
+      const auto kernel = nkt == 7 ? attn_fwd_p2_kernel<7> : nkt == 6 ? attn_fwd_p2_kernel<6> : attn_fwd_p2_kernel<5>;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(PF_WAVES * 64), plds, st, qkv, out, lse, N, H, BH, scale);
+      break;
+    }
+    case AttnPath::LONG:   // (the workgroup walks its head's query groups: K / V staged once per head)
+      hipLaunchKernelGGL(attn_fwd_long_kernel, dim3(BH, 1), dim3(LONG_WAVES * 64), lds, st, qkv, out, lse, N, H, scale, npad);
+      break;
+    case AttnPath::STREAMED:
+      hipLaunchKernelGGL(attn_fwd_stream_kernel, dim3(BH, (N + ST_WAVES * 32 - 1) / (ST_WAVES * 32)), dim3(ST_WAVES * 64), 0, st, qkv, out,
+                         lse, N, H, scale);
+      break;
   }
-  const int npad = (N + 31) / 32 * 32, lds = 2 * npad * 128;
-  // The two-sweep kernel is also the default for 128 < N <= 224: 123 VGPRs instead of 210 put two 7-wave
-  // workgroups on a CU, which more than pays for computing Q K^T twice (same-box 36.9 vs 41.4 us at N = 197).
-  // CARA_ATTN_LONG=0 keeps the register-resident score rows for A/B runs.  (Capping the backward kernels at
-  // 128 VGPRs for the same reason: dK/dV spills 38 registers, 145 vs 101 us for the pair; dQ alone 43.7 vs
-  // 44.6 us, i.e. nothing -- not done.)
-  static int use_long = -1;
-  if (use_long < 0) {
-    const char* e = getenv("CARA_ATTN_LONG");
-    use_long = e ? atoi(e) : 1;
-  }
-  static const int use_persist = [] { const char* e = getenv("CARA_ATTN_PERSIST"); return e ? atoi(e) : 1; }();
-  if (use_persist && N > 128 && N <= NMAX) {
-    // one workgroup per CU walks the (batch, head) pairs: K / V of the next pair stream in while this one computes
-    const int BH = B * H, grid = BH < 256 ? BH : 256;
-    // CARA_ATTN_FWD_V=1: the round-3 body (any tile count in one kernel) for A/B runs; default: the specialised schedule
-    static const int fwd_v = [] { const char* e = getenv("CARA_ATTN_FWD_V"); return e ? atoi(e) : 2; }();
-    const size_t plds = 4 * 224 * 128 + PF_WAVES * 4096;
-    const int nkt = (N + 31) / 32;
-    if (fwd_v == 1)
-      hipLaunchKernelGGL(attn_fwd_persist_kernel, dim3(grid), dim3(PF_WAVES * 64), plds, st, (const bf16*)qkv, (bf16*)out, lse, N, H, BH, scale);
-    else if (nkt == 7)
-      hipLaunchKernelGGL(attn_fwd_p2_kernel<7>, dim3(grid), dim3(PF_WAVES * 64), plds, st, (const bf16*)qkv, (bf16*)out, lse, N, H, BH, scale);
-    else if (nkt == 6)
-      hipLaunchKernelGGL(attn_fwd_p2_kernel<6>, dim3(grid), dim3(PF_WAVES * 64), plds, st, (const bf16*)qkv, (bf16*)out, lse, N, H, BH, scale);
-    else
-      hipLaunchKernelGGL(attn_fwd_p2_kernel<5>, dim3(grid), dim3(PF_WAVES * 64), plds, st, (const bf16*)qkv, (bf16*)out, lse, N, H, BH, scale);
-  } else if (N > NMAX || (use_long && N > 128))
-    hipLaunchKernelGGL(attn_fwd_long_kernel<7>, dim3(B * H, 1), dim3(448), lds, st, (const bf16*)qkv, (bf16*)out, lse, N,
-                       H, scale, npad);   // (the workgroup walks its head's query groups: K / V staged once per head)
-  else if (attn_waves(N) == 7)
-    hipLaunchKernelGGL(attn_fwd_kernel<7>, dim3(B * H, (N + 223) / 224), dim3(448), lds, st, (const bf16*)qkv, (bf16*)out, lse, N, H,
-                       scale, npad);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(B * H, (N + 127) / 128), dim3(256), lds, st, (const bf16*)qkv, (bf16*)out, lse, N, H,
-                       scale, npad);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }
 
-extern "C" int cara_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+extern "C" int cara_attention_bwd(const void* qkv_, const void* out_, const void* dout_, const float* lse, void* dqkv_,
                                   int B, int N, int H, float scale, void* stream) {
-  if (!qkv || !out || !dout || !lse || !dqkv || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
+  if (!qkv_ || !out_ || !dout_ || !lse || !dqkv_ || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
   attn_set_lds_limits();
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (attn_streamed(N)) {
-    const dim3 grid(B * H, (N + ST_WAVES * 32 - 1) / (ST_WAVES * 32));
-    hipLaunchKernelGGL(attn_bwd_dkv_stream_kernel, grid, dim3(ST_WAVES * 64), 0, st, (const bf16*)qkv, (const bf16*)out,
-                       (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale);
-    CARA_CHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_bwd_dq_stream_kernel, grid, dim3(ST_WAVES * 64), 0, st, (const bf16*)qkv, (const bf16*)out,
-                       (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale);
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
+  const bf16 *qkv = static_cast<const bf16*>(qkv_), *out = static_cast<const bf16*>(out_), *dout = static_cast<const bf16*>(dout_);
+  bf16* dqkv = static_cast<bf16*>(dqkv_);
+  const int BH = B * H, npad = (N + 31) / 32 * 32, lds = 2 * npad * 128;
+  const AttnPath path = attn_path(N);
+  switch (path) {
+    case AttnPath::HEADLINE:
+      hipLaunchKernelGGL(attn_bwd_fused_kernel, dim3(BH < 256 ? BH : 256), dim3(448), 5 * 224 * 128 + (256 + 224) * 4, st, qkv, out, dout,
+                         lse, dqkv, N, H, BH, scale);
+      break;
+    case AttnPath::SHORT:
+    case AttnPath::LONG:   // (both kernels of LONG walk their head's key / query groups: one staging per head)
+      hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(BH, 1), dim3(BWD_WAVES * 64), dkv_lds_bytes(npad), st, qkv, out, dout, lse, dqkv, N, H,
+                         scale, npad);
+      CARA_CHECK_LAUNCH();
+      if (path == AttnPath::LONG)
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<7>, dim3(BH, 1), dim3(448), lds, st, qkv, out, dout, lse, dqkv, N, H, scale, npad);
+      else
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<4>, dim3(BH, (N + 127) / 128), dim3(256), lds, st, qkv, out, dout, lse, dqkv, N, H, scale,
+                           npad);
+      break;
+    case AttnPath::STREAMED: {
+      const dim3 grid(BH, (N + ST_WAVES * 32 - 1) / (ST_WAVES * 32));
+      hipLaunchKernelGGL(attn_bwd_dkv_stream_kernel, grid, dim3(ST_WAVES * 64), 0, st, qkv, out, dout, lse, dqkv, N, H, scale);
+      CARA_CHECK_LAUNCH();
+      hipLaunchKernelGGL(attn_bwd_dq_stream_kernel, grid, dim3(ST_WAVES * 64), 0, st, qkv, out, dout, lse, dqkv, N, H, scale);
+      break;
+    }
   }
-  const int npad = (N + 31) / 32 * 32, lds = 2 * npad * 128;
-  static const int use_fused = [] { const char* e = getenv("CARA_ATTN_PERSIST"); return e ? atoi(e) : 1; }();
-  if (use_fused && N > 128 && N <= NMAX) {
-    const int BH = B * H, grid = BH < 256 ? BH : 256;
-    // CARA_ATTN_BWD_V=1: the four-barrier protocol of round 3 for A/B runs; default (r05): two barriers per head
-    static const int bwd_v = [] { const char* e = getenv("CARA_ATTN_BWD_V"); return e ? atoi(e) : 2; }();
-    if (bwd_v == 1)
-      hipLaunchKernelGGL(attn_bwd_fused_kernel<false>, dim3(grid), dim3(448), 5 * 224 * 128 + (256 + 224) * 4, st, (const bf16*)qkv, (const bf16*)out,
-                         (const bf16*)dout, lse, (bf16*)dqkv, N, H, BH, scale);
-    else
-      hipLaunchKernelGGL(attn_bwd_fused_kernel<true>, dim3(grid), dim3(448), 5 * 224 * 128 + (256 + 224) * 4, st, (const bf16*)qkv, (const bf16*)out,
-                         (const bf16*)dout, lse, (bf16*)dqkv, N, H, BH, scale);
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
-  }
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(B * H, 1), dim3(448), dkv_lds_bytes(npad), st, (const bf16*)qkv,
-                     (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale, npad);
-  CARA_CHECK_LAUNCH();
-  if (N > NMAX || attn_waves(N) == 7)
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<7>, dim3(B * H, 1), dim3(448), lds, st, (const bf16*)qkv,
-                       (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale, npad);
-  else
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<4>, dim3(B * H, (N + 127) / 128), dim3(256), lds, st, (const bf16*)qkv,
-                       (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, N, H, scale, npad);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }
-
 
 extern "C" int cara_attention_cls_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream) {
   if (!qkv || !out || !lse || !attn_shape_ok(B, N, H)) return CARA_E_ARG;
-  if (attn_streamed(N))   // (no score row in LDS)
+  if (attn_path(N) == AttnPath::STREAMED)   // (no score row in LDS)
     hipLaunchKernelGGL(attn_cls_fwd_stream_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16*)qkv, (bf16*)out,
                        lse, N, H, scale);
   else
