@@ -566,6 +566,50 @@ def _mlp_factored(xn, w, p, fac, r):
     return adapter_linear(h, w[p + "mlp.fc2.weight"], w[p + "mlp.fc2.bias"], fac["fc2"], r, "h")
 
 
+def attn_rounding_model(qkv, dout, B, N, H, scale, dtype):
+    """Attention forward and backward of cara_amd/csrc/attention.hip in float64, rounded to the operand type ``dtype`` where the
+    kernels round and nowhere else: ``(out [B N, H 64], lse [B, H, N], dqkv [B N, 3 H 64])``.  ``qkv`` [B N, 3 H 64] and ``dout``
+    [B N, H 64] hold values of ``dtype``; any device.  What the device accumulates in fp32 is exact here, so the distance of
+    this model from plain fp64 attention is the rounding noise the kernels may carry and no more.
+
+    Rounding points, with the lines of attention.hip they restate (the four MFMA paths share them; the cls pair has the same ones):
+
+    forward
+    * P = exp(S - rowmax) is rounded UNNORMALISED, as the A operand of P.V: ``pack8`` in ``fwd_pv_block`` (179), ``attn_fwd_kernel``
+      (284), ``attn_fwd_p2_kernel`` (630-654); cls: ``sc[n] = (float)(bf16)e`` (1458).
+    * the row sum is taken of the unrounded exponentials (175, 270; cls 1457) and divides the fp32 accumulator; ``out`` is rounded
+      once: ``(bf16)(o[dt][r] * iv)`` in ``fwd_store_rows`` (199), 303, ``cvt_pk_dword(po * pinv)`` (505); cls 1486.
+    * ``lse = mx * scale + __logf(sum)`` is an fp32 number (202, 306, 681; cls 1487): rounded to float32 here.
+    backward
+    * ``D = rowsum(dO . out)`` from the ROUNDED ``out`` the forward stored, summed in fp32: ``dq_rows`` (780),
+      ``attn_bwd_dkv_kernel`` (889), ``attn_bwd_fused_kernel`` (1108); cls 1517.
+    * P is recomputed as ``exp2(S c2 - lse log2 e)`` from that fp32 lse (``dkv_block`` 727, ``dq_block`` 804, fused 1168) and
+      rounded as the B operand of dV^T += dO^T P (``pack8(p)`` 736, ``pk16`` 1169; cls 1548).
+    * ``dS = P (dP - D)`` is formed from the UNROUNDED P in fp32 and rounded as the operand of dK^T += Q^T dS and of
+      dQ^T += K^T dS^T (731 + 736, 806 + 810, fused 1170 and 1288; cls 1549).
+    * ``scale`` multiplies the fp32 accumulators of dQ and dK before their one rounding: ``dkv_store`` (756), ``dq_store`` (828),
+      fused 1329; cls 1555 and 1572 (the cls kernels fold it into q in fp32, 1427 / 1515).  dV is rounded unscaled (758; cls 1554).
+    """
+    def r(t):
+        return t.to(dtype).double()
+    q, k, v = qkv.double().reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)
+    s = (q @ k.transpose(-2, -1)) * scale
+    m = s.amax(-1, keepdim=True)
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    o = r((r(e) @ v) / l)
+    lse = (m + l.log()).float().double()
+    do = dout.double().reshape(B, N, H, 64).transpose(1, 2)
+    P = torch.exp(s - lse)
+    D = (do * o).sum(-1, keepdim=True)
+    dV = r(r(P).transpose(-2, -1) @ do)
+    dS = r(P * (do @ v.transpose(-2, -1) - D))
+    dQ = r(dS @ k * scale)
+    dK = r(dS.transpose(-2, -1) @ q * scale)
+    dqkv = torch.stack([dQ, dK, dV], 0).permute(1, 3, 0, 2, 4).reshape(B * N, 3 * H * 64)
+    return o.transpose(1, 2).reshape(B * N, H * 64), lse.squeeze(-1), dqkv
+
+
 # ----------------------------------------------------------------------------------------------
 # Synthetic inputs of SURVEY.md section 8(d) (shared by tests, smoke and bench; deterministic)
 # ----------------------------------------------------------------------------------------------
