@@ -33,7 +33,7 @@ struct Ws {
   size_t pack, patches, emb, head_wb, clsn, meanF, rstdF, x_last;
   LayerWs layer[64];
   // backward
-  size_t dx, dXn, dAO, slabs, dclsn, gscratch, gemm_scratch;
+  size_t dx, dXn, dAO, dclsn, gscratch, gemm_scratch;
   // dY of the four linears, G' = dY Vs and its transpose: one set, reused by every block (everything runs in
   // stream order on the caller's stream)
   struct Bwd { size_t dyb_fc2, dyb_proj, dH, dQKV, G[4], Gt[4]; } bwd;
@@ -63,8 +63,20 @@ int dw_slabs(int out, int in, int M) {
   return n < 1 ? 1 : n;
 }
 
+// A/B switches, read ONCE per process (tools/ab_env.sh); the defaults are what DESIGN.md reports.
+int env_once(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// CARA_DV (default 0; bit 0: fc1, bit 1: qkv): dVs (+ dc) of fc1 / qkv out of their dX GEMM's own A tiles on the 160 x 256 x 64 tile
+// (plan_block); the workspace then holds one slab per 160-row tile and K step for them (layout)
+int dv_env() {
+  static const int v = env_once("CARA_DV", 0);
+  return v;
+}
+
 bool epi_riders_geom(const cara_geom* g, int Mr, bool exact);
-int env_once(const char* name, int dflt);
 bool save_gelu_grad(const cara_geom* g, const cara_vit_shape* s);
 bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   if (!g || !s || g->depth <= 0 || g->depth > 64 || g->dim % g->heads || g->dim / g->heads != 64) return false;
@@ -126,7 +138,7 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   }
   for (int l = nsets; l < g->depth; ++l) w->layer[l] = w->layer[l - 2];
   if (inference) {
-    w->dx = w->dXn = w->dAO = w->slabs = w->dclsn = w->gscratch = 0;
+    w->dx = w->dXn = w->dAO = w->dclsn = w->gscratch = 0;
     w->bwd = Ws::Bwd{};
     w->ldk = (int)((M + 63) / 64 * 64);
     w->nslab = 1;
@@ -147,7 +159,6 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
       R.Gt[i] = c.take(Rp * ldt * 2);
     }
   }
-  w->slabs = 0;
   w->dclsn = c.take((size_t)s->B * D * 2);
   w->gscratch = c.take(cara_factor_grad_scratch_bytes(g));
   const size_t ins[4] = {D, D, D, 4 * D}, outs[4] = {3 * D, D, 4 * D, D};
@@ -163,7 +174,7 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
     if (i == 2 && epi_riders_geom(g, (int)M, s->wd_exact != 0) && er_bytes > w->strideV[i]) w->strideV[i] = er_bytes;
     // (CARA_DV: fc1's / qkv's dVs out of their dX tiles, one slab per 160-row tile and K step: K1 = the linear's out features)
     const size_t dv_bytes = (cara_gemm_epi_rider_scratch_bytes((int)((M + 159) / 160), (int)outs[i]) + 255) & ~(size_t)255;
-    if ((i == 0 || i == 2) && env_once("CARA_DV", 0) != 0 && g->Rp == 32 && dv_bytes > w->strideV[i]) w->strideV[i] = dv_bytes;
+    if ((i == 0 || i == 2) && dv_env() != 0 && g->Rp == 32 && dv_bytes > w->strideV[i]) w->strideV[i] = dv_bytes;
     w->slabU[i] = c.take(w->strideU[i] * g->depth);
     w->slabV[i] = c.take(w->strideV[i] * g->depth);
   }
@@ -212,17 +223,6 @@ struct Prof {
 };
 Prof g_prof;
 
-// A linear's two transposed skinny products (dU = X^T G', dVs = dY^T T, dc) as arguments of cara_tskinny_partial2 /
-// cara_gemm_with_tskinny: the pair waits here until a GEMM launch carries it (its own dX GEMM, or -- CARA_DEFER_TS -- the
-// NEXT dX GEMM of the pass, which lets a GEMM compute the G' its own products read) or it is flushed as a launch of its own.
-struct TsPending {
-  bool valid = false;
-  const void *Xa, *Gta, *Xb, *Gtb;
-  void *slabs_a, *slabs_b;
-  int ldxa, K1a, ldxb, K1b, want_cs, ldg, M, Rp;
-  int slot = 0, layer = 0;   // the linear the pair belongs to
-};
-
 // How a linear's transposed skinny products left their partial sums, per layer: 0 = one slab per block, 1 = one per wave
 // (cara_gemm_rider_slab_format: the launches of the 160 x 256 x 64 tile stream their riding products with helper waves).
 // The end-of-pass reduction groups the layers of a linear by it.
@@ -230,12 +230,25 @@ struct SlabFormats {
   unsigned short U[4][64] = {}, V[4][64] = {};   // (>= 2: that many slabs per column block, cara_ts_reduce::wave_slabs)
 };
 
-// The products the fc2 dX launch computes in its epilogue (cara_gemm_args::er_*): fc1's dVs = dH^T T (+ dc) and fc2's own dU = h^T G'
-struct EpiRider {
-  const void* Tt;    // fc1's T^T
-  void* slabV;       // fc1's dVs slab region of this layer
-  size_t bytes;      // size of that region and of fc2's dU region
-  bool done = false; // set by the launch that computed them
+// One transposed skinny product of the backward -- a linear's dU = X^T G' or its dVs = dY^T T (+ dc = colsum dY) -- as
+// cara_tskinny_partial2_r / cara_gemm_with_tskinny_r take it.  X == nullptr: none.
+struct Product {
+  const void* X = nullptr;   // [M, K1], row stride ldx (ldx < 0: K-panel-major with -ldx rows per panel)
+  int ldx = 0;
+  const void* Gt = nullptr;  // the skinny operand, transposed (G'^T or T^T)
+  void* slabs = nullptr;     // its partial sums, this layer's region
+  int K1 = 0, colsum = 0, M = 0;
+  unsigned short* format = nullptr;   // its cell of SlabFormats: written by whatever launch computes the product
+};
+
+// Where the two products of a linear are computed (plan_block decides, once per block; lin_bwd has one arm per value)
+enum class Riders {
+  Own,        // dVs (+ dc) behind the tiles of the linear's own dX launch, dU behind those of the NEXT dX launch of the pass
+  Epilogue,   // fc2 under CARA_EPI_RIDERS: the epilogue of its dX launch computes its dU and fc1's dVs (+ dc)
+  DoneAbove,  // fc1 after such a launch: a plain dX GEMM, only its dU waits
+  ATiles,     // CARA_DV: dVs (+ dc) out of the A tiles of the linear's own dX launch on the 160 x 256 x 64 tile
+  BothHome,   // fc2 beside an ATiles fc1: both its products behind its own tiles; the dU that waits rides behind fc1's (19 MB, not fc2's 77)
+  Side,       // CARA_FC1_SIDE: fc1's dVs (+ dc) and the waiting dU as a launch on the side stream under fc1's dX GEMM
 };
 
 // CARA_FC1_SIDE=1 (default 0): the two heavy riders of the backward -- fc1's dVs = dH^T T (+ dc) and fc2's dU = h^T G', 154 MB -- as a
@@ -265,9 +278,12 @@ SideStream* side_stream() {
   }
   return s.ok ? &s : nullptr;
 }
-struct SideRiders {   // per backward pass
-  SideStream* ss = nullptr;
-  bool pending_join = false;   // the side stream holds work the caller's stream has not waited for
+// What a backward pass carries from one launch to the next
+struct BwdPass {
+  Product waiting;            // the dU of the linear before, until the next dX launch carries it (flush_waiting runs it alone otherwise)
+  SlabFormats formats;
+  bool epilogue_ran = false;  // this block's fc2 dX launch took the Epilogue placement (it falls back to Own where the launch says no)
+  bool side_join = false;     // the side stream holds work the caller's stream has not waited for
 };
 
 // per-call context: what lin_fwd / lin_bwd need besides their operands (nothing here outlives the call)
@@ -276,33 +292,47 @@ struct Ctx {
   char* scratch;   // split-K scratch of the workspace in use (few-row products)
   int layer;
   bool full;       // this block runs on all token rows (not the cls-row-only last block)
-  TsPending* pend = nullptr;   // backward: the pair of products waiting for a carrier
-  int rank = 0;                // the adapter's rank (0: unknown, the skinny passes compute all Rp columns)
-  SlabFormats* fmt = nullptr;  // backward: where the launches note the slab format of the products they carry
+  BwdPass* bwd = nullptr;
+  int rank = 0;    // the adapter's rank (0: unknown, the skinny passes compute all Rp columns)
 };
 
-// the rank the transposed skinny products are told (0 in the context = unknown: all Rp columns).  Deferred products
-// (CARA_DEFER_TS) ride in adapter-inside GEMMs, whose kernel has no 16-column form: they keep all columns.
-bool defer_ts();
-int env_once(const char* name, int dflt);
-inline int ts_rank(const Ctx& cx, int Rp) {
-  static const int full = env_once("CARA_TS_ALL_COLUMNS", 0);   // 1: the products compute all Rp columns whatever the rank (A/B runs)
-  return (cx.rank > 0 && !defer_ts() && !full) ? cx.rank : Rp;
+// the rank the transposed skinny products are told
+inline int ts_rank(const Ctx& cx, int Rp) { return cx.rank > 0 ? cx.rank : Rp; }
+
+// One or two products as a launch of their own (a lone product takes the launch's second slot).  small: the two-stage-ring form
+// that fits beside a GEMM of the 160 x 256 x 64 tile.
+int launch_products(const Ctx& cx, const Product* p0, const Product* p1, int Rp, int ldt, void* stream, bool small = false) {
+  if (!p1) { p1 = p0; p0 = nullptr; }
+  const Product none, &a = p0 ? *p0 : none, &b = *p1;
+  if (p0) *a.format = 0;
+  *b.format = 0;
+  return (small ? cara_tskinny_partial2_small : cara_tskinny_partial2_r)(a.X, a.ldx, a.Gt, a.slabs, a.K1, b.X, b.ldx, b.Gt, b.slabs, b.K1, b.colsum, ldt,
+                                                                         b.M, Rp, ts_rank(cx, Rp), stream);
 }
 
-bool defer_du();
+// One dX GEMM launch with zero, one or two products riding behind its tiles (a lone product takes the launch's second slot); the
+// launch says how its riders leave their partial sums (it depends on the arguments only)
+int gemm_with_riders(const Ctx& cx, const cara_gemm_args& a, const Product* p0, const Product* p1, int Rp, int ldt) {
+  if (!p1) { p1 = p0; p0 = nullptr; }
+  if (!p1) return cara_gemm_bf16(&a, cx.stream);
+  const Product none, &r0 = p0 ? *p0 : none, &r1 = *p1;
+  const unsigned short f = (unsigned short)cara_gemm_rider_slab_format(&a, Rp, ts_rank(cx, Rp));
+  if (p0) *r0.format = f;
+  *r1.format = f;
+  return cara_gemm_with_tskinny_r(&a, r0.X, r0.ldx, r0.Gt, r0.slabs, r0.K1, r1.X, r1.ldx, r1.Gt, r1.slabs, r1.K1, r1.colsum, ldt, a.M, Rp, ts_rank(cx, Rp),
+                                  cx.stream);
+}
+
+// the dU that found no carrier, as a launch of its own
+int flush_waiting(const Ctx& cx, int Rp, int ldt) {
+  Product& q = cx.bwd->waiting;
+  if (!q.X) return CARA_OK;
+  const Product dU = q;
+  q = Product{};
+  return launch_products(cx, &dU, nullptr, Rp, ldt, cx.stream);
+}
+
 bool g_inside_enabled(int slot);
-
-int flush_pending(const Ctx& cx) {
-  TsPending* q = cx.pend;
-  if (!q || !q->valid) return CARA_OK;
-  q->valid = false;
-  if (defer_du())   // (only the dU half of a linear waits in this mode: the first product of the entry)
-    return cara_tskinny_partial2_r(nullptr, 0, nullptr, nullptr, 0, q->Xa, q->ldxa, q->Gta, q->slabs_a, q->K1a, 0, q->ldg, q->M, q->Rp,
-                                   ts_rank(cx, q->Rp), cx.stream);
-  return cara_tskinny_partial2_r(q->Xa, q->ldxa, q->Gta, q->slabs_a, q->K1a, q->Xb, q->ldxb, q->Gtb, q->slabs_b, q->K1b, q->want_cs,
-                                 q->ldg, q->M, q->Rp, ts_rank(cx, q->Rp), cx.stream);
-}
 
 struct SiteBracket {   // RAII: event 0 .. kernel(s) .. event 1, event 2 (an empty bracket: the markers' own cost)
   hipEvent_t* ev = nullptr;
@@ -328,12 +358,6 @@ struct Lin {  // one adapted linear of one layer
   const bf16 *Wp = nullptr, *Wtp = nullptr;   // K-panel-major images of W / Wt (cara_gemm_args::Bp), or null
 };
 
-// A/B switches, read ONCE per process (tools/ab_env.sh); the defaults are what DESIGN.md reports.
-int env_once(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 // CARA_FUSE_XU=0 keeps the K = dim adapter contractions (T = LN(x) U of qkv / fc1, G' = dY Vs of proj / fc2) as
 // separate cara_skinny_xu passes instead of fusing them into the LayerNorm kernels
 bool fuse_xu(const cara_geom* g) {
@@ -341,12 +365,11 @@ bool fuse_xu(const cara_geom* g) {
   return v != 0 && (g->Rp == 32 || g->Rp == 64) && (g->dim == 768 || g->dim == 1024 || g->dim == 256);   // what cara_layernorm_*_xu take
 }
 
-// CARA_FUSE_GEMM_T: bit 0 (default on) computes T = X U of forward proj / fc2 inside the GEMM that consumes it
-// (cara_gemm_args::Ut) instead of a separate cara_skinny_xu pass; bit 1 (default off: measured slower) the same
-// for G' = dY Vs of the backward's qkv / fc1.
-bool fuse_gemm_t(int Mr, int Rp, bool backward) {
+// CARA_FUSE_GEMM_T bit 0 (default on) computes T = X U of forward proj / fc2 inside the GEMM that consumes it
+// (cara_gemm_args::Ut) instead of a separate cara_skinny_xu pass
+bool fuse_gemm_t(int Mr, int Rp) {
   static const int v = env_once("CARA_FUSE_GEMM_T", 1);
-  return (v & (backward ? 2 : 1)) != 0 && (Rp == 32 || Rp == 64) && Mr >= 1024;
+  return (v & 1) != 0 && (Rp == 32 || Rp == 64) && Mr >= 1024;
 }
 
 // CARA_PANEL_ACTS = mask of the activation groups written K-panel-major ([K/32][M][32], cara_gemm_args::c_panels /
@@ -366,19 +389,6 @@ bool fuse_ts(int Mr, int Rp) {
   return v != 0 && (Rp == 32 || Rp == 64) && Mr >= 1024;
 }
 
-// CARA_DEFER_TS=1 (default off): a linear's transposed skinny products ride in the NEXT dX GEMM launch of the backward pass
-// instead of its own (everything they read -- dY, G'^T, the saved input, T^T -- stays untouched until well after that launch:
-// the dY / G' buffers of a linear are next written one block later).  That frees a dX GEMM to compute the G' = dY Vs its own
-// products read (CARA_FUSE_GEMM_T bit 1: no separate pass over dY), and lets any launch be the carrier of any pair.
-// Measured (same box, r03): it LOSES -- 8.95 -> 9.20 ms per step alone, 9.11 with G' inside the dX GEMMs (rank 16); rank 64
-// 10.53 -> 10.85 / 10.27.  A pair that rides in its OWN linear's launch reads the dY the GEMM is streaming as its A operand
-// at that moment (cache hits); a deferred pair reads 96 MB nothing else touches, and the heaviest pair lands on the
-// shortest GEMM (fc1's on proj dX).
-bool defer_ts() {
-  static const int v = env_once("CARA_DEFER_TS", 0);
-  return v != 0;
-}
-
 void with_scratch(cara_gemm_args& a, const Ctx& cx) {
   a.scratch = cx.scratch;
   a.scratch_bytes = cx.scratch ? cara_gemm_scratch_bytes() : 0;
@@ -395,7 +405,7 @@ int lin_fwd(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, int ldt, char*
   void* st = cx.stream;
   bf16* T = reinterpret_cast<bf16*>(ws + lw.T[L.slot]);
   bf16* Tt = reinterpret_cast<bf16*>(ws + lw.Tt[L.slot]);
-  const bool inside = !have_T && fuse_gemm_t(Mr, Rp, false);   // T computed by the GEMM itself
+  const bool inside = !have_T && fuse_gemm_t(Mr, Rp);   // T computed by the GEMM itself
   if (!have_T && !inside) {
     SiteBracket b(CARA_SITE_SKINNY_FWD, cx);
     TRY(cara_skinny_xu_r(X, ldx, L.Ut, T, Tt, ldt, Mr, L.in, Rp, cx.rank > 0 ? cx.rank : Rp, st));
@@ -416,176 +426,97 @@ int lin_fwd(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, int ldt, char*
 // backward of one adapted linear given dY (bf16, Mr rows, row stride lddy) and its saved input X
 // (row stride ldx; a negative stride = K-panel-major with that many rows per panel):
 //   G' = dY Vs ; dX = [dY | G'] [W^T | U]^T (optional) ; dU = X^T G' ; dVs = dY^T T ; dc = colsum dY
-// The two transposed skinny products ride in the launch of the dX GEMM when they can (cara_gemm_with_tskinny),
-// otherwise they are one launch of their own behind it, on the same stream.
+// The two transposed skinny products go where `where` says when the dX launch can carry products (fuse_ts); otherwise they are
+// one launch of their own behind it, on the same stream.
+// (have_G: the LayerNorm backward that produced dY already left G' and its transpose, cara_layernorm_bwd_xu)
 int lin_bwd(const Lin& L, const bf16* dY, int lddy, const bf16* X, int ldx, int Mr, int Rp, int ldt, char* ws, const Ws& W,
-            const LayerWs& lw, bool want_dx, cara_gemm_args a, bool want_dc, const Ctx& cx, bool have_G = false, EpiRider* er = nullptr,
-            bool dvs_done = false, SideRiders* side = nullptr, int dv = 0) {
-  // dv: 1 = this linear's dVs (+ dc) out of its dX GEMM's own A tiles where the launch can (cara_gemm_dv_chunks); 2 = this linear carries
-  // BOTH its products in its own launch and leaves the waiting dU for the next one (the linear before a dv = 1 one: CARA_DV)
+            const LayerWs& lw, bool want_dx, cara_gemm_args a, bool want_dc, const Ctx& cx, Riders where = Riders::Own, bool have_G = false) {
   void* st = cx.stream;
-  const Ws::Bwd& R = W.bwd;
-  bf16* G = reinterpret_cast<bf16*>(ws + R.G[L.slot]);
-  bf16* Gt = reinterpret_cast<bf16*>(ws + R.Gt[L.slot]);
-  void* slabU = ws + W.slabU[L.slot] + (size_t)cx.layer * W.strideU[L.slot];
-  void* slabV = ws + W.slabV[L.slot] + (size_t)cx.layer * W.strideV[L.slot];
-  const void* Tt = ws + lw.Tt[L.slot];
-  // (have_G: the LayerNorm backward that produced dY already left G' and its transpose, cara_layernorm_bwd_xu)
-  // inside: the dX GEMM computes G' = dY Vs itself (cara_gemm_args::Ut) and leaves G / Gt behind -- its own products then
-  // cannot ride in it (they read that G'): only with deferred products (a later launch carries them)
-  TsPending* pend = cx.pend;
-  const bool can_carry = fuse_ts(Mr, Rp);
-  const bool defer = pend && defer_ts() && can_carry;
-  const bool inside = !have_G && want_dx && fuse_gemm_t(Mr, Rp, true) && defer && a.epi == CARA_EPI_BF16;
-  // with the dU products riding one launch later (CARA_DEFER_DU) nothing in a linear's own dX launch reads its G', so the GEMM
-  // can compute it inside and the separate pass over dY goes (CARA_GEMM_G_INSIDE=0 keeps the pass)
-  const bool g_inside = !inside && !have_G && want_dx && can_carry && defer_du() && pend && g_inside_enabled(L.slot) &&
-                        (Rp == 32 || Rp == 64) && Mr >= 1024 && a.epi == CARA_EPI_BF16;   // (its own switch: CARA_GEMM_G_INSIDE)
-  if (!have_G && !inside && !g_inside) {
+  BwdPass& pass = *cx.bwd;
+  const int slot = L.slot, layer = cx.layer;
+  bf16* G = reinterpret_cast<bf16*>(ws + W.bwd.G[slot]);
+  bf16* Gt = reinterpret_cast<bf16*>(ws + W.bwd.Gt[slot]);
+  const bool carries = want_dx && fuse_ts(Mr, Rp);
+  // a dU rides one launch later, so nothing in a linear's own dX launch reads its G': the GEMM computes it on the tiles it streams
+  // and the separate pass over dY goes (CARA_GEMM_G_INSIDE=0 keeps the pass)
+  const bool g_inside = !have_G && carries && g_inside_enabled(slot) && a.epi == CARA_EPI_BF16;
+  if (!have_G && !g_inside) {
     SiteBracket b(CARA_SITE_SKINNY_BWD, cx);
     TRY(cara_skinny_xu_r(dY, lddy, L.Vst, G, Gt, ldt, Mr, L.out, Rp, cx.rank > 0 ? cx.rank : Rp, st));
   }
-  TsPending mine;
-  mine.valid = true;
-  mine.Xa = X; mine.ldxa = ldx; mine.Gta = Gt; mine.slabs_a = slabU; mine.K1a = L.in;
-  mine.Xb = dY; mine.ldxb = lddy; mine.Gtb = Tt; mine.slabs_b = slabV; mine.K1b = L.out; mine.want_cs = want_dc ? 1 : 0;
-  mine.ldg = ldt; mine.M = Mr; mine.Rp = Rp; mine.slot = L.slot; mine.layer = cx.layer;
+  const Product dU{X, ldx, Gt, ws + W.slabU[slot] + (size_t)layer * W.strideU[slot], L.in, 0, Mr, &pass.formats.U[slot][layer]};
+  const Product dVs{dY, lddy, ws + lw.Tt[slot], ws + W.slabV[slot] + (size_t)layer * W.strideV[slot], L.out, want_dc ? 1 : 0, Mr, &pass.formats.V[slot][layer]};
   if (want_dx) {
-    a.A = dY; a.lda = lddy; a.B = L.Wt; a.Bp = L.Wtp; a.ldb = L.out; a.A2 = inside ? nullptr : G; a.B2 = L.U; a.Rp = Rp;
+    a.A = dY; a.lda = lddy; a.B = L.Wt; a.Bp = L.Wtp; a.ldb = L.out; a.A2 = G; a.B2 = L.U; a.Rp = Rp;
     if (lddy < 0) { a.a_panels = -lddy; a.lda = 0; }
-    if (inside) { a.Ut = L.Vst; a.T_out = G; a.Tt_out = Gt; a.ldt = ldt; }
+    if (g_inside) { a.A2 = nullptr; a.Ut = L.Vst; a.T_out = G; a.Tt_out = Gt; a.ldt = ldt; a.Ut_rank = ts_rank(cx, Rp) <= 16 ? ts_rank(cx, Rp) : 0; }
     a.M = Mr; a.N = L.in; a.K = L.out; a.bias = nullptr;
     if (a.ldc == 0) a.ldc = L.in;
     with_scratch(a, cx);
-    SiteBracket b(SITE_BWD[L.slot], cx);
-    // (CARA_DEFER_DU, default on) this launch carries its linear's dVs = dY^T T (which reads the dY the GEMM is streaming) and the dU = X^T G'
-    // of the PREVIOUS linear of the pass (a dU never shares an operand with its own dX GEMM, so it loses nothing by riding
-    // elsewhere): fc2's dU, the 77-MB read of h, leaves the two-round fc2 dX launch for the single-round fc1 dX launch
-    if (can_carry && defer_du() && pend && !inside) {
-      bool take = pend->valid && pend->Rp == Rp && pend->M == Mr && pend->ldg == ldt;
-      if (pend->valid && (!take || dvs_done)) {
-        TRY(flush_pending(cx));
-        take = false;
-      }
-      if (g_inside) {   // G' = dY Vs computed by this GEMM on the tiles it streams (its own dVs does not read G'; its dU rides later)
-        a.A2 = nullptr; a.Ut = L.Vst; a.T_out = G; a.Tt_out = Gt; a.ldt = ldt; a.Ut_rank = ts_rank(cx, Rp) <= 16 ? ts_rank(cx, Rp) : 0;
-      }
-      if (dv == 2 && !dvs_done && !er) {
-        if (cx.fmt) {
-          const unsigned short f = (unsigned short)cara_gemm_rider_slab_format(&a, Rp, ts_rank(cx, Rp));
-          cx.fmt->U[L.slot][cx.layer] = f;
-          cx.fmt->V[L.slot][cx.layer] = f;
-        }
-        TRY(cara_gemm_with_tskinny_r(&a, mine.Xa, mine.ldxa, mine.Gta, mine.slabs_a, mine.K1a, mine.Xb, mine.ldxb, mine.Gtb, mine.slabs_b, mine.K1b,
-                                     mine.want_cs, ldt, Mr, Rp, ts_rank(cx, Rp), st));
-        return CARA_OK;                // (the waiting dU, if any, stays for the next launch)
-      }
-      if (dv == 1 && !dvs_done && !er) {
-        cara_gemm_args d = a;
-        d.er_Tt = Tt; d.er_ldg = ldt; d.er_slabs_v = slabV; d.er_colsum = want_dc ? 1 : 0;
-        const int ch = cara_gemm_dv_chunks(&d, take ? 1 : 0);
-        if (ch > 0 && ch <= 65535 && cara_gemm_epi_rider_scratch_bytes(ch, L.out) <= W.strideV[L.slot]) {
-          if (take) {   // the waiting dU rides behind the tiles (the launch's only product: slot b, no column sums)
-            if (cx.fmt) cx.fmt->U[pend->slot][pend->layer] = 0;
-            TRY(cara_gemm_with_tskinny_r(&d, nullptr, 0, nullptr, nullptr, 0, pend->Xa, pend->ldxa, pend->Gta, pend->slabs_a, pend->K1a, 0, ldt, Mr, Rp,
-                                         ts_rank(cx, Rp), st));
-          } else {
-            TRY(cara_gemm_bf16(&d, st));
-          }
-          if (cx.fmt) cx.fmt->V[L.slot][cx.layer] = (unsigned short)ch;
-          *pend = mine;   // (its dU half waits for the next dX GEMM of the pass)
-          return CARA_OK;
-        }
-      }
-      if (side && side->ss && !dvs_done) {
-        // this linear's dVs (+ dc) and the waiting dU as a launch of their own on the side stream, under this GEMM
-        SideStream* ss = side->ss;
-        if (hipEventRecord(ss->fork, static_cast<hipStream_t>(st)) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess) return CARA_E_LAUNCH;
-        TRY(cara_tskinny_partial2_small(take ? pend->Xa : nullptr, take ? pend->ldxa : 0, take ? pend->Gta : nullptr, take ? pend->slabs_a : nullptr,
-                                        take ? pend->K1a : 0, mine.Xb, mine.ldxb, mine.Gtb, mine.slabs_b, mine.K1b, mine.want_cs, ldt, Mr, Rp,
-                                        ts_rank(cx, Rp), ss->stream));
-        if (hipEventRecord(ss->join, ss->stream) != hipSuccess) return CARA_E_LAUNCH;
-        side->pending_join = true;
-        if (cx.fmt) {
-          if (take) cx.fmt->U[pend->slot][pend->layer] = 0;
-          cx.fmt->V[L.slot][cx.layer] = 0;
-        }
-        TRY(cara_gemm_bf16(&a, st));
-        *pend = mine;   // (its dU half waits for the next dX GEMM of the pass)
-        return CARA_OK;
-      }
-      if (dvs_done) {   // dVs and dc of this linear came out of the epilogue of the launch that produced its dY: a plain GEMM, its dU waits
-        TRY(cara_gemm_bf16(&a, st));
-        *pend = mine;
-        return CARA_OK;
-      }
-      int er_chunks = 0;
-      if (er) {   // this launch's epilogue computes the next linear's dVs (+ dc) and this linear's dU
-        a.er_Tt = er->Tt; a.er_Gt = Gt; a.er_slabs_v = er->slabV; a.er_slabs_u = slabU; a.er_ldg = ldt; a.er_colsum = 1;
-        a.er_h = X; a.er_h_panels = ldx < 0 ? -ldx : 0;   // (this linear's saved input: h)
-        er_chunks = cara_gemm_epi_rider_chunks(&a);
-        if (!er_chunks || er_chunks > 65535 || cara_gemm_epi_rider_scratch_bytes(er_chunks, L.in) > er->bytes) {
-          er_chunks = 0;
-          a.er_Tt = a.er_Gt = a.er_h = nullptr; a.er_slabs_v = a.er_slabs_u = nullptr;
-        }
-      }
-      if (cx.fmt) {   // (depends on the arguments only: asked before the launch, valid for it)
-        const unsigned short f = (unsigned short)cara_gemm_rider_slab_format(&a, Rp, ts_rank(cx, Rp));
-        if (take) cx.fmt->U[pend->slot][pend->layer] = f;
-        cx.fmt->V[L.slot][cx.layer] = f;
-      }
-#ifdef CARA_ABLATE_DVS   // timing experiment only (tools/build_variant.sh): fc1 / qkv dX WITHOUT their own dVs products (wrong gradients) --
-      // the bound on what computing dVs from the dX tile's own A sub-buffers could return
-      if ((L.slot == 0 || L.slot == 2) && g_inside) {
-        if (take) TRY(cara_gemm_with_tskinny_r(&a, nullptr, 0, nullptr, nullptr, 0, pend->Xa, pend->ldxa, pend->Gta, pend->slabs_a, pend->K1a, 0, ldt, Mr, Rp,
-                                               ts_rank(cx, Rp), st));
-        else TRY(cara_gemm_bf16(&a, st));
-        *pend = mine;
-        return CARA_OK;
-      }
-#endif
-      TRY(cara_gemm_with_tskinny_r(&a, take ? pend->Xa : nullptr, take ? pend->ldxa : 0, take ? pend->Gta : nullptr, take ? pend->slabs_a : nullptr,
-                                   take ? pend->K1a : 0, mine.Xb, mine.ldxb, mine.Gtb, mine.slabs_b, mine.K1b, mine.want_cs, ldt, Mr, Rp,
-                                   ts_rank(cx, Rp), st));
-      if (er_chunks) {   // (nothing of this linear waits: its dU is in the slabs the epilogue wrote)
-        pend->valid = false;
-        er->done = true;
-        if (cx.fmt) cx.fmt->U[L.slot][cx.layer] = (unsigned short)er_chunks;
-        return CARA_OK;
-      }
-      *pend = mine;   // (its dU half waits for the next dX GEMM of the pass; flush_pending runs it alone otherwise)
-      return CARA_OK;
-    }
-    // which pair this launch carries: the one that waits (deferred), else its own
-    const TsPending* carry = nullptr;
-    if (can_carry) {
-      if (defer) carry = (pend->valid && pend->Rp == Rp) ? pend : nullptr;
-      else if (!inside) carry = &mine;
-    }
-#ifdef CARA_ABLATE_TS   // timing experiment only (tools/build_variant.sh): the dX GEMMs WITHOUT their riding products (wrong gradients)
-    if (carry) { TRY(cara_gemm_bf16(&a, st)); return CARA_OK; }
-#endif
-    if (carry && cx.fmt) {
-      const unsigned short f = (unsigned short)cara_gemm_rider_slab_format(&a, carry->Rp, ts_rank(cx, carry->Rp));
-      cx.fmt->U[carry->slot][carry->layer] = f;
-      cx.fmt->V[carry->slot][carry->layer] = f;
-    }
-    if (carry) {
-      TRY(cara_gemm_with_tskinny_r(&a, carry->Xa, carry->ldxa, carry->Gta, carry->slabs_a, carry->K1a, carry->Xb, carry->ldxb, carry->Gtb,
-                                   carry->slabs_b, carry->K1b, carry->want_cs, carry->ldg, carry->M, carry->Rp, ts_rank(cx, carry->Rp), st));
-      if (carry == pend) pend->valid = false;
-      if (carry == &mine) return CARA_OK;
-    } else {
+  }
+  if (!carries) {   // nothing rides (no dX, few rows, CARA_FUSE_TS=0): what waits and this linear's pair run as launches of their own
+    if (want_dx) {
+      SiteBracket b(SITE_BWD[slot], cx);
       TRY(cara_gemm_bf16(&a, st));
     }
+    TRY(flush_waiting(cx, Rp, ldt));
+    return launch_products(cx, &dU, &dVs, Rp, ldt, st);
   }
-  if (defer) {
-    TRY(flush_pending(cx));   // (a pair that found no carrier -- none waits in the steady state)
-    *pend = mine;
-    return CARA_OK;
+  SiteBracket b(SITE_BWD[slot], cx);
+  // the dU of the linear before rides here when it has this launch's rows (fc2's, the 77-MB read of h, thus leaves the two-round fc2
+  // dX launch for the single-round fc1 dX launch; a dU never shares an operand with its own dX GEMM, so it loses nothing elsewhere)
+  if (pass.waiting.X && pass.waiting.M != Mr) TRY(flush_waiting(cx, Rp, ldt));
+  const Product* carried = pass.waiting.X ? &pass.waiting : nullptr;
+  // the placements whose products the launch computes itself: one slab per row tile (chunk); Own where the launch or the scratch says no
+  int chunks = 0;
+  if (where == Riders::ATiles) {
+    cara_gemm_args d = a;
+    d.er_Tt = dVs.Gt; d.er_ldg = ldt; d.er_slabs_v = dVs.slabs; d.er_colsum = dVs.colsum;
+    chunks = cara_gemm_dv_chunks(&d, carried ? 1 : 0);
+    if (chunks > 0 && chunks <= 65535 && cara_gemm_epi_rider_scratch_bytes(chunks, L.out) <= W.strideV[slot]) a = d;
+    else where = Riders::Own;
   }
-  if (pend) TRY(flush_pending(cx));
-  return cara_tskinny_partial2_r(X, ldx, Gt, slabU, L.in, dY, lddy, Tt, slabV, L.out, want_dc ? 1 : 0, ldt, Mr, Rp, ts_rank(cx, Rp), st);
+  if (where == Riders::Epilogue) {   // (this linear is fc2, X its saved input h; the dVs the epilogue computes is fc1's)
+    cara_gemm_args d = a;
+    d.er_Tt = ws + lw.Tt[2]; d.er_Gt = Gt; d.er_slabs_v = ws + W.slabV[2] + (size_t)layer * W.strideV[2]; d.er_slabs_u = dU.slabs; d.er_ldg = ldt; d.er_colsum = 1;
+    d.er_h = X; d.er_h_panels = ldx < 0 ? -ldx : 0;
+    chunks = cara_gemm_epi_rider_chunks(&d);
+    const size_t room = W.strideV[2] < W.strideU[3] ? W.strideV[2] : W.strideU[3];
+    if (chunks > 0 && chunks <= 65535 && cara_gemm_epi_rider_scratch_bytes(chunks, L.in) <= room) a = d;
+    else where = Riders::Own;
+  }
+  switch (where) {
+    case Riders::Own:
+      TRY(gemm_with_riders(cx, a, carried, &dVs, Rp, ldt));
+      break;
+    case Riders::Epilogue:   // (nothing of this linear waits: its dU is in the slabs the epilogue wrote)
+      TRY(gemm_with_riders(cx, a, carried, &dVs, Rp, ldt));
+      *dU.format = pass.formats.V[2][layer] = (unsigned short)chunks;   // (fc1's dVs slabs: the same launch, the same count of row tiles)
+      pass.epilogue_ran = true;
+      pass.waiting = Product{};
+      return CARA_OK;
+    case Riders::DoneAbove:
+      TRY(gemm_with_riders(cx, a, carried, nullptr, Rp, ldt));
+      break;
+    case Riders::ATiles:
+      TRY(gemm_with_riders(cx, a, carried, nullptr, Rp, ldt));
+      *dVs.format = (unsigned short)chunks;
+      break;
+    case Riders::BothHome:   // (the dU that waits stays for the next launch)
+      return gemm_with_riders(cx, a, &dU, &dVs, Rp, ldt);
+    case Riders::Side: {
+      SideStream* ss = side_stream();
+      if (!ss) return CARA_E_LAUNCH;
+      if (hipEventRecord(ss->fork, static_cast<hipStream_t>(st)) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess) return CARA_E_LAUNCH;
+      TRY(launch_products(cx, carried, &dVs, Rp, ldt, ss->stream, true));
+      if (hipEventRecord(ss->join, ss->stream) != hipSuccess) return CARA_E_LAUNCH;
+      pass.side_join = true;
+      TRY(cara_gemm_bf16(&a, st));
+      break;
+    }
+  }
+  pass.waiting = dU;   // (until the next dX GEMM of the pass)
+  return CARA_OK;
 }
 
 // ---- order-2 QKV tensorisation: the QKV linear as y = x W^T + x Dm^T with the dense scaled delta Dm (cara_dense_delta_*) ----
@@ -731,12 +662,6 @@ bool g_inside_enabled(int slot) {   // CARA_GEMM_G_INSIDE: bit 0 qkv, bit 1 fc1 
   return (v & (slot == 0 ? 1 : 2)) != 0;
 }
 
-// A linear's dU = X^T G' rides in the NEXT dX GEMM of the pass, its dVs in its own (lin_bwd); CARA_DEFER_DU=0: both in its own
-bool defer_du() {
-  static const int v = env_once("CARA_DEFER_DU", 1);
-  return v != 0 && !defer_ts();
-}
-
 // CARA_SAVE_GELU_GRAD (default: on where CARA_EPI_RIDERS is): fc1 forward keeps gelu'(u) (IEEE half) instead of the pre-activation u, and
 // the fc2 dX epilogue is one multiply per element instead of the erf arithmetic (CARA_EPI_GELU_DG / CARA_EPI_MULH, include/cara_hip.h).
 // Where the LayerNorms compute T = X U (the forward's fc1 GEMM then never has the adapter inside, a form the new epilogue does not
@@ -749,11 +674,6 @@ static int epi_riders_env() {
 bool save_gelu_grad(const cara_geom* g, const cara_vit_shape* s) {
   static const int v = env_once("CARA_SAVE_GELU_GRAD", -1);
   return (v < 0 ? epi_riders_env() != 0 : v != 0) && fuse_xu(g) && !s->wd_exact;
-}
-
-static bool env_once_dv_off() {   // (the epilogue riders and CARA_DV are two placements of the same product)
-  static const int v = env_once("CARA_DV", 0);
-  return v == 0;
 }
 
 // CARA_EPI_RIDERS (default 0): fc1's dVs = dH^T T (+ dc) and fc2's dU = h^T G' are computed by the epilogue of the fc2 dX GEMM, on the dH
@@ -945,6 +865,37 @@ static bool tile_policy(const cara_geom* g, int M, int N, int K, int riders) {
   return g->Rp == 32 && g->rank > 0 && g->rank <= 16 && cara_gemm8_policy(M, N, K, riders);
 }
 
+// Which launch of a block's backward computes which products (Riders), decided once per block from the geometry, the block's rows
+// (Mr: all M token rows, or the cls rows of the last block) and the switches.  proj always takes Own.  The three placements other
+// than Own are measured and off; all need launches that carry products (fuse_ts), one r-tile (Rp = 32,
+// rank <= 16) and the factored mode, and exclude one another: the epilogue riders and CARA_DV are two placements of the same product.
+struct BlockPlan {
+  Riders fc2 = Riders::Own, fc1 = Riders::Own, qkv = Riders::Own;
+  bool dh_panels = false;   // fc2's dX GEMM writes dH K-panel-major (fc1's dX GEMM stays on the 128-tile family)
+};
+BlockPlan plan_block(const cara_geom* g, const cara_vit_shape* s, int M, int Mr, bool cls_only) {
+  static const int fc1_side = env_once("CARA_FC1_SIDE", 0);
+  const int D = g->dim;
+  const bool ex = s->wd_exact != 0;
+  const bool one_rtile = g->Rp == 32 && g->rank > 0 && g->rank <= 16;
+  const bool can = !ex && one_rtile && fuse_ts(Mr, g->Rp);
+  const bool fc1_tile = g_inside_enabled(2) && tile_policy(g, Mr, D, 4 * D, 0);   // fc1's dX GEMM without riders runs on the 160 x 256 x 64 tile
+  BlockPlan p;
+  if (can && dv_env() == 0 && epi_riders_geom(g, Mr, ex)) {
+    p.fc2 = Riders::Epilogue;
+    p.fc1 = Riders::DoneAbove;
+  } else if (can && !cls_only && (dv_env() & 1) && fc1_tile) {
+    p.fc2 = Riders::BothHome;
+    p.fc1 = Riders::ATiles;
+  } else if (can && fc1_side != 0 && fc1_tile && side_stream() != nullptr) {
+    p.fc1 = Riders::Side;
+  }
+  if (can && !cls_only && (dv_env() & 2) && g_inside_enabled(0) && tile_policy(g, M, D, 3 * D, 0)) p.qkv = Riders::ATiles;
+  // (dH as fc1's dX GEMM reads it: row-major where that launch runs on the tile, which it does sooner where it carries nothing)
+  p.dh_panels = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, p.fc1 == Riders::Own ? 1 : 0);
+  return p;
+}
+
 // The forward behind both entries: the image is either fp32 (`images`) or resident uint8 pixels with their per-channel
 // mean / std (`pixels`); everything behind the patch rows is the same.
 static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
@@ -1083,11 +1034,9 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
   if (s && s->inference != 0 && !s->wd_exact) return CARA_E_ARG;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !dlogits || !workspace || !grads || !dhead_w || !dhead_b) return CARA_E_ARG;
   char* ws = static_cast<char*>(workspace);
-  TsPending pending;
-  SlabFormats formats;
-  Ctx cx{stream, ws + W.gemm_scratch, 0, false, &pending};
-  cx.rank = g->rank;
-  cx.fmt = &formats;
+  BwdPass pass;
+  const SlabFormats& formats = pass.formats;
+  Ctx cx{stream, ws + W.gemm_scratch, 0, false, &pass, g->rank};
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const int D = g->dim, M = W.M, Rp = g->Rp, B = s->B, N = s->tokens;
   const float att_scale = 1.0f / sqrtf((float)(D / g->heads));
@@ -1116,7 +1065,6 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
   const bool fx = fuse_xu(g) && !ex;
   const bool dense_qkv = g->cp_length == 2;
   bool have_G_fc2 = false;   // G' of this block's fc2 was left by the LayerNorm backward of the block above
-  SideRiders side;
   for (int l = g->depth - 1; l >= 0; --l) {
     const LayerWs& lw = W.layer[l];
     Lin lin[4];
@@ -1144,37 +1092,21 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
     // panels -- except in the last block, where the final norm's backward left it row-major on the cls rows.
     // (h as the forward wrote it: row-major where fc2 forward runs on the 160 x 256 x 64 tile; dH: row-major where fc1 dX does)
     const bool pa_x = panel_acts(M, s, 2) && !dense_qkv, pa = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, 0), pa_n = panel_acts(Mr, s, 2);
-    // fc1's dVs / dc and fc2's dU out of the fc2 dX epilogue: the fc1 dX launch then carries nothing and runs on the 160 x 256 x 64 tile
-    const bool er_on = epi_riders_geom(g, Mr, ex) && ts_rank(cx, Rp) <= 16 && fuse_ts(Mr, Rp) && defer_du() && env_once_dv_off();
-    // CARA_DV (default 0; bit 0: fc1, bit 1: qkv): dVs (+ dc) of fc1 / qkv out of their dX GEMM's own A tiles on the 160 x 256 x 64 tile;
-    // CARA_DV_DU_HOME (default 1): fc2 then carries BOTH its products in its own launch, and the dU waiting from the block above rides
-    // behind fc1's tiles (19 MB instead of fc2's 77)
-    static const int dv_env = env_once("CARA_DV", 0), dv_home = env_once("CARA_DV_DU_HOME", 1);
-    const bool dv_ok = dv_env != 0 && !ex && Rp == 32 && ts_rank(cx, Rp) <= 16 && fuse_ts(Mr, Rp) && defer_du() && !cls_only;
-    const bool dv_fc1 = dv_ok && (dv_env & 1) && g_inside_enabled(2) && tile_policy(g, Mr, D, 4 * D, 0);
-    const bool dv_qkv = dv_ok && (dv_env & 2) && g_inside_enabled(0) && tile_policy(g, M, D, 3 * D, 0);
-    static const int fc1_side = env_once("CARA_FC1_SIDE", 0);
-    const bool side_on = fc1_side != 0 && !er_on && !ex && Rp == 32 && ts_rank(cx, Rp) <= 16 && fuse_ts(Mr, Rp) && defer_du() && g_inside_enabled(2) &&
-                         tile_policy(g, Mr, D, 4 * D, 0) && !dv_fc1 && side_stream() != nullptr;
-    side.ss = side_on ? side_stream() : nullptr;
-    EpiRider er;
-    er.Tt = ws + lw.Tt[2];
-    er.slabV = ws + W.slabV[2] + (size_t)l * W.strideV[2];
-    er.bytes = W.strideV[2] < W.strideU[3] ? W.strideV[2] : W.strideU[3];
-    const bool pa_dh = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, (er_on || side_on || dv_fc1) ? 0 : 1);
+    const BlockPlan plan = plan_block(g, s, M, Mr, cls_only);
+    const bool pa_dh = plan.dh_panels;
+    pass.epilogue_ran = false;
     const bool pa_dp = panel_acts(Mr, s, 4), pa_dx = panel_acts(M, s, 4);   // dyp here; dyb of the block below
     const bool pa_dyb = pa_dx && l < g->depth - 1;
     if (pa_dh) { e.c_panels = Mr; e.ldc = 4 * D; }
     if (ex) TRY(lin_bwd_exact(lin[3], dyb, reinterpret_cast<bf16*>(ws + lw.h), Mr, Rp, ws, W, s, true, e, true, cx));
     else TRY(lin_bwd(lin[3], dyb, pa_dyb ? -M : ldr, reinterpret_cast<bf16*>(ws + lw.h), pa ? -Mr : 4 * D, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx,
-                     have_G_fc2, er_on ? &er : nullptr, false, nullptr, (dv_fc1 && dv_home) ? 2 : 0));
-    if (er.done) formats.V[2][l] = formats.U[3][l];   // (fc1's dVs slabs: the same launch, the same count of row tiles)
+                     plan.fc2, have_G_fc2));
+    const Riders fc1 = (plan.fc1 == Riders::DoneAbove && !pass.epilogue_ran) ? Riders::Own : plan.fc1;   // (the epilogue said no: fc1 carries its own)
     have_G_fc2 = false;
     e = {};
     e.epi = CARA_EPI_BF16; e.C = ws + W.dXn;
     if (ex) TRY(lin_bwd_exact(lin[2], dH, reinterpret_cast<bf16*>(ws + lw.xn2), Mr, Rp, ws, W, s, true, e, true, cx));
-    else TRY(lin_bwd(lin[2], dH, pa_dh ? -Mr : 4 * D, reinterpret_cast<bf16*>(ws + lw.xn2), pa_n ? -Mr : D, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx, false,
-                     nullptr, er.done, side_on ? &side : nullptr, dv_fc1 ? 1 : 0));
+    else TRY(lin_bwd(lin[2], dH, pa_dh ? -Mr : 4 * D, reinterpret_cast<bf16*>(ws + lw.xn2), pa_n ? -Mr : D, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx, fc1));
     // dyp = dY of this block's proj: its G' = dY Vs comes out of the same kernel (CARA_LN2B_XU=0: out of proj's dX GEMM instead)
     static const int ln2b_xu = env_once("CARA_LN2B_XU", 1);
     const bool fxp = fx && (ln2b_xu != 0 || cls_only);
@@ -1190,7 +1122,7 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
     const bool cls_attn = cls_only && cls_attention_enabled();   // (then only the cls rows of dAO are ever read)
     if (cls_only && !cls_attn && hipMemsetAsync(ws + W.dAO, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
     if (ex) TRY(lin_bwd_exact(lin[1], dyp, reinterpret_cast<bf16*>(ws + lw.ao), Mr, Rp, ws, W, s, true, e, true, cx));
-    else TRY(lin_bwd(lin[1], dyp, pa_dp ? -Mr : ldr, reinterpret_cast<bf16*>(ws + lw.ao), ldr, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx, fxp));
+    else TRY(lin_bwd(lin[1], dyp, pa_dp ? -Mr : ldr, reinterpret_cast<bf16*>(ws + lw.ao), ldr, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx, Riders::Own, fxp));
     {
       SiteBracket sb(CARA_SITE_ATTN_BWD, cx_all);
       if (cls_attn)
@@ -1207,13 +1139,12 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
     else if (dense_qkv)
       TRY(lin_bwd_dense(lin[0], dQKV, reinterpret_cast<bf16*>(ws + lw.xn1), M, reinterpret_cast<bf16*>(ws + W.ddt) + (size_t)l * 3 * D * D,
                         reinterpret_cast<float*>(ws + W.dD) + (size_t)l * 3 * D * D, reinterpret_cast<float*>(ws + W.dd_slabs), l > 0, e, cx_all));
-    else TRY(lin_bwd(lin[0], dQKV, 3 * D, reinterpret_cast<bf16*>(ws + lw.xn1), pa_x ? -M : D, M, Rp, W.ldt, ws, W, lw, l > 0, e, false, cx_all, false, nullptr,
-                     false, nullptr, dv_qkv ? 1 : 0));
+    else TRY(lin_bwd(lin[0], dQKV, 3 * D, reinterpret_cast<bf16*>(ws + lw.xn1), pa_x ? -M : D, M, Rp, W.ldt, ws, W, lw, l > 0, e, false, cx_all, plan.qkv));
     // the side stream's products read dH and G' of fc2, which the kernels below overwrite: the caller's stream waits for them (they
     // were launched some 300 us ago)
-    if (side.pending_join) {
-      if (hipStreamWaitEvent(hs, side.ss ? side.ss->join : side_stream()->join, 0) != hipSuccess) return CARA_E_LAUNCH;
-      side.pending_join = false;
+    if (pass.side_join) {
+      if (hipStreamWaitEvent(hs, side_stream()->join, 0) != hipSuccess) return CARA_E_LAUNCH;
+      pass.side_join = false;
     }
     if (l > 0) {
       // dyb = dY of fc2 of the block BELOW (all M rows there: only the last block runs on cls rows); this block's
@@ -1228,7 +1159,7 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
       have_G_fc2 = fx;
     }
   }
-  TRY(flush_pending(cx));   // block 0's qkv products have no dX GEMM behind them
+  TRY(flush_waiting(cx, Rp, W.ldt));   // (block 0's proj dU still waits where its qkv is not lin_bwd's: order 2)
   if (!ex) {   // (the exact mode wrote dU / dVs / dc of every layer directly)
     const int ins[4] = {D, D, D, 4 * D}, outs[4] = {3 * D, D, 4 * D, D};
     const int L = g->depth;

@@ -1288,6 +1288,45 @@ def test_odd_ranks_token_counts_and_batches(rank, img, batch, precision):
     assert worst < grad_bar(precision), worst
 
 
+_SCHEDULE_CASES = {}
+
+
+def _schedule_case(batch, depth=3, rank=16, img=96):
+    """Inputs and oracle results of one schedule-regimes case, computed once and shared by the precisions (read-only)."""
+    if batch not in _SCHEDULE_CASES:
+        from oracle import cara_oracle as O
+        w = O.synthetic_backbone(depth=depth, img=img)
+        cp = O.synthetic_cp(rank=rank, depth=depth)
+        x, y = O.synthetic_batch(batch=batch, img=img)
+        with torch.no_grad():
+            ref = O.vit_cara_forward(x, w, cp, s=0.1, depth=depth)
+            sim = O.vit_cara_forward(x, w, cp, s=0.1, depth=depth, factored=True, bf16_sim=True)
+        head = {"weight": w["head.weight"], "bias": w["head.bias"]}
+        _, _, gref = O.train_step_as_written(x, y, w, cp, head, s=0.1, depth=depth)
+        _SCHEDULE_CASES[batch] = (w, cp, x, y, ref, sim, gref)
+    return _SCHEDULE_CASES[batch]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("batch", [28, 112])
+def test_backward_schedule_regimes_with_a_middle_block(batch, precision):
+    """The backward's schedule of riding products at depth 3, rank 16, 96 px (37 tokens), whole model against the oracle: a first
+    block (whose qkv has no dX launch: what waits is flushed and its pair runs alone), a middle block (a dU waits from one block's
+    qkv launch to the next block's fc2 launch) and the cls-rows-only last block (Mr = batch < 1024: nothing rides).  Batch 28,
+    M = 1036: the products ride behind 128-tile GEMMs; batch 112, M = 4144 = 16 x 259: the 160 x 256 x 64 tile with its per-wave /
+    per-chunk slab formats, the only regime in which the CARA_EPI_RIDERS / CARA_FC1_SIDE / CARA_DV placements engage."""
+    from oracle import cara_oracle as O
+    depth, rank, img = 3, 16, 96
+    w, cp, x, y, ref, sim, gref = _schedule_case(batch, depth, rank, img)
+    m = build(w, cp, rank, 0.1, depth, img, precision=precision).eval()
+    logits = m(x.to(DEV))
+    check_logits(logits, ref, sim, precision, f"depth {depth}, {img} px, batch {batch} (M = {batch * 37})")
+    torch.nn.functional.cross_entropy(logits, y.to(DEV)).backward()
+    worst = max(rel(getattr(m, n).grad, gref[n]) for n in O.CP_NAMES)
+    print(f"depth {depth}, {img} px, batch {batch} [{precision}]: worst CP gradient {worst:.2e}")
+    assert worst < grad_bar(precision), worst
+
+
 def test_forward_and_backward_capture_into_a_hip_graph():
     """include/cara_hip.h promises that cara_vit_forward / cara_vit_backward only enqueue work on the caller's stream (no
     allocation, no synchronisation, no state): the pair must therefore capture into a hipGraph, and replaying the graph must
@@ -1333,13 +1372,15 @@ def test_rider_placement_switches_pass_the_whole_model_parity_tests(switch):
     """Three measured-and-off placements of the backward's heavy riders (read once per process): CARA_EPI_RIDERS=1 -- fc1's dVs / dc and
     fc2's dU out of the fc2 dX epilogue, gelu'(u) kept as IEEE half by fc1 forward; CARA_FC1_SIDE=1 -- the same products as a launch on a
     side stream under the fc1 dX GEMM; CARA_DV=3 -- fc1's and qkv's dVs / dc out of the A tiles of their own dX GEMM.  The batch-64
-    whole-model test, the train-step test and the fp16 headline test run again in a process with the switch set."""
+    whole-model test, the train-step test, the fp16 headline test and the schedule-regimes test (M = 4144 with a middle block) run
+    again in a process with the switch set."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, **dict([switch.split("=")]))
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_model_gpu.py"), "-x", "-q", "-s", "-k",
-                          "headline_batch_64_whole_model or train_step_against_oracle or fp16_precision_at_the_headline_size"],
+                          "headline_batch_64_whole_model or train_step_against_oracle or fp16_precision_at_the_headline_size or "
+                          "backward_schedule_regimes_with_a_middle_block"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     tail = "\n".join(out.stdout.strip().split("\n")[-12:])
     print(tail)
