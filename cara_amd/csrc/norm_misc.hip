@@ -322,6 +322,13 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
 // operation order of data.normalize_u8 -- u / 255, - mean[c], / std[c], two correctly rounded divisions (no reciprocal
 // multiply: the build has no fast-math flag) -- then the one rounding to the build's 16-bit type that im2col_kernel applies
 // to the fp32 image.  The fp32 image tensor is never written.  Four pixels (one dword) per lane.
+__device__ __forceinline__ bf16x4 normalize_u8x4(unsigned u, float mu, float sd) {
+  const float v0 = ((float)(u & 255u) / 255.0f - mu) / sd;
+  const float v1 = ((float)((u >> 8) & 255u) / 255.0f - mu) / sd;
+  const float v2 = ((float)((u >> 16) & 255u) / 255.0f - mu) / sd;
+  const float v3 = ((float)(u >> 24) / 255.0f - mu) / sd;
+  return bf16x4{(bf16)v0, (bf16)v1, (bf16)v2, (bf16)v3};
+}
 __global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ mean,
                                                         const float* __restrict__ stdv, bf16* __restrict__ out,
                                                         int B, int C, int Hi, int Wi, int p, long total4) {
@@ -336,13 +343,47 @@ __global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restric
   const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
   const int gy = pr / gw, gx = pr % gw;
   const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)b * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
-  const float mu = mean[c], sd = stdv[c];
-  const float v0 = ((float)(u & 255u) / 255.0f - mu) / sd;
-  const float v1 = ((float)((u >> 8) & 255u) / 255.0f - mu) / sd;
-  const float v2 = ((float)((u >> 16) & 255u) / 255.0f - mu) / sd;
-  const float v3 = ((float)(u >> 24) / 255.0f - mu) / sd;
-  bf16x4 o = {(bf16)v0, (bf16)v1, (bf16)v2, (bf16)v3};
-  *reinterpret_cast<bf16x4*>(out + e) = o;
+  *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
+}
+
+// im2col_u8_kernel over rows of a whole resident split [n_split,C,Hi,Wi] chosen by an index vector: the patch rows of sample b
+// come from image rows[b] (any order, duplicates allowed).  An index outside [0, n_split) is never dereferenced: that sample's
+// patch rows are zeros, and the lane that writes their first dword counts the sample in *bad (may be NULL).
+__global__ __launch_bounds__(256) void im2col_u8_rows_kernel(const uint8_t* __restrict__ img, long n_split,
+                                                             const int64_t* __restrict__ rows, const float* __restrict__ mean,
+                                                             const float* __restrict__ stdv, bf16* __restrict__ out,
+                                                             int* __restrict__ bad, int B, int C, int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const int kcols = C * p * p;
+  const long e = idx * 4;
+  const long row = e / kcols;
+  const int col = (int)(e - row * kcols);
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
+  const int gy = pr / gw, gx = pr % gw;
+  const int64_t r = rows[b];
+  if (r < 0 || r >= n_split) {
+    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
+    const bf16 z = (bf16)0.0f;
+    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
+    return;
+  }
+  const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)r * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
+  *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
+}
+
+// out[i] = labels[rows[i]]; a row outside [0, n_split) is not dereferenced: it gives 0 and is counted in *bad (may be NULL)
+__global__ __launch_bounds__(256) void gather_labels_kernel(const int64_t* __restrict__ labels, long n_split,
+                                                            const int64_t* __restrict__ rows, int64_t* __restrict__ out,
+                                                            int B, int* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const int64_t r = rows[i];
+  const bool ok = r >= 0 && r < n_split;
+  if (!ok && bad) atomicAdd(bad, 1);
+  out[i] = ok ? labels[r] : 0;
 }
 
 __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__ emb, const float* __restrict__ cls,
@@ -631,6 +672,28 @@ extern "C" int cara_im2col_patches_u8(const unsigned char* pixels, const float* 
   const long total4 = (long)B * C * Hi * Wi / 4;
   hipLaunchKernelGGL(im2col_u8_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      pixels, mean, stdv, (bf16*)patches, B, C, Hi, Wi, p, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_im2col_patches_u8_rows(const unsigned char* pixels, int n_split, const int64_t* rows, const float* mean,
+                                           const float* stdv, void* patches, int* bad, int B, int C, int Hi, int Wi, int p,
+                                           void* stream) {
+  if (!pixels || !rows || n_split <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi % p || Wi % p || (Wi & 3))
+    return CARA_E_ARG;
+  if (reinterpret_cast<uintptr_t>(pixels) & 3) return CARA_E_ARG;   // (with p % 4 == 0 and Wi % 4 == 0 every image starts dword-aligned)
+  const long total4 = (long)B * C * Hi * Wi / 4;
+  hipLaunchKernelGGL(im2col_u8_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     pixels, (long)n_split, rows, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
+                                  void* stream) {
+  if (!labels || !rows || !out || n_split <= 0 || B <= 0) return CARA_E_ARG;
+  hipLaunchKernelGGL(gather_labels_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     labels, (long)n_split, rows, out, B, bad);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }

@@ -896,11 +896,13 @@ BlockPlan plan_block(const cara_geom* g, const cara_vit_shape* s, int M, int Mr,
   return p;
 }
 
-// The forward behind both entries: the image is either fp32 (`images`) or resident uint8 pixels with their per-channel
-// mean / std (`pixels`); everything behind the patch rows is the same.
+// The forward behind the three entries: the image is either fp32 (`images`) or resident uint8 pixels with their per-channel
+// mean / std (`pixels`: the batch itself, or with `rows` a whole split of `n_split` images that `rows` indexes); everything
+// behind the patch rows is the same.
 static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                             const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
-                            const unsigned char* pixels, const float* mean, const float* stdv,
+                            const unsigned char* pixels, int n_split, const int64_t* rows, int* bad,
+                            const float* mean, const float* stdv,
                             const float* droppath, void* workspace, float* logits, void* stream) {
   Ws W;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !workspace || !logits) return CARA_E_ARG;
@@ -915,7 +917,9 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
   if (dense_qkv) TRY(cara_dense_delta_materialize(g, cp, ws + W.dd, ws + W.ddt, stream));
   // patch embedding: Conv2d(k = s = patch) as a GEMM over im2col rows, then cls + pos_embed
   const int kp = s->chans * s->patch * s->patch;
-  if (pixels) TRY(cara_im2col_patches_u8(pixels, mean, stdv, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
+  if (pixels && rows)
+    TRY(cara_im2col_patches_u8_rows(pixels, n_split, rows, mean, stdv, ws + W.patches, bad, B, s->chans, s->img, s->img, s->patch, stream));
+  else if (pixels) TRY(cara_im2col_patches_u8(pixels, mean, stdv, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
   else TRY(cara_im2col_patches(images, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
   cara_gemm_args a = {};
   a.A = ws + W.patches; a.lda = kp; a.B = w->patch_w; a.ldb = kp; a.M = B * P; a.N = D; a.K = kp;
@@ -1015,7 +1019,8 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
 extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                                 const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
                                 const float* droppath, void* workspace, float* logits, void* stream) {
-  return vit_forward_body(g, s, w, cp, head_w, head_b, images, nullptr, nullptr, nullptr, droppath, workspace, logits, stream);
+  return vit_forward_body(g, s, w, cp, head_w, head_b, images, nullptr, 0, nullptr, nullptr, nullptr, nullptr, droppath, workspace,
+                          logits, stream);
 }
 
 extern "C" int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
@@ -1023,7 +1028,17 @@ extern "C" int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, 
                                    const float* mean, const float* stdv, const float* droppath, void* workspace, float* logits,
                                    void* stream) {
   if (!pixels) return CARA_E_ARG;
-  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, mean, stdv, droppath, workspace, logits, stream);
+  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, 0, nullptr, nullptr, mean, stdv, droppath, workspace, logits,
+                          stream);
+}
+
+extern "C" int cara_vit_forward_u8_rows(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                        const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                        int n_split, const int64_t* rows, const float* mean, const float* stdv,
+                                        const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
+  if (!pixels || !rows || n_split <= 0) return CARA_E_ARG;
+  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, n_split, rows, bad, mean, stdv, droppath, workspace, logits,
+                          stream);
 }
 
 extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,

@@ -130,6 +130,27 @@ class ResidentSplit:
                 yield normalize_u8(self.pixels.index_select(0, idx)), self.labels.index_select(0, idx)
         return epoch_iter
 
+    def train_rows(self, batch_size: int = 64, seed: int = 0, rank: Optional[int] = None,
+                   world: Optional[int] = None) -> Callable[[int], Iterator[torch.Tensor]]:
+        """``f(epoch)`` -> iterator of int64 [batch_size] index vectors on the device: the indices ``train_batches`` draws
+        (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
+        and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
+        and uploaded once as one [steps, batch_size] tensor; every step gets a row view of it."""
+        rank = D.get_rank() if rank is None else rank
+        world = D.world_size() if world is None else world
+
+        def epoch_iter(epoch: int):
+            idx = D.epoch_shard(len(self), epoch, rank, world, batch_size, seed)
+            if not idx:
+                return
+            table = torch.stack(idx)
+            if int(table.min()) < 0 or int(table.max()) >= len(self):
+                raise ValueError(f"epoch {epoch}: a drawn index is outside [0, {len(self)})")
+            table = table.to(self.pixels.device)
+            for step in range(table.shape[0]):
+                yield table[step]
+        return epoch_iter
+
     def eval_batches(self, batch_size: int = 256) -> Callable[[], Iterator[Tuple[torch.Tensor, torch.Tensor]]]:
         """In file order, last batch partial (vtab.py:96-100: shuffle False, no drop_last)."""
         def it():
@@ -158,14 +179,17 @@ class ResidentSplit:
 
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
-             seed: int = 0, workers: int = 8, shard_eval: bool = False):
+             seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
     ``shard_eval = True``: the second value is the test ``ResidentSplit`` itself, the form ``fit(eval_mode="sharded")`` and
-    ``CaraEngine.evaluate`` take (every rank then scores its own part, ``ResidentSplit.eval_shard``)."""
+    ``CaraEngine.evaluate`` take (every rank then scores its own part, ``ResidentSplit.eval_shard``).
+    ``resident_feed = True``: the first value is ``(train split, its train_rows(batch_size, seed=seed))``, the form
+    ``fit(feed="resident")`` takes: the steps read the split's uint8 pixels by index instead of a normalised fp32 batch."""
     root = root if root is not None else "./data/vtab-1k/" + name
     tr, te = ("train800val200.txt", "test.txt") if evaluate else ("train800.txt", "val200.txt")
     train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers)
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
-    return train.train_batches(batch_size, seed=seed), (test if shard_eval else test.eval_batches(256))
+    feed = (train, train.train_rows(batch_size, seed=seed)) if resident_feed else train.train_batches(batch_size, seed=seed)
+    return feed, (test if shard_eval else test.eval_batches(256))

@@ -120,6 +120,10 @@ class CaraEngine:
     def _lib(self):
         return L.lib(self._operands())
 
+    def _refuse_fp16_unfactored(self):
+        if self.precision == "fp16" and (self.weight_dropout == "exact" or self.cp_length == 2):
+            raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
+
     # ------------------------------------------------------------------ frozen weights -> HBM layout
     def _backbone_params(self, model):
         return [p for n, p in model.named_parameters() if not n.startswith("CP_") and not n.startswith("head.")]
@@ -227,8 +231,15 @@ class CaraEngine:
         with torch.cuda.device(dev):   # the library enqueues on the stream it is given and launches on the current device
             return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev)
 
-    def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev):
-        st = self._state(model, images.shape[0], images.shape[2], dev)
+    def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None):
+        """``resident = (split, rows)``: the images are rows of a resident uint8 split (``images`` is None then)"""
+        if resident is None:
+            st = self._state(model, images.shape[0], images.shape[2], dev)
+        else:
+            split, rows = resident
+            st = self._state(model, rows.shape[0], split.pixels.shape[2], dev)
+            if st["shape"].chans != 3:
+                raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
         # weight-space dropout is a train-mode thing (nn.Dropout is the identity in eval); the backward of this
         # forward reads the same struct, i.e. the same seed, and regenerates the masks
         use_exact = self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0
@@ -247,9 +258,16 @@ class CaraEngine:
         st["shape"].inference = 0 if need_backward else 1
         cps = self._cp_ptrs([t.detach().contiguous() for t in cp])
         logits = torch.empty_like(st["logits"])
-        check(self._lib().cara_vit_forward(C.byref(st["geom"]), C.byref(st["shape"]), C.byref(self._ingested[1]), C.byref(cps),
-                                       ptr(head_w.detach().contiguous()), ptr(head_b.detach().contiguous()), ptr(images),
-                                       ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)), "cara_vit_forward")
+        args = (C.byref(st["geom"]), C.byref(st["shape"]), C.byref(self._ingested[1]), C.byref(cps),
+                ptr(head_w.detach().contiguous()), ptr(head_b.detach().contiguous()))
+        if resident is None:
+            check(self._lib().cara_vit_forward(*args, ptr(images), ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)),
+                  "cara_vit_forward")
+        else:
+            mean, std = self._eval_norm(dev)
+            check(self._lib().cara_vit_forward_u8_rows(*args, ptr(split.pixels), len(split), ptr(rows), ptr(mean), ptr(std),
+                                                       ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)),
+                                                       stream(dev)), "cara_vit_forward_u8_rows")
         self._fwd_serial += 1
         self._bwd_ready = self._fwd_serial if need_backward else -1
         return logits
@@ -371,8 +389,7 @@ class CaraEngine:
         self._need_backward = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         if self.precision not in ("bf16", "fp16"):
             raise CaraError(f"precision must be 'bf16' or 'fp16', not {self.precision!r}")
-        if self.precision == "fp16" and (self.weight_dropout == "exact" or self.cp_length == 2):
-            raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
+        self._refuse_fp16_unfactored()
         return _VitFn.apply(self, images, droppath, *params)
 
     # ------------------------------------------------------------------ fused train step
@@ -419,24 +436,31 @@ class CaraEngine:
         process group has more than one rank -> ``optimizer.step()``.  Returns the loss (device
         scalar, local to this rank).  ``p.grad`` of every trainable parameter is a view of the flat
         buffer, so any torch optimizer consumes it unchanged."""
-        model = self._model()
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
+        return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp),
+                          lambda: labels.contiguous(), optimizer, group, droppath)
+
+    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath):
+        """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
+        head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
+        (called inside the step, on ``dev``)."""
+        model = self._model()
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
         if not hasattr(model.head, "weight"):
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
         hw, hb = model.head.weight, model.head.bias
         if hw.device != dev or any(t.device != dev for t in cp):
             raise CaraError("model parameters and images must be on the same device")
-        if self.precision == "fp16" and (self.weight_dropout == "exact" or self.cp_length == 2):
-            raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
+        self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
-                droppath = self.draw_droppath(model, images.shape[0], dev)
-            logits = self._run_forward(images, droppath, hw, hb, cp)
+                droppath = self.draw_droppath(model, B, dev)
+            logits = forward(droppath, hw, hb, cp)
+            labels = labels_of()
             B, ncls = logits.shape
             if self.__dict__.get("_loss_buf") is None or self._loss_buf.numel() != 1 + B or self._loss_buf.device != dev:
                 self._loss_buf = torch.empty(1 + B, device=dev)
@@ -448,12 +472,85 @@ class CaraEngine:
             from .dist import world_size
             fp16 = self.precision == "fp16"
             gv = self._grad_buffers(model, dev)
-            check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels.contiguous()), ptr(self._loss_buf), ptr(self._dlogits),
+            check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(self._loss_buf), ptr(self._dlogits),
                                                     B, ncls, C.c_float(1.0 / world_size(group)), ptr(self._amp(dev)) if fp16 else None,
                                                     ptr(gv["_found_inf"]) if fp16 else None, stream(dev)), "cara_cross_entropy_ex")
             self._run_backward(self._dlogits, droppath, hw, cp, prescaled=True)
             self._apply_gradients(optimizer, group, prescaled=True)
         return self._loss_buf[0]
+
+    # ------------------------------------------------------------------ training from a resident uint8 split
+    def _bad_rows(self, dev):
+        """device int32 [1] per device: samples whose row index was outside the split (cara_im2col_patches_u8_rows and
+        cara_gather_labels count them instead of reading); never read inside a step -- resident_bad_rows()"""
+        dev = self._norm_device(dev)
+        bad = self.__dict__.setdefault("_bad", {})
+        if dev not in bad:
+            bad[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+        return bad[dev]
+
+    def resident_bad_rows(self) -> int:
+        """Out-of-range row indices counted since the last call (an image row and its label row count one each); reads and
+        clears the counter: one host read."""
+        n = 0
+        for t in self.__dict__.get("_bad", {}).values():
+            n += int(t.item())
+            t.zero_()
+        return n
+
+    def _resident_args(self, split, rows):
+        model = self._model()
+        dev = model.head.weight.device if hasattr(model.head, "weight") else None
+        if dev is None:
+            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+        if dev.type != "cuda":
+            raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
+        px, lb = getattr(split, "pixels", None), getattr(split, "labels", None)
+        if px is None or lb is None or px.dtype != torch.uint8 or px.ndim != 4 or px.shape[1] != 3 or px.shape[2] != px.shape[3] or px.device != dev \
+                or not px.is_contiguous() or lb.dtype != torch.int64 or lb.device != dev or lb.shape != px.shape[:1] or len(split) != px.shape[0]:
+            raise CaraError("split must be a ResidentSplit (uint8 [N,3,H,H] pixels, int64 [N] labels) on the model's device")
+        if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.device != dev or rows.ndim != 1 or rows.shape[0] == 0 \
+                or not rows.is_contiguous():
+            raise CaraError("rows must be a contiguous int64 [batch] tensor on the model's device")
+        return model, dev
+
+    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward):
+        model = self._model()
+        dev = rows.device
+        with torch.cuda.device(dev):
+            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows))
+
+    def _gather_labels(self, split, rows):
+        dev, B = rows.device, rows.shape[0]
+        # one buffer per (device, batch size), never replaced: a captured step holds its address, and a step of another batch
+        # size in between must not free it (8 bytes per sample)
+        bufs = self.__dict__.setdefault("_labels_bufs", {})
+        buf = bufs.get((dev, B))
+        if buf is None:
+            buf = bufs[(dev, B)] = torch.empty(B, dtype=torch.int64, device=dev)
+        check(self._lib().cara_gather_labels(ptr(split.labels.contiguous()), len(split), ptr(rows), ptr(buf), B, ptr(self._bad_rows(dev)),
+                                             stream(dev)), "cara_gather_labels")
+        return buf
+
+    def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None):
+        """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
+        ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
+        (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
+        else is train_step's.  A row outside the split is not read: it trains on a zero image with label 0 and is counted
+        (``resident_bad_rows``)."""
+        _, dev = self._resident_args(split, rows)
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True),
+                          lambda: self._gather_labels(split, rows), optimizer, group, droppath)
+
+    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None):
+        """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools)"""
+        model, dev = self._resident_args(split, rows)
+        cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
+        self._refuse_fp16_unfactored()
+        with torch.no_grad(), torch.cuda.device(dev):
+            if droppath is None:
+                droppath = self.draw_droppath(model, rows.shape[0], dev)
+            return self._forward_rows(split, rows, droppath, model.head.weight, model.head.bias, cp, False)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):

@@ -106,7 +106,9 @@ class GraphedTrainStep:
     and learning rates live in device memory).  One graph per (batch shape, train / eval mode): the first call with a new key runs
     eagerly (weights ingested, workspaces sized), the second captures, later ones copy the batch into the graph's input buffers,
     upload { step, lr } and replay.  What a capture cannot hold runs eagerly, every time: more than one rank (the all-reduce) and the
-    exact weight-dropout mode (a fresh host-side seed per step).  Same switch as ``bench.py --graph``."""
+    exact weight-dropout mode (a fresh host-side seed per step).  Same switch as ``bench.py --graph``.
+    The resident form ``step(split, rows)`` captures ``train_step_resident``: one graph per (split, shape of ``rows``, mode), whose
+    only static input is the index vector -- 8 bytes per sample are copied per step, no image."""
 
     def __init__(self, engine, optimizer):
         if not getattr(optimizer, "capturable", False):
@@ -115,33 +117,41 @@ class GraphedTrainStep:
         self._graphs = {}
 
     def __call__(self, x, y, group=None):
+        """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
+        resident = hasattr(x, "pixels")
+        step = eng.train_step_resident if resident else eng.train_step
         self.opt.advance()
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
-            return eng.train_step(x, y, self.opt, group=group)
-        key = (tuple(x.shape), bool(model.training), eng.precision)
+            return step(x, y, self.opt, group=group)
+        # (the split itself is part of a resident key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
+        key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
-            return eng.train_step(x, y, self.opt, group=group)
+            return step(x, y, self.opt, group=group)
+        dev = y.device
         if ent == "warm":
-            xs, ys = x.clone(), y.clone()
-            torch.cuda.synchronize(x.device)
+            xs, ys = (x if resident else x.clone()), y.clone()
+            torch.cuda.synchronize(dev)
             gr = torch.cuda.CUDAGraph()
-            gen = eng._device_generator(x.device)
+            gen = eng._device_generator(dev)
             if gen is not None:
                 gr.register_generator_state(gen)
-            side = torch.cuda.Stream(x.device)
-            side.wait_stream(torch.cuda.current_stream(x.device))
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 with torch.cuda.graph(gr, stream=side):
-                    loss = eng.train_step(xs, ys, self.opt, group=group)
-            torch.cuda.current_stream(x.device).wait_stream(side)
-            ent = self._graphs[key] = (gr, xs, ys, loss)
+                    loss = step(xs, ys, self.opt, group=group)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            # (the last element keeps what the engine would replace at an eager step of another batch size in between -- its dlogits
+            # buffer and the workspace of this shape -- as ``loss`` keeps its loss buffer: the graph holds their addresses)
+            ent = self._graphs[key] = (gr, xs, ys, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
             # (the capture itself ran nothing: fall through to the replay, which is this call's step)
-        gr, xs, ys, loss = ent
-        xs.copy_(x)
+        gr, xs, ys, loss = ent[:4]
+        if not resident:
+            xs.copy_(x)
         ys.copy_(y)
         gr.replay()
         return loss
@@ -150,7 +160,7 @@ class GraphedTrainStep:
 def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[Callable[[], Iterable]] = None,
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
         on_eval: Optional[Callable[[int, float], None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
-        graph: bool = False, eval_mode: str = "reference"):
+        graph: bool = False, eval_mode: str = "reference", feed: str = "batches"):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -168,9 +178,16 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``eval_mode = "sharded"``: ``test_batches`` is a ``data.ResidentSplit`` (or a callable returning batches in the form of
     its ``eval_shard``) and the evaluation epochs run ``CaraEngine.evaluate`` on it -- every rank scores its own part of
     the split on the device and all of them get the global top-1 accuracy.  ``"reference"`` (default): ``evaluate`` below
-    over ``test_batches()``, on every rank."""
+    over ``test_batches()``, on every rank.
+    ``feed = "resident"``: ``train_batches`` is ``(split, rows_of)`` -- a ``data.ResidentSplit`` on the model's device and its
+    ``train_rows(...)`` (``get_data(resident_feed=True)`` returns the pair) -- and every step is ``CaraEngine.train_step_resident``
+    on an index vector: the same samples in the same order as ``split.train_batches(...)`` with the same seed, without the
+    normalised fp32 batch.  An index outside the split is counted on the device, not read; the count is looked at where the
+    evaluation epochs read from the device anyway and once more after the last epoch, and a non-zero one raises."""
     if eval_mode not in ("reference", "sharded"):
         raise CaraError(f"eval_mode must be 'reference' or 'sharded', not {eval_mode!r}")
+    if feed not in ("batches", "resident"):
+        raise CaraError(f"feed must be 'batches' or 'resident', not {feed!r}")
     from . import dist as cdist
     model.train()
     params = trainable_parameters(model)
@@ -188,17 +205,31 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     eng = model._cara_engine
     gstep = GraphedTrainStep(eng, opt) if graph else None
     best = 0.0
+    if feed == "resident":
+        split, rows_of = train_batches
+        train_batches = lambda epoch: ((split, rows) for rows in rows_of(epoch))   # noqa: E731
+        step = eng.train_step_resident
+    else:
+        step = eng.train_step
+
+    def check_rows(upto):
+        # (data parallel: a rank that raised alone would leave the others waiting in the next all-reduce.  train_rows range-checks
+        # an epoch's indices on the host before it uploads them, on every rank, so only a hand-made feed can get here)
+        bad = eng.resident_bad_rows() if feed == "resident" else 0
+        if bad:
+            raise CaraError(f"fit: {bad} row index(es) outside the training split reached the device up to epoch {upto}")
     for epoch in range(epochs):
         for x, y in train_batches(epoch):
             if gstep is not None:
                 gstep(x, y, group=group)
             else:
-                eng.train_step(x, y, opt, group=group)
+                step(x, y, opt, group=group)
             if sched is not None:
                 sched.step(epoch)
         if epoch % 10 == 0 and epoch != 0:
             if epoch >= 50:
                 sched = None
+            check_rows(epoch)
             if test_batches is not None:
                 if eval_mode == "sharded":
                     acc = eng.evaluate(test_batches, group=group)["top1"]
@@ -217,4 +248,5 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
                     on_eval(epoch, acc)
                 if not reference_eval_quirk:
                     model.train()
+    check_rows(epochs - 1)   # one host read per fit: the epochs after the last evaluation, or a fit shorter than 11 epochs
     return best, opt

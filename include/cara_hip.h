@@ -301,6 +301,16 @@ int cara_im2col_patches(const float* img, void* patches, int B, int C, int Hi, i
  * image is never written; the rows are bitwise those of cara_im2col_patches on the fp32 image so computed.          */
 int cara_im2col_patches_u8(const unsigned char* pixels, const float* mean, const float* std, void* patches,
                            int B, int C, int Hi, int Wi, int p, void* stream);
+/* cara_im2col_patches_u8 over rows of a whole resident split: pixels uint8 [n_split,C,Hi,Wi], rows device int64 [B] (any
+ * order, duplicates allowed); the patch rows of sample i come from image rows[i], same arithmetic and rounding points.  An
+ * index outside [0, n_split) is never dereferenced: that sample's patch rows are zeros and *bad (device int, may be NULL;
+ * the caller clears it) is incremented once per such sample.                                                            */
+int cara_im2col_patches_u8_rows(const unsigned char* pixels, int n_split, const int64_t* rows, const float* mean,
+                                const float* std, void* patches, int* bad, int B, int C, int Hi, int Wi, int p, void* stream);
+/* out[i] = labels[rows[i]] (device int64 [B] each; labels int64 [n_split]); a row outside [0, n_split) is not
+ * dereferenced: it gives 0 and is counted in *bad (device int, may be NULL)                                    */
+int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
+                       void* stream);
 /* x fp32 [B,1+P,D]: row 0 = cls + pos[0]; row 1+i = emb[b*P+i] + pos[1+i]                      */
 int cara_assemble_tokens(const float* emb, const float* cls, const float* pos, float* x, int B,
                          int P, int D, void* stream);
@@ -528,6 +538,13 @@ int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, const cara_
                         const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
                         const float* mean, const float* std, const float* droppath, void* workspace, float* logits,
                         void* stream);
+/* cara_vit_forward_u8 on B images of a whole resident split (pixels uint8 [n_split,chans,img,img]) chosen by the device
+ * index vector rows (int64 [B]): the patch rows come from cara_im2col_patches_u8_rows (bad: its counter, may be NULL), every
+ * later stage is shared; on a workspace of either size, and a cara_vit_backward may follow as after cara_vit_forward.      */
+int cara_vit_forward_u8_rows(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                             const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                             int n_split, const int64_t* rows, const float* mean, const float* std, const float* droppath,
+                             void* workspace, float* logits, int* bad, void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,

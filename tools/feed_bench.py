@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Time the training step of the headline configuration (ViT-B/16 + CaRA rank 16, batch 64, 224 px, DropPath 0.1, factored
+adapters, AdamW) over a synthetic resident split of 1 000 uint8 images under its two feeds:
+
+  batches   ResidentSplit.train_batches + CaraEngine.train_step: index upload, index_select, four normalisation passes, then
+            the patch rows from the fp32 batch (under --graph also the copy of the batch into the graph's static input);
+  resident  ResidentSplit.train_rows + CaraEngine.train_step_resident: one index upload per epoch, the patch rows straight
+            from the uint8 pixels by index.
+
+Eager and from a hipGraph (recipe.GraphedTrainStep).  The legs run interleaved in one process -- per round a window of
+--steps steps of each, barrier + synchronize on both sides of a window, after --warmup steps of every leg -- and the line
+printed says ms per step of each leg (median / min / max over the rounds) and the run-to-run spread of each.  Standalone:
+not part of bench.py."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=1000)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=60, help="steps per timed window")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--depth", type=int, default=12)
+    ap.add_argument("--rank", type=int, default=16)
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"])
+    ap.add_argument("--legs", default="eager,graph")
+    args = ap.parse_args()
+    import torch.distributed as dist
+    from cara_amd import cara, create_model
+    from cara_amd.data import ResidentSplit
+    from cara_amd.optim import AdamW
+    from cara_amd.recipe import GraphedTrainStep
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(14)
+    m = create_model("vit_base_patch16_224_in21k", depth=args.depth, num_classes=100, drop_path_rate=0.1)
+    m = cara({"model": m, "rank": args.rank, "scale": 0.1, "l_mu": 1.5, "l_std": 0.1, "precision": args.precision})
+    g = torch.Generator().manual_seed(3)
+    with torch.no_grad():   # non-zero adapters, as bench.py's model
+        m.CP_A2.copy_(0.05 * torch.randn(m.CP_A2.shape, generator=g))
+        m.CP_P2.copy_(0.05 * torch.randn(m.CP_P2.shape, generator=g))
+    m = m.to(dev).train()
+    eng = m._cara_engine
+    eng.seed_rank_streams(2024, 0)
+    for n, p in m.named_parameters():
+        p.requires_grad = "CP" in n or "head" in n
+    opt = AdamW(eng.trainable_parameters(), lr=1e-3, weight_decay=1e-4, capturable=True)
+    gd = torch.Generator(device=dev).manual_seed(1)
+    px = torch.randint(0, 256, (args.images, 3, 224, 224), generator=gd, dtype=torch.uint8, device=dev)
+    y = torch.randint(0, 100, (args.images,), generator=gd, device=dev)
+    split = ResidentSplit.from_tensors(px, y)
+
+    def feeder(of_epoch):
+        """the feed's items across epochs, as a training loop draws them"""
+        epoch = 0
+        while True:
+            yield from of_epoch(epoch)
+            epoch += 1
+
+    gstep = GraphedTrainStep(eng, opt)
+
+    def eager_batches(item):
+        opt.advance()
+        return eng.train_step(item[0], item[1], opt)
+
+    def eager_resident(rows):
+        opt.advance()
+        return eng.train_step_resident(split, rows, opt)
+    legs = {}
+    for mode in args.legs.split(","):
+        if mode == "eager":
+            legs["eager/batches"] = (feeder(split.train_batches(args.batch)), eager_batches)
+            legs["eager/resident"] = (feeder(split.train_rows(args.batch)), eager_resident)
+        elif mode == "graph":
+            legs["graph/batches"] = (feeder(split.train_batches(args.batch)), lambda item: gstep(item[0], item[1]))
+            legs["graph/resident"] = (feeder(split.train_rows(args.batch)), lambda rows: gstep(split, rows))
+        else:
+            raise SystemExit(f"unknown leg {mode!r}")
+
+    def fence():
+        if dist.is_available() and dist.is_initialized():
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+
+    def window(name, steps):
+        feed, step = legs[name]
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            loss = step(next(feed))
+        fence()
+        return (time.perf_counter() - t0) * 1e3 / steps, loss
+
+    for name in legs:
+        window(name, args.warmup)
+    ms = {name: [] for name in legs}
+    last = {}
+    for _ in range(args.rounds):
+        for name in legs:
+            t, loss = window(name, args.steps)
+            ms[name].append(t)
+            last[name] = float(loss)
+    res = {"config": {"model": "vit_base_patch16_224_in21k", "depth": args.depth, "batch": args.batch, "rank": args.rank,
+                      "images": args.images, "precision": args.precision, "steps_per_window": args.steps, "rounds": args.rounds,
+                      "warmup": args.warmup, "device": torch.cuda.get_device_name(dev)}}
+    for name, ts in ms.items():
+        med = statistics.median(ts)
+        res[name] = {"ms_per_step": [round(t, 4) for t in ts], "median": round(med, 4), "min": round(min(ts), 4), "max": round(max(ts), 4),
+                     "spread_ms": round(max(ts) - min(ts), 4), "last_loss": last[name]}
+    for mode in args.legs.split(","):
+        b, r = res[f"{mode}/batches"], res[f"{mode}/resident"]
+        res[f"{mode}/resident_minus_batches_ms"] = round(r["median"] - b["median"], 4)
+        res[f"{mode}/not_slower_within_batches_spread"] = bool(r["median"] - b["median"] <= b["spread_ms"])
+    res["bad_rows"] = eng.resident_bad_rows()
+    for name, v in ms.items():
+        print(f"{name:15s} {statistics.median(v):8.4f} ms/step (min {min(v):.4f}, max {max(v):.4f})")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
