@@ -24,15 +24,18 @@
 // tile with DMA-only loader waves -- live in tools/experimental/, outside the library.)
 // Also here: the adapter-inside form (gemm32ft_*: T = A Ut^T accumulated on the tiles the workgroup streams anyway, Rp = 32 or
 // 64), the forms that carry a pair of transposed skinny products behind their tiles (gemm32_ts_kernel, gemm32ft_ts_kernel),
-// the two-B-operand form of the exact weight-dropout mode (one K loop, both B tiles on the same A fragments), 8-wave
-// 192 / 256-row tiles (a switch: measured a tie), and gemm_tn_kernel (C = At^T Bt from row-major operands through
-// transposing LDS reads: the dense dW of the exact mode).
+// the two-B-operand form of the exact weight-dropout mode (one K loop, both B tiles on the same A fragments), the few-row kernel
+// (small_m_direct_kernel) and gemm_tn_kernel (C = At^T Bt from row-major operands through transposing LDS reads: the dense dW of
+// the exact mode).
+// Host side, at the end of the file: ONE plan per call (gemm_plan: validation, policy, family, tile, grid, LDS, riders) and
+// launchers that only turn a plan into a template instantiation; the tile of gemm8.hip answers through cara_gemm8_plan.
 #include <stdlib.h>
 
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "tskinny_body.h"
 #include "gemm8.h"
+#include "gemm_dispatch.h"
 
 #ifdef CARA_GEMM_STAMPS
 // Diagnostic build (tools/gemm_stamps.py): wave 0 of every workgroup records s_memrealtime (100 MHz) at its start, at the
@@ -407,17 +410,6 @@ __global__ __launch_bounds__(256, (TWOB || ER || (MI == 5 && (EPI == CARA_EPI_RE
   gemm32_body<EPI, MI, 4, TWOB, ER>(p, tiles_n, nwg, gm, blockIdx.x, blockIdx.y, smem);
 }
 
-// 8-wave workgroups (4 along M x 2 along N, 64-column wave tiles): MI = 3 -> 192 x 128 tiles, MI = 4 -> 256 x 128.  For the
-// N = 768 products: their 594 tiles of 128 rows put THREE workgroups on 82 of the 256 CUs and two on the rest, and a CU's
-// K loops run at what its load path delivers, so the launch lasts as long as three tiles on one CU;
-// 66 x 6 = 396 tiles of 192 rows are at most two per CU, 0.83 of the staged bytes per flop, and two 8-wave workgroups keep
-// 16 waves feeding the path.
-template <int EPI, int MI>
-__global__ __launch_bounds__(512, 4) void gemm32w8_kernel(const cara_gemm_args p, const int tiles_n, const int nwg, const int gm) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemm32_body<EPI, MI, 8>(p, tiles_n, nwg, gm, blockIdx.x, 0, smem);
-}
-
 // The dX GEMM of a linear and the two transposed skinny products of the SAME linear (dU = X^T G', dVs = dY^T T) in
 // one grid: blocks [0, nts) are tskinny blocks (HBM-bound, one LDS stage per wave), the rest GEMM tiles (MFMA-bound).
 // The products used to run on a side stream under the GEMM, which costs a fork (an event record = 3..7 us of idle
@@ -656,184 +648,12 @@ __global__ __launch_bounds__(256, NU == 1 ? 4 : 3) void gemm32ft_ts_kernel(const
   else gemm32ft_body<EPI, NU, HALFT>(p, tiles_n, nwg, gm, b, smem);
 }
 
-static int group_m(int tiles_n);
-struct TsPair;
-template <int EPI>
-int launch32ft(const cara_gemm_args* a, hipStream_t st, const TsPair* ts = nullptr);
-
-// rows per supertile (1 = plain row-major order)
-static int group_m(int tiles_n) {
-  // measured with rocprofv3 FETCH_SIZE (x2 gfx950 correction), per launch, plain order -> groups of 8:
-  // fc1 fwd (24 column tiles) 224 -> 133 MB, fc2 bwd 297 -> 207 MB, but the 6-column products
-  // 82 -> 113 MB and qkv (18 columns) flat: group only when there are many column tiles
-  static const int gm_wide = [] { const char* e = getenv("CARA_GEMM_GM"); return e ? atoi(e) : 8; }();       // (A/B: rows per supertile of the wide products)
-  static const int gm_minn = [] { const char* e = getenv("CARA_GEMM_GM_MINT"); return e ? atoi(e) : 20; }();   // (A/B: fewest column tiles that get supertiles)
-  if (tiles_n >= gm_minn) return gm_wide > 0 ? gm_wide : 1;
-  // CARA_GEMM_CUSHARE=1: the narrow products (plain order) with the workgroups of a CU on consecutive tiles (xcd_remap_cu)
-  static const int cushare = [] { const char* e = getenv("CARA_GEMM_CUSHARE"); return e ? atoi(e) : 0; }();
-  return (cushare && tiles_n <= 8) ? -1 : 1;
-}
-
-// the transposed skinny products a GEMM launch can carry (cara_gemm_with_tskinny)
-struct TsPair {
-  TsProblem a, b;
-  int ldg, M;
-  bool any_cs;
-  int nt;   // column tiles of 16 the products compute: Rp / 16 = 2 or 4, or 1 at Rp = 32 and rank <= 16
-};
-
-// one launch of the GEMM-with-riders kernel: COLSUM and NT (the products' Rp / 16) picked at run time
-template <int EPI, int MI, bool ER = false>
-void launch_ts(const cara_gemm_args* a, hipStream_t st, const TsPair* ts, int tiles_n, int nwg, int gm, int gemm_lds) {
-  const int nts = ts->a.nblk + ts->b.nblk;
-  const dim3 grid(nwg + nts), block(256);
-#define TS_GO(CS, NT)                                                                                                       \
-  do {                                                                                                                      \
-    constexpr int RB = TsRing<NT, 1>::BLOCK_BYTES;                                                                          \
-    const int lds = RB > gemm_lds ? RB : gemm_lds;                                                                          \
-    hipLaunchKernelGGL((gemm32_ts_kernel<EPI, CS, MI, NT, ER>), grid, block, lds, st, *a, tiles_n, nwg, gm, ts->a, ts->b, ts->ldg, ts->M); \
-  } while (0)
-  if constexpr (ER) {   // (epilogue riders: rank <= 16, so are the products that ride as workgroups)
-    if (ts->any_cs) TS_GO(true, 1); else TS_GO(false, 1);
-    return;
-  }
-  if (ts->nt == 4) {
-    if (ts->any_cs) TS_GO(true, 4); else TS_GO(false, 4);
-  } else if (ts->nt == 1) {   // rank <= 16: the products compute 16 of their 32 columns (16-wide slabs)
-    if (ts->any_cs) TS_GO(true, 1); else TS_GO(false, 1);
-  } else {
-    if (ts->any_cs) TS_GO(true, 2); else TS_GO(false, 2);
-  }
-#undef TS_GO
-}
-
-template <int EPI>
-int launch32ft(const cara_gemm_args* a, hipStream_t st, const TsPair* ts) {
-  const int tiles_n = (a->N + BN - 1) / BN;
-  const int gm = group_m(tiles_n);
-  const int nwg = ((a->M + 127) / 128) * tiles_n;
-  // consumers read Tt in whole 32-row steps: keep columns [M, roundup32(M)) zero, as cara_skinny_xu does
-  const int m32 = (a->M + 31) / 32 * 32;
-  if (a->Tt_out && m32 > a->M && m32 <= a->ldt &&
-      hipMemset2DAsync(static_cast<bf16*>(a->Tt_out) + a->M, (size_t)a->ldt * 2, 0, (size_t)(m32 - a->M) * 2, a->Rp, st) != hipSuccess)
-    return CARA_E_LAUNCH;
-  const int lds1 = 2 * (128 * BK32 * 2 + B32_BYTES + 32 * BK32 * 2), lds2 = 2 * (128 * BK32 * 2 + B32_BYTES + 64 * BK32 * 2);
-  if (ts) {   // (plain bf16 output only: the backward's fc1 / qkv dX)
-    if constexpr (EPI == CARA_EPI_BF16) {
-      const bool half = a->Rp == 32 && ts->nt == 1;   // rank <= 16: one r-tile in the riding products, 16 columns of the adapter inside
-      if (ts->nt != a->Rp / 16 && !half) return CARA_E_ARG;
-      if (half && !(a->Ut_rank > 0 && a->Ut_rank <= 16)) return CARA_E_ARG;
-      const dim3 grid(nwg + ts->a.nblk + ts->b.nblk), block(256);
-      constexpr int RB = TsRing<2, 1>::BLOCK_BYTES;   // the same for every NT (two-pass combine)
-#define FT_GO(NU, CS, L, NTS, HT)                                                                                           \
-      hipLaunchKernelGGL((gemm32ft_ts_kernel<EPI, NU, CS, NTS, HT>), grid, block, (RB > L ? RB : L), st, *a, tiles_n, nwg, gm, ts->a, ts->b, ts->ldg, ts->M)
-      if (a->Rp == 64) {
-        if (ts->any_cs) FT_GO(2, true, lds2, 4, false); else FT_GO(2, false, lds2, 4, false);
-      } else if (half) {
-        if (ts->any_cs) FT_GO(1, true, lds1, 1, true); else FT_GO(1, false, lds1, 1, true);
-      } else {
-        if (ts->any_cs) FT_GO(1, true, lds1, 2, false); else FT_GO(1, false, lds1, 2, false);
-      }
-#undef FT_GO
-      CARA_CHECK_LAUNCH();
-      return CARA_OK;
-    } else {
-      return CARA_E_ARG;
-    }
-  }
-  if (a->Rp == 64) hipLaunchKernelGGL((gemm32ft_kernel<EPI, 2>), dim3(nwg), dim3(256), lds2, st, *a, tiles_n, nwg, gm);
-  else if (a->Ut_rank > 0 && a->Ut_rank <= 16) hipLaunchKernelGGL((gemm32ft_kernel<EPI, 1, true>), dim3(nwg), dim3(256), lds1, st, *a, tiles_n, nwg, gm);
-  else hipLaunchKernelGGL((gemm32ft_kernel<EPI>), dim3(nwg), dim3(256), lds1, st, *a, tiles_n, nwg, gm);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-// rows of the tile that carries epilogue riders: CARA_ER_ROWS = 128 (default: 64 accumulator registers leave room for the riders' 32 +
-// the operand buffers inside the 168 of three workgroups per CU) or 160
-static int er_rows() {
-  static const int v = [] { const char* e = getenv("CARA_ER_ROWS"); return e ? atoi(e) : 128; }();
-  return v == 160 ? 160 : 128;
-}
-// the 160-row tile takes the widest products (launch32)
-static bool tile160(const cara_gemm_args* a) {
-  static const int bm = [] { const char* e = getenv("CARA_GEMM_BM"); return e ? atoi(e) : 160; }();
-  static const int bm_minn = [] { const char* e = getenv("CARA_GEMM_BM_MINN"); return e ? atoi(e) : 3072; }();   // A/B: 2304 adds qkv forward
-  return bm == 160 && a->N >= bm_minn && a->M > 1024 && a->batch <= 1 && !a->B3;
-}
-
-template <int EPI>
-int launch32(const cara_gemm_args* a, hipStream_t st, const TsPair* ts = nullptr) {
-  const int tiles_n = (a->N + BN - 1) / BN;
-  const int gm = group_m(tiles_n);
-  const int nwg = ((a->M + 127) / 128) * tiles_n;
-  constexpr int GEMM_LDS = 2 * (128 * BK32 * 2 + B32_BYTES);
-  // CARA_GEMM_BM=160: the 160-row tile for the widest products (A/B)
-  // The 160-row tile for the widest products (N >= 3072: fc1 forward, fc2 dX).  CARA_GEMM_BM=128 keeps the 128-row tile (A/B runs:
-  // 9.22 -> 9.08 and 9.37 -> 9.28 ms per step on two boxes; for the N = 768 products, whose 594 / 474 tiles are a single
-  // round either way, it made no difference in the step and stays off)
-  // launches that carry riding products: the dX GEMMs' epilogues only
-  constexpr bool TS_EPI = EPI == CARA_EPI_BF16 || EPI == CARA_EPI_DGELU || EPI == CARA_EPI_MULH;
-  if (tile160(a)) {
-    constexpr int LDS160 = 2 * (160 * BK32 * 2 + B32_BYTES);
-    const int nwg5 = ((a->M + 159) / 160) * tiles_n;
-    if constexpr (EPI == CARA_EPI_MULH) {
-      if (a->er_Tt) {   // epilogue riders (checked by the caller: cara_gemm_epi_rider_chunks)
-        if (er_rows() == 160) {
-          constexpr int L = LDS160 > ER_LDS_BYTES ? LDS160 : ER_LDS_BYTES;
-          if (ts) launch_ts<EPI, 5, true>(a, st, ts, tiles_n, nwg5, gm, L);
-          else hipLaunchKernelGGL((gemm32_kernel<EPI, false, 5, true>), dim3(nwg5), dim3(256), L, st, *a, tiles_n, nwg5, gm);
-        } else {
-          constexpr int L = GEMM_LDS > ER_LDS_BYTES ? GEMM_LDS : ER_LDS_BYTES;
-          if (ts) launch_ts<EPI, 4, true>(a, st, ts, tiles_n, nwg, gm, L);
-          else hipLaunchKernelGGL((gemm32_kernel<EPI, false, 4, true>), dim3(nwg), dim3(256), L, st, *a, tiles_n, nwg, gm);
-        }
-        CARA_CHECK_LAUNCH();
-        return CARA_OK;
-      }
-    }
-    if (ts) {
-      if constexpr (TS_EPI) launch_ts<EPI, 5>(a, st, ts, tiles_n, nwg5, gm, LDS160);
-      else return CARA_E_ARG;
-    } else {
-      hipLaunchKernelGGL((gemm32_kernel<EPI, false, 5>), dim3(nwg5), dim3(256), LDS160, st, *a, tiles_n, nwg5, gm);
-    }
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
-  }
-  if (ts) {
-    if constexpr (TS_EPI) launch_ts<EPI, 4>(a, st, ts, tiles_n, nwg, gm, GEMM_LDS);
-    else return CARA_E_ARG;
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
-  }
-  // CARA_GEMM_W8 = 3 / 4: 192 x 128 / 256 x 128 tiles of 8 waves for the narrow products (N <= 1024)
-  static const int w8 = [] { const char* e = getenv("CARA_GEMM_W8"); return e ? atoi(e) : 0; }();
-  if ((w8 == 3 || w8 == 4) && a->N <= 1024 && a->M > 1024 && a->batch <= 1 && !a->B3) {
-    if (w8 == 3) {
-      const int nw = ((a->M + 191) / 192) * tiles_n;
-      hipLaunchKernelGGL((gemm32w8_kernel<EPI, 3>), dim3(nw), dim3(512), 2 * (192 * BK32 * 2 + B32_BYTES), st, *a, tiles_n, nw, gm);
-    } else {
-      const int nw = ((a->M + 255) / 256) * tiles_n;
-      hipLaunchKernelGGL((gemm32w8_kernel<EPI, 4>), dim3(nw), dim3(512), 2 * (256 * BK32 * 2 + B32_BYTES), st, *a, tiles_n, nw, gm);
-    }
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
-  }
-  const int nb = a->batch > 1 ? a->batch : 1;
-  if (a->B3) hipLaunchKernelGGL((gemm32_kernel<EPI, true>), dim3(nwg, nb), dim3(256), GEMM_LDS + 2 * B32_BYTES, st, *a, tiles_n, nwg, gm);
-  else hipLaunchKernelGGL((gemm32_kernel<EPI>), dim3(nwg, nb), dim3(256), GEMM_LDS, st, *a, tiles_n, nwg, gm);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
 // Few-row products (the last block's cls-row-only proj / fc1 / fc2 and their dX: M = batch rows): one 128-row tile
 // per 128 columns is 6-24 workgroups each walking all of K (24-96 K steps back to back: 20-70 us of latency).
-// With caller scratch the K loop is cut into slabs that run as ONE batched launch of the default kernel (fp32
-// partial products into scratch), and a small finishing kernel adds the slabs in fixed order, the rank-R term
-// T Vs^T, the bias, and applies the epilogue.
+// They get a kernel of their own (small_m_direct_kernel below) where the caller passes scratch (small_m_slabs()).
 // ---------------------------------------------------------------------------------------------
 // the tail of a few-row product for outputs (m, n .. n + 3), v = their A B^T sums: + the rank-R term T Vs^T, + bias, the epilogue
 template <int EPI>
@@ -882,8 +702,8 @@ __device__ __forceinline__ void small_m_finish4(const cara_gemm_args& p, const i
   }
 }
 
-// The few-row product in ONE launch (the default; CARA_SMALL_M_DIRECT=0: the batched split-K launch + the finishing kernel below,
-// 8 + 9 us per product, seven of them per step).  A workgroup of 8 waves owns ONE 16 x 16 output tile; its waves split K (wave w: the
+// The few-row product in ONE launch (it replaced a batched split-K launch + a finishing kernel, 8 + 9 us per product, seven of
+// them per step: docs/findings/r05.md).  A workgroup of 8 waves owns ONE 16 x 16 output tile; its waves split K (wave w: the
 // 32-wide K steps w, w + 8, ...), every MFMA operand fragment is one 16-byte global load per lane straight into registers (rows of
 // A / W are 64-byte runs: no LDS staging for a product whose operands are read once), six K steps of loads in flight; the eight
 // partial tiles meet in LDS, are added in a fixed order, and 64 threads finish four outputs of a row each (small_m_finish4).
@@ -948,62 +768,6 @@ __global__ __launch_bounds__(NW * 64) void small_m_direct_kernel(const cara_gemm
       small_m_finish4<EPI>(p, m, n0 + c4, v);
     }
   }
-}
-
-template <int EPI>
-__global__ __launch_bounds__(256) void small_m_finish_kernel(const cara_gemm_args p, const float* __restrict__ slabs, const int nslab) {
-  const int n4 = (p.N + 3) / 4;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.M * n4) return;
-  const int m = idx / n4, n = (idx - m * n4) * 4;
-  const size_t slab_stride = (size_t)p.M * p.N;
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool full = n + 4 <= p.N && (p.N & 3) == 0;
-  for (int s = 0; s < nslab; ++s) {
-    const float* src = slabs + s * slab_stride + (size_t)m * p.N + n;
-    if (full) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(src);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] += t[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (n + k < p.N) v[k] += src[k];
-    }
-  }
-  small_m_finish4<EPI>(p, m, n, v);
-}
-
-// K slabs of at least 128 columns, at most 16 of them; 0 = not worth it
-static int small_m_slabs(const cara_gemm_args* a) {
-  if (a->M > 128 || a->K < 512 || !a->scratch || a->Ut || a->batch > 1 || a->B3) return 0;
-  int s = a->K / 128;
-  if (s > 16) s = 16;
-  while (s > 1 && (a->K % (s * 64)) != 0) --s;   // equal slabs, each a multiple of 64 columns
-  if (s < 2 || (size_t)s * a->M * a->N * sizeof(float) > a->scratch_bytes) return 0;
-  return s;
-}
-
-template <int EPI>
-static int launch_small_m(const cara_gemm_args* a, int nslab, hipStream_t st) {
-  static const int direct = [] { const char* e = getenv("CARA_SMALL_M_DIRECT"); return e ? atoi(e) : 1; }();
-  if (direct) {   // (B: the row-major weights, also where a K-panel-major image exists)
-    const dim3 grid((a->N + 15) / 16, (a->M + 15) / 16);
-    if (a->K > 1024) hipLaunchKernelGGL((small_m_direct_kernel<EPI, 8>), grid, dim3(512), 0, st, *a);
-    else hipLaunchKernelGGL((small_m_direct_kernel<EPI, 4>), grid, dim3(256), 0, st, *a);
-    CARA_CHECK_LAUNCH();
-    return CARA_OK;
-  }
-  cara_gemm_args d = {};
-  d.A = a->A; d.lda = a->lda; d.B = a->B; d.ldb = a->ldb; d.M = a->M; d.N = a->N; d.K = a->K / nslab;
-  d.epi = CARA_EPI_F32; d.C = a->scratch; d.ldc = a->N;
-  d.batch = nslab; d.strideA = d.K; d.strideB = d.K; d.strideC = (long long)a->M * a->N;
-  const int rc = launch32<CARA_EPI_F32>(&d, st);
-  if (rc != CARA_OK) return rc;
-  const int n4 = (a->N + 3) / 4;
-  hipLaunchKernelGGL((small_m_finish_kernel<EPI>), dim3((a->M * n4 + 255) / 256), dim3(256), 0, st, *a, static_cast<const float*>(a->scratch), nslab);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
 }
 
 // B [N, K] row-major -> K-panel-major [K/32][N][32] (cara_gemm_args::Bp): one 16-byte chunk per thread
@@ -1170,7 +934,91 @@ extern "C" int cara_gemm_tn_f32(const void* At, int lda, const void* Bt, int ldb
   return CARA_OK;
 }
 
-static int gemm_bf16_impl(const cara_gemm_args* a, void* stream, const TsPair* ts);
+// ---------------------------------------------------------------------------------------------
+// The front end: which kernel serves a cara_gemm_bf16 / cara_gemm_with_tskinny_r call is decided ONCE, by gemm_plan(), from the
+// arguments and the riders' shape; it validates everything, reads every policy and launches nothing.  The launchers below it take
+// the plan, pick the template instantiation and launch.  The queries callers lay memory out by (cara_gemm_rider_slab_format,
+// cara_gemm_epi_rider_chunks, cara_gemm_dv_chunks) answer from the predicates the plan uses (docs/findings/gemm_plan.md).
+// ---------------------------------------------------------------------------------------------
+enum GemmFamily {
+  FAM_TILE8 = 1,       // the 160 x 256 x 64 one-workgroup-per-CU tile (gemm8.hip)
+  FAM_TILE8_256 = 2,   // its 256-row yardstick form (cara_debug_set_gemm8(256): plain products)
+  FAM_FT = 3,          // gemm32ft*: the adapter inside, 128-row tiles
+  FAM_G32 = 4,         // gemm32*: 128- or 160-row tiles
+  FAM_BATCHED = 5,     // gemm32_kernel, one product per blockIdx.y
+  FAM_FEW_ROWS = 6,    // small_m_direct_kernel: one 16 x 16 output tile per workgroup
+};
+struct GemmPlan {
+  int family;
+  int nt;                // riders: the column tiles of 16 they compute (0: the launch carries none)
+  bool colsum;           // riders: the second product leaves column sums
+  cara_g8_plan g8;       // FAM_TILE8*: tile rows, mode, helper waves, DV, grid, block, LDS (cara_gemm8_plan); the fields below: the other families
+  int tile_rows;         // rows of a tile
+  int tiles_n, nwg;      // column tiles, tile workgroups (the riders' blocks sit behind them)
+  int gm;                // rows per supertile (group_m)
+  int block, lds;        // threads per workgroup, dynamic LDS bytes
+  int batch;             // grid.y
+  bool er;               // epilogue riders (er_Tt with CARA_EPI_MULH)
+  bool twob;             // two B operands (B3)
+  int nu;                // adapter inside: Rp / 32
+  bool halft;            // adapter inside: the 16-column form (rank <= 16)
+};
+
+// the transposed skinny products a GEMM launch can carry (cara_gemm_with_tskinny)
+struct TsPair {
+  TsProblem a, b;
+  int ldg, M;
+  bool any_cs;
+  int nt;   // column tiles of 16 the products compute: Rp / 16 = 2 or 4, or 1 at Rp = 32 and rank <= 16
+};
+// ... = 1 where both the products (rank <= 16 at Rp = 32) and an adapter inside the launch (Ut_rank stated and <= 16) live in 16 columns
+static int riders_nt(const cara_gemm_args* a, int Rp, int rank) {
+  return (Rp == 32 && rank <= 16 && (!a->Ut || (a->Ut_rank > 0 && a->Ut_rank <= 16))) ? 1 : Rp / 16;
+}
+static cara_g8_riders g8_riders(const TsPair& ts) {
+  auto cp = [](const TsProblem& t) { return cara_g8_product{t.X, t.Gt, t.slabs, t.cs_slabs, t.ldx, t.K1, t.nchunks, t.nblk}; };
+  return cara_g8_riders{cp(ts.a), cp(ts.b), ts.ldg, ts.M, ts.any_cs ? 1 : 0, ts.nt};
+}
+static int ts_block_bytes(int nt) {   // LDS of a riding products' block (one stage per wave)
+  return nt == 4 ? TsRing<4, 1>::BLOCK_BYTES : (nt == 1 ? TsRing<1, 1>::BLOCK_BYTES : TsRing<2, 1>::BLOCK_BYTES);
+}
+
+// ---- policy ----
+// rows per supertile (1 = plain row-major order).  Measured with rocprofv3 FETCH_SIZE (x2 gfx950 correction), per launch, plain
+// order -> groups of 8: fc1 fwd (24 column tiles) 224 -> 133 MB, fc2 bwd 297 -> 207 MB, but the 6-column products 82 -> 113 MB
+// and qkv (18 columns) flat: group only when there are many column tiles
+constexpr int GM_ROWS = 8, GM_MIN_TILES_N = 20;
+static int group_m(int tiles_n) {
+  if (tiles_n >= GM_MIN_TILES_N) return GM_ROWS;
+  // CARA_GEMM_CUSHARE=1: the narrow products (plain order) with the workgroups of a CU on consecutive tiles (xcd_remap_cu)
+  static const int cushare = [] { const char* e = getenv("CARA_GEMM_CUSHARE"); return e ? atoi(e) : 0; }();
+  return (cushare && tiles_n <= 8) ? -1 : 1;
+}
+// rows of the tile that carries epilogue riders: CARA_ER_ROWS = 128 (default: 64 accumulator registers leave room for the riders' 32 +
+// the operand buffers inside the 168 of three workgroups per CU) or 160
+static int er_rows() {
+  static const int v = [] { const char* e = getenv("CARA_ER_ROWS"); return e ? atoi(e) : 128; }();
+  return v == 160 ? 160 : 128;
+}
+// The 160-row tile takes the widest products (N >= 3072: fc1 forward, fc2 dX).  CARA_GEMM_BM=128 keeps the 128-row tile (A/B runs:
+// 9.22 -> 9.08 and 9.37 -> 9.28 ms per step on two boxes; for the N = 768 products, whose 594 / 474 tiles are a single round
+// either way, it made no difference in the step and stays off)
+constexpr int BM160_MIN_N = 3072;
+static bool tile160(const cara_gemm_args* a) {
+  static const int bm = [] { const char* e = getenv("CARA_GEMM_BM"); return e ? atoi(e) : 160; }();
+  return bm == 160 && a->N >= BM160_MIN_N && a->M > 1024 && a->batch <= 1 && !a->B3;
+}
+// the few-row kernel takes: M <= 128 with caller scratch for K slabs of at least 128 columns, at most 16 of them (the conditions of
+// the split-K form the kernel replaced: they decide which calls it serves); 0 = not this product
+static int small_m_slabs(const cara_gemm_args* a) {
+  if (a->M > 128 || a->K < 512 || !a->scratch || a->Ut || a->batch > 1 || a->B3) return 0;
+  int s = a->K / 128;
+  if (s > 16) s = 16;
+  while (s > 1 && (a->K % (s * 64)) != 0) --s;   // equal slabs, each a multiple of 64 columns
+  if (s < 2 || (size_t)s * a->M * a->N * sizeof(float) > a->scratch_bytes) return 0;
+  return s;
+}
+
 // measurement tools only (tools/gemm8_bench.py): pick the tile family per call sequence inside one process -- 160 / 256: that tile for
 // every product it takes; 0: never; -1: the policy below decides (the default)
 static int g_gemm8_override = -1;
@@ -1185,6 +1033,10 @@ extern "C" int cara_debug_set_gemm8(int mt) {
   g_gemm8_override = mt;
   return CARA_OK;
 }
+static bool gemm8_env_on() {   // CARA_GEMM8=0 turns the tile off
+  static const int on = [] { const char* e = getenv("CARA_GEMM8"); return e ? atoi(e) : 160; }();
+  return on == 160;
+}
 // Which products run on the 160 x 256 x 64 tile (same-box A/Bs of the step, profiles/r04_b_*): the long-K, narrow-N ones --
 //   * fc2 forward (K = 4 dim, N = dim, the adapter inside: 86 -> 74 us) and qkv dX (K = 3 dim, with its riding products as
 //     workgroups behind the tiles: 64.7 -> 60.3 us);
@@ -1192,23 +1044,246 @@ extern "C" int cara_debug_set_gemm8(int mt) {
 //     reads h) that the 128 x 128 x 32 kernel streams under its four resident workgroups per CU (87 us in all); one tile per CU
 //     leaves them to the end (100 us) or to helper waves that cost the tile more than they hide (92 us).  riders = 1 asks for a
 //     launch that carries products: K <= CARA_GEMM8_MAXK_TS (2304) then.
-// CARA_GEMM8=0 turns the tile off, CARA_GEMM8_MINK / _MAXN / _MAXK_TS move the bounds (A/B runs).  Callers that lay activations
-// out for a GEMM (vit.hip: K-panel-major h / dH) ask here first: the tile reads row-major operands.
+// CARA_GEMM8_MINK / _MAXN / _MAXK_TS move the bounds (A/B runs).  Callers that lay activations out for a GEMM (vit.hip:
+// K-panel-major h / dH) ask here first: the tile reads row-major operands.
 bool cara_gemm8_policy(int M, int N, int K, int riders) {
-  static const int on = [] { const char* e = getenv("CARA_GEMM8"); return e ? atoi(e) : 160; }();
   static const int mink = [] { const char* e = getenv("CARA_GEMM8_MINK"); return e ? atoi(e) : 2048; }();
   static const int maxn = [] { const char* e = getenv("CARA_GEMM8_MAXN"); return e ? atoi(e) : 1024; }();
   static const int maxk_ts = [] { const char* e = getenv("CARA_GEMM8_MAXK_TS"); return e ? atoi(e) : 2304; }();
-  // CARA_GEMM8_ALSO (A/B runs): more shape classes on the tile -- 1: N = 3 dim, K = dim without riders (qkv forward); 2: N = K = dim
-  // without riders (proj forward); 4: N = K = dim with riders (proj dX)
-  static const int also = [] { const char* e = getenv("CARA_GEMM8_ALSO"); return e ? atoi(e) : 0; }();
-  if (on != 160 || M < 4096 || (M % 16) || (N % 16)) return false;
-  if (N <= maxn && K >= mink && (!riders || K <= maxk_ts)) return true;
-  if ((also & 1) && !riders && N == 3 * K) return true;
-  if ((also & 2) && !riders && N == K && N <= maxn) return true;
-  if ((also & 4) && riders && N == K && N <= maxn) return true;
-  if ((also & 8) && !riders && N == 4 * K) return true;   // 8: N = 4 dim, K = dim without riders (fc1 forward)
-  return false;
+  if (!gemm8_env_on() || M < 4096 || (M % 16) || (N % 16)) return false;
+  return N <= maxn && K >= mink && (!riders || K <= maxk_ts);
+}
+// rows of the tile the policy (or the debug setter) wants for this product; 0: the 128 x 128 x 32 family
+static int g8_choice(const cara_gemm_args* a, bool riders) {
+  return g_gemm8_override > 0 ? g_gemm8_override : (g_gemm8_override < 0 && cara_gemm8_policy(a->M, a->N, a->K, riders ? 1 : 0) ? 160 : 0);
+}
+// dVs from the A tiles (er_Tt with CARA_EPI_BF16): the 160-row tile whatever the shape policy says, unless the tile is off
+static bool dv_tile_on() { return gemm8_env_on() && g_gemm8_override != 0; }
+// epilogue riders (er_Tt with CARA_EPI_MULH): the products of the 160-row class of the 128 x 128 x 32 family
+static bool er_geometry(const cara_gemm_args* a) {
+  return a->epi == CARA_EPI_MULH && tile160(a) && !a->Ut && !(a->N & 127) && !(a->ldc & 7) && !(a->M & 3) && a->M > 0 && g_gemm8_override <= 0;
+}
+
+// ---- the plan: CARA_OK and *p filled, or the status the call returns.  nt: riders_nt() of the riding products, 0: none ----
+static int gemm_plan(const cara_gemm_args* a, const int nt, const bool colsum, GemmPlan* p) {
+  *p = GemmPlan{};
+  const bool ts = nt != 0;
+  if (!a || !a->A || !a->B || !a->C) return CARA_E_ARG;
+  if (a->M <= 0 || a->N <= 0 || a->K <= 0 || (a->K % BK) != 0) return CARA_E_ARG;
+  if ((!a->a_panels && (a->lda < a->K || (a->lda & 7))) || a->ldb < a->K || (a->ldb & 7) || a->ldc < a->N) return CARA_E_ARG;
+  if (a->a_panels || a->c_panels) {   // K-panel-major activations: bf16 outputs
+    if (a->a_panels < 0 || a->c_panels < 0 || (a->a_panels && a->a_panels < a->M) || (a->c_panels && a->c_panels < a->M))
+      return CARA_E_ARG;
+    if (a->c_panels && ((a->N & 31) || !(a->epi == CARA_EPI_BF16 || a->epi == CARA_EPI_GELU || a->epi == CARA_EPI_DGELU || a->epi == CARA_EPI_GELU_DG ||
+                                         a->epi == CARA_EPI_MULH)))
+      return CARA_E_ARG;
+    if (a->batch > 1 || a->M <= 128) return CARA_E_ARG;
+  }
+  if (!(a->Rp == 0 || a->Rp == 32 || a->Rp == 64)) return CARA_E_ARG;
+  if (a->Rp && ((!a->A2 && !a->Ut) || !a->B2)) return CARA_E_ARG;
+  // operands are addressed with 32-bit byte offsets from the (batch-adjusted) base pointer
+  const bool small_ptrs = (unsigned long long)a->M * (a->a_panels ? 32 : a->lda) * 2 < (1ull << 32) && (unsigned long long)a->N * a->ldb * 2 < (1ull << 32);
+  if (!small_ptrs) return CARA_E_ARG;
+  if (a->epi == CARA_EPI_RESID && (!a->aux || (a->rowscale && a->rows_per_sample <= 0))) return CARA_E_ARG;
+  if ((a->epi == CARA_EPI_DGELU || a->epi == CARA_EPI_MULH) && !a->aux) return CARA_E_ARG;
+  if (a->epi == CARA_EPI_MULH && a->bias) return CARA_E_ARG;
+  if (ts && (a->batch > 1 || a->M <= 128 || a->B3 || (a->Ut && a->epi != CARA_EPI_BF16))) return CARA_E_ARG;
+  if (a->B3 && (a->Bp || a->Ut || a->batch > 1 || a->a_panels)) return CARA_E_ARG;
+  p->nt = nt;
+  p->colsum = ts && colsum;
+  p->batch = 1;
+  p->block = 256;
+  auto tile8 = [&](int mt) {   // (everything else about such a launch is in p->g8, nowhere else)
+    p->family = mt == 256 ? FAM_TILE8_256 : FAM_TILE8;
+    return CARA_OK;
+  };
+  if (a->er_Tt && a->epi == CARA_EPI_BF16) {
+    // dVs (+ dc) of the GEMM's own linear out of the A sub-buffers of its K loop: the 160 x 256 x 64 tile only (cara_gemm_dv_chunks)
+    if (!dv_tile_on() || !cara_gemm8_plan(a, 160, nt, colsum, &p->g8)) return CARA_E_ARG;
+    return tile8(160);
+  }
+  if (a->er_Tt) {   // epilogue riders: only where cara_gemm_epi_rider_chunks() says so
+    if (!er_geometry(a) || !a->er_Gt || !a->er_h || !a->er_slabs_v || !a->er_slabs_u || a->er_ldg < a->M || (a->er_ldg & 3) ||
+        a->er_h_panels < 0 || (a->er_h_panels && a->er_h_panels < a->M))
+      return CARA_E_ARG;
+    // (the riders' epilogue addresses C, aux, h, T^T and G'^T with 32-bit byte offsets)
+    const unsigned long long pmax = a->c_panels > a->er_h_panels ? a->c_panels : a->er_h_panels;
+    if ((unsigned long long)a->M * a->ldc * 2 >= (1ull << 32) || (unsigned long long)(a->N / 32) * pmax * 64 >= (1ull << 32) ||
+        (unsigned long long)a->er_ldg * 32 >= (1ull << 32))
+      return CARA_E_ARG;
+    if (ts && nt != 1) return CARA_E_ARG;
+    p->er = true;
+  } else if (const int mt = g8_choice(a, ts)) {
+    // the MT x 256 x 64 tile where the policy asks for it and the tile takes the product; otherwise the 128 x 128 x 32 family below
+    if (cara_gemm8_plan(a, mt, nt, colsum, &p->g8)) return tile8(mt);
+  }
+  const auto epi_in = [&](unsigned mask) { return a->epi >= 0 && a->epi < 7 && ((mask >> a->epi) & 1u); };
+  p->tile_rows = 128;
+  p->tiles_n = (a->N + BN - 1) / BN;
+  p->gm = group_m(p->tiles_n);
+  p->nwg = ((a->M + 127) / 128) * p->tiles_n;
+  if (a->Ut) {   // whole adapter inside the GEMM: T produced here
+    if (a->A2 || !a->B2 || !(a->Rp == 32 || a->Rp == 64) || !a->T_out || a->batch > 1 || (a->Tt_out && (a->ldt < a->M || (a->ldt & 7)))) return CARA_E_ARG;
+    if (!epi_in(EPI_MASK_TILE)) return CARA_E_ARG;
+    const bool rank16 = a->Ut_rank > 0 && a->Ut_rank <= 16;
+    p->family = FAM_FT;
+    p->nu = a->Rp / 32;
+    p->halft = a->Rp == 32 && rank16;
+    p->lds = 2 * (128 * BK32 * 2 + B32_BYTES + a->Rp * BK32 * 2);
+    if (ts) {   // (plain bf16 output only: the backward's fc1 / qkv dX)
+      const bool half = a->Rp == 32 && nt == 1;   // rank <= 16: one r-tile in the riding products, 16 columns of the adapter inside
+      if (nt != a->Rp / 16 && !half) return CARA_E_ARG;
+      if (half && !rank16) return CARA_E_ARG;
+      p->halft = half;
+      const int rb = ts_block_bytes(2);   // the same for every NT (two-pass combine)
+      if (rb > p->lds) p->lds = rb;
+    }
+    return CARA_OK;
+  }
+  if (a->batch > 1) {   // batched products: plain epilogues
+    if (a->A2 || a->aux || a->C2 || a->Bp || !(a->epi == CARA_EPI_F32 || a->epi == CARA_EPI_BF16) || a->batch > 65535) return CARA_E_ARG;
+    p->family = FAM_BATCHED;
+    p->batch = a->batch;
+    p->lds = 2 * (128 * BK32 * 2 + B32_BYTES);
+    return CARA_OK;
+  }
+  if (!epi_in(EPI_MASK_ALL)) return CARA_E_ARG;
+  if (!ts && small_m_slabs(a)) {   // (B: the row-major weights, also where a K-panel-major image exists)
+    p->family = FAM_FEW_ROWS;
+    p->tile_rows = 16;
+    p->tiles_n = (a->N + 15) / 16;
+    p->batch = (a->M + 15) / 16;
+    p->nwg = p->tiles_n * p->batch;
+    p->gm = 0;
+    p->block = a->K > 1024 ? 512 : 256;   // 8 waves split the long K loops, 4 where K <= 1024
+    return CARA_OK;
+  }
+  // riding products: the dX GEMMs' epilogues only
+  if (ts && !(a->epi == CARA_EPI_BF16 || a->epi == CARA_EPI_DGELU || a->epi == CARA_EPI_MULH)) return CARA_E_ARG;
+  p->family = FAM_G32;
+  if (tile160(a)) {
+    p->tile_rows = p->er ? er_rows() : 160;
+    p->nwg = ((a->M + p->tile_rows - 1) / p->tile_rows) * p->tiles_n;
+  }
+  p->twob = a->B3 != nullptr;
+  p->lds = 2 * (p->tile_rows * BK32 * 2 + (p->twob ? 2 : 1) * B32_BYTES);
+  if (p->er && p->lds < ER_LDS_BYTES) p->lds = ER_LDS_BYTES;
+  if (ts && ts_block_bytes(nt) > p->lds) p->lds = ts_block_bytes(nt);
+  return CARA_OK;
+}
+
+// ---- the launchers: plan -> template instantiation -> launch ----
+// the GEMM-with-riders kernel: COLSUM and NT (the products' column tiles) picked at run time
+template <int EPI, int MI, bool ER = false>
+static void launch_ts(const cara_gemm_args* a, hipStream_t st, const GemmPlan& p, const TsPair* ts) {
+  const dim3 grid(p.nwg + ts->a.nblk + ts->b.nblk), block(256);
+#define TS_GO(CS, NT) \
+  hipLaunchKernelGGL((gemm32_ts_kernel<EPI, CS, MI, NT, ER>), grid, block, p.lds, st, *a, p.tiles_n, p.nwg, p.gm, ts->a, ts->b, ts->ldg, ts->M)
+  if (ER || p.nt == 1) {   // rank <= 16: the products compute 16 of their 32 columns (16-wide slabs); epilogue riders: always
+    if (p.colsum) TS_GO(true, 1); else TS_GO(false, 1);
+  } else if constexpr (!ER) {
+    if (p.nt == 4) {
+      if (p.colsum) TS_GO(true, 4); else TS_GO(false, 4);
+    } else {
+      if (p.colsum) TS_GO(true, 2); else TS_GO(false, 2);
+    }
+  }
+#undef TS_GO
+}
+
+template <int EPI>
+static int launch_g32(const cara_gemm_args* a, hipStream_t st, const GemmPlan& p, const TsPair* ts) {
+  constexpr bool TS_EPI = EPI == CARA_EPI_BF16 || EPI == CARA_EPI_DGELU || EPI == CARA_EPI_MULH;
+  const dim3 grid(p.nwg, p.batch), block(256);
+#define G32_GO(...) hipLaunchKernelGGL((gemm32_kernel<__VA_ARGS__>), grid, block, p.lds, st, *a, p.tiles_n, p.nwg, p.gm)
+  if constexpr (EPI == CARA_EPI_MULH) {
+    if (p.er) {
+      if (p.tile_rows == 160) {
+        if (ts) launch_ts<EPI, 5, true>(a, st, p, ts); else G32_GO(EPI, false, 5, true);
+      } else {
+        if (ts) launch_ts<EPI, 4, true>(a, st, p, ts); else G32_GO(EPI, false, 4, true);
+      }
+      CARA_CHECK_LAUNCH();
+      return CARA_OK;
+    }
+  }
+  if (ts) {
+    if constexpr (TS_EPI) {
+      if (p.tile_rows == 160) launch_ts<EPI, 5>(a, st, p, ts); else launch_ts<EPI, 4>(a, st, p, ts);
+    } else {
+      return CARA_E_ARG;   // (riders behind another epilogue: no plan says that)
+    }
+  } else if (p.tile_rows == 160) {
+    G32_GO(EPI, false, 5);
+  } else if (p.twob) {
+    G32_GO(EPI, true);
+  } else {
+    G32_GO(EPI);
+  }
+#undef G32_GO
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+template <int EPI>
+static int launch_ft(const cara_gemm_args* a, hipStream_t st, const GemmPlan& p, const TsPair* ts) {
+  // consumers read Tt in whole 32-row steps: keep columns [M, roundup32(M)) zero, as cara_skinny_xu does
+  const int m32 = (a->M + 31) / 32 * 32;
+  if (a->Tt_out && m32 > a->M && m32 <= a->ldt &&
+      hipMemset2DAsync(static_cast<bf16*>(a->Tt_out) + a->M, (size_t)a->ldt * 2, 0, (size_t)(m32 - a->M) * 2, a->Rp, st) != hipSuccess)
+    return CARA_E_LAUNCH;
+  if (ts) {
+    if constexpr (EPI == CARA_EPI_BF16) {
+      const dim3 grid(p.nwg + ts->a.nblk + ts->b.nblk), block(256);
+#define FT_GO(NU, CS, NTS, HT) \
+  hipLaunchKernelGGL((gemm32ft_ts_kernel<EPI, NU, CS, NTS, HT>), grid, block, p.lds, st, *a, p.tiles_n, p.nwg, p.gm, ts->a, ts->b, ts->ldg, ts->M)
+      if (p.nu == 2) {
+        if (p.colsum) FT_GO(2, true, 4, false); else FT_GO(2, false, 4, false);
+      } else if (p.halft) {
+        if (p.colsum) FT_GO(1, true, 1, true); else FT_GO(1, false, 1, true);
+      } else {
+        if (p.colsum) FT_GO(1, true, 2, false); else FT_GO(1, false, 2, false);
+      }
+#undef FT_GO
+    } else {
+      return CARA_E_ARG;   // (riders beside the adapter inside: plain bf16 output only; no plan says otherwise)
+    }
+  } else {
+    const dim3 grid(p.nwg), block(256);
+    if (p.nu == 2) hipLaunchKernelGGL((gemm32ft_kernel<EPI, 2>), grid, block, p.lds, st, *a, p.tiles_n, p.nwg, p.gm);
+    else if (p.halft) hipLaunchKernelGGL((gemm32ft_kernel<EPI, 1, true>), grid, block, p.lds, st, *a, p.tiles_n, p.nwg, p.gm);
+    else hipLaunchKernelGGL((gemm32ft_kernel<EPI>), grid, block, p.lds, st, *a, p.tiles_n, p.nwg, p.gm);
+  }
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+template <int EPI>
+static int launch_few_rows(const cara_gemm_args* a, hipStream_t st, const GemmPlan& p) {
+  const dim3 grid(p.tiles_n, p.batch);
+  if (p.block == 512) hipLaunchKernelGGL((small_m_direct_kernel<EPI, 8>), grid, dim3(512), 0, st, *a);
+  else hipLaunchKernelGGL((small_m_direct_kernel<EPI, 4>), grid, dim3(256), 0, st, *a);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+// ts != NULL: the launch also carries a pair of transposed skinny products
+static int gemm_bf16_impl(const cara_gemm_args* a, void* stream, const TsPair* ts) {
+  GemmPlan p;
+  const int rc = gemm_plan(a, ts ? ts->nt : 0, ts && ts->any_cs, &p);
+  if (rc != CARA_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (p.family) {
+    case FAM_TILE8:
+    case FAM_TILE8_256: {
+      cara_g8_riders rd;
+      if (ts) rd = g8_riders(*ts);
+      return cara_gemm8_launch(a, st, p.g8, ts ? &rd : nullptr);
+    }
+    case FAM_FT: return cara_dispatch_epi<EPI_MASK_TILE>(a->epi, [&](auto e) { return launch_ft<decltype(e)::value>(a, st, p, ts); });
+    case FAM_FEW_ROWS: return cara_dispatch_epi<EPI_MASK_ALL>(a->epi, [&](auto e) { return launch_few_rows<decltype(e)::value>(a, st, p); });
+    default: return cara_dispatch_epi<EPI_MASK_ALL>(a->epi, [&](auto e) { return launch_g32<decltype(e)::value>(a, st, p, ts); });
+  }
 }
 
 extern "C" int cara_gemm_bf16(const cara_gemm_args* a, void* stream) { return gemm_bf16_impl(a, stream, nullptr); }
@@ -1229,30 +1304,21 @@ extern "C" int cara_gemm_with_tskinny_r(const cara_gemm_args* a, const void* Xa,
   ts.a = ts_problem(Xa ? Xa : Xb, Xa ? ldxa : ldxb, Xa ? Gta : Gtb, Xa ? slabs_a : slabs_b, 0, M, Xa ? K1a : K1b, Rp);
   if (!Xa) ts.a.nblk = 0;
   ts.b = ts_problem(Xb, ldxb, Gtb, slabs_b, want_colsum_b, M, K1b, Rp);
-  ts.ldg = ldg; ts.M = M; ts.any_cs = want_colsum_b != 0; ts.nt = (Rp == 32 && rank <= 16 && (!a->Ut || (a->Ut_rank > 0 && a->Ut_rank <= 16))) ? 1 : Rp / 16;
+  ts.ldg = ldg; ts.M = M; ts.any_cs = want_colsum_b != 0; ts.nt = riders_nt(a, Rp, rank);
   return gemm_bf16_impl(a, stream, &ts);
 }
 
-static int g8_choice(const cara_gemm_args* a, bool riders) {
-  return g_gemm8_override > 0 ? g_gemm8_override : (g_gemm8_override < 0 && cara_gemm8_policy(a->M, a->N, a->K, riders ? 1 : 0) ? 160 : 0);
-}
 extern "C" int cara_gemm_rider_slab_format(const cara_gemm_args* a, int Rp, int rank) {
   if (!a || !(Rp == 32 || Rp == 64) || rank <= 0 || rank > Rp) return 0;
-  const int g8 = g8_choice(a, true);
-  if (!g8) return 0;
-  const int nt = (Rp == 32 && rank <= 16 && (!a->Ut || (a->Ut_rank > 0 && a->Ut_rank <= 16))) ? 1 : Rp / 16;
-  return cara_gemm8_plan(a, g8, nt) == 2 ? 1 : 0;
+  const int mt = g8_choice(a, true);
+  return mt && cara_gemm8_plan(a, mt, riders_nt(a, Rp, rank), 0, nullptr) == 2 ? 1 : 0;
 }
-
 extern "C" int cara_gemm_epi_rider_chunks(const cara_gemm_args* a) {
-  if (!a || a->epi != CARA_EPI_MULH || !tile160(a) || a->Ut || (a->N & 127) || (a->ldc & 7) || (a->M & 3) || a->M <= 0) return 0;
-  if (g_gemm8_override > 0) return 0;
-  return (a->M + er_rows() - 1) / er_rows();
+  return a && er_geometry(a) ? (a->M + er_rows() - 1) / er_rows() : 0;
 }
 extern "C" int cara_gemm_dv_chunks(const cara_gemm_args* a, int riders) {
-  static const int on = [] { const char* e = getenv("CARA_GEMM8"); return e ? atoi(e) : 160; }();
-  if (!a || !a->er_Tt || a->epi != CARA_EPI_BF16 || on != 160 || g_gemm8_override == 0) return 0;
-  return cara_gemm8_plan(a, 160, riders ? 1 : 0) == 1 ? (a->M + 159) / 160 : 0;
+  if (!a || !a->er_Tt || a->epi != CARA_EPI_BF16 || !dv_tile_on()) return 0;
+  return cara_gemm8_plan(a, 160, riders ? 1 : 0, 0, nullptr) == 1 ? (a->M + 159) / 160 : 0;
 }
 extern "C" size_t cara_gemm_epi_rider_scratch_bytes(int chunks, int N) {
   if (chunks <= 0 || N <= 0 || (N & 63)) return 0;
@@ -1260,102 +1326,27 @@ extern "C" size_t cara_gemm_epi_rider_scratch_bytes(int chunks, int N) {
   return nblk * 64 * 32 * sizeof(float) + nblk * 64 * sizeof(float);   // (the column sums sit behind slabs of the full width 32, cara_tskinny_reduce*)
 }
 
-// ts != NULL: the launch also carries a pair of transposed skinny products; only the default 128 x 128 x 32 kernel can
-static int gemm_bf16_impl(const cara_gemm_args* a, void* stream, const TsPair* ts) {
-  if (!a || !a->A || !a->B || !a->C) return CARA_E_ARG;
-  if (a->M <= 0 || a->N <= 0 || a->K <= 0 || (a->K % BK) != 0) return CARA_E_ARG;
-  if ((!a->a_panels && (a->lda < a->K || (a->lda & 7))) || a->ldb < a->K || (a->ldb & 7) || a->ldc < a->N) return CARA_E_ARG;
-  const bool panels = a->a_panels || a->c_panels;
-  if (panels) {   // K-panel-major activations: bf16 outputs
-    if (a->a_panels < 0 || a->c_panels < 0 || (a->a_panels && a->a_panels < a->M) || (a->c_panels && a->c_panels < a->M))
-      return CARA_E_ARG;
-    if (a->c_panels && ((a->N & 31) || !(a->epi == CARA_EPI_BF16 || a->epi == CARA_EPI_GELU || a->epi == CARA_EPI_DGELU || a->epi == CARA_EPI_GELU_DG ||
-                                         a->epi == CARA_EPI_MULH)))
-      return CARA_E_ARG;
-    if (a->batch > 1 || a->M <= 128) return CARA_E_ARG;
+// Test hook beside cara_debug_set_gemm8 (not in include/cara_hip.h): the plan of cara_gemm_bf16(a) (riders_nt = 0) or of
+// cara_gemm_with_tskinny_r(a, ...) whose products compute riders_nt column tiles of 16, the second one with column sums or not.
+// Host code only: no operand is dereferenced, nothing is launched.  Returns the status the call would return; on CARA_OK
+// out = {family (GemmFamily), tile rows, tile workgroups, threads per workgroup, dynamic LDS bytes, nt, flags, rows per supertile},
+// flags: 1 column sums, 2 epilogue riders, 4 dVs from the A tiles, 8 two B operands, 16 the adapter's 16-column form, 32 Rp = 64
+// inside, 64 helper waves.
+extern "C" int cara_debug_gemm_plan(const cara_gemm_args* a, int riders_nt, int riders_colsum, int out[8]) {
+  GemmPlan p;
+  const int rc = gemm_plan(a, riders_nt, riders_colsum != 0, &p);
+  if (rc != CARA_OK || !out) return rc;
+  out[0] = p.family; out[5] = p.nt;
+  if (p.family == FAM_TILE8 || p.family == FAM_TILE8_256) {   // (the tile's adapter inside, modes 2 and 3, is always the 16-column form)
+    const cara_g8_plan& g = p.g8;
+    out[1] = g.mt; out[2] = g.nwg; out[3] = g.block; out[4] = g.lds; out[7] = 0;
+    out[6] = (p.colsum ? 1 : 0) | (g.dv ? 4 : 0) | (g.mode >= 2 ? 16 : 0) | (g.helpers ? 64 : 0);
+  } else {
+    out[1] = p.tile_rows; out[2] = p.nwg; out[3] = p.block; out[4] = p.lds; out[7] = p.gm;
+    out[6] = (p.colsum ? 1 : 0) | (p.er ? 2 : 0) | (p.twob ? 8 : 0) | (p.halft ? 16 : 0) | (p.nu == 2 ? 32 : 0);
   }
-  if (!(a->Rp == 0 || a->Rp == 32 || a->Rp == 64)) return CARA_E_ARG;
-  if (a->Rp && ((!a->A2 && !a->Ut) || !a->B2)) return CARA_E_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // operands are addressed with 32-bit byte offsets from the (batch-adjusted) base pointer
-  const bool small_ptrs = (unsigned long long)a->M * (a->a_panels ? 32 : a->lda) * 2 < (1ull << 32) && (unsigned long long)a->N * a->ldb * 2 < (1ull << 32);
-  if (!small_ptrs) return CARA_E_ARG;
-  if (a->epi == CARA_EPI_RESID && (!a->aux || (a->rowscale && a->rows_per_sample <= 0))) return CARA_E_ARG;
-  if ((a->epi == CARA_EPI_DGELU || a->epi == CARA_EPI_MULH) && !a->aux) return CARA_E_ARG;
-  if (a->epi == CARA_EPI_MULH && a->bias) return CARA_E_ARG;
-  if (ts && (a->batch > 1 || a->M <= 128 || a->B3 || (a->Ut && a->epi != CARA_EPI_BF16))) return CARA_E_ARG;
-  if (a->B3 && (a->Bp || a->Ut || a->batch > 1 || a->a_panels)) return CARA_E_ARG;
-  if (a->er_Tt && a->epi == CARA_EPI_BF16) {
-    // dVs (+ dc) of the GEMM's own linear out of the A sub-buffers of its K loop: the 160 x 256 x 64 tile only (cara_gemm_dv_chunks)
-    if (!cara_gemm_dv_chunks(a, ts ? 1 : 0)) return CARA_E_ARG;
-    cara_g8_riders rd;
-    if (ts) {
-      auto cp = [](const TsProblem& t) { return cara_g8_product{t.X, t.Gt, t.slabs, t.cs_slabs, t.ldx, t.K1, t.nchunks, t.nblk}; };
-      rd.a = cp(ts->a); rd.b = cp(ts->b); rd.ldg = ts->ldg; rd.M = ts->M; rd.any_cs = ts->any_cs ? 1 : 0; rd.nt = ts->nt;
-    }
-    const int rc = cara_gemm8_launch(a, static_cast<hipStream_t>(stream), 160, ts ? &rd : nullptr);
-    return rc < 0 ? CARA_E_ARG : rc;
-  }
-  if (a->er_Tt) {   // epilogue riders: only where cara_gemm_epi_rider_chunks() says so
-    if (!cara_gemm_epi_rider_chunks(a) || !a->er_Gt || !a->er_h || !a->er_slabs_v || !a->er_slabs_u || a->er_ldg < a->M || (a->er_ldg & 3) ||
-        a->er_h_panels < 0 || (a->er_h_panels && a->er_h_panels < a->M))
-      return CARA_E_ARG;
-    // (the riders' epilogue addresses C, aux, h, T^T and G'^T with 32-bit byte offsets)
-    const unsigned long long pmax = a->c_panels > a->er_h_panels ? a->c_panels : a->er_h_panels;
-    if ((unsigned long long)a->M * a->ldc * 2 >= (1ull << 32) || (unsigned long long)(a->N / 32) * pmax * 64 >= (1ull << 32) ||
-        (unsigned long long)a->er_ldg * 32 >= (1ull << 32))
-      return CARA_E_ARG;
-    if (ts && ts->nt != 1) return CARA_E_ARG;
-  }
-  // The MT x 256 x 64 one-workgroup-per-CU tile (gemm8.hip) where the policy asks for it (cara_gemm8_policy) and the tile takes the product
-  const int g8 = a->er_Tt ? 0 : g8_choice(a, ts != nullptr);
-  if (g8) {
-    cara_g8_riders rd;
-    if (ts) {
-      auto cp = [](const TsProblem& t) { return cara_g8_product{t.X, t.Gt, t.slabs, t.cs_slabs, t.ldx, t.K1, t.nchunks, t.nblk}; };
-      rd.a = cp(ts->a); rd.b = cp(ts->b); rd.ldg = ts->ldg; rd.M = ts->M; rd.any_cs = ts->any_cs ? 1 : 0; rd.nt = ts->nt;
-    }
-    const int rc = cara_gemm8_launch(a, st, g8, ts ? &rd : nullptr);
-    if (rc >= 0) return rc;
-  }
-  if (a->Ut) {   // whole adapter inside the GEMM: Rp = 32, T produced here
-    if (a->A2 || !a->B2 || !(a->Rp == 32 || a->Rp == 64) || !a->T_out || a->batch > 1 || (a->Tt_out && (a->ldt < a->M || (a->ldt & 7)))) return CARA_E_ARG;
-    switch (a->epi) {
-      case CARA_EPI_BF16: return launch32ft<CARA_EPI_BF16>(a, st, ts);
-      case CARA_EPI_F32: return launch32ft<CARA_EPI_F32>(a, st);
-      case CARA_EPI_GELU: return launch32ft<CARA_EPI_GELU>(a, st);
-      case CARA_EPI_RESID: return launch32ft<CARA_EPI_RESID>(a, st);
-      case CARA_EPI_DGELU: return launch32ft<CARA_EPI_DGELU>(a, st);
-      default: return CARA_E_ARG;
-    }
-  }
-  if (a->batch > 1) {   // batched products: plain epilogues
-    if (a->A2 || a->aux || a->C2 || a->Bp || !(a->epi == CARA_EPI_F32 || a->epi == CARA_EPI_BF16) || a->batch > 65535) return CARA_E_ARG;
-    return a->epi == CARA_EPI_F32 ? launch32<CARA_EPI_F32>(a, st) : launch32<CARA_EPI_BF16>(a, st);
-  }
-  if (const int nslab = ts ? 0 : small_m_slabs(a)) {
-    switch (a->epi) {
-      case CARA_EPI_BF16: return launch_small_m<CARA_EPI_BF16>(a, nslab, st);
-      case CARA_EPI_F32: return launch_small_m<CARA_EPI_F32>(a, nslab, st);
-      case CARA_EPI_GELU: return launch_small_m<CARA_EPI_GELU>(a, nslab, st);
-      case CARA_EPI_RESID: return launch_small_m<CARA_EPI_RESID>(a, nslab, st);
-      case CARA_EPI_DGELU: return launch_small_m<CARA_EPI_DGELU>(a, nslab, st);
-      case CARA_EPI_GELU_DG: return launch_small_m<CARA_EPI_GELU_DG>(a, nslab, st);
-      case CARA_EPI_MULH: return launch_small_m<CARA_EPI_MULH>(a, nslab, st);
-      default: return CARA_E_ARG;
-    }
-  }
-  switch (a->epi) {
-    case CARA_EPI_BF16: return launch32<CARA_EPI_BF16>(a, st, ts);
-    case CARA_EPI_F32: return launch32<CARA_EPI_F32>(a, st, ts);
-    case CARA_EPI_GELU: return launch32<CARA_EPI_GELU>(a, st, ts);
-    case CARA_EPI_RESID: return launch32<CARA_EPI_RESID>(a, st, ts);
-    case CARA_EPI_DGELU: return launch32<CARA_EPI_DGELU>(a, st, ts);
-    case CARA_EPI_GELU_DG: return ts ? CARA_E_ARG : launch32<CARA_EPI_GELU_DG>(a, st);
-    case CARA_EPI_MULH: return launch32<CARA_EPI_MULH>(a, st, ts);
-    default: return CARA_E_ARG;
-  }
+  return CARA_OK;
 }
 
-// scratch for the few-row split-K path: up to 16 slabs of 128 rows x 4096 columns of fp32 partial products
+// (the few-row products used to cut K into slabs of fp32 partial products in caller scratch; small_m_slabs() still asks for it)
 extern "C" size_t cara_gemm_scratch_bytes(void) { return (size_t)16 * 128 * 4096 * sizeof(float); }

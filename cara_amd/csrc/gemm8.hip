@@ -30,6 +30,8 @@
 //  * the transposed skinny products a dX launch carries (cara_gemm_with_tskinny_r) are 512-thread workgroups of two tskinny blocks
 //    behind the tiles: they take the CUs the tiles leave free and then the CUs whose tile is done.
 //  * M = 12608 rows: 79 tiles of 160 rows x 3 column tiles = 237 workgroups = 92.6 % of the CUs in ONE round.
+// Host side (end of the file): cara_gemm8_plan says whether and how the tile takes a product -- exactly what cara_gemm8_launch then
+// launches; gemm.hip's gemm_plan asks it before anything is enqueued.
 //
 // Sequence numbers of the sub-buffers (what the counted waits are derived from): K step t holds seq 4t .. 4t + 3 =
 // A0, B0, B1, A1; phase phi = 4t + (p - 1) issues seq phi + 6 and then waits until seq <= phi + 2 has landed (read
@@ -39,6 +41,7 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm8.h"
+#include "gemm_dispatch.h"
 #include "tskinny_body.h"
 
 namespace {
@@ -178,7 +181,6 @@ __device__ __forceinline__ void g8_tile(const cara_gemm_args& p, const int tiles
     const bool x_ = EXT && (KT) == nk;                                                                                     \
     G8_DMA((x_ ? rsEB : rsB), ((KT) < nk ? vB : (x_ ? vE : vD)), (x_ ? sEB[t_] : sB0[t_] + (KT) * 128), C::B, G::B0_OFF, BUFX); \
   } while (0)
-
 
   // ---- fragment addresses: row (.. + fr) of a sub-buffer, 16-byte chunk (4 kh + fq) ^ (row & 7) ----
   int pa0[2], pa1[2], pb[2];
@@ -887,101 +889,77 @@ TsProblem g8_problem(const cara_g8_product& q) {
   return t;
 }
 
+template <class K>   // (more than 64 KiB of dynamic LDS: asked for once per kernel)
+bool g8_allow_lds(K* kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+}
+
+template <class G>   // LDS of a launch whose riding products are workgroups behind the tiles (two tskinny blocks per workgroup)
+constexpr int g8_lds_ts() {
+  constexpr int TSB2 = 2 * TsRing<1, 3>::BLOCK_BYTES;
+  return G::LDS > TSB2 ? G::LDS : TSB2;
+}
+
+// One launch of what cara_gemm8_plan decided (pl) for this tile, epilogue and mode.  Each form exists for the (G, EPI, MODE) the plan
+// can ask it for and for no other; the return behind them is not reached (docs/findings/gemm_plan.md lists why).
 template <class G, int EPI, int MODE>
-int g8_launch(const cara_gemm_args* a, hipStream_t st, const cara_g8_riders* ts, const bool helpers) {
-  const int tiles_n = (a->N + 255) / 256, tiles_m = (a->M + G::MT - 1) / G::MT;
-  const int nwg = tiles_m * tiles_n;
+int g8_launch(const cara_gemm_args* a, hipStream_t st, const cara_g8_plan& pl, const cara_g8_riders* ts) {
+  const int tiles_n = pl.tiles_n, nwg = pl.nwg;
+  TsProblem t0 = {}, t1 = {};
+  if (ts) { t0 = g8_problem(ts->a); t1 = g8_problem(ts->b); }
+  const int ldg = ts ? ts->ldg : 0, Mts = ts ? ts->M : 0;
+  const bool cs = ts && ts->any_cs;
+  const dim3 tiles(nwg), tiles_and_riders(nwg + (t0.nblk + t1.nblk + 1) / 2);
   if constexpr (G::MT == 160 && (MODE == 1 || MODE == 3)) {
-    // helper waves: the riders' streams and, MODE 3, T = A Ut^T
-    if (helpers && !a->er_Tt) {
-      if (ts && !(EPI == CARA_EPI_BF16 || EPI == CARA_EPI_DGELU)) return -1;
-      TsProblem t0 = {}, t1 = {};
-      if (ts) { t0 = g8_problem(ts->a); t1 = g8_problem(ts->b); }
-      const bool cs = ts && ts->any_cs;
+    if (pl.helpers) {   // helper waves: the riders' streams and, MODE 3, T = A Ut^T
       static bool attr = false;
       if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8h_kernel<G, EPI, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, H8<G>::LDS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8h_kernel<G, EPI, MODE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, H8<G>::LDS) != hipSuccess)
-          return CARA_E_LAUNCH;
+        if (!g8_allow_lds(gemm8h_kernel<G, EPI, MODE, true>, H8<G>::LDS) || !g8_allow_lds(gemm8h_kernel<G, EPI, MODE, false>, H8<G>::LDS)) return CARA_E_LAUNCH;
         attr = true;
       }
-      if (cs) hipLaunchKernelGGL((gemm8h_kernel<G, EPI, MODE, true>), dim3(nwg), dim3(768), H8<G>::LDS, st, *a, tiles_n, nwg, t0, t1, ts ? ts->ldg : 0, ts ? ts->M : 0);
-      else hipLaunchKernelGGL((gemm8h_kernel<G, EPI, MODE, false>), dim3(nwg), dim3(768), H8<G>::LDS, st, *a, tiles_n, nwg, t0, t1, ts ? ts->ldg : 0, ts ? ts->M : 0);
+      if (cs) hipLaunchKernelGGL((gemm8h_kernel<G, EPI, MODE, true>), tiles, dim3(768), pl.lds, st, *a, tiles_n, nwg, t0, t1, ldg, Mts);
+      else hipLaunchKernelGGL((gemm8h_kernel<G, EPI, MODE, false>), tiles, dim3(768), pl.lds, st, *a, tiles_n, nwg, t0, t1, ldg, Mts);
       CARA_CHECK_LAUNCH();
       return CARA_OK;
     }
   }
-  if constexpr (EPI == CARA_EPI_BF16 && (MODE == 1 || MODE == 2) && G::MT == 160) {
-    if (a->er_Tt) {   // dVs (+ dc) of the GEMM's own linear out of its A sub-buffers (g8_tile<.., DV>); riders: a pending dU at most
-      constexpr int TSB2 = 2 * TsRing<1, 3>::BLOCK_BYTES;
-      constexpr int LDS_TS = G::LDS > TSB2 ? G::LDS : TSB2;
+  if constexpr (G::MT == 160 && EPI == CARA_EPI_BF16 && (MODE == 1 || MODE == 2)) {
+    if (pl.dv) {   // dVs (+ dc) of the GEMM's own linear out of its A sub-buffers (g8_tile<.., DV>); riders: a pending dU, no column sums
       static bool attr = false;
       if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8_kernel<G, EPI, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8_ts_kernel<G, EPI, MODE, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TS) != hipSuccess)
-          return CARA_E_LAUNCH;
+        if (!g8_allow_lds(gemm8_kernel<G, EPI, MODE, true>, G::LDS) || !g8_allow_lds(gemm8_ts_kernel<G, EPI, MODE, false, true>, g8_lds_ts<G>())) return CARA_E_LAUNCH;
         attr = true;
       }
-      if (ts) {
-        if (ts->any_cs) return -1;
-        const TsProblem t0 = g8_problem(ts->a), t1 = g8_problem(ts->b);
-        const int nts = (t0.nblk + t1.nblk + 1) / 2;
-        hipLaunchKernelGGL((gemm8_ts_kernel<G, EPI, MODE, false, true>), dim3(nwg + nts), dim3(512), LDS_TS, st, *a, tiles_n, nwg, t0, t1, ts->ldg, ts->M);
-      } else {
-        hipLaunchKernelGGL((gemm8_kernel<G, EPI, MODE, true>), dim3(nwg), dim3(512), G::LDS, st, *a, tiles_n, nwg, 0);
-      }
+      if (ts) hipLaunchKernelGGL((gemm8_ts_kernel<G, EPI, MODE, false, true>), tiles_and_riders, dim3(512), pl.lds, st, *a, tiles_n, nwg, t0, t1, ldg, Mts);
+      else hipLaunchKernelGGL((gemm8_kernel<G, EPI, MODE, true>), tiles, dim3(512), pl.lds, st, *a, tiles_n, nwg, 0);
       CARA_CHECK_LAUNCH();
       return CARA_OK;
     }
   }
-  if (a->er_Tt) return -1;
-  if (ts) {
-    if constexpr ((EPI == CARA_EPI_BF16 || EPI == CARA_EPI_DGELU) && MODE != 3) {   // (the dX products; riders behind the tiles)
-      constexpr int TSB2 = 2 * TsRing<1, 3>::BLOCK_BYTES;
-      constexpr int LDS_TS = G::LDS > TSB2 ? G::LDS : TSB2;
+  if constexpr (G::MT == 160 && (EPI == CARA_EPI_BF16 || EPI == CARA_EPI_DGELU) && MODE != 3) {
+    if (ts) {   // the dX products; riders behind the tiles
       static bool attr = false;
       if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8_ts_kernel<G, EPI, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TS) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8_ts_kernel<G, EPI, MODE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TS) != hipSuccess)
-          return CARA_E_LAUNCH;
+        if (!g8_allow_lds(gemm8_ts_kernel<G, EPI, MODE, true>, g8_lds_ts<G>()) || !g8_allow_lds(gemm8_ts_kernel<G, EPI, MODE, false>, g8_lds_ts<G>())) return CARA_E_LAUNCH;
         attr = true;
       }
-      const TsProblem t0 = g8_problem(ts->a), t1 = g8_problem(ts->b);
-      const int nts = (t0.nblk + t1.nblk + 1) / 2;
-      if (ts->any_cs) hipLaunchKernelGGL((gemm8_ts_kernel<G, EPI, MODE, true>), dim3(nwg + nts), dim3(512), LDS_TS, st, *a, tiles_n, nwg, t0, t1, ts->ldg, ts->M);
-      else hipLaunchKernelGGL((gemm8_ts_kernel<G, EPI, MODE, false>), dim3(nwg + nts), dim3(512), LDS_TS, st, *a, tiles_n, nwg, t0, t1, ts->ldg, ts->M);
+      if (cs) hipLaunchKernelGGL((gemm8_ts_kernel<G, EPI, MODE, true>), tiles_and_riders, dim3(512), pl.lds, st, *a, tiles_n, nwg, t0, t1, ldg, Mts);
+      else hipLaunchKernelGGL((gemm8_ts_kernel<G, EPI, MODE, false>), tiles_and_riders, dim3(512), pl.lds, st, *a, tiles_n, nwg, t0, t1, ldg, Mts);
       CARA_CHECK_LAUNCH();
       return CARA_OK;
-    } else {
-      return -1;
     }
   }
-  if constexpr (MODE == 3) {
-    return -1;
-  } else {
+  if constexpr (MODE != 3) {
     static bool attr = false;
     if (!attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8_kernel<G, EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) != hipSuccess)
-        return CARA_E_LAUNCH;
+      if (!g8_allow_lds(gemm8_kernel<G, EPI, MODE>, G::LDS)) return CARA_E_LAUNCH;
       attr = true;
     }
-    static const int stagger_env = [] { const char* e = getenv("CARA_GEMM8_STAGGER"); return e ? atoi(e) : 0; }();
-    hipLaunchKernelGGL((gemm8_kernel<G, EPI, MODE>), dim3(nwg), dim3(512), G::LDS, st, *a, tiles_n, nwg, nwg > 256 ? stagger_env : 0);
+    hipLaunchKernelGGL((gemm8_kernel<G, EPI, MODE>), tiles, dim3(512), pl.lds, st, *a, tiles_n, nwg, pl.stagger);
     CARA_CHECK_LAUNCH();
     return CARA_OK;
   }
-}
-
-template <class G, int MODE>
-int g8_launch_epi(const cara_gemm_args* a, hipStream_t st, const cara_g8_riders* ts, const bool helpers) {
-  switch (a->epi) {
-    case CARA_EPI_BF16: return g8_launch<G, CARA_EPI_BF16, MODE>(a, st, ts, helpers);
-    case CARA_EPI_F32: return g8_launch<G, CARA_EPI_F32, MODE>(a, st, ts, helpers);
-    case CARA_EPI_GELU: return g8_launch<G, CARA_EPI_GELU, MODE>(a, st, ts, helpers);
-    case CARA_EPI_RESID: return g8_launch<G, CARA_EPI_RESID, MODE>(a, st, ts, helpers);
-    case CARA_EPI_DGELU: return g8_launch<G, CARA_EPI_DGELU, MODE>(a, st, ts, helpers);
-    default: return -1;
-  }
+  return CARA_E_ARG;   // (MODE 3 without helper waves: no plan says that)
 }
 
 }  // namespace
@@ -997,18 +975,17 @@ extern "C" int cara_debug_set_gemm8_helpers(int on) {
   g_helpers_override = on;
   return CARA_OK;
 }
-static bool g8_helpers() {
+bool cara_gemm8_helpers_on() {
   static const int env = [] { const char* e = getenv("CARA_GEMM8_HELPERS"); return e ? atoi(e) : 0; }();
   return (g_helpers_override >= 0 ? g_helpers_override : env) != 0;
 }
 
-bool cara_gemm8_helpers_on() { return g8_helpers(); }
-
-int cara_gemm8_plan(const cara_gemm_args* a, int mt, int riders_nt) {
-  // what the tile takes: row-major A and B (whole 128-byte lines per K step of 64); the K-extension at Rp = 32 with T given (A2) or
-  // computed inside (Ut, rank <= 16); riding products of one r-tile (rank <= 16)
+int cara_gemm8_plan(const cara_gemm_args* a, int mt, int riders_nt, int riders_colsum, cara_g8_plan* out) {
+  // what the tile takes: row-major A and B (whole 128-byte lines per K step of 64); every epilogue but CARA_EPI_GELU_DG / _MULH; the
+  // K-extension at Rp = 32 with T given (A2) or computed inside (Ut, rank <= 16); riding products of one r-tile behind the dX epilogues
   if (a->a_panels || a->batch > 1 || a->B3 || a->K < 128 || (a->K % 64) || a->M < 1024 || (a->M % 16) || (a->N % 16)) return 0;
   if ((unsigned long long)a->M * a->lda * 2 >= 0x7fffff00ull || (unsigned long long)a->N * a->ldb * 2 >= 0x7fffff00ull) return 0;
+  if (a->epi < 0 || a->epi > 6 || !((EPI_MASK_TILE >> a->epi) & 1u)) return 0;
   int mode = 0;
   if (a->Ut) {
     if (a->A2 || !a->B2 || a->Rp != 32 || !a->T_out || a->Ut_rank < 1 || a->Ut_rank > 16 || (a->Tt_out && (a->ldt < a->M || (a->ldt & 7)))) return 0;
@@ -1019,30 +996,51 @@ int cara_gemm8_plan(const cara_gemm_args* a, int mt, int riders_nt) {
   }
   const bool riders = riders_nt != 0;
   if (riders && (riders_nt != 1 || !(a->epi == CARA_EPI_BF16 || a->epi == CARA_EPI_DGELU))) return 0;
+  bool dv = false, helpers = false;
   if (a->er_Tt) {   // dVs out of the A sub-buffers: CARA_EPI_BF16, the 160-row tile, a K-extension (given or inside), 32-bit slab offsets
     if (a->epi != CARA_EPI_BF16 || mt != 160 || !mode || a->er_h || !a->er_slabs_v || a->er_ldg < a->M || (a->er_ldg & 7)) return 0;
     const unsigned long long chunks = (a->M + 159) / 160;
     if (chunks * (a->K / 64) * (64 * 16 * 4) >= 0x7fffff00ull) return 0;
-    return 1;
+    if (riders && riders_colsum) return 0;   // (the riders beside DV: a pending dU, which has no column sums)
+    dv = true;
+  } else if (mt == 256) {
+    if (mode || riders) return 0;   // (the yardstick tile: plain products)
+  } else if (mt != 160) {
+    return 0;
+  } else {
+    helpers = cara_gemm8_helpers_on() && (mode == 2 || (riders && mode == 1));
   }
-  if (mt == 256) return (mode || riders) ? 0 : 1;   // (the yardstick tile: plain products)
-  if (mt != 160) return 0;
-  if (g8_helpers() && (mode == 2 || (riders && mode == 1))) return 2;
-  return 1;
+  if (out) {
+    using G = G8<3, 2>;
+    out->mt = mt;
+    out->mode = (mode == 2 && helpers) ? 3 : mode;
+    out->helpers = helpers;
+    out->dv = dv;
+    out->tiles_n = (a->N + 255) / 256;
+    out->nwg = ((a->M + mt - 1) / mt) * out->tiles_n;
+    out->block = helpers ? 768 : 512;
+    out->lds = mt == 256 ? G8<4, 4>::LDS : (helpers ? H8<G>::LDS : (riders ? g8_lds_ts<G>() : G::LDS));
+    static const int stagger_env = [] { const char* e = getenv("CARA_GEMM8_STAGGER"); return e ? atoi(e) : 0; }();
+    out->stagger = (!helpers && !dv && !riders && out->nwg > 256) ? stagger_env : 0;
+  }
+  return helpers ? 2 : 1;
 }
 
-int cara_gemm8_launch(const cara_gemm_args* a, hipStream_t st, int mt, const cara_g8_riders* ts) {
-  const int plan = cara_gemm8_plan(a, mt, ts ? ts->nt : 0);
-  if (!plan) return -1;
-  if (mt == 256) return g8_launch_epi<G8<4, 4>, 0>(a, st, nullptr, false);
-  const int mode = a->Ut ? 2 : (a->Rp ? 1 : 0);
-  if (mode == 2) {
+int cara_gemm8_launch(const cara_gemm_args* a, hipStream_t st, const cara_g8_plan& pl, const cara_g8_riders* ts) {
+  const auto go = [&](auto g, auto mode) {
+    using G = decltype(g);
+    return cara_dispatch_epi<EPI_MASK_TILE>(a->epi, [&](auto e) { return g8_launch<G, decltype(e)::value, decltype(mode)::value>(a, st, pl, ts); });
+  };
+  if (pl.mt == 256) return go(G8<4, 4>{}, std::integral_constant<int, 0>{});
+  if (pl.mode >= 2) {
     // consumers read Tt in whole 32-row steps: keep columns [M, roundup32(M)) zero, as cara_skinny_xu does
     const int m32 = (a->M + 31) / 32 * 32;
     if (a->Tt_out && m32 > a->M && m32 <= a->ldt &&
         hipMemset2DAsync(static_cast<bf16*>(a->Tt_out) + a->M, (size_t)a->ldt * 2, 0, (size_t)(m32 - a->M) * 2, a->Rp, st) != hipSuccess)
       return CARA_E_LAUNCH;
-    return plan == 2 ? g8_launch_epi<G8<3, 2>, 3>(a, st, ts, true) : g8_launch_epi<G8<3, 2>, 2>(a, st, ts, false);
   }
-  return mode == 1 ? g8_launch_epi<G8<3, 2>, 1>(a, st, ts, plan == 2) : g8_launch_epi<G8<3, 2>, 0>(a, st, ts, false);
+  if (pl.mode == 3) return go(G8<3, 2>{}, std::integral_constant<int, 3>{});
+  if (pl.mode == 2) return go(G8<3, 2>{}, std::integral_constant<int, 2>{});
+  if (pl.mode == 1) return go(G8<3, 2>{}, std::integral_constant<int, 1>{});
+  return go(G8<3, 2>{}, std::integral_constant<int, 0>{});
 }

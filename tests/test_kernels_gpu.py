@@ -273,8 +273,9 @@ def _sk_scratch():
 
 @pytest.mark.parametrize("M,N,K,Rp", [(64, 768, 3072, 32), (64, 3072, 768, 32), (64, 768, 768, 64), (17, 300, 2304, 0), (128, 768, 768, 32)])
 def test_gemm_few_rows_split_k(M, N, K, Rp):
-    """Few-row products with caller scratch: K slabs in one batched launch + a finishing kernel (bias, rank-R term,
-    epilogue).  Rows strided as the last block's cls rows are (row stride 5 * width)."""
+    """Few-row products with caller scratch (what makes a call take the few-row kernel): one launch of small_m_direct_kernel,
+    a workgroup per 16 x 16 output tile whose waves split K and whose tail adds the bias, the rank-R term and the epilogue.
+    Rows strided as the last block's cls rows are (row stride 5 * width)."""
     sc = _sk_scratch()
     stride = 5
     Abig, B = rnd(M * stride, K, seed=1, scale=0.3), rnd(N, K, seed=2, scale=0.3)
