@@ -566,7 +566,7 @@ def _mlp_factored(xn, w, p, fac, r):
     return adapter_linear(h, w[p + "mlp.fc2.weight"], w[p + "mlp.fc2.bias"], fac["fc2"], r, "h")
 
 
-def attn_rounding_model(qkv, dout, B, N, H, scale, dtype):
+def attn_rounding_model(qkv, dout, B, N, H, scale, dtype, mm=None):
     """Attention forward and backward of cara_amd/csrc/attention.hip in float64, rounded to the operand type ``dtype`` where the
     kernels round and nowhere else: ``(out [B N, H 64], lse [B, H, N], dqkv [B N, 3 H 64])``.  ``qkv`` [B N, 3 H 64] and ``dout``
     [B N, H 64] hold values of ``dtype``; any device.  What the device accumulates in fp32 is exact here, so the distance of
@@ -579,7 +579,8 @@ def attn_rounding_model(qkv, dout, B, N, H, scale, dtype):
       (284), ``attn_fwd_p2_kernel`` (630-654); cls: ``sc[n] = (float)(bf16)e`` (1458).
     * the row sum is taken of the unrounded exponentials (175, 270; cls 1457) and divides the fp32 accumulator; ``out`` is rounded
       once: ``(bf16)(o[dt][r] * iv)`` in ``fwd_store_rows`` (199), 303, ``cvt_pk_dword(po * pinv)`` (505); cls 1486.
-    * ``lse = mx * scale + __logf(sum)`` is an fp32 number (202, 306, 681; cls 1487): rounded to float32 here.
+    * ``lse = mx * scale + __logf(sum)`` is an fp32 number (202, 306, 681; cls 1487): rounded to float32 here -- except with ``dtype``
+      torch.float64, which asks for the exact attention (nothing is rounded then, lse included).
     backward
     * ``D = rowsum(dO . out)`` from the ROUNDED ``out`` the forward stored, summed in fp32: ``dq_rows`` (780),
       ``attn_bwd_dkv_kernel`` (889), ``attn_bwd_fused_kernel`` (1108); cls 1517.
@@ -592,20 +593,24 @@ def attn_rounding_model(qkv, dout, B, N, H, scale, dtype):
     """
     def r(t):
         return t.to(dtype).double()
+    # ``mm``: the matrix product (backward_rounding_model's second evaluation passes one that accumulates in fp32, in another order)
+    mm = mm or torch.matmul
     q, k, v = qkv.double().reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)
-    s = (q @ k.transpose(-2, -1)) * scale
+    s = mm(q, k.transpose(-2, -1)) * scale
     m = s.amax(-1, keepdim=True)
     e = torch.exp(s - m)
     l = e.sum(-1, keepdim=True)
-    o = r((r(e) @ v) / l)
-    lse = (m + l.log()).float().double()
+    o = r(mm(r(e), v) / l)
+    lse = m + l.log()
+    if dtype != torch.float64:   # (float64: the exact attention, for the identity checks of the backward model)
+        lse = lse.float().double()
     do = dout.double().reshape(B, N, H, 64).transpose(1, 2)
     P = torch.exp(s - lse)
     D = (do * o).sum(-1, keepdim=True)
-    dV = r(r(P).transpose(-2, -1) @ do)
-    dS = r(P * (do @ v.transpose(-2, -1) - D))
-    dQ = r(dS @ k * scale)
-    dK = r(dS.transpose(-2, -1) @ q * scale)
+    dV = r(mm(r(P).transpose(-2, -1), do))
+    dS = r(P * (mm(do, v.transpose(-2, -1)) - D))
+    dQ = r(mm(dS, k) * scale)
+    dK = r(mm(dS.transpose(-2, -1), q) * scale)
     dqkv = torch.stack([dQ, dK, dV], 0).permute(1, 3, 0, 2, 4).reshape(B * N, 3 * H * 64)
     return o.transpose(1, 2).reshape(B * N, H * 64), lse.squeeze(-1), dqkv
 
@@ -683,3 +688,262 @@ def train_step_as_written(images, labels, w, cp, head, *, s, depth=12, num_heads
     grads = {k: v.grad for k, v in cpv.items()}
     grads.update({"head." + k: v.grad for k, v in hv.items()})
     return loss.detach(), logits.detach(), grads
+
+
+# ----------------------------------------------------------------------------------------------
+# The factored train step with the device's rounding points, forward AND backward
+# ----------------------------------------------------------------------------------------------
+
+# rounding points of the backward that backward_rounding_model can leave out one at a time (``skip``), for the sensitivity tables
+BACKWARD_POINTS = ("dyb", "G", "dX16", "dXn", "u", "attn", "head_xn", "dxn")
+
+
+class _Arith:
+    """How a rounding model computes: ``r(t, point)`` rounds to the operand type (not for the points in ``skip``), ``mm`` is the
+    matrix product and ``f`` marks a number the device holds in fp32.  The committed model accumulates exactly (float64) and ``f``
+    is the identity; ``acc32`` is the second evaluation of the device tests' yardstick: products accumulated in fp32 over K chunks
+    taken in descending order, fp32 numbers rounded to fp32."""
+
+    def __init__(self, dtype, skip=(), acc32=False, slip=None):
+        self.dtype, self.skip, self.acc32, self.slip = dtype, set(skip), acc32, dict(slip or {})
+
+    def r(self, t, point=None):
+        if self.dtype is None or point in self.skip:
+            return t
+        return t.to(self.dtype).double()
+
+    def f(self, t):
+        return t.float().double() if self.acc32 else t
+
+    def mm(self, a, b, chunk=96):
+        if not self.acc32:
+            return a @ b
+        a, b, acc = a.float(), b.float(), None
+        for k0 in reversed(range(0, a.shape[-1], chunk)):
+            part = a[..., k0:k0 + chunk] @ b[..., k0:k0 + chunk, :]
+            acc = part if acc is None else acc + part
+        return acc.double()
+
+
+def _gelu_grad(u):
+    return 0.5 * (1 + torch.erf(u * 2 ** -0.5)) + u * torch.exp(-0.5 * u * u) / math.sqrt(2 * math.pi)
+
+
+def _ln_fwd(x, g, b, eps):
+    mu = x.mean(-1, keepdim=True)
+    rs = ((x - mu).pow(2).mean(-1, keepdim=True) + eps).rsqrt()
+    return (x - mu) * rs * g + b, (mu, rs)
+
+
+def _ln_bwd(dy, x, g, stats):
+    """ln_bwd_kernel (norm_misc.hip:252-274): dx = rstd (g - mean g - xhat mean(g xhat)), g = dy gamma"""
+    mu, rs = stats
+    xh, gg = (x - mu) * rs, dy * g
+    return rs * (gg - gg.mean(-1, keepdim=True) - xh * (gg * xh).mean(-1, keepdim=True))
+
+
+def _lin_fwd_model(c, x, wgt, bias, fac):
+    """adapter_linear on an already rounded x: (fp32 accumulator + biases, the stored T)"""
+    U, Vs, cs = fac
+    T = c.r(c.mm(x, c.r(U)), "T")
+    y = c.mm(x, c.r(wgt).t()) + c.mm(T, c.r(Vs).t()) + bias
+    return c.f(y if cs is None else y + cs), T
+
+
+def _lin_bwd_model(c, dy, x, T, wgt, fac, tag=None):
+    """modules._lin_bwd / vit.hip lin_bwd: (the fp32 accumulator of dX, dU, dVs, dc) from the operand-type dY, the stored X and T"""
+    U, Vs, _ = fac
+    G = c.r(c.mm(dy, c.r(Vs)), "G")
+    dx = c.f(c.mm(dy, c.r(wgt)) + c.mm(G, c.r(U).t()))
+    xu, gu = x, G
+    if c.slip.get("rider_rows", (None, 0))[0] == tag:   # SLIP: this linear's dU = X^T G' leaves out its last n rows (a ragged row tile)
+        n = c.slip["rider_rows"][1]
+        xu, gu = x[:-n], G[:-n]
+    return dx, c.f(c.mm(xu.t(), gu)), c.f(c.mm(dy.t(), T)), c.f(dy.sum(0))
+
+
+def _attn_branch(c, x, dy_of, w, p, fac, B, N, H, scale, path):
+    """Forward of the attention branch on x [B N, D]; ``dy_of(y)`` hands back the branch gradient.  Returns y, dx and the pieces."""
+    D = x.shape[1]
+    xb = c.r(x, "xn")
+    acc, T1 = _lin_fwd_model(c, xb, w[p + "attn.qkv.weight"], w[p + "attn.qkv.bias"], fac["qkv"])
+    qkv = c.r(acc, "qkv")
+    at = c.dtype if (c.dtype is not None and "attn" not in c.skip) else torch.float64
+    mm = c.mm if c.acc32 else None
+    ao = attn_rounding_model(qkv, torch.zeros_like(xb), B, N, H, scale, at, mm)[0]
+    ao = c.r(ao, "ao")   # (a no-op on the model's own output; with the "attn" points left out it is the forward's one rounding of `out`)
+    y, T2 = _lin_fwd_model(c, ao, w[p + "attn.proj.weight"], w[p + "attn.proj.bias"], fac["proj"])
+    dy = dy_of(y)
+    if dy is None:
+        return y, None, {}
+    dyb = c.r(dy, "dyb")
+    dacc, dU_p, dV_p, dc_p = _lin_bwd_model(c, dyb, ao, T2, w[p + "attn.proj.weight"], fac["proj"], p + "proj")
+    dao = c.r(dacc, "dX16")
+    dqkv = attn_rounding_model(qkv, dao, B, N, H, scale, at, mm)[2]
+    if at is torch.float64:   # ("attn" left out: dqkv still crosses to the next kernel in the operand type)
+        dqkv = c.r(dqkv, "dX16")
+    dx, dU_q, dV_q, _ = _lin_bwd_model(c, dqkv, xb, T1, w[p + "attn.qkv.weight"], fac["qkv"], p + "qkv")
+    if path == "model":
+        dx = c.r(dx, "dXn")
+    return y, dx, {"dU_qkv": dU_q, "dVs_qkv": dV_q, "dU_proj": dU_p, "dVs_proj": dV_p, "dc_proj": dc_p}
+
+
+def _mlp_branch(c, x, dy_of, w, p, fac, path, saved_gelu_grad):
+    xb = c.r(x, "xn")
+    up, T1 = _lin_fwd_model(c, xb, w[p + "mlp.fc1.weight"], w[p + "mlp.fc1.bias"], fac["fc1"])
+    h = c.r(F.gelu(up), "h")
+    y, T2 = _lin_fwd_model(c, h, w[p + "mlp.fc2.weight"], w[p + "mlp.fc2.bias"], fac["fc2"])
+    dy = dy_of(y)
+    if dy is None:
+        return y, None, {}
+    dyb = c.r(dy, "dyb")
+    dacc, dU2, dV2, dc2 = _lin_bwd_model(c, dyb, h, T2, w[p + "mlp.fc2.weight"], fac["fc2"], p + "fc2")
+    if saved_gelu_grad:   # gelu'(u) of the fp32 accumulator, kept as IEEE half in both builds
+        gp = _gelu_grad(up) if c.dtype is None or "u" in c.skip else _gelu_grad(up).to(torch.float16).double()
+    elif p in c.slip.get("dgelu_from_h", ()):   # SLIP: gelu' taken of the rounded h instead of the stored pre-activation
+        gp = _gelu_grad(h)
+    else:
+        gp = _gelu_grad(c.r(up, "u"))
+    dh = c.r(c.f(dacc * gp), "dX16")
+    dx, dU1, dV1, dc1 = _lin_bwd_model(c, dh, xb, T1, w[p + "mlp.fc1.weight"], fac["fc1"], p + "fc1")
+    if path == "model":
+        dx = c.r(dx, "dXn")
+    return y, dx, {"dU_fc1": dU1, "dVs_fc1": dV1, "dc_fc1": dc1, "dU_fc2": dU2, "dVs_fc2": dV2, "dc_fc2": dc2}
+
+
+def _cp_grads_from_pieces(cp, s, depth, heads, pieces):
+    """cara_factor_grad_reduce (factors.hip: fp32 sums over the UNROUNDED CP tensors) as the chain rule through build_factored,
+    which is differentiable: d/dCP of  sum_l <U_l, dU_l> + <Vs_l, dVs_l> + <c_l, dc_l>."""
+    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in cp.items()}
+    fac = build_factored(leaves, s, depth=depth, heads=heads)
+    total = 0.0
+    for l in range(depth):
+        for n in ("qkv", "proj", "fc1", "fc2"):
+            U, Vs, cs = fac[l][n]
+            total = total + (U * pieces[l]["dU_" + n]).sum() + (Vs * pieces[l]["dVs_" + n]).sum()
+            if cs is not None:
+                total = total + (cs * pieces[l]["dc_" + n]).sum()
+    names = list(leaves)
+    g = torch.autograd.grad(total, [leaves[k] for k in names], allow_unused=True)
+    return {k: (torch.zeros_like(leaves[k]) if gi is None else gi) for k, gi in zip(names, g)}
+
+
+def block_rounding_model(kind, x, dy, w, cp, *, layer, s, depth, num_heads=12, dtype=None, skip=(), acc32=False,
+                         saved_gelu_grad=False):
+    """One branch (``kind`` = "attn" | "mlp") of block ``layer`` as the MODULE-LEVEL path runs it (cara_amd/modules.py AttnFn / MlpFn):
+    x, dy [B, N, D] hold values of ``dtype``.  Returns (y, dx, pieces): the branch output, the input gradient -- the fp32
+    accumulator of the qkv / fc1 dX GEMM, which this path does not round (modules.py:168-170, 221-223: L.EPI_F32) -- and the
+    per-linear dU_*, dVs_*, dc_* [.., rank].  Rounding points: those of backward_rounding_model's table without "dXn"."""
+    c = _Arith(dtype, skip, acc32)
+    B, N, D = x.shape
+    cpd = {k: v.double() for k, v in cp.items()}
+    wd = {k: v.double() for k, v in w.items() if k.startswith(f"blocks.{layer}.")}
+    fac = build_factored(cpd, s, depth=depth, heads=num_heads)[layer]
+    x2, dy2, p = x.double().reshape(B * N, D), dy.double().reshape(B * N, D), f"blocks.{layer}."
+    if kind == "attn":
+        y, dx, pieces = _attn_branch(c, x2, lambda y: dy2, wd, p, fac, B, N, num_heads, (D // num_heads) ** -0.5, "module")
+    else:
+        y, dx, pieces = _mlp_branch(c, x2, lambda y: dy2, wd, p, fac, "module", saved_gelu_grad)
+    return y.reshape(B, N, D), dx.reshape(B, N, D), pieces
+
+
+def backward_rounding_model(images, labels, w, cp, head, *, s, depth, num_heads=12, patch=16, eps=1e-6, dtype=None,
+                            drop_path_keep=None, loss_scale=1.0, skip=(), acc32=False, saved_gelu_grad=False, want_pieces=False, slip=None):
+    """The factored train step of cara_vit_forward / cara_vit_backward (cara_amd/csrc/vit.hip) in float64, rounded to the operand
+    type ``dtype`` (torch.bfloat16, torch.float16; None: nowhere) where the device rounds and nowhere else.  What the device
+    accumulates in fp32 is exact here, so the distance of this model from float64 autograd is the rounding noise the kernels may
+    carry and no more.  Returns (loss, logits, grads[, pieces]): grads of every CP tensor, "head.weight" and "head.bias";
+    ``pieces[l]``: dx_attn / dx_mlp (what each branch hands its LayerNorm backward) and dU_*, dVs_*, dc_* of each linear.
+
+    The forward is ``vit_cara_forward(factored=True, sim_dtype=dtype, drop_path_keep=...)`` (tests/test_backward_model.py holds the
+    two equal) and the mean cross-entropy.  The backward is written out kernel by kernel, not taken from autograd of the rounded
+    forward: a rounder has no gradient, and the backward rounds at points of its own.  Rounding points of the backward, with the
+    lines they restate (vit.hip unless named; every name can be passed in ``skip``):
+
+    * "dxn", "head_xn"  head_bwd_kernel: dhead_w from the 16-bit copy of the normalised cls row (710), dxn rounded once (730); dlogits,
+      the loss (norm_misc.hip xent_kernel) and the final LayerNorm's backward are fp32.  ``loss_scale`` multiplies dlogits
+      (engine.py:470-477; 1024 in the fp16 build) and is divided out of the finished gradients in fp32 (703, factors.hip).
+    * "dyb"   the branch gradient: ``dyb = (bf16)(dx * rowscale)`` (norm_misc.hip:280), dx itself stays fp32 (279, ``o += dx_in`` 277).
+    * "G"     G' = dY Vs rounded as a GEMM operand: the separate pass (skinny.hip, lin_bwd 445), the LayerNorm-fused
+      ``block_contract`` (norm_misc.hip:297) and the GEMM's own (``a.T_out = G`` 452) write 16-bit G / Gt.
+    * "dX16"  dX = dY W + G' U^T accumulates in fp32 and is rounded once: dAO (``e.epi = CARA_EPI_BF16`` 1136), dH (1104;
+      gemm_epilogue.h:106 ``(bf16)(v * gelu_erf_grad((float)u))``, :84 ``(bf16)(v * (float)gv)``), dQKV (attention.hip).
+    * "u"     dGELU from the stored operand-type pre-activation (gemm_epilogue.h:93 writes it, :97-106 read it); with
+      ``saved_gelu_grad`` (CARA_SAVE_GELU_GRAD / CARA_EPI_RIDERS) from gelu'(fp32 accumulator) kept as IEEE half (:72, :84).
+    * "dXn"   WHOLE MODEL ONLY: the dX of fc1 and of qkv is rounded too before the LayerNorm backward reads it (``e.epi =
+      CARA_EPI_BF16; e.C = ws + W.dXn`` 1122, 1151; ln_bwd_kernel takes ``const bf16* dy``).  The module-level path keeps that dX in
+      fp32 (modules.py:168-170, 221-223) -- block_rounding_model.
+    * "attn"  the attention points of attn_rounding_model, as one.
+    * dVs = dY^T T from the stored (forward-rounded) T^T, dU = X^T G' from the stored X, dc = colsum dY: fp32 sums of 16-bit
+      operands (tskinny_body.h; the riders of gemm.hip / gemm8.hip), reduced in fp32 (cara_tskinny_reduce_many 1221), scattered
+      onto the CP tensors in fp32 from the unrounded CP values (factors.hip grad_stage1 / 2).
+    The last block's cls shortcut (946, 1090) is exact: rows it skips carry no gradient here either.  Not modelled: the order-2
+    tensorisation and the exact weight-dropout mode.
+
+    ``slip`` puts ONE deliberate defect into the model, for the would-it-notice tables (tests/test_backward_model.py): {"no_rowscale":
+    ("blocks.1.", ..)} -- the DropPath rowscale missing from the 16-bit branch gradients of those blocks; {"dgelu_from_h": (..)} --
+    gelu' of the rounded h; {"rider_rows": ("blocks.1.fc2", n)} -- that linear's dU without its last n token rows."""
+    if cp_length_of(cp) == 2:
+        raise ValueError("the order-2 tensorisation is not modelled")
+    c = _Arith(dtype, skip, acc32, slip)
+    dev = images.device
+    wd = {k: v.double().to(dev) for k, v in w.items()}
+    cpd = {k: v.double().to(dev) for k, v in cp.items()}
+    hw, hb = head["weight"].double().to(dev), head["bias"].double().to(dev)
+    B = images.shape[0]
+    dim = wd["cls_token"].shape[-1]
+    scale = (dim // num_heads) ** -0.5
+    gh = images.shape[2] // patch
+    cols = images.double().reshape(B, images.shape[1], gh, patch, gh, patch).permute(0, 2, 4, 1, 3, 5).reshape(B * gh * gh, -1)
+    emb = c.f(c.mm(c.r(cols, "images"), c.r(wd["patch_embed.proj.weight"].reshape(dim, -1)).t()) + wd["patch_embed.proj.bias"])
+    x = torch.cat((wd["cls_token"].expand(B, -1, -1), emb.reshape(B, gh * gh, dim)), dim=1) + wd["pos_embed"]
+    N = x.shape[1]
+    x = c.f(x.reshape(B * N, dim))
+    fac = build_factored(cpd, s, depth=depth, heads=num_heads)
+    keep = None if drop_path_keep is None else drop_path_keep.double().to(dev)
+
+    def rows(l, j, backward=False):   # the DropPath multiplier of every token row
+        if keep is None or (backward and f"blocks.{l}." in c.slip.get("no_rowscale", ())):
+            return 1.0
+        return keep[l, j].repeat_interleave(N).unsqueeze(1)
+
+    # forward, keeping what the backward reads; each branch is re-entered with its gradient below (``dy_of``)
+    tape = []
+    for l in range(depth):
+        p = f"blocks.{l}."
+        xn1, st1 = _ln_fwd(x, wd[p + "norm1.weight"], wd[p + "norm1.bias"], eps)
+        ya = _attn_branch(c, c.f(xn1), lambda y: None, wd, p, fac[l], B, N, num_heads, scale, "model")[0]
+        x_mid = c.f(x + rows(l, 0) * ya)
+        xn2, st2 = _ln_fwd(x_mid, wd[p + "norm2.weight"], wd[p + "norm2.bias"], eps)
+        ym = _mlp_branch(c, c.f(xn2), lambda y: None, wd, p, fac[l], "model", saved_gelu_grad)[0]
+        tape.append((x, st1, xn1, x_mid, st2, xn2))
+        x = c.f(x_mid + rows(l, 1) * ym)
+    xc, stF = _ln_fwd(x.reshape(B, N, dim)[:, 0], wd["norm.weight"], wd["norm.bias"], eps)
+    xc = c.f(xc)
+    logits = c.f(c.mm(xc, hw.t()) + hb)
+    logp = logits.log_softmax(-1)
+    loss = -logp[torch.arange(B, device=dev), labels.to(dev)].mean()
+    # backward
+    dl = logp.exp()
+    dl[torch.arange(B, device=dev), labels.to(dev)] -= 1.0
+    dl = c.f(dl * (loss_scale / B))
+    grads = {"head.weight": c.f(c.mm(dl.t(), c.r(xc, "head_xn")) / loss_scale), "head.bias": c.f(dl.sum(0) / loss_scale)}
+    dxn = c.r(c.f(c.mm(dl, hw)), "dxn")
+    dx = torch.zeros(B, N, dim, dtype=torch.float64, device=dev)
+    dx[:, 0] = _ln_bwd(dxn, x.reshape(B, N, dim)[:, 0], wd["norm.weight"], stF)
+    dx = c.f(dx.reshape(B * N, dim))
+    pieces = [None] * depth
+    for l in reversed(range(depth)):
+        p = f"blocks.{l}."
+        x_in, st1, xn1, x_mid, st2, xn2 = tape[l]
+        _, dxm, pm = _mlp_branch(c, c.f(xn2), lambda y: dx * rows(l, 1, True), wd, p, fac[l], "model", saved_gelu_grad)
+        dx = c.f(_ln_bwd(dxm, x_mid, wd[p + "norm2.weight"], st2) + dx)
+        _, dxa, pa = _attn_branch(c, c.f(xn1), lambda y: dx * rows(l, 0, True), wd, p, fac[l], B, N, num_heads, scale, "model")
+        if l > 0:   # (block 0 has nothing trainable upstream: its qkv dX GEMM and LayerNorm backward do not run, vit.hip:1152)
+            dx = c.f(_ln_bwd(dxa, x_in, wd[p + "norm1.weight"], st1) + dx)
+        pieces[l] = dict(pm, **pa)
+        pieces[l].update(dx_mlp=dxm, dx_attn=dxa)
+    unscaled = [{k: v / loss_scale for k, v in pc.items()} for pc in pieces]
+    grads.update(_cp_grads_from_pieces(cpd, s, depth, num_heads, unscaled))
+    out = (loss.detach(), logits.detach(), {k: v.detach() for k, v in grads.items()})
+    return out + (unscaled,) if want_pieces else out

@@ -1372,15 +1372,17 @@ def test_rider_placement_switches_pass_the_whole_model_parity_tests(switch):
     """Three measured-and-off placements of the backward's heavy riders (read once per process): CARA_EPI_RIDERS=1 -- fc1's dVs / dc and
     fc2's dU out of the fc2 dX epilogue, gelu'(u) kept as IEEE half by fc1 forward; CARA_FC1_SIDE=1 -- the same products as a launch on a
     side stream under the fc1 dX GEMM; CARA_DV=3 -- fc1's and qkv's dVs / dc out of the A tiles of their own dX GEMM.  The batch-64
-    whole-model test, the train-step test, the fp16 headline test and the schedule-regimes test (M = 4144 with a middle block) run
-    again in a process with the switch set."""
+    whole-model test, the train-step test, the fp16 headline test, the schedule-regimes test (M = 4144 with a middle block) and the depth-3 /
+    batch-8 case of tests/test_backward_contract_gpu.py (every gradient within 1.15 x its rounding model's error) run again in a
+    process with the switch set."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, **dict([switch.split("=")]))
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_model_gpu.py"), "-x", "-q", "-s", "-k",
+    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_model_gpu.py"),
+                          os.path.join(root, "tests", "test_backward_contract_gpu.py"), "-x", "-q", "-s", "-k",
                           "headline_batch_64_whole_model or train_step_against_oracle or fp16_precision_at_the_headline_size or "
-                          "backward_schedule_regimes_with_a_middle_block"],
+                          "backward_schedule_regimes_with_a_middle_block or (whole_model_gradients and d3-b8)"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     tail = "\n".join(out.stdout.strip().split("\n")[-12:])
     print(tail)
