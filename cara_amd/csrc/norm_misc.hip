@@ -374,6 +374,66 @@ __global__ __launch_bounds__(256) void im2col_u8_rows_kernel(const uint8_t* __re
   *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
 }
 
+// im2col_u8_rows_kernel through a crop box per sample: pixels [n_split,C,Hs,Ws] of any size, boxes int32 [B,5] = (x0, y0, w, h,
+// flip) in source pixels.  Output pixel (oy, ox) is the bilinear sample (half-pixel centres, no antialiasing filter: what
+// F.interpolate(crop, (Hi,Wi), "bilinear", align_corners=False) gives) of the box at ox' = flip ? Wi-1-ox : ox, with indices
+// clamped inside the box.  Each axis is evaluated as a + f * (b - a): the same polynomial as (1-f) a + f b, and exact where
+// f == 0 or a == b -- a box of the output's size gives the source bytes themselves and a 1x1 box a constant image, bit for
+// bit what normalize_u8x4 gives for that byte.  A lane keeps four adjacent output pixels of one patch row (one 8-byte store;
+// the row pair iy0 / iy1 and fy are shared) and fetches its source with byte loads: the box starts at any byte and Ws need
+// not be a multiple of 4, so no dword of the source is aligned; neighbouring lanes read neighbouring bytes of the same two
+// source rows.  A row outside [0, n_split) or a box not inside the source is never dereferenced: zeros, counted once in *bad.
+struct CropAxis { int i0, i1; float f; };
+__device__ __forceinline__ CropAxis crop_axis(int o, int n_out, int n_box, bool flip) {
+  const int of = flip ? n_out - 1 - o : o;
+  const float s = fmaxf(((float)of + 0.5f) * ((float)n_box / (float)n_out) - 0.5f, 0.0f);
+  const int i0 = min((int)s, n_box - 1);
+  return CropAxis{i0, min(i0 + 1, n_box - 1), s - (float)i0};
+}
+// normalize_u8x4's operations on a value that is no longer a byte
+__device__ __forceinline__ float normalize_f32(float v, float mu, float sd) { return (v / 255.0f - mu) / sd; }
+__global__ __launch_bounds__(256) void im2col_u8_rows_crop_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                                  const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                                  const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                  bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
+                                                                  int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const int kcols = C * p * p;
+  const long e = idx * 4;
+  const long row = e / kcols;
+  const int col = (int)(e - row * kcols);
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
+  const int gy = pr / gw, gx = pr % gw;
+  const int64_t r = rows[b];
+  const int* box = boxes + (size_t)b * 5;
+  const int x0 = box[0], y0 = box[1], w = box[2], h = box[3];
+  const bool flip = box[4] != 0;
+  // (x0, y0 >= 0 is checked before Ws - x0, Hs - y0 are formed: no overflow for any int)
+  if (r < 0 || r >= n_split || w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > Ws - x0 || h > Hs - y0) {
+    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
+    const bf16 z = (bf16)0.0f;
+    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
+    return;
+  }
+  const CropAxis ay = crop_axis(gy * p + py, Hi, h, false);
+  const uint8_t* plane = img + ((size_t)r * C + c) * Hs * Ws;
+  const uint8_t* top = plane + (size_t)(y0 + ay.i0) * Ws + x0;
+  const uint8_t* bot = plane + (size_t)(y0 + ay.i1) * Ws + x0;
+  const float mu = mean[c], sd = stdv[c];
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const CropAxis ax = crop_axis(gx * p + px + j, Wi, w, flip);
+    const float t0 = (float)top[ax.i0], t1 = (float)top[ax.i1], b0 = (float)bot[ax.i0], b1 = (float)bot[ax.i1];
+    const float t = t0 + ax.f * (t1 - t0), u = b0 + ax.f * (b1 - b0);
+    v[j] = normalize_f32(t + ay.f * (u - t), mu, sd);
+  }
+  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+}
+
 // out[i] = labels[rows[i]]; a row outside [0, n_split) is not dereferenced: it gives 0 and is counted in *bad (may be NULL)
 __global__ __launch_bounds__(256) void gather_labels_kernel(const int64_t* __restrict__ labels, long n_split,
                                                             const int64_t* __restrict__ rows, int64_t* __restrict__ out,
@@ -685,6 +745,19 @@ extern "C" int cara_im2col_patches_u8_rows(const unsigned char* pixels, int n_sp
   const long total4 = (long)B * C * Hi * Wi / 4;
   hipLaunchKernelGGL(im2col_u8_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      pixels, (long)n_split, rows, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_im2col_patches_u8_rows_crop(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                                const int* boxes, const float* mean, const float* stdv, void* patches, int* bad,
+                                                int B, int C, int Hi, int Wi, int p, void* stream) {
+  if (!pixels || !rows || !boxes || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 ||
+      (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p)
+    return CARA_E_ARG;
+  const long total4 = (long)B * C * Hi * Wi / 4;
+  hipLaunchKernelGGL(im2col_u8_rows_crop_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     pixels, (long)n_split, Hs, Ws, rows, boxes, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }

@@ -898,12 +898,14 @@ BlockPlan plan_block(const cara_geom* g, const cara_vit_shape* s, int M, int Mr,
 
 // The forward behind the three entries: the image is either fp32 (`images`) or resident uint8 pixels with their per-channel
 // mean / std (`pixels`: the batch itself, or with `rows` a whole split of `n_split` images that `rows` indexes); everything
-// behind the patch rows is the same.
+// behind the patch rows is the same.  `crop` (with `rows` only): the split has Hs x Ws pixels of its own and every sample is read
+// through its box (cara_im2col_patches_u8_rows_crop).
+struct CropBoxes { int Hs, Ws; const int* boxes; };
 static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                             const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
                             const unsigned char* pixels, int n_split, const int64_t* rows, int* bad,
                             const float* mean, const float* stdv,
-                            const float* droppath, void* workspace, float* logits, void* stream) {
+                            const float* droppath, void* workspace, float* logits, void* stream, const CropBoxes* crop = nullptr) {
   Ws W;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !workspace || !logits) return CARA_E_ARG;
   if (pixels ? (!mean || !stdv) : !images) return CARA_E_ARG;
@@ -917,7 +919,10 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
   if (dense_qkv) TRY(cara_dense_delta_materialize(g, cp, ws + W.dd, ws + W.ddt, stream));
   // patch embedding: Conv2d(k = s = patch) as a GEMM over im2col rows, then cls + pos_embed
   const int kp = s->chans * s->patch * s->patch;
-  if (pixels && rows)
+  if (pixels && rows && crop)
+    TRY(cara_im2col_patches_u8_rows_crop(pixels, n_split, crop->Hs, crop->Ws, rows, crop->boxes, mean, stdv, ws + W.patches, bad, B, s->chans,
+                                         s->img, s->img, s->patch, stream));
+  else if (pixels && rows)
     TRY(cara_im2col_patches_u8_rows(pixels, n_split, rows, mean, stdv, ws + W.patches, bad, B, s->chans, s->img, s->img, s->patch, stream));
   else if (pixels) TRY(cara_im2col_patches_u8(pixels, mean, stdv, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
   else TRY(cara_im2col_patches(images, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
@@ -1039,6 +1044,17 @@ extern "C" int cara_vit_forward_u8_rows(const cara_geom* g, const cara_vit_shape
   if (!pixels || !rows || n_split <= 0) return CARA_E_ARG;
   return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, n_split, rows, bad, mean, stdv, droppath, workspace, logits,
                           stream);
+}
+
+extern "C" int cara_vit_forward_u8_rows_crop(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                             const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                             int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const float* mean,
+                                             const float* stdv, const float* droppath, void* workspace, float* logits, int* bad,
+                                             void* stream) {
+  if (!pixels || !rows || !boxes || n_split <= 0 || Hs <= 0 || Ws <= 0) return CARA_E_ARG;
+  const CropBoxes crop{Hs, Ws, boxes};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, n_split, rows, bad, mean, stdv, droppath, workspace, logits,
+                          stream, &crop);
 }
 
 extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,

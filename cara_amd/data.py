@@ -15,6 +15,7 @@ against an independent numpy computation in tests/test_data.py.
 """
 from __future__ import annotations
 
+import math
 import os
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Iterator, List, Optional, Sequence, Tuple
@@ -71,6 +72,106 @@ def normalize_u8(x: torch.Tensor) -> torch.Tensor:
 def decode_image(path: str, size: int = 224) -> torch.Tensor:
     """The whole transform of vtab.py:91-94 for one file: fp32 [3,size,size]."""
     return normalize_u8(decode_image_u8(path, size))
+
+
+class RandomResizedCropFlip:
+    """Crop boxes for the augmented resident feed: the published definition of torchvision's ``RandomResizedCrop.get_params``
+    plus a coin flip, restated (torchvision is not installed).  Per sample, up to ten tries of an area ``Hs * Ws * U(scale)``
+    and an aspect ratio ``exp(U(log ratio))``, ``w = round(sqrt(area * r))``, ``h = round(sqrt(area / r))``; the first try with
+    ``0 < w <= Ws`` and ``0 < h <= Hs`` is taken at a uniform integer offset.  If none fits: the centre crop of the whole image
+    clamped to the ratio bounds.  ``size`` is the side the crop is resized to (the model's input); the boxes do not depend on it
+    -- the kernel that reads them resamples to the model's own size.  No colour jitter, mixup / cutmix or antialiasing."""
+
+    TRIES = 10
+
+    def __init__(self, size: int, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip: float = 0.5):
+        if not (0 < scale[0] <= scale[1]) or not (0 < ratio[0] <= ratio[1]) or not (0.0 <= flip <= 1.0) or int(size) <= 0:
+            raise ValueError("RandomResizedCropFlip: size > 0, 0 < scale[0] <= scale[1], 0 < ratio[0] <= ratio[1], flip in [0, 1]")
+        self.size, self.scale, self.ratio, self.flip = int(size), (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1])), float(flip)
+
+    def draw(self, Hs: int, Ws: int, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """int32 [n, 5] = (x0, y0, w, h, flip) in the pixels of an ``Hs`` x ``Ws`` source, on the host.  A fixed number of
+        variates per sample (ten tries of four, one flip), so sample ``i`` of a table does not depend on ``n``."""
+        T = self.TRIES
+        u = torch.rand(n, T, 4, generator=generator, dtype=torch.float64)
+        coin = torch.rand(n, generator=generator, dtype=torch.float64)
+        area = Hs * Ws * (self.scale[0] + (self.scale[1] - self.scale[0]) * u[..., 0])
+        lo, hi = math.log(self.ratio[0]), math.log(self.ratio[1])
+        r = torch.exp(lo + (hi - lo) * u[..., 1])
+        w = torch.round(torch.sqrt(area * r)).to(torch.int64)
+        h = torch.round(torch.sqrt(area / r)).to(torch.int64)
+        ok = (w > 0) & (w <= Ws) & (h > 0) & (h <= Hs)
+        first = torch.where(ok.any(1), ok.to(torch.int64).argmax(1), torch.zeros(n, dtype=torch.int64))
+        pick = lambda t: t.gather(1, first[:, None])[:, 0]   # noqa: E731
+        w, h = pick(w), pick(h)
+        x0 = torch.floor(pick(u[..., 2]) * (Ws - w + 1).clamp(min=1)).to(torch.int64)
+        y0 = torch.floor(pick(u[..., 3]) * (Hs - h + 1).clamp(min=1)).to(torch.int64)
+        # the fallback: whole image, centre crop clamped to the ratio bounds
+        in_ratio = Ws / Hs
+        if in_ratio < self.ratio[0]:
+            fw, fh = Ws, int(round(Ws / self.ratio[0]))
+        elif in_ratio > self.ratio[1]:
+            fw, fh = int(round(Hs * self.ratio[1])), Hs
+        else:
+            fw, fh = Ws, Hs
+        fw, fh = min(max(fw, 1), Ws), min(max(fh, 1), Hs)
+        none = ~ok.any(1)
+        w, h = torch.where(none, torch.full_like(w, fw), w), torch.where(none, torch.full_like(h, fh), h)
+        x0 = torch.where(none, torch.full_like(x0, (Ws - fw) // 2), x0).clamp_(min=0)
+        y0 = torch.where(none, torch.full_like(y0, (Hs - fh) // 2), y0).clamp_(min=0)
+        x0, y0 = torch.minimum(x0, Ws - w), torch.minimum(y0, Hs - h)
+        return torch.stack([x0, y0, w, h, (coin < self.flip).to(torch.int64)], 1).to(torch.int32).contiguous()
+
+
+def check_boxes(boxes: torch.Tensor, Hs: int, Ws: int) -> None:
+    """ValueError unless ``boxes`` is an int32 [..., 5] table whose every box lies inside an ``Hs`` x ``Ws`` image"""
+    if not torch.is_tensor(boxes) or boxes.dtype != torch.int32 or boxes.ndim < 1 or boxes.shape[-1] != 5:
+        raise ValueError("boxes must be an int32 [..., 5] tensor (x0, y0, w, h, flip)")
+    b = boxes.reshape(-1, 5).to(torch.int64)
+    x0, y0, w, h = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    bad = (w < 1) | (h < 1) | (x0 < 0) | (y0 < 0) | (x0 + w > Ws) | (y0 + h > Hs)
+    if bool(bad.any()):
+        raise ValueError(f"{int(bad.sum())} crop box(es) outside the {Hs} x {Ws} source, the first: {boxes.reshape(-1, 5)[int(bad.to(torch.int64).argmax())].tolist()}")
+
+
+def resized_crop_reference(pixels_u8: torch.Tensor, rows, boxes, size, dtype=torch.float64) -> torch.Tensor:
+    """What ``cara_im2col_patches_u8_rows_crop`` samples, before normalisation, in torch ops on the CPU: [B,C,Hi,Wi] of
+    ``dtype`` with ``size`` = Hi or (Hi, Wi).  Output pixel (oy, ox) of sample b: ``ox' = flip ? Wi-1-ox : ox``,
+    ``sx = max((ox' + 0.5) * (w / Wi) - 0.5, 0)``, ``ix0 = min(int(sx), w-1)``, ``ix1 = min(ix0+1, w-1)``, ``fx = sx - ix0``, the
+    same for y, ``v = (1-fy) ((1-fx) u00 + fx u01) + fy ((1-fx) u10 + fx u11)`` on the bytes at (y0+iy*, x0+ix*) of image
+    ``rows[b]``: bilinear ``interpolate(align_corners=False, antialias=False)`` of the box, then a horizontal flip."""
+    Hi, Wi = (size, size) if isinstance(size, int) else size
+    px = pixels_u8.cpu()
+    rows = torch.as_tensor(rows).cpu().tolist()
+    boxes = torch.as_tensor(boxes).cpu().tolist()
+    out = torch.empty(len(rows), px.shape[1], Hi, Wi, dtype=dtype)
+
+    def axis(n_out, n_box, flip):
+        o = torch.arange(n_out, dtype=dtype)
+        if flip:
+            o = n_out - 1 - o
+        s = ((o + 0.5) * (torch.tensor(n_box, dtype=dtype) / n_out) - 0.5).clamp_(min=0)
+        i0 = s.to(torch.int64).clamp_(max=n_box - 1)
+        return i0, (i0 + 1).clamp_(max=n_box - 1), s - i0.to(dtype)
+    for b, (r, (x0, y0, w, h, flip)) in enumerate(zip(rows, boxes)):
+        src = px[r, :, y0:y0 + h, x0:x0 + w].to(dtype)
+        iy0, iy1, fy = axis(Hi, h, False)
+        ix0, ix1, fx = axis(Wi, w, flip != 0)
+        fy = fy[:, None]
+        top = (1 - fx) * src[:, iy0][:, :, ix0] + fx * src[:, iy0][:, :, ix1]
+        bot = (1 - fx) * src[:, iy1][:, :, ix0] + fx * src[:, iy1][:, :, ix1]
+        out[b] = (1 - fy) * top + fy * bot
+    return out
+
+
+def box_seed(seed: int, epoch: int, rank: int) -> int:
+    """32-bit seed (torch's host generator keeps no more) of the generator that draws the crop boxes of one rank's epoch: each
+    of seed, epoch and rank enters through an odd multiplier, so changing one of them alone always changes the value, and a
+    bijective finaliser (murmur3's) spreads neighbouring values"""
+    x = (int(seed) * 0x9E3779B1 + int(epoch) * 0x85EBCA77 + int(rank) * 0xC2B2AE3D + 0x27D4EB2F) & 0xffffffff
+    x = ((x ^ (x >> 16)) * 0x85EBCA6B) & 0xffffffff
+    x = ((x ^ (x >> 13)) * 0xC2B2AE35) & 0xffffffff
+    return x ^ (x >> 16)
 
 
 class ResidentSplit:
@@ -131,11 +232,15 @@ class ResidentSplit:
         return epoch_iter
 
     def train_rows(self, batch_size: int = 64, seed: int = 0, rank: Optional[int] = None,
-                   world: Optional[int] = None) -> Callable[[int], Iterator[torch.Tensor]]:
+                   world: Optional[int] = None, augment=None) -> Callable[[int], Iterator[torch.Tensor]]:
         """``f(epoch)`` -> iterator of int64 [batch_size] index vectors on the device: the indices ``train_batches`` draws
         (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
         and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
-        and uploaded once as one [steps, batch_size] tensor; every step gets a row view of it."""
+        and uploaded once as one [steps, batch_size] tensor; every step gets a row view of it.
+        ``augment`` (a ``RandomResizedCropFlip``, or anything with its ``draw``): the iterator yields ``(rows, boxes)`` --
+        the same index vectors, each with an int32 [batch_size, 5] view of one [steps, batch_size, 5] box upload per epoch
+        (``train_step_resident(..., boxes=)``).  The boxes are drawn on the host from a generator seeded by (seed, epoch,
+        rank) and range-checked before the upload, like the indices."""
         rank = D.get_rank() if rank is None else rank
         world = D.world_size() if world is None else world
 
@@ -146,9 +251,18 @@ class ResidentSplit:
             table = torch.stack(idx)
             if int(table.min()) < 0 or int(table.max()) >= len(self):
                 raise ValueError(f"epoch {epoch}: a drawn index is outside [0, {len(self)})")
-            table = table.to(self.pixels.device)
+            if augment is None:
+                table = table.to(self.pixels.device)
+                for step in range(table.shape[0]):
+                    yield table[step]
+                return
+            Hs, Ws = self.pixels.shape[2:]
+            gen = torch.Generator().manual_seed(box_seed(seed, epoch, rank))
+            boxes = augment.draw(Hs, Ws, table.numel(), gen).reshape(*table.shape, 5)
+            check_boxes(boxes, Hs, Ws)
+            table, boxes = table.to(self.pixels.device), boxes.to(self.pixels.device)
             for step in range(table.shape[0]):
-                yield table[step]
+                yield table[step], boxes[step]
         return epoch_iter
 
     def eval_batches(self, batch_size: int = 256) -> Callable[[], Iterator[Tuple[torch.Tensor, torch.Tensor]]]:
@@ -179,17 +293,28 @@ class ResidentSplit:
 
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
-             seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False):
+             seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False, augment=None,
+             train_size: Optional[int] = None):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
     ``shard_eval = True``: the second value is the test ``ResidentSplit`` itself, the form ``fit(eval_mode="sharded")`` and
     ``CaraEngine.evaluate`` take (every rank then scores its own part, ``ResidentSplit.eval_shard``).
     ``resident_feed = True``: the first value is ``(train split, its train_rows(batch_size, seed=seed))``, the form
-    ``fit(feed="resident")`` takes: the steps read the split's uint8 pixels by index instead of a normalised fp32 batch."""
+    ``fit(feed="resident")`` takes: the steps read the split's uint8 pixels by index instead of a normalised fp32 batch.
+    ``augment`` / ``train_size`` (with ``resident_feed``): the training split is decoded at ``train_size`` (default 224, the
+    model's size) and its ``train_rows`` yields ``(rows, boxes)`` drawn by ``augment`` -- "resize 256, random-resized-crop
+    224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size."""
+    if (augment is not None or train_size is not None) and not resident_feed:
+        raise ValueError("augment / train_size belong to the resident feed: pass resident_feed=True")
+    if train_size is not None and train_size != 224 and augment is None:
+        raise ValueError("a training split of another size than the model's is read through crop boxes: pass augment")
     root = root if root is not None else "./data/vtab-1k/" + name
     tr, te = ("train800val200.txt", "test.txt") if evaluate else ("train800.txt", "val200.txt")
-    train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers)
+    train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers, size=224 if train_size is None else train_size)
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
-    feed = (train, train.train_rows(batch_size, seed=seed)) if resident_feed else train.train_batches(batch_size, seed=seed)
+    if resident_feed:
+        feed = (train, train.train_rows(batch_size, seed=seed) if augment is None else train.train_rows(batch_size, seed=seed, augment=augment))
+    else:
+        feed = train.train_batches(batch_size, seed=seed)
     return feed, (test if shard_eval else test.eval_batches(256))

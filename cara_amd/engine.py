@@ -232,12 +232,14 @@ class CaraEngine:
             return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev)
 
     def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None):
-        """``resident = (split, rows)``: the images are rows of a resident uint8 split (``images`` is None then)"""
+        """``resident = (split, rows[, boxes])``: the images are rows of a resident uint8 split (``images`` is None then), with
+        ``boxes`` read through a crop box per sample at the model's own input size"""
+        boxes = None
         if resident is None:
             st = self._state(model, images.shape[0], images.shape[2], dev)
         else:
-            split, rows = resident
-            st = self._state(model, rows.shape[0], split.pixels.shape[2], dev)
+            split, rows, boxes = resident if len(resident) == 3 else (*resident, None)
+            st = self._state(model, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
             if st["shape"].chans != 3:
                 raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
         # weight-space dropout is a train-mode thing (nn.Dropout is the identity in eval); the backward of this
@@ -263,6 +265,12 @@ class CaraEngine:
         if resident is None:
             check(self._lib().cara_vit_forward(*args, ptr(images), ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)),
                   "cara_vit_forward")
+        elif boxes is not None:
+            mean, std = self._eval_norm(dev)
+            check(self._lib().cara_vit_forward_u8_rows_crop(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
+                                                            split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mean), ptr(std),
+                                                            ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)),
+                                                            stream(dev)), "cara_vit_forward_u8_rows_crop")
         else:
             mean, std = self._eval_norm(dev)
             check(self._lib().cara_vit_forward_u8_rows(*args, ptr(split.pixels), len(split), ptr(rows), ptr(mean), ptr(std),
@@ -498,27 +506,44 @@ class CaraEngine:
             t.zero_()
         return n
 
-    def _resident_args(self, split, rows):
+    @staticmethod
+    def _model_img(model):
+        img = getattr(model.patch_embed, "img_size", None)
+        img = img[0] if isinstance(img, (tuple, list)) else img
+        if not isinstance(img, int) or img <= 0:
+            raise CaraError("boxes need a model that states its input size (patch_embed.img_size)")
+        return img
+
+    def _resident_args(self, split, rows, boxes=None):
         model = self._model()
+        box_msg = "boxes must be a contiguous int32 [batch, 5] tensor (x0, y0, w, h, flip) on the model's device"
+        # (what a box table is, before where it lives: a host-made table of the wrong type is refused as such)
+        if boxes is not None and (not torch.is_tensor(boxes) or boxes.dtype != torch.int32 or boxes.ndim != 2 or boxes.shape[1] != 5
+                                  or not boxes.is_contiguous()):
+            raise CaraError(box_msg)
         dev = model.head.weight.device if hasattr(model.head, "weight") else None
         if dev is None:
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
         if dev.type != "cuda":
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         px, lb = getattr(split, "pixels", None), getattr(split, "labels", None)
-        if px is None or lb is None or px.dtype != torch.uint8 or px.ndim != 4 or px.shape[1] != 3 or px.shape[2] != px.shape[3] or px.device != dev \
+        if px is None or lb is None or px.dtype != torch.uint8 or px.ndim != 4 or px.shape[1] != 3 \
+                or (boxes is None and px.shape[2] != px.shape[3]) or px.device != dev \
                 or not px.is_contiguous() or lb.dtype != torch.int64 or lb.device != dev or lb.shape != px.shape[:1] or len(split) != px.shape[0]:
             raise CaraError("split must be a ResidentSplit (uint8 [N,3,H,H] pixels, int64 [N] labels) on the model's device")
         if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.device != dev or rows.ndim != 1 or rows.shape[0] == 0 \
                 or not rows.is_contiguous():
             raise CaraError("rows must be a contiguous int64 [batch] tensor on the model's device")
+        if boxes is not None and (boxes.device != dev or boxes.shape[0] != rows.shape[0]):
+            raise CaraError(box_msg)
         return model, dev
 
-    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward):
+    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None):
         model = self._model()
         dev = rows.device
         with torch.cuda.device(dev):
-            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows))
+            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev,
+                                        resident=(split, rows) if boxes is None else (split, rows, boxes))
 
     def _gather_labels(self, split, rows):
         dev, B = rows.device, rows.shape[0]
@@ -532,25 +557,30 @@ class CaraEngine:
                                              stream(dev)), "cara_gather_labels")
         return buf
 
-    def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None):
+    def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
         else is train_step's.  A row outside the split is not read: it trains on a zero image with label 0 and is counted
-        (``resident_bad_rows``)."""
-        _, dev = self._resident_args(split, rows)
-        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True),
+        (``resident_bad_rows``).
+        ``boxes`` (device int32 [batch, 5] = (x0, y0, w, h, flip) in the split's pixels, e.g. ``data.RandomResizedCropFlip.draw``):
+        sample ``i`` is the bilinear resize of that box of image ``rows[i]`` to the model's input size, flipped where ``flip`` is
+        non-zero (``cara_vit_forward_u8_rows_crop``); the split's pixels may then be [N,3,Hs,Ws] of any size.  A box that is not
+        inside the image is not read either: a zero image, counted like a bad row."""
+        _, dev = self._resident_args(split, rows, boxes)
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath)
 
-    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None):
-        """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools)"""
-        model, dev = self._resident_args(split, rows)
+    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None):
+        """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``
+        as in ``train_step_resident`` (a centre-cropped evaluation by hand)"""
+        model, dev = self._resident_args(split, rows, boxes)
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
         self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, model.head.weight, model.head.bias, cp, False)
+            return self._forward_rows(split, rows, droppath, model.head.weight, model.head.bias, cp, False, boxes)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):

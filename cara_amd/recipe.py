@@ -108,7 +108,9 @@ class GraphedTrainStep:
     upload { step, lr } and replay.  What a capture cannot hold runs eagerly, every time: more than one rank (the all-reduce) and the
     exact weight-dropout mode (a fresh host-side seed per step).  Same switch as ``bench.py --graph``.
     The resident form ``step(split, rows)`` captures ``train_step_resident``: one graph per (split, shape of ``rows``, mode), whose
-    only static input is the index vector -- 8 bytes per sample are copied per step, no image."""
+    only static input is the index vector -- 8 bytes per sample are copied per step, no image.  ``step(split, (rows, boxes))``
+    captures the augmented step (``train_step_resident(..., boxes=)``): one graph per (split, shapes, mode) again, whose static
+    inputs are the index vector and the box table -- both copied before every replay, 28 bytes per sample."""
 
     def __init__(self, engine, optimizer):
         if not getattr(optimizer, "capturable", False):
@@ -117,10 +119,13 @@ class GraphedTrainStep:
         self._graphs = {}
 
     def __call__(self, x, y, group=None):
-        """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector"""
+        """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector, or
+        ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
         resident = hasattr(x, "pixels")
+        if resident and isinstance(y, (tuple, list)):
+            return self._call_boxes(x, y[0], y[1], group)
         step = eng.train_step_resident if resident else eng.train_step
         self.opt.advance()
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
@@ -156,6 +161,40 @@ class GraphedTrainStep:
         gr.replay()
         return loss
 
+    def _call_boxes(self, split, rows, boxes, group):
+        """the resident form through crop boxes: warm, capture, replay as above, with two static inputs"""
+        from . import dist as cdist
+        eng, model = self.eng, self.eng._model()
+        eng._resident_args(split, rows, boxes)     # (refused here, not inside a capture)
+        self.opt.advance()
+        if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
+            return eng.train_step_resident(split, rows, self.opt, group=group, boxes=boxes)
+        key = (("rows+boxes", split, tuple(rows.shape), tuple(boxes.shape)), bool(model.training), eng.precision)
+        ent = self._graphs.get(key)
+        if ent is None:
+            self._graphs[key] = "warm"
+            return eng.train_step_resident(split, rows, self.opt, group=group, boxes=boxes)
+        dev = rows.device
+        if ent == "warm":
+            rs, bs = rows.clone(), boxes.clone()
+            torch.cuda.synchronize(dev)
+            gr = torch.cuda.CUDAGraph()
+            gen = eng._device_generator(dev)
+            if gen is not None:
+                gr.register_generator_state(gen)
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(gr, stream=side):
+                    loss = eng.train_step_resident(split, rs, self.opt, group=group, boxes=bs)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            ent = self._graphs[key] = (gr, split, (rs, bs), loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
+        gr, _, (rs, bs), loss = ent[:4]
+        rs.copy_(rows)
+        bs.copy_(boxes)
+        gr.replay()
+        return loss
+
 
 def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[Callable[[], Iterable]] = None,
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
@@ -183,7 +222,9 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``train_rows(...)`` (``get_data(resident_feed=True)`` returns the pair) -- and every step is ``CaraEngine.train_step_resident``
     on an index vector: the same samples in the same order as ``split.train_batches(...)`` with the same seed, without the
     normalised fp32 batch.  An index outside the split is counted on the device, not read; the count is looked at where the
-    evaluation epochs read from the device anyway and once more after the last epoch, and a non-zero one raises."""
+    evaluation epochs read from the device anyway and once more after the last epoch, and a non-zero one raises.
+    A ``rows_of`` that yields ``(rows, boxes)`` pairs (``train_rows(..., augment=data.RandomResizedCropFlip(...))``) trains
+    through a crop box per sample (``train_step_resident(..., boxes=)``); a box outside its image is counted like a bad row."""
     if eval_mode not in ("reference", "sharded"):
         raise CaraError(f"eval_mode must be 'reference' or 'sharded', not {eval_mode!r}")
     if feed not in ("batches", "resident"):
@@ -208,7 +249,12 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     if feed == "resident":
         split, rows_of = train_batches
         train_batches = lambda epoch: ((split, rows) for rows in rows_of(epoch))   # noqa: E731
-        step = eng.train_step_resident
+
+        def step(split, rows, opt, group=None):
+            if isinstance(rows, (tuple, list)):
+                rows, boxes = rows
+                return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes)
+            return eng.train_step_resident(split, rows, opt, group=group)
     else:
         step = eng.train_step
 
@@ -217,7 +263,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         # an epoch's indices on the host before it uploads them, on every rank, so only a hand-made feed can get here)
         bad = eng.resident_bad_rows() if feed == "resident" else 0
         if bad:
-            raise CaraError(f"fit: {bad} row index(es) outside the training split reached the device up to epoch {upto}")
+            raise CaraError(f"fit: {bad} row index(es) outside the training split (or crop boxes outside their image) reached the "
+                            f"device up to epoch {upto}")
     for epoch in range(epochs):
         for x, y in train_batches(epoch):
             if gstep is not None:

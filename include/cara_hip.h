@@ -307,6 +307,20 @@ int cara_im2col_patches_u8(const unsigned char* pixels, const float* mean, const
  * the caller clears it) is incremented once per such sample.                                                            */
 int cara_im2col_patches_u8_rows(const unsigned char* pixels, int n_split, const int64_t* rows, const float* mean,
                                 const float* std, void* patches, int* bad, int B, int C, int Hi, int Wi, int p, void* stream);
+/* cara_im2col_patches_u8_rows through a crop box per sample (random-resized crop and flip by index): pixels uint8
+ * [n_split,C,Hs,Ws] -- any size, not the model's, Ws need not be a multiple of 4, no alignment asked -- and boxes device int32
+ * [B,5] = (x0, y0, w, h, flip) in source pixels.  Output pixel (oy, ox) of sample b, channel c, in fp32:
+ *   ox' = flip ? Wi-1-ox : ox;  sx = max((ox' + 0.5) * (w / Wi) - 0.5, 0);  ix0 = min((int)sx, w-1);  ix1 = min(ix0+1, w-1);
+ *   fx = sx - ix0;  the same for y with h / Hi;  v = (1-fy) ((1-fx) u00 + fx u01) + fy ((1-fx) u10 + fx u11)
+ * on the bytes at (y0+iy*, x0+ix*) of image rows[b], each axis evaluated as a + f (b - a) (exact where f == 0 or a == b); then
+ * (v / 255 - mean[c]) / std[c] and the one rounding to the build's 16-bit type, as in cara_im2col_patches_u8.  That is bilinear
+ * interpolate(align_corners = false, no antialias filter) of the box followed by a horizontal flip; indices are clamped inside
+ * the box.  A box of the output's size gives bit for bit the patch rows of cara_im2col_patches_u8 on those bytes.  A row
+ * outside [0, n_split) or a box not inside the source (w < 1, h < 1, x0 < 0, y0 < 0, x0+w > Ws, y0+h > Hs) is never
+ * dereferenced: zero patch rows, *bad (may be NULL) incremented once per such sample.  flip: non-zero means flip.        */
+int cara_im2col_patches_u8_rows_crop(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                     const int* boxes, const float* mean, const float* std, void* patches, int* bad, int B,
+                                     int C, int Hi, int Wi, int p, void* stream);
 /* out[i] = labels[rows[i]] (device int64 [B] each; labels int64 [n_split]); a row outside [0, n_split) is not
  * dereferenced: it gives 0 and is counted in *bad (device int, may be NULL)                                    */
 int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
@@ -545,6 +559,14 @@ int cara_vit_forward_u8_rows(const cara_geom* g, const cara_vit_shape* s, const 
                              const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
                              int n_split, const int64_t* rows, const float* mean, const float* std, const float* droppath,
                              void* workspace, float* logits, int* bad, void* stream);
+/* cara_vit_forward_u8_rows on a split of Hs x Ws pixels (pixels uint8 [n_split,chans,Hs,Ws], any size) read through a crop
+ * box per sample (boxes device int32 [B,5]): the patch rows come from cara_im2col_patches_u8_rows_crop, every later stage is
+ * shared, the workspace is that of cara_vit_workspace_bytes unchanged, and a cara_vit_backward may follow.                 */
+int cara_vit_forward_u8_rows_crop(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                  const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                  int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const float* mean,
+                                  const float* std, const float* droppath, void* workspace, float* logits, int* bad,
+                                  void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,

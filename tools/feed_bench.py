@@ -10,7 +10,12 @@ adapters, AdamW) over a synthetic resident split of 1 000 uint8 images under its
 Eager and from a hipGraph (recipe.GraphedTrainStep).  The legs run interleaved in one process -- per round a window of
 --steps steps of each, barrier + synchronize on both sides of a window, after --warmup steps of every leg -- and the line
 printed says ms per step of each leg (median / min / max over the rounds) and the run-to-run spread of each.  Standalone:
-not part of bench.py."""
+not part of bench.py.
+
+--augment runs other legs instead (the lines above are then not printed): the eager resident step as it is, the same step through
+crop boxes (data.RandomResizedCropFlip on a 256-px split of the same images count: "resize 256, random-resized-crop 224"), and the
+two patch-row kernels alone (cara_im2col_patches_u8_rows / cara_im2col_patches_u8_rows_crop at the step's output shape, device
+events around --kernel-launches back-to-back launches), all interleaved round by round."""
 import argparse
 import json
 import os
@@ -33,6 +38,9 @@ def main():
     ap.add_argument("--rank", type=int, default=16)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"])
     ap.add_argument("--legs", default="eager,graph")
+    ap.add_argument("--augment", action="store_true", help="time the augmented resident step and the two patch-row kernels instead")
+    ap.add_argument("--source", type=int, default=256, help="--augment: side of the split the boxes are drawn on")
+    ap.add_argument("--kernel-launches", type=int, default=200, help="--augment: launches per timed kernel window")
     args = ap.parse_args()
     import torch.distributed as dist
     from cara_amd import cara, create_model
@@ -65,6 +73,8 @@ def main():
             yield from of_epoch(epoch)
             epoch += 1
 
+    if args.augment:
+        return augment_legs(args, eng, opt, split, feeder, dev, gd)
     gstep = GraphedTrainStep(eng, opt)
 
     def eager_batches(item):
@@ -122,6 +132,83 @@ def main():
     res["bad_rows"] = eng.resident_bad_rows()
     for name, v in ms.items():
         print(f"{name:15s} {statistics.median(v):8.4f} ms/step (min {min(v):.4f}, max {max(v):.4f})")
+    print(json.dumps(res))
+
+
+def augment_legs(args, eng, opt, split, feeder, dev, gd):
+    from cara_amd import _lib as L
+    from cara_amd.data import IMAGENET_MEAN, IMAGENET_STD, RandomResizedCropFlip, ResidentSplit
+    S, B = args.source, args.batch
+    big = ResidentSplit.from_tensors(torch.randint(0, 256, (args.images, 3, S, S), generator=gd, dtype=torch.uint8, device=dev), split.labels)
+    aug = RandomResizedCropFlip(224)
+
+    def plain(rows):
+        opt.advance()
+        return eng.train_step_resident(split, rows, opt)
+
+    def augmented(item):
+        opt.advance()
+        return eng.train_step_resident(big, item[0], opt, boxes=item[1])
+    steps = {"eager/resident": (feeder(split.train_rows(B)), plain),
+             f"eager/resident+crop{S}": (feeder(big.train_rows(B, augment=aug)), augmented)}
+    # the kernels alone, on the rows and boxes of one drawn batch, into one patches buffer of the step's shape
+    lib, dt = L.lib(args.precision), L.act_dtype(args.precision)
+    rows, boxes = next(big.train_rows(B, augment=aug)(0))
+    mean, std = torch.tensor(IMAGENET_MEAN, device=dev), torch.tensor(IMAGENET_STD, device=dev)
+    patches = torch.empty(B * 196, 768, dtype=dt, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = L.stream(dev)
+
+    def k_rows():
+        L.check(lib.cara_im2col_patches_u8_rows(L.ptr(split.pixels), len(split), L.ptr(rows), L.ptr(mean), L.ptr(std), L.ptr(patches),
+                                                L.ptr(bad), B, 3, 224, 224, 16, st), "cara_im2col_patches_u8_rows")
+
+    def k_crop():
+        L.check(lib.cara_im2col_patches_u8_rows_crop(L.ptr(big.pixels), len(big), S, S, L.ptr(rows), L.ptr(boxes), L.ptr(mean), L.ptr(std),
+                                                     L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st), "cara_im2col_patches_u8_rows_crop")
+    kernels = {"kernel/u8_rows": k_rows, f"kernel/u8_rows_crop{S}": k_crop}
+
+    def step_window(name, n):
+        feed, step = steps[name]
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = step(next(feed))
+        torch.cuda.synchronize(dev)
+        return (time.perf_counter() - t0) * 1e3 / n, float(loss)
+
+    def kernel_window(name, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            kernels[name]()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1) * 1e3 / n      # us per launch
+    for name in steps:
+        step_window(name, args.warmup)
+    for name in kernels:
+        kernel_window(name, 20)
+    ms, us, last = {n: [] for n in steps}, {n: [] for n in kernels}, {}
+    for _ in range(args.rounds):
+        for name in steps:
+            t, last[name] = step_window(name, args.steps)
+            ms[name].append(t)
+        for name in kernels:
+            us[name].append(kernel_window(name, args.kernel_launches))
+    res = {"config": {"model": "vit_base_patch16_224_in21k", "depth": args.depth, "batch": B, "rank": args.rank, "images": args.images,
+                      "source": S, "precision": args.precision, "steps_per_window": args.steps, "rounds": args.rounds,
+                      "kernel_launches": args.kernel_launches, "device": torch.cuda.get_device_name(dev)}}
+    for unit, table in (("ms_per_step", ms), ("us_per_launch", us)):
+        for name, ts in table.items():
+            res[name] = {unit: [round(t, 4) for t in ts], "median": round(statistics.median(ts), 4), "min": round(min(ts), 4),
+                         "max": round(max(ts), 4), "spread": round(max(ts) - min(ts), 4)}
+            print(f"{name:26s} {statistics.median(ts):9.4f} {unit.split('_')[0]} (min {min(ts):.4f}, max {max(ts):.4f})")
+    a, b = res["eager/resident"], res[f"eager/resident+crop{S}"]
+    res["crop_minus_plain_ms"] = round(b["median"] - a["median"], 4)
+    res["crop_not_slower_within_plain_spread"] = bool(b["median"] - a["median"] <= a["spread"])
+    res["last_loss"] = last
+    res["bad_rows"] = eng.resident_bad_rows()
     print(json.dumps(res))
 
 
