@@ -277,7 +277,14 @@ __global__ __launch_bounds__(XU ? XU_WAVES * 64 : 256) void ln_bwd_kernel(const 
       o.x += pq.x; o.y += pq.y; o.z += pq.z; o.w += pq.w;
     }
     *reinterpret_cast<float4*>(dor + c0) = o;
-    bf16x4 b = {(bf16)(o.x * sc), (bf16)(o.y * sc), (bf16)(o.z * sc), (bf16)(o.w * sc)};
+    float4 os = make_float4(o.x * sc, o.y * sc, o.z * sc, o.w * sc);
+#ifdef CARA_F16_OPERANDS
+    // IEEE-half build: the compiler folds product + conversion into v_fma_mixlo_f16 (ONE rounding of the exact product) in some
+    // instantiations and keeps v_mul_f32 + v_cvt_f16_f32 (two) in others, so the fused and the plain kernels disagreed on dyb
+    // where the fp32 product lands on a half tie (tests/test_small_kernels_gpu.py).  The product is an fp32 value everywhere:
+    asm volatile("" : "+v"(os.x), "+v"(os.y), "+v"(os.z), "+v"(os.w));
+#endif
+    bf16x4 b = {(bf16)os.x, (bf16)os.y, (bf16)os.z, (bf16)os.w};
     if (db && !(XU && yp)) *reinterpret_cast<bf16x4*>(yp ? dyb + ((size_t)(c0 >> 5) * yp + row) * 32 + (c0 & 31) : db + c0) = b;
     yb[i] = b;
   }
@@ -463,6 +470,9 @@ __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__
 }
 
 // one wave per sample; loss = mean_b (lse_b - logit_b[y_b]); dlogits = (softmax - onehot) / B
+// A label outside [0, C) (torch's ignore index -100, a split with more classes than the head, an int64 that only its low
+// 32 bits would bring into range) never indexes the row: that sample's loss term and its dlogits row are NaN, so the mean
+// loss is NaN too and the step is visibly wrong instead of quietly so.  Every other sample's outputs are unaffected.
 __global__ __launch_bounds__(64) void xent_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                   float* __restrict__ loss_per, float* __restrict__ dlogits,
                                                   int B, int C, float dscale, const float* __restrict__ loss_scale) {
@@ -475,14 +485,17 @@ __global__ __launch_bounds__(64) void xent_kernel(const float* __restrict__ logi
   for (int c = lane; c < C; c += 64) s += __expf(lr[c] - m);
   s = wave_sum(s);
   const float lse = m + __logf(s);
-  const int y = (int)labels[b];
+  const int64_t yl = labels[b];
+  const bool ok = yl >= 0 && yl < C;   // (wave-uniform)
+  const int y = ok ? (int)yl : 0;
+  const float qnan = __builtin_nanf("");
   const float invB = 1.0f / B;
   // (the gradient's scale: 1/B of the mean, times 1/world of a data-parallel job, times the loss scale of the IEEE-half build)
   const float gsc = invB * dscale * (loss_scale ? *loss_scale : 1.f);
   if (dlogits)
     for (int c = lane; c < C; c += 64)
-      dlogits[(size_t)b * C + c] = (__expf(lr[c] - lse) - (c == y ? 1.f : 0.f)) * gsc;
-  if (lane == 0) loss_per[b] = (lse - lr[y]) * invB;
+      dlogits[(size_t)b * C + c] = ok ? (__expf(lr[c] - lse) - (c == y ? 1.f : 0.f)) * gsc : qnan;
+  if (lane == 0) loss_per[b] = ok ? (lse - lr[y]) * invB : qnan;
 }
 __global__ __launch_bounds__(64) void xent_sum_kernel(const float* __restrict__ loss_per, float* __restrict__ loss, int B,
                                                       float* __restrict__ found_inf) {

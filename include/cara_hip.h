@@ -329,7 +329,8 @@ int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, 
 int cara_assemble_tokens(const float* emb, const float* cls, const float* pos, float* x, int B,
                          int P, int D, void* stream);
 /* loss[0] = mean cross-entropy over B (loss must hold 1 + B floats: [1..B] is scratch);
- * dlogits (optional) = (softmax - onehot)/B ; logits fp32 [B,C]   (vit_cp.py:47)              */
+ * dlogits (optional) = (softmax - onehot)/B ; logits fp32 [B,C]   (vit_cp.py:47)
+ * A label outside [0, C) is never used as an index: that sample's term loss[1 + b], its dlogits row and loss[0] are NaN. */
 int cara_cross_entropy(const float* logits, const int64_t* labels, float* loss, float* dlogits,
                        int B, int C, void* stream);
 /* The same with the gradient pre-scaled, so that a train step needs no separate scaling launches:

@@ -19,6 +19,16 @@ def L():
     return _lib
 
 
+def _K():
+    from oracle import small_kernels
+    return small_kernels
+
+
+def _S():
+    from tests import small_kernels_common
+    return small_kernels_common
+
+
 def rnd(*shape, seed=0, scale=1.0, dtype=torch.bfloat16):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return (torch.randn(*shape, generator=g) * scale).to(dtype).to(DEV)
@@ -533,6 +543,11 @@ def test_layernorm_fwd_bwd(M, C_):
     ref = torch.nn.functional.layer_norm(xd, (C_,), g.double(), b.double(), 1e-6)
     close(y, ref, 2 ** -8, 1e-3, "ln fwd")
     close(mean, x.double().mean(1), 1e-5, 1e-5, "ln mean")
+    # ... and to the derived bounds of oracle/small_kernels.py (rstd included), which the fixed bars above are far looser than
+    f = _K().ln_fwd(x, g, b, 1e-6)
+    _S().check_32("mean", mean, f["mean"])
+    _S().check_32("rstd", rstd, f["rstd"])
+    _S().check_16("y", y, f["y"], torch.bfloat16, 0.02)
     dy = rnd(M, C_, seed=4)
     ref.backward(dy.double())
     dx_in = rnd(M, C_, seed=5, dtype=torch.float32)
@@ -545,6 +560,9 @@ def test_layernorm_fwd_bwd(M, C_):
     refdx = dx_in.double() + xd.grad
     close(dx, refdx, 1e-4, 1e-4, "ln bwd dx")
     close(dyb, refdx * rs.double().repeat_interleave(rps)[:M, None], 2 ** -8, 1e-3, "ln bwd dyb")
+    bw = _K().ln_bwd(dy, x, g, mean, rstd, dx_in, rs, rps)
+    _S().check_32("dx", dx, bw["dx"])
+    _S().check_16("dyb", dyb, bw["dyb"], torch.bfloat16, 0.02)
 
 
 @pytest.mark.parametrize("M,C_,rank,Rp", [(12608, 768, 16, 32), (333, 768, 8, 32), (197, 1024, 16, 32), (70, 768, 32, 32), (5, 256, 3, 32),
@@ -643,6 +661,10 @@ def test_layernorm_strided_cls_rows():
     L().check(lib.cara_layernorm_fwd(p(x), C.c_long(T * C_), p(g), p(b), p(y), p(mean), p(rstd), B, C_, C.c_float(1e-6), st()), "ln")
     ref = torch.nn.functional.layer_norm(x.double().reshape(B, T, C_)[:, 0], (C_,), g.double(), b.double(), 1e-6)
     close(y, ref, 2 ** -8, 1e-3, "ln strided")
+    f = _K().ln_fwd(x.reshape(B, T, C_)[:, 0], g, b, 1e-6)
+    _S().check_32("mean", mean, f["mean"])
+    _S().check_32("rstd", rstd, f["rstd"])
+    _S().check_16("y", y, f["y"], torch.bfloat16, 0.02)
 
 
 # ------------------------------------------------------------------------------------------
@@ -729,6 +751,10 @@ def test_im2col_assemble_xent_transpose():
     rl.backward()
     close(loss[0], rl.detach(), 1e-5, 1e-6, "xent loss")
     close(dl, ld.grad, 1e-4, 1e-7, "xent grad")
+    xe = _K().xent(logits, labels)
+    _S().check_32("xent terms", loss[1:], xe["terms"])
+    _S().check_32("xent loss", loss[0], xe["loss"])
+    _S().check_32("xent dlogits", dl, xe["dlogits"])
     src = rnd(100, 70, seed=7)
     dst = torch.empty(70, 100, dtype=torch.bfloat16, device=DEV)
     L().check(lib.cara_transpose_bf16(p(src), p(dst), 100, 70, st()), "transpose")
@@ -1221,6 +1247,11 @@ def test_head_forward_in_fp32(B, classes, D, tokens):
     close(mean, mu[:, 0], 1e-5, 1e-6, "mean")
     close(rstd, 1 / torch.sqrt(var[:, 0] + 1e-6), 1e-5, 1e-7, "rstd")
     close(xn16, xn, 2 ** -8, 1e-6, "xn16")
+    h = _K().head_fwd(x[:, 0], gamma, beta, W, b, 1e-6)
+    _S().check_32("mean", mean, h["mean"])
+    _S().check_32("rstd", rstd, h["rstd"])
+    _S().check_32("logits", logits, h["logits"])
+    _S().check_16("xn16", xn16, h["xn16"], torch.bfloat16, 0.02)
 
 
 def test_cross_entropy_ex_amp_update_and_adamw_skip_word():

@@ -25,6 +25,22 @@ BWD_VS_MODEL_ORDER = 4.0
 # draw order or initialiser moves entries by ~0.1.  What comes straight from the RNG is compared bitwise.
 HOST_ATOL = 1.0e-5
 
+# The kernels around the blocks (oracle/small_kernels.py): a 16-bit output may be the NEIGHBOUR of the model's rounded value only
+# where the float64 value lies within the derived fp32 error term of a rounding boundary, and only this share of a tensor's
+# elements may use that.  Each cap is chosen with the test inputs (tests/test_small_kernels_model.py): an fp32 restatement of the
+# kernel in another summation order uses at most HALF of it on every case, on the host; never fitted to a device.  Shares per
+# case: docs/findings/small_kernels_contract.md.
+# Row families of tests/test_small_kernels_model.py::family_rows: 0 Gaussian, 1 offset (mean 100, spread 1e-2), 2 constant, 3 one
+# outlier channel, 4 tiny, 5 all zero.  The other-order restatement's largest share over all cases and both operand types is 0.0039
+# (one element of a 256-wide outlier row; Gaussian 0.0013, tiny 0.0007, constant and zero rows none), so twice that, rounded up to
+# 2 %, is the cap of every family but one.  The OFFSET rows have no cap (None): there the derived term -- gamma(kappa + 2) |mu| rstd
+# = 20 x 2^-24 x 100 x 100 = 1.2e-2 -- is several 16-bit steps of y (bf16 7.8e-3, fp16 9.8e-4 at 1), the restatement itself moves
+# 92 % of an fp16 row off the model's value, and a cap below 1 would be fitted, not derived: the interval alone holds those rows.
+# "xu_T" (T = y U and G' = dyb U of the fused LayerNorm kernels): counted over all M of one (C, rank, build) -- at M = 1 a tensor
+# has 32 elements and ONE neighbour case is 3 % -- where the restatement uses at most 0.0013 (fp16; none in bf16): the same 2 %.
+_FAMILY_CAPS = {0: 0.02, 1: None, 2: 0.02, 3: 0.02, 4: 0.02, 5: 0.02}
+SMALL_CAPS = {"ln_y": _FAMILY_CAPS, "ln_dyb": 0.02, "head_xn16": _FAMILY_CAPS, "head_dxn": 0.02, "xu_T": 0.02}
+
 
 def logits_ok(r_ref: float, r_model: float) -> bool:
     return r_ref <= LOGITS_ABS and r_ref <= LOGITS_VS_MODEL * max(r_model, MODEL_FLOOR)
