@@ -61,6 +61,10 @@ int cara_layernorm_bwd_rows_in(const void* dy, const float* x, long ldx, const f
                                const void* Vst, int rank, int Rp, void* G, void* Gt, int ldt, int dyb_panels, int dx_in_every,
                                void* stream);
 
+// Which row lengths C the LayerNorm kernels (cara_layernorm_*) take, with and without the fused adapter contraction.  The one list:
+// norm_misc.hip's argument check and dispatch, and vit.hip's plan (fuse only what the kernels take).
+bool cara_layernorm_takes(int C, bool fused);
+
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 

@@ -3,6 +3,8 @@
 // (restated in oracle/cara_oracle.py).  The residual stream stays fp32; normalised activations
 // leave as bf16 GEMM operands.  All kernels are HBM-bound streaming passes: one wave per row,
 // 16-byte accesses, wave shuffles for the two row reductions.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -585,7 +587,7 @@ bool xu_ok(const XuArgs& a, int M, int C) {
   if (!a.Ut) return true;
   // Rp / 16 column tiles of 16 (rows of Ut beyond the rank are zero, so the pad columns come out zero)
   return a.T && (a.Rp == 32 || a.Rp == 64) && a.rank > 0 && a.rank <= a.Rp && (!a.Tt || (a.ldt >= M && !(a.ldt & 7))) &&
-         (C == 768 || C == 256 || C == 1024);
+         cara_layernorm_takes(C, true);
 }
 // consumers (cara_tskinny_*) read Tt in whole 32-row steps: keep columns [M, roundup32(M)) zero (as cara_skinny_xu does)
 int xu_pad(const XuArgs& a, int M, hipStream_t st) {
@@ -596,6 +598,25 @@ int xu_pad(const XuArgs& a, int M, hipStream_t st) {
   return CARA_OK;
 }
 
+// (C, fused contraction?, its column tiles) -> the template arguments <V4, XU, NT> of ln_fwd_kernel / ln_bwd_kernel, handed to
+// `launch` as integral constants.  Column tiles of the contraction: Rp / 16, or one where half of the padded rank is structurally
+// zero (Rp = 32, rank <= 16).  false: a C the kernels do not take.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class Launch>
+bool ln_dispatch(int C, const XuArgs& a, Launch&& launch) {
+  if (!cara_layernorm_takes(C, a.Ut != nullptr)) return false;
+  auto with_dim = [&](auto xu, auto nt) {
+    if (C == 768) launch(Int<3>{}, xu, nt);
+    else if (C == 1024) launch(Int<4>{}, xu, nt);
+    else launch(Int<1>{}, xu, nt);
+  };
+  if (a.Ut && a.Rp == 64) with_dim(std::true_type{}, Int<4>{});
+  else if (a.Ut && a.rank <= 16) with_dim(std::true_type{}, Int<1>{});
+  else if (a.Ut) with_dim(std::true_type{}, Int<2>{});
+  else with_dim(std::false_type{}, Int<2>{});
+  return true;
+}
+
 int ln_fwd_launch(const float* x, long ldx, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M,
                   int C, float eps, const XuArgs& a, void* stream, int yp = 0) {
   if (!x || !gamma || !beta || !y || !mean || !rstd || M <= 0 || ldx < C || (ldx & 3) || !xu_ok(a, M, C)) return CARA_E_ARG;
@@ -604,31 +625,11 @@ int ln_fwd_launch(const float* x, long ldx, const float* gamma, const float* bet
   if (xu_pad(a, M, st) != CARA_OK) return CARA_E_LAUNCH;
   const int rows_per_block = a.Ut ? 16 : 4;
   const dim3 grid((M + rows_per_block - 1) / rows_per_block), block(a.Ut ? XU_WAVES * 64 : 256);
-#define LNF(V, X) hipLaunchKernelGGL((ln_fwd_kernel<V, X>), grid, block, 0, st, x, ldx, gamma, beta, (bf16*)y, mean, rstd, M, eps, \
-                                     a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp)
-#define LNF4(V) hipLaunchKernelGGL((ln_fwd_kernel<V, true, 4>), grid, block, 0, st, x, ldx, gamma, beta, (bf16*)y, mean, rstd, M, eps, \
-                                   a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp)
-#define LNF1(V) hipLaunchKernelGGL((ln_fwd_kernel<V, true, 1>), grid, block, 0, st, x, ldx, gamma, beta, (bf16*)y, mean, rstd, M, eps, \
-                                   a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp)
-  if (a.Ut && a.Rp == 64) {
-    if (C == 768) LNF4(3);
-    else if (C == 1024) LNF4(4);
-    else LNF4(1);
-  } else if (a.Ut && a.rank <= 16) {   // half of the padded rank is structurally zero: one column tile of the contraction
-    if (C == 768) LNF1(3);
-    else if (C == 1024) LNF1(4);
-    else LNF1(1);
-  } else if (a.Ut) {
-    if (C == 768) LNF(3, true);
-    else if (C == 1024) LNF(4, true);
-    else LNF(1, true);
-  } else if (C == 768) LNF(3, false);
-  else if (C == 1024) LNF(4, false);
-  else if (C == 256) LNF(1, false);
-  else return CARA_E_ARG;
-#undef LNF
-#undef LNF4
-#undef LNF1
+  if (!ln_dispatch(C, a, [&](auto v, auto xu, auto nt) {
+        hipLaunchKernelGGL((ln_fwd_kernel<decltype(v)::value, decltype(xu)::value, decltype(nt)::value>), grid, block, 0, st, x, ldx, gamma, beta, (bf16*)y, mean, rstd, M, eps,
+                           a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp);
+      }))
+    return CARA_E_ARG;
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }
@@ -643,35 +644,21 @@ int ln_bwd_launch(const void* dy, const float* x, long ldx, const float* gamma, 
   if (xu_pad(a, M, st) != CARA_OK) return CARA_E_LAUNCH;
   const int rows_per_block = a.Ut ? 16 : 4;
   const dim3 grid((M + rows_per_block - 1) / rows_per_block), block(a.Ut ? XU_WAVES * 64 : 256);
-#define LNB(V, X) hipLaunchKernelGGL((ln_bwd_kernel<V, X>), grid, block, 0, st, (const bf16*)dy, x, ldx, gamma, mean, rstd, \
-                                     dx_in, dx_out, (bf16*)dyb, rowscale, rows_per_sample, M, a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp, dx_in_every)
-#define LNB4(V) hipLaunchKernelGGL((ln_bwd_kernel<V, true, 4>), grid, block, 0, st, (const bf16*)dy, x, ldx, gamma, mean, rstd, \
-                                   dx_in, dx_out, (bf16*)dyb, rowscale, rows_per_sample, M, a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp, dx_in_every)
-#define LNB1(V) hipLaunchKernelGGL((ln_bwd_kernel<V, true, 1>), grid, block, 0, st, (const bf16*)dy, x, ldx, gamma, mean, rstd, \
-                                   dx_in, dx_out, (bf16*)dyb, rowscale, rows_per_sample, M, a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp, dx_in_every)
-  if (a.Ut && a.Rp == 64) {
-    if (C == 768) LNB4(3);
-    else if (C == 1024) LNB4(4);
-    else LNB4(1);
-  } else if (a.Ut && a.rank <= 16) {
-    if (C == 768) LNB1(3);
-    else if (C == 1024) LNB1(4);
-    else LNB1(1);
-  } else if (a.Ut) {
-    if (C == 768) LNB(3, true);
-    else if (C == 1024) LNB(4, true);
-    else LNB(1, true);
-  } else if (C == 768) LNB(3, false);
-  else if (C == 1024) LNB(4, false);
-  else if (C == 256) LNB(1, false);
-  else return CARA_E_ARG;
-#undef LNB
-#undef LNB4
-#undef LNB1
+  if (!ln_dispatch(C, a, [&](auto v, auto xu, auto nt) {
+        hipLaunchKernelGGL((ln_bwd_kernel<decltype(v)::value, decltype(xu)::value, decltype(nt)::value>), grid, block, 0, st, (const bf16*)dy, x, ldx, gamma, mean, rstd, dx_in,
+                           dx_out, (bf16*)dyb, rowscale, rows_per_sample, M, a.Ut, a.rank, a.Rp, a.T, a.Tt, a.ldt, yp, dx_in_every);
+      }))
+    return CARA_E_ARG;
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }
 }  // namespace
+
+// The row lengths ln_fwd_kernel / ln_bwd_kernel are instantiated for (V4 = C / 256 float4 per lane), with and without the fused
+// contraction: today the same three (declared in common.h: vit.hip's plan asks before it fuses)
+bool cara_layernorm_takes(int C, bool /* fused */) {
+  return C == 768 || C == 1024 || C == 256;
+}
 
 extern "C" int cara_layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, void* y,
                                   float* mean, float* rstd, int M, int C, float eps, void* stream) {

@@ -69,15 +69,12 @@ int env_once(const char* name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
-// CARA_DV (default 0; bit 0: fc1, bit 1: qkv): dVs (+ dc) of fc1 / qkv out of their dX GEMM's own A tiles on the 160 x 256 x 64 tile
-// (plan_block); the workspace then holds one slab per 160-row tile and K step for them (layout)
-int dv_env() {
-  static const int v = env_once("CARA_DV", 0);
-  return v;
-}
+// The placements of the backward's products that need slab regions of their own size, as far as the shape and the switches allow them
+// at all (the block plan below): layout() sizes the regions for them, plan_block() chooses among them per block.  epilogue
+// (CARA_EPI_RIDERS): fc2's dU and fc1's dVs out of the fc2 dX epilogue; a_tiles (CARA_DV): fc1's / qkv's dVs out of their dX tiles.
+struct Placements { bool epilogue, a_tiles; };
+Placements placements(const cara_geom* g, const cara_vit_shape* s, int rows);
 
-bool epi_riders_geom(const cara_geom* g, int Mr, bool exact);
-bool save_gelu_grad(const cara_geom* g, const cara_vit_shape* s);
 bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   if (!g || !s || g->depth <= 0 || g->depth > 64 || g->dim % g->heads || g->dim / g->heads != 64) return false;
   if (!(g->Rp == 32 || g->Rp == 64) || g->rank > g->Rp || s->B <= 0 || s->tokens <= 1) return false;
@@ -162,6 +159,7 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   w->dclsn = c.take((size_t)s->B * D * 2);
   w->gscratch = c.take(cara_factor_grad_scratch_bytes(g));
   const size_t ins[4] = {D, D, D, 4 * D}, outs[4] = {3 * D, D, 4 * D, D};
+  const Placements can = placements(g, s, (int)M);
   for (int i = 0; i < 4; ++i) {
     w->dU[i] = c.take((size_t)g->depth * ins[i] * Rp * 4);
     w->dVs[i] = c.take((size_t)g->depth * outs[i] * Rp * 4);
@@ -170,11 +168,11 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
     w->strideV[i] = (cara_tskinny_scratch_bytes((int)M, (int)outs[i], (int)Rp) + 255) & ~(size_t)255;
     // fc2's dU and fc1's dVs may come out of the fc2 dX epilogue, one slab per 160-row tile (cara_gemm_args::er_*)
     const size_t er_bytes = (cara_gemm_epi_rider_scratch_bytes((int)((M + 127) / 128), (int)(4 * D)) + 255) & ~(size_t)255;   // (row tiles of 128 or 160)
-    if (i == 3 && epi_riders_geom(g, (int)M, s->wd_exact != 0) && er_bytes > w->strideU[i]) w->strideU[i] = er_bytes;
-    if (i == 2 && epi_riders_geom(g, (int)M, s->wd_exact != 0) && er_bytes > w->strideV[i]) w->strideV[i] = er_bytes;
+    if (i == 3 && can.epilogue && er_bytes > w->strideU[i]) w->strideU[i] = er_bytes;
+    if (i == 2 && can.epilogue && er_bytes > w->strideV[i]) w->strideV[i] = er_bytes;
     // (CARA_DV: fc1's / qkv's dVs out of their dX tiles, one slab per 160-row tile and K step: K1 = the linear's out features)
     const size_t dv_bytes = (cara_gemm_epi_rider_scratch_bytes((int)((M + 159) / 160), (int)outs[i]) + 255) & ~(size_t)255;
-    if ((i == 0 || i == 2) && dv_env() != 0 && g->Rp == 32 && dv_bytes > w->strideV[i]) w->strideV[i] = dv_bytes;
+    if ((i == 0 || i == 2) && can.a_tiles && dv_bytes > w->strideV[i]) w->strideV[i] = dv_bytes;
     w->slabU[i] = c.take(w->strideU[i] * g->depth);
     w->slabV[i] = c.take(w->strideV[i] * g->depth);
   }
@@ -286,50 +284,70 @@ struct BwdPass {
   bool side_join = false;     // the side stream holds work the caller's stream has not waited for
 };
 
-// per-call context: what lin_fwd / lin_bwd need besides their operands (nothing here outlives the call)
+// A 16-bit activation of the workspace and how it lies there: row-major with row stride ld, or K-panel-major ([K/32][panels][32],
+// cara_gemm_args::a_panels / c_panels) with `panels` rows per panel (0: row-major), as the block plan says (made by Ctx::act).
+struct Act {
+  bf16* p;
+  int ld, panels;
+  int stride() const { return panels ? -panels : ld; }   // the signed stride of the C ABI (cara_skinny_xu_r, Product::ldx)
+};
+// ... as the A operand of a GEMM / as its 16-bit output
+void reads(cara_gemm_args& a, const Act& x) { a.A = x.p; a.lda = x.panels ? 0 : x.ld; if (x.panels) a.a_panels = x.panels; }
+void writes(cara_gemm_args& a, const Act& y) { a.C = y.p; if (y.panels) { a.c_panels = y.panels; a.ldc = y.ld; } }
+
+// per-pass context: what lin_fwd / lin_bwd and their exact / dense variants need besides their operands (nothing here outlives the
+// call).  The first group is set once per pass, the second once per block.
 struct Ctx {
   void* stream;
-  char* scratch;   // split-K scratch of the workspace in use (few-row products)
-  int layer;
-  bool full;       // this block runs on all token rows (not the cls-row-only last block)
+  char* ws;          // the workspace and its layout
+  const Ws* W;
+  const cara_vit_shape* s;
+  int Rp, ldt;
+  int rank;          // the adapter's rank (0: unknown, the skinny passes compute all Rp columns)
   BwdPass* bwd = nullptr;
-  int rank = 0;    // the adapter's rank (0: unknown, the skinny passes compute all Rp columns)
+  const LayerWs* lw = nullptr;
+  int layer = 0;
+  int rows = 0;      // the rows this half of the block runs on: all M token rows, or the cls rows of the last block
+  bool full = false; // ... all token rows (site brackets); on(): the pass's context for one half of a block
+  Act act(size_t off, int ld, int panels = 0) const { return Act{reinterpret_cast<bf16*>(ws + off), ld, panels}; }
+  float* f32(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  Ctx on(const LayerWs& l, int layer_, int rows_, bool full_) const { Ctx c = *this; c.lw = &l; c.layer = layer_; c.rows = rows_; c.full = full_; return c; }
 };
 
 // the rank the transposed skinny products are told
-inline int ts_rank(const Ctx& cx, int Rp) { return cx.rank > 0 ? cx.rank : Rp; }
+inline int ts_rank(const Ctx& cx) { return cx.rank > 0 ? cx.rank : cx.Rp; }
 
 // One or two products as a launch of their own (a lone product takes the launch's second slot).  small: the two-stage-ring form
 // that fits beside a GEMM of the 160 x 256 x 64 tile.
-int launch_products(const Ctx& cx, const Product* p0, const Product* p1, int Rp, int ldt, void* stream, bool small = false) {
+int launch_products(const Ctx& cx, const Product* p0, const Product* p1, void* stream, bool small = false) {
   if (!p1) { p1 = p0; p0 = nullptr; }
   const Product none, &a = p0 ? *p0 : none, &b = *p1;
   if (p0) *a.format = 0;
   *b.format = 0;
-  return (small ? cara_tskinny_partial2_small : cara_tskinny_partial2_r)(a.X, a.ldx, a.Gt, a.slabs, a.K1, b.X, b.ldx, b.Gt, b.slabs, b.K1, b.colsum, ldt,
-                                                                         b.M, Rp, ts_rank(cx, Rp), stream);
+  return (small ? cara_tskinny_partial2_small : cara_tskinny_partial2_r)(a.X, a.ldx, a.Gt, a.slabs, a.K1, b.X, b.ldx, b.Gt, b.slabs, b.K1, b.colsum, cx.ldt,
+                                                                         b.M, cx.Rp, ts_rank(cx), stream);
 }
 
 // One dX GEMM launch with zero, one or two products riding behind its tiles (a lone product takes the launch's second slot); the
 // launch says how its riders leave their partial sums (it depends on the arguments only)
-int gemm_with_riders(const Ctx& cx, const cara_gemm_args& a, const Product* p0, const Product* p1, int Rp, int ldt) {
+int gemm_with_riders(const Ctx& cx, const cara_gemm_args& a, const Product* p0, const Product* p1) {
   if (!p1) { p1 = p0; p0 = nullptr; }
   if (!p1) return cara_gemm_bf16(&a, cx.stream);
   const Product none, &r0 = p0 ? *p0 : none, &r1 = *p1;
-  const unsigned short f = (unsigned short)cara_gemm_rider_slab_format(&a, Rp, ts_rank(cx, Rp));
+  const unsigned short f = (unsigned short)cara_gemm_rider_slab_format(&a, cx.Rp, ts_rank(cx));
   if (p0) *r0.format = f;
   *r1.format = f;
-  return cara_gemm_with_tskinny_r(&a, r0.X, r0.ldx, r0.Gt, r0.slabs, r0.K1, r1.X, r1.ldx, r1.Gt, r1.slabs, r1.K1, r1.colsum, ldt, a.M, Rp, ts_rank(cx, Rp),
-                                  cx.stream);
+  return cara_gemm_with_tskinny_r(&a, r0.X, r0.ldx, r0.Gt, r0.slabs, r0.K1, r1.X, r1.ldx, r1.Gt, r1.slabs, r1.K1, r1.colsum, cx.ldt, a.M, cx.Rp,
+                                  ts_rank(cx), cx.stream);
 }
 
 // the dU that found no carrier, as a launch of its own
-int flush_waiting(const Ctx& cx, int Rp, int ldt) {
+int flush_waiting(const Ctx& cx) {
   Product& q = cx.bwd->waiting;
   if (!q.X) return CARA_OK;
   const Product dU = q;
   q = Product{};
-  return launch_products(cx, &dU, nullptr, Rp, ldt, cx.stream);
+  return launch_products(cx, &dU, nullptr, cx.stream);
 }
 
 bool g_inside_enabled(int slot);
@@ -358,28 +376,11 @@ struct Lin {  // one adapted linear of one layer
   const bf16 *Wp = nullptr, *Wtp = nullptr;   // K-panel-major images of W / Wt (cara_gemm_args::Bp), or null
 };
 
-// CARA_FUSE_XU=0 keeps the K = dim adapter contractions (T = LN(x) U of qkv / fc1, G' = dY Vs of proj / fc2) as
-// separate cara_skinny_xu passes instead of fusing them into the LayerNorm kernels
-bool fuse_xu(const cara_geom* g) {
-  static const int v = env_once("CARA_FUSE_XU", 1);
-  return v != 0 && (g->Rp == 32 || g->Rp == 64) && (g->dim == 768 || g->dim == 1024 || g->dim == 256);   // what cara_layernorm_*_xu take
-}
-
 // CARA_FUSE_GEMM_T bit 0 (default on) computes T = X U of forward proj / fc2 inside the GEMM that consumes it
 // (cara_gemm_args::Ut) instead of a separate cara_skinny_xu pass
 bool fuse_gemm_t(int Mr, int Rp) {
   static const int v = env_once("CARA_FUSE_GEMM_T", 1);
   return (v & 1) != 0 && (Rp == 32 || Rp == 64) && Mr >= 1024;
-}
-
-// CARA_PANEL_ACTS = mask of the activation groups written K-panel-major ([K/32][M][32], cara_gemm_args::c_panels /
-// a_panels) so that the GEMM that consumes them stages whole cache lines: 1 = h / dH (written by GEMM epilogues),
-// 2 = xn1 / xn2 (LayerNorm forward), 4 = the dY of fc2 / proj (LayerNorm backward).  Default 5: group 2 costs
-// 0.2 ms per step although the GEMMs reading xn1 / xn2 gain 5-8 us each when timed alone (DESIGN.md section 7).
-// Not in the exact-dropout mode, not on the cls-row-only last block.
-bool panel_acts(int Mr, const cara_vit_shape* s, int what = 1) {
-  static const int v = env_once("CARA_PANEL_ACTS", 5);
-  return (v & what) != 0 && !s->wd_exact && Mr >= 1024;
 }
 
 // CARA_FUSE_TS=0: the transposed skinny products of a linear run as their own launch behind its dX GEMM instead of
@@ -389,29 +390,28 @@ bool fuse_ts(int Mr, int Rp) {
   return v != 0 && (Rp == 32 || Rp == 64) && Mr >= 1024;
 }
 
-void with_scratch(cara_gemm_args& a, const Ctx& cx) {
-  a.scratch = cx.scratch;
-  a.scratch_bytes = cx.scratch ? cara_gemm_scratch_bytes() : 0;
+void with_scratch(cara_gemm_args& a, const Ctx& cx) {   // split-K scratch of the workspace in use (few-row products)
+  a.scratch = cx.ws + cx.W->gemm_scratch;
+  a.scratch_bytes = cara_gemm_scratch_bytes();
 }
 
 constexpr int SITE_FWD[4] = {CARA_SITE_QKV_FWD, CARA_SITE_PROJ_FWD, CARA_SITE_FC1_FWD, CARA_SITE_FC2_FWD};
 constexpr int SITE_BWD[4] = {CARA_SITE_QKV_BWD, CARA_SITE_PROJ_BWD, CARA_SITE_FC1_BWD, CARA_SITE_FC2_BWD};
 
-// forward of one adapted linear on Mr rows of X (row stride ldx; ldx < 0: K-panel-major, -ldx rows per panel): T = X U ;
-// C = [X | T] [W | Vs]^T + bias -> epilogue (a.ldc == 0: dense output)
+// forward of one adapted linear on cx.rows rows of X: T = X U ; C = [X | T] [W | Vs]^T + bias -> epilogue (a.ldc == 0: dense output)
 // (have_T: the LayerNorm that produced X already left T = X U and its transpose, cara_layernorm_fwd_xu)
-int lin_fwd(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, int ldt, char* ws, const LayerWs& lw, cara_gemm_args a, const Ctx& cx,
-            bool have_T = false) {
+int lin_fwd(const Lin& L, const Act& X, cara_gemm_args a, const Ctx& cx, bool have_T = false) {
   void* st = cx.stream;
-  bf16* T = reinterpret_cast<bf16*>(ws + lw.T[L.slot]);
-  bf16* Tt = reinterpret_cast<bf16*>(ws + lw.Tt[L.slot]);
+  const int Mr = cx.rows, Rp = cx.Rp, ldt = cx.ldt;
+  bf16* T = cx.act(cx.lw->T[L.slot], Rp).p;
+  bf16* Tt = cx.act(cx.lw->Tt[L.slot], ldt).p;
   const bool inside = !have_T && fuse_gemm_t(Mr, Rp);   // T computed by the GEMM itself
   if (!have_T && !inside) {
     SiteBracket b(CARA_SITE_SKINNY_FWD, cx);
-    TRY(cara_skinny_xu_r(X, ldx, L.Ut, T, Tt, ldt, Mr, L.in, Rp, cx.rank > 0 ? cx.rank : Rp, st));
+    TRY(cara_skinny_xu_r(X.p, X.stride(), L.Ut, T, Tt, ldt, Mr, L.in, Rp, ts_rank(cx), st));
   }
-  a.A = X; a.lda = ldx; a.B = L.W; a.Bp = L.Wp; a.ldb = L.in; a.A2 = inside ? nullptr : T; a.B2 = L.Vs; a.Rp = Rp;
-  if (ldx < 0) { a.a_panels = -ldx; a.lda = 0; }   // (ldx < 0: X is K-panel-major with -ldx rows per panel, as in cara_skinny_xu)
+  reads(a, X);
+  a.B = L.W; a.Bp = L.Wp; a.ldb = L.in; a.A2 = inside ? nullptr : T; a.B2 = L.Vs; a.Rp = Rp;
   if (inside) {
     static const int t_all = env_once("CARA_GEMM_T_ALL_COLUMNS", 0);   // 1: T inside the GEMM with all Rp columns whatever the rank (A/B runs)
     a.Ut = L.Ut; a.T_out = T; a.Tt_out = Tt; a.ldt = ldt; a.Ut_rank = t_all ? 0 : cx.rank;
@@ -423,33 +423,34 @@ int lin_fwd(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, int ldt, char*
   return cara_gemm_bf16(&a, st);
 }
 
-// backward of one adapted linear given dY (bf16, Mr rows, row stride lddy) and its saved input X
-// (row stride ldx; a negative stride = K-panel-major with that many rows per panel):
+// backward of one adapted linear given dY (cx.rows rows) and its saved input X:
 //   G' = dY Vs ; dX = [dY | G'] [W^T | U]^T (optional) ; dU = X^T G' ; dVs = dY^T T ; dc = colsum dY
 // The two transposed skinny products go where `where` says when the dX launch can carry products (fuse_ts); otherwise they are
 // one launch of their own behind it, on the same stream.
 // (have_G: the LayerNorm backward that produced dY already left G' and its transpose, cara_layernorm_bwd_xu)
-int lin_bwd(const Lin& L, const bf16* dY, int lddy, const bf16* X, int ldx, int Mr, int Rp, int ldt, char* ws, const Ws& W,
-            const LayerWs& lw, bool want_dx, cara_gemm_args a, bool want_dc, const Ctx& cx, Riders where = Riders::Own, bool have_G = false) {
+int lin_bwd(const Lin& L, const Act& dY, const Act& X, bool want_dx, cara_gemm_args a, bool want_dc, const Ctx& cx, Riders where = Riders::Own,
+            bool have_G = false) {
   void* st = cx.stream;
   BwdPass& pass = *cx.bwd;
-  const int slot = L.slot, layer = cx.layer;
-  bf16* G = reinterpret_cast<bf16*>(ws + W.bwd.G[slot]);
-  bf16* Gt = reinterpret_cast<bf16*>(ws + W.bwd.Gt[slot]);
+  char* ws = cx.ws;
+  const Ws& W = *cx.W; const LayerWs& lw = *cx.lw;
+  const int slot = L.slot, layer = cx.layer, Mr = cx.rows, Rp = cx.Rp, ldt = cx.ldt;
+  bf16* G = cx.act(W.bwd.G[slot], Rp).p;
+  bf16* Gt = cx.act(W.bwd.Gt[slot], ldt).p;
   const bool carries = want_dx && fuse_ts(Mr, Rp);
   // a dU rides one launch later, so nothing in a linear's own dX launch reads its G': the GEMM computes it on the tiles it streams
   // and the separate pass over dY goes (CARA_GEMM_G_INSIDE=0 keeps the pass)
   const bool g_inside = !have_G && carries && g_inside_enabled(slot) && a.epi == CARA_EPI_BF16;
   if (!have_G && !g_inside) {
     SiteBracket b(CARA_SITE_SKINNY_BWD, cx);
-    TRY(cara_skinny_xu_r(dY, lddy, L.Vst, G, Gt, ldt, Mr, L.out, Rp, cx.rank > 0 ? cx.rank : Rp, st));
+    TRY(cara_skinny_xu_r(dY.p, dY.stride(), L.Vst, G, Gt, ldt, Mr, L.out, Rp, ts_rank(cx), st));
   }
-  const Product dU{X, ldx, Gt, ws + W.slabU[slot] + (size_t)layer * W.strideU[slot], L.in, 0, Mr, &pass.formats.U[slot][layer]};
-  const Product dVs{dY, lddy, ws + lw.Tt[slot], ws + W.slabV[slot] + (size_t)layer * W.strideV[slot], L.out, want_dc ? 1 : 0, Mr, &pass.formats.V[slot][layer]};
+  const Product dU{X.p, X.stride(), Gt, ws + W.slabU[slot] + (size_t)layer * W.strideU[slot], L.in, 0, Mr, &pass.formats.U[slot][layer]};
+  const Product dVs{dY.p, dY.stride(), ws + lw.Tt[slot], ws + W.slabV[slot] + (size_t)layer * W.strideV[slot], L.out, want_dc ? 1 : 0, Mr, &pass.formats.V[slot][layer]};
   if (want_dx) {
-    a.A = dY; a.lda = lddy; a.B = L.Wt; a.Bp = L.Wtp; a.ldb = L.out; a.A2 = G; a.B2 = L.U; a.Rp = Rp;
-    if (lddy < 0) { a.a_panels = -lddy; a.lda = 0; }
-    if (g_inside) { a.A2 = nullptr; a.Ut = L.Vst; a.T_out = G; a.Tt_out = Gt; a.ldt = ldt; a.Ut_rank = ts_rank(cx, Rp) <= 16 ? ts_rank(cx, Rp) : 0; }
+    reads(a, dY);
+    a.B = L.Wt; a.Bp = L.Wtp; a.ldb = L.out; a.A2 = G; a.B2 = L.U; a.Rp = Rp;
+    if (g_inside) { a.A2 = nullptr; a.Ut = L.Vst; a.T_out = G; a.Tt_out = Gt; a.ldt = ldt; a.Ut_rank = ts_rank(cx) <= 16 ? ts_rank(cx) : 0; }
     a.M = Mr; a.N = L.in; a.K = L.out; a.bias = nullptr;
     if (a.ldc == 0) a.ldc = L.in;
     with_scratch(a, cx);
@@ -459,13 +460,13 @@ int lin_bwd(const Lin& L, const bf16* dY, int lddy, const bf16* X, int ldx, int 
       SiteBracket b(SITE_BWD[slot], cx);
       TRY(cara_gemm_bf16(&a, st));
     }
-    TRY(flush_waiting(cx, Rp, ldt));
-    return launch_products(cx, &dU, &dVs, Rp, ldt, st);
+    TRY(flush_waiting(cx));
+    return launch_products(cx, &dU, &dVs, st);
   }
   SiteBracket b(SITE_BWD[slot], cx);
   // the dU of the linear before rides here when it has this launch's rows (fc2's, the 77-MB read of h, thus leaves the two-round fc2
   // dX launch for the single-round fc1 dX launch; a dU never shares an operand with its own dX GEMM, so it loses nothing elsewhere)
-  if (pass.waiting.X && pass.waiting.M != Mr) TRY(flush_waiting(cx, Rp, ldt));
+  if (pass.waiting.X && pass.waiting.M != Mr) TRY(flush_waiting(cx));
   const Product* carried = pass.waiting.X ? &pass.waiting : nullptr;
   // the placements whose products the launch computes itself: one slab per row tile (chunk); Own where the launch or the scratch says no
   int chunks = 0;
@@ -479,7 +480,7 @@ int lin_bwd(const Lin& L, const bf16* dY, int lddy, const bf16* X, int ldx, int 
   if (where == Riders::Epilogue) {   // (this linear is fc2, X its saved input h; the dVs the epilogue computes is fc1's)
     cara_gemm_args d = a;
     d.er_Tt = ws + lw.Tt[2]; d.er_Gt = Gt; d.er_slabs_v = ws + W.slabV[2] + (size_t)layer * W.strideV[2]; d.er_slabs_u = dU.slabs; d.er_ldg = ldt; d.er_colsum = 1;
-    d.er_h = X; d.er_h_panels = ldx < 0 ? -ldx : 0;
+    d.er_h = X.p; d.er_h_panels = X.panels;
     chunks = cara_gemm_epi_rider_chunks(&d);
     const size_t room = W.strideV[2] < W.strideU[3] ? W.strideV[2] : W.strideU[3];
     if (chunks > 0 && chunks <= 65535 && cara_gemm_epi_rider_scratch_bytes(chunks, L.in) <= room) a = d;
@@ -487,28 +488,28 @@ int lin_bwd(const Lin& L, const bf16* dY, int lddy, const bf16* X, int ldx, int 
   }
   switch (where) {
     case Riders::Own:
-      TRY(gemm_with_riders(cx, a, carried, &dVs, Rp, ldt));
+      TRY(gemm_with_riders(cx, a, carried, &dVs));
       break;
     case Riders::Epilogue:   // (nothing of this linear waits: its dU is in the slabs the epilogue wrote)
-      TRY(gemm_with_riders(cx, a, carried, &dVs, Rp, ldt));
+      TRY(gemm_with_riders(cx, a, carried, &dVs));
       *dU.format = pass.formats.V[2][layer] = (unsigned short)chunks;   // (fc1's dVs slabs: the same launch, the same count of row tiles)
       pass.epilogue_ran = true;
       pass.waiting = Product{};
       return CARA_OK;
     case Riders::DoneAbove:
-      TRY(gemm_with_riders(cx, a, carried, nullptr, Rp, ldt));
+      TRY(gemm_with_riders(cx, a, carried, nullptr));
       break;
     case Riders::ATiles:
-      TRY(gemm_with_riders(cx, a, carried, nullptr, Rp, ldt));
+      TRY(gemm_with_riders(cx, a, carried, nullptr));
       *dVs.format = (unsigned short)chunks;
       break;
     case Riders::BothHome:   // (the dU that waits stays for the next launch)
-      return gemm_with_riders(cx, a, &dU, &dVs, Rp, ldt);
+      return gemm_with_riders(cx, a, &dU, &dVs);
     case Riders::Side: {
       SideStream* ss = side_stream();
       if (!ss) return CARA_E_LAUNCH;
       if (hipEventRecord(ss->fork, static_cast<hipStream_t>(st)) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess) return CARA_E_LAUNCH;
-      TRY(launch_products(cx, carried, &dVs, Rp, ldt, ss->stream, true));
+      TRY(launch_products(cx, carried, &dVs, ss->stream, true));
       if (hipEventRecord(ss->join, ss->stream) != hipSuccess) return CARA_E_LAUNCH;
       pass.side_join = true;
       TRY(cara_gemm_bf16(&a, st));
@@ -520,21 +521,25 @@ int lin_bwd(const Lin& L, const bf16* dY, int lddy, const bf16* X, int ldx, int 
 }
 
 // ---- order-2 QKV tensorisation: the QKV linear as y = x W^T + x Dm^T with the dense scaled delta Dm (cara_dense_delta_*) ----
-int lin_fwd_dense(const Lin& L, const bf16* X, int ldx, int Mr, const bf16* Dm, cara_gemm_args a, const Ctx& cx) {
-  a.A = X; a.lda = ldx; a.B = L.W; a.B3 = Dm; a.ldb = L.in; a.A2 = nullptr; a.B2 = nullptr; a.Rp = 0;
-  a.M = Mr; a.N = L.out; a.K = L.in; a.bias = L.bias;
+int lin_fwd_dense(const Lin& L, const Act& X, cara_gemm_args a, const Ctx& cx) {
+  const size_t D = L.in;
+  a.A = X.p; a.lda = X.ld; a.B = L.W; a.B3 = cx.act(cx.W->dd, L.in).p + (size_t)cx.layer * 3 * D * D; a.ldb = L.in; a.A2 = nullptr; a.B2 = nullptr; a.Rp = 0;
+  a.M = cx.rows; a.N = L.out; a.K = L.in; a.bias = L.bias;
   if (a.ldc == 0) a.ldc = L.out;
   with_scratch(a, cx);
   SiteBracket b(SITE_FWD[L.slot], cx);
   return cara_gemm_bf16(&a, cx.stream);
 }
 // backward: dX = dY W + dY Dm (optional), and dD[k] = X^T dY_k for the three projections (split-K slabs, summed)
-int lin_bwd_dense(const Lin& L, const bf16* dY, const bf16* X, int Mr, const bf16* Dmt, float* dD_l, float* slabs, bool want_dx,
-                  cara_gemm_args a, const Ctx& cx) {
+int lin_bwd_dense(const Lin& L, const Act& dYa, const Act& Xa, bool want_dx, cara_gemm_args a, const Ctx& cx) {
   void* st = cx.stream;
-  const int D = L.in;
+  const bf16 *dY = dYa.p, *X = Xa.p;   // (both row-major and dense)
+  const int D = L.in, Mr = cx.rows;
+  const size_t layer_dd = (size_t)cx.layer * 3 * D * D;   // this layer's three deltas in dd / ddt / dD
+  float* dD_l = reinterpret_cast<float*>(cx.ws + cx.W->dD) + layer_dd;
+  float* slabs = reinterpret_cast<float*>(cx.ws + cx.W->dd_slabs);
   if (want_dx) {
-    a.A = dY; a.lda = L.out; a.B = L.Wt; a.B3 = Dmt; a.ldb = L.out; a.A2 = nullptr; a.B2 = nullptr; a.Rp = 0;
+    a.A = dY; a.lda = L.out; a.B = L.Wt; a.B3 = cx.act(cx.W->ddt, D).p + layer_dd; a.ldb = L.out; a.A2 = nullptr; a.B2 = nullptr; a.Rp = 0;
     a.M = Mr; a.N = L.in; a.K = L.out; a.bias = nullptr;
     if (a.ldc == 0) a.ldc = L.in;
     with_scratch(a, cx);
@@ -552,10 +557,11 @@ int lin_bwd_dense(const Lin& L, const bf16* dY, const bf16* X, int Mr, const bf1
 
 // ---- exact weight-dropout mode (cara_vit_shape::wd_exact): y = x W^T + x (keep/(1-p) dW)^T, two accumulated products ----
 // forward of one linear: materialise the masked delta (and its transpose, for dX) of this layer, then C = X (W + Dm)^T + bias
-int lin_fwd_exact(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, char* ws, const Ws& W, const cara_vit_shape* s,
-                  cara_gemm_args a, const Ctx& cx) {
+int lin_fwd_exact(const Lin& L, const Act& X, cara_gemm_args a, const Ctx& cx) {
   void* st = cx.stream;
-  const int layer = cx.layer;
+  char* ws = cx.ws;
+  const Ws& W = *cx.W; const cara_vit_shape* s = cx.s;
+  const int layer = cx.layer, Rp = cx.Rp;
   const size_t wbytes = (size_t)L.out * L.in * 2;
   bf16* weff = reinterpret_cast<bf16*>(ws + W.weff[L.slot] + layer * wbytes);
   bf16* wefft = reinterpret_cast<bf16*>(ws + W.wefft[L.slot] + layer * wbytes);
@@ -564,8 +570,8 @@ int lin_fwd_exact(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, char* ws
   // would vanish (the reference's zero-initialised A2 / P2: the whole adapter early in training)
   TRY(cara_materialize_merge(nullptr, L.U, L.Vs, Rp, L.out, L.in, s->wd_p, s->wd_seed, (unsigned)(4 * layer + L.slot), weff, st));
   TRY(cara_transpose_bf16_ld(weff, L.in, wefft, L.out, L.out, L.in, st));
-  a.A = X; a.lda = ldx; a.B = L.W; a.B3 = weff; a.ldb = L.in; a.A2 = nullptr; a.B2 = nullptr; a.Rp = 0;
-  a.M = Mr; a.N = L.out; a.K = L.in; a.bias = L.bias;
+  a.A = X.p; a.lda = X.ld; a.B = L.W; a.B3 = weff; a.ldb = L.in; a.A2 = nullptr; a.B2 = nullptr; a.Rp = 0;
+  a.M = cx.rows; a.N = L.out; a.K = L.in; a.bias = L.bias;
   if (a.ldc == 0) a.ldc = L.out;
   with_scratch(a, cx);
   return cara_gemm_bf16(&a, st);
@@ -573,10 +579,12 @@ int lin_fwd_exact(const Lin& L, const bf16* X, int ldx, int Mr, int Rp, char* ws
 
 // backward of one linear: dc = colsum dY; dW = dY^T X (dense, fp32) -> dU, dVs through the regenerated mask;
 // dX = dY W_eff (optional).  X and dY are dense [Mr, in] / [Mr, out] (the cls-row shortcut is off in this mode).
-int lin_bwd_exact(const Lin& L, const bf16* dY, const bf16* X, int Mr, int Rp, char* ws, const Ws& W,
-                  const cara_vit_shape* s, bool want_dx, cara_gemm_args a, bool want_dc, const Ctx& cx) {
+int lin_bwd_exact(const Lin& L, const Act& dYa, const Act& Xa, bool want_dx, cara_gemm_args a, bool want_dc, const Ctx& cx) {
   void* st = cx.stream;
-  const int layer = cx.layer;
+  char* ws = cx.ws;
+  const Ws& W = *cx.W; const cara_vit_shape* s = cx.s;
+  const bf16 *dY = dYa.p, *X = Xa.p;
+  const int layer = cx.layer, Mr = cx.rows, Rp = cx.Rp;
   hipStream_t hs = static_cast<hipStream_t>(st);
   const size_t wbytes = (size_t)L.out * L.in * 2;
   bf16* wefft = reinterpret_cast<bf16*>(ws + W.wefft[L.slot] + layer * wbytes);
@@ -645,6 +653,14 @@ void make_lins(const cara_geom* g, const cara_vit_weights* w, const char* pack, 
   }
 }
 
+bool g_inside_enabled(int slot) {   // CARA_GEMM_G_INSIDE: bit 0 qkv, bit 1 fc1 (default 3: both)
+  static const int v = env_once("CARA_GEMM_G_INSIDE", 3);
+  return (v & (slot == 0 ? 1 : 2)) != 0;
+}
+
+// ---- The block plan: everything the forward of a block, its backward and the workspace layout decide about it, decided in one place.
+// The switches and predicates of this section are read and called here only (plan_block, placements); the two passes take the plan. ----
+
 // CARA_CLS_SHORTCUT=0 turns the exact last-block shortcut off (A/B measurements only)
 bool cls_shortcut_enabled() {
   static const int v = env_once("CARA_CLS_SHORTCUT", 1);
@@ -657,9 +673,28 @@ bool cls_attention_enabled() {
   return v != 0;
 }
 
-bool g_inside_enabled(int slot) {   // CARA_GEMM_G_INSIDE: bit 0 qkv, bit 1 fc1 (default 3: both)
-  static const int v = env_once("CARA_GEMM_G_INSIDE", 3);
-  return (v & (slot == 0 ? 1 : 2)) != 0;
+// CARA_DV (default 0; bit 0: fc1, bit 1: qkv): dVs (+ dc) of fc1 / qkv out of their dX GEMM's own A tiles on the 160 x 256 x 64 tile;
+// the workspace then holds one slab per 160-row tile and K step for them (placements)
+int dv_env() {
+  static const int v = env_once("CARA_DV", 0);
+  return v;
+}
+
+// CARA_FUSE_XU=0 keeps the K = dim adapter contractions (T = LN(x) U of qkv / fc1, G' = dY Vs of proj / fc2) as
+// separate cara_skinny_xu passes instead of fusing them into the LayerNorm kernels
+bool fuse_xu(const cara_geom* g) {
+  static const int v = env_once("CARA_FUSE_XU", 1);
+  return v != 0 && (g->Rp == 32 || g->Rp == 64) && cara_layernorm_takes(g->dim, true);
+}
+
+// CARA_PANEL_ACTS = mask of the activation groups written K-panel-major ([K/32][M][32], cara_gemm_args::c_panels /
+// a_panels) so that the GEMM that consumes them stages whole cache lines: 1 = h / dH (written by GEMM epilogues),
+// 2 = xn1 / xn2 (LayerNorm forward), 4 = the dY of fc2 / proj (LayerNorm backward).  Default 5: group 2 costs
+// 0.2 ms per step although the GEMMs reading xn1 / xn2 gain 5-8 us each when timed alone (DESIGN.md section 7).
+// Not in the exact-dropout mode, not on the cls-row-only last block.
+bool panel_acts(int Mr, const cara_vit_shape* s, int what) {
+  static const int v = env_once("CARA_PANEL_ACTS", 5);
+  return (v & what) != 0 && !s->wd_exact && Mr >= 1024;
 }
 
 // CARA_SAVE_GELU_GRAD (default: on where CARA_EPI_RIDERS is): fc1 forward keeps gelu'(u) (IEEE half) instead of the pre-activation u, and
@@ -689,6 +724,89 @@ bool epi_riders_geom(const cara_geom* g, int Mr, bool exact) {
   cara_vit_shape sh = {};
   sh.wd_exact = exact ? 1 : 0;
   return v != 0 && !exact && save_gelu_grad(g, &sh) && g->Rp == 32 && g->rank > 0 && g->rank <= 16 && Mr > 1024 && (Mr & 3) == 0 && 4 * g->dim >= 3072 && ((4 * g->dim) & 127) == 0;
+}
+
+Placements placements(const cara_geom* g, const cara_vit_shape* s, int rows) {
+  return Placements{epi_riders_geom(g, rows, s->wd_exact != 0), dv_env() != 0 && g->Rp == 32};
+}
+
+// Does the 160 x 256 x 64 tile really take this product of the model?  cara_gemm8_policy looks at the shape only; the tile's
+// adapter-inside path and its riders are built for one r-tile (cara_gemm8_plan: Rp = 32, rank <= 16).  The activation LAYOUT
+// (K-panel-major h / dH for the 128-tile family, row-major for the tile) must follow what will run: at rank 64 the shape-only
+// answer left fc2 forward on the 128-tile kernel reading row-major A (ADVICE r04: 9.696 -> 9.75 ms on the rank-64 leg).
+bool tile_policy(const cara_geom* g, int M, int N, int K, int riders) {
+  return g->Rp == 32 && g->rank > 0 && g->rank <= 16 && cara_gemm8_policy(M, N, K, riders);
+}
+
+struct BlockPlan {
+  // Rows.  Only the cls token of the LAST block's output reaches the logits (timm takes x[:, 0] after the final norm), and proj /
+  // LayerNorm-2 / fc1 / fc2 act per token: in the last block they run on the B cls rows only (row stride N * D).  Exact, not an
+  // approximation: every other row of that block's proj / MLP output is dead, and only the cls rows carry gradient into them.  qkv and
+  // attention still see all tokens (keys / values); with cls_attn only the cls query runs (only that row of the output is read).
+  bool cls_only, cls_attn;
+  int Mr, ldr, rps;   // rows of the proj / MLP half (M or B), row stride of the residual-stream rows used, rows per sample for DropPath
+  // Mode: exact weight dropout (plain GEMMs on the merged weights); order 2 (the QKV linear in the dense-delta form); no backward will
+  // follow (cara_vit_shape::inference: the forward does not keep what only it reads); fx: the LayerNorm kernels compute the K = dim
+  // adapter contractions (T of qkv / fc1, G' of fc2), fxp: and LayerNorm-2 backward the G' of proj (CARA_LN2B_XU=0: proj's dX GEMM does,
+  // except on the cls rows); fc1 forward keeps gelu'(u) instead of u (CARA_EPI_GELU_DG / CARA_EPI_MULH)
+  bool exact, dense_qkv, inference, fx, fxp, save_gelu_grad;
+  // Layout of each 16-bit activation the block writes or reads: rows per K-panel, 0 = row-major (Act).  xn1 and the dyb left for the
+  // block below have all M rows, the others Mr.  (Order 2: xn1 stays row-major -- the dense dD = xn1^T dY of the backward reads it with
+  // transposing LDS reads.  h is row-major where fc2 forward runs on the 160 x 256 x 64 tile, which stages whole 128-byte lines of
+  // row-major operands, dH where fc1 dX does.  The last block's dyb comes from the final norm's backward: row-major, on the cls rows.)
+  int xn1, xn2, h, dH, dyp, dyb_in, dyb_out;
+  // Gradient enters the token stream only through the cls rows.  With the last block on its cls rows every kernel of that block reads
+  // dx / dyb on those rows only, and its LayerNorm-1 backward -- the first launch that touches every row of dx -- is told so (dx_in on
+  // every N-th row): the two buffers need no zeroing (58 MB of memset + 39 MB of zeros read back, ~18 us per step, r05).  Otherwise
+  // (CARA_CLS_SHORTCUT=0, exact weight dropout, CARA_BWD_MEMSETS=1 for A/B runs) the pass starts with the memsets and reads every row.
+  bool dx_on_cls;
+  int dx_in_every;
+  // Which launch of the backward computes which products (proj: always Own).  The placements other than Own are measured and off
+  // (DESIGN.md 7.3); all need launches that carry products (fuse_ts), one r-tile and the factored mode, and exclude one another.
+  Riders fc2 = Riders::Own, fc1 = Riders::Own, qkv = Riders::Own;
+};
+BlockPlan plan_block(const cara_geom* g, const cara_vit_shape* s, int M, int l) {
+  static const int fc1_side = env_once("CARA_FC1_SIDE", 0);
+  static const int ln2b_xu = env_once("CARA_LN2B_XU", 1);
+  static const int force_zero = env_once("CARA_BWD_MEMSETS", 0);
+  const int D = g->dim, N = s->tokens;
+  const bool last = l == g->depth - 1;
+  BlockPlan p;
+  p.exact = s->wd_exact != 0;
+  p.dense_qkv = g->cp_length == 2;
+  p.inference = s->inference != 0 && !p.exact;
+  p.cls_only = last && cls_shortcut_enabled() && !p.exact;
+  p.cls_attn = p.cls_only && cls_attention_enabled();
+  const int Mr = p.Mr = p.cls_only ? s->B : M;
+  p.ldr = p.cls_only ? N * D : D;
+  p.rps = p.cls_only ? 1 : N;
+  p.fx = fuse_xu(g) && !p.exact;
+  p.fxp = p.fx && (ln2b_xu != 0 || p.cls_only);
+  p.save_gelu_grad = save_gelu_grad(g, s);
+  p.dx_on_cls = p.cls_only && !force_zero;
+  p.dx_in_every = p.dx_on_cls ? N : 0;
+  p.xn1 = panel_acts(M, s, 2) && !p.dense_qkv ? M : 0;
+  p.xn2 = panel_acts(Mr, s, 2) ? Mr : 0;
+  p.h = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, 0) ? Mr : 0;
+  p.dyp = panel_acts(Mr, s, 4) ? Mr : 0;
+  p.dyb_out = panel_acts(M, s, 4) ? M : 0;
+  p.dyb_in = last ? 0 : p.dyb_out;
+  const bool one_rtile = g->Rp == 32 && g->rank > 0 && g->rank <= 16;
+  const bool can = !p.exact && one_rtile && fuse_ts(Mr, g->Rp);
+  const Placements open = placements(g, s, Mr);
+  const bool fc1_tile = g_inside_enabled(2) && tile_policy(g, Mr, D, 4 * D, 0);   // fc1's dX GEMM without riders runs on the 160 x 256 x 64 tile
+  if (can && !open.a_tiles && open.epilogue) {
+    p.fc2 = Riders::Epilogue;
+    p.fc1 = Riders::DoneAbove;
+  } else if (can && !p.cls_only && (dv_env() & 1) && fc1_tile) {
+    p.fc2 = Riders::BothHome;
+    p.fc1 = Riders::ATiles;
+  } else if (can && fc1_side != 0 && fc1_tile && side_stream() != nullptr) {
+    p.fc1 = Riders::Side;
+  }
+  if (can && !p.cls_only && (dv_env() & 2) && g_inside_enabled(0) && tile_policy(g, M, D, 3 * D, 0)) p.qkv = Riders::ATiles;
+  p.dH = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, p.fc1 == Riders::Own ? 1 : 0) ? Mr : 0;
+  return p;
 }
 
 // tiny classifier-head backward (B x classes x D, fp32 VALU).  The three outputs are independent: blocks
@@ -857,193 +975,137 @@ extern "C" int cara_head_backward(const float* dlogits, const void* xn, const fl
   return head_backward_scaled(dlogits, xn, head_w, dhead_w, dhead_b, dxn, B, classes, D, nullptr, nullptr, stream);
 }
 
-// Does the 160 x 256 x 64 tile really take this product of the model?  cara_gemm8_policy looks at the shape only; the tile's
-// adapter-inside path and its riders are built for one r-tile (cara_gemm8_plan: Rp = 32, rank <= 16).  The activation LAYOUT
-// (K-panel-major h / dH for the 128-tile family, row-major for the tile) must follow what will run: at rank 64 the shape-only
-// answer left fc2 forward on the 128-tile kernel reading row-major A (ADVICE r04: 9.696 -> 9.75 ms on the rank-64 leg).
-static bool tile_policy(const cara_geom* g, int M, int N, int K, int riders) {
-  return g->Rp == 32 && g->rank > 0 && g->rank <= 16 && cara_gemm8_policy(M, N, K, riders);
-}
-
-// Which launch of a block's backward computes which products (Riders), decided once per block from the geometry, the block's rows
-// (Mr: all M token rows, or the cls rows of the last block) and the switches.  proj always takes Own.  The three placements other
-// than Own are measured and off; all need launches that carry products (fuse_ts), one r-tile (Rp = 32,
-// rank <= 16) and the factored mode, and exclude one another: the epilogue riders and CARA_DV are two placements of the same product.
-struct BlockPlan {
-  Riders fc2 = Riders::Own, fc1 = Riders::Own, qkv = Riders::Own;
-  bool dh_panels = false;   // fc2's dX GEMM writes dH K-panel-major (fc1's dX GEMM stays on the 128-tile family)
+// The image of a forward: an fp32 batch, or resident uint8 pixels with their per-channel mean / std -- the batch itself, or a whole
+// split of n_split images that `rows` indexes, each sample read whole or through its box out of the split's own Hs x Ws pixels
+// (cara_im2col_patches_u8_rows_crop).  Each entry checks and sets the fields of its kind; everything behind the patch rows is the same.
+struct ImageSource {
+  enum Kind { F32Batch, U8Batch, U8Rows, U8RowsCrop } kind;
+  const float* images;                                      // F32Batch
+  const unsigned char* pixels; const float *mean, *stdv;   // the three U8 kinds
+  int n_split; const int64_t* rows; int* bad;               // U8Rows, U8RowsCrop
+  int Hs, Ws; const int* boxes;                             // U8RowsCrop
 };
-BlockPlan plan_block(const cara_geom* g, const cara_vit_shape* s, int M, int Mr, bool cls_only) {
-  static const int fc1_side = env_once("CARA_FC1_SIDE", 0);
-  const int D = g->dim;
-  const bool ex = s->wd_exact != 0;
-  const bool one_rtile = g->Rp == 32 && g->rank > 0 && g->rank <= 16;
-  const bool can = !ex && one_rtile && fuse_ts(Mr, g->Rp);
-  const bool fc1_tile = g_inside_enabled(2) && tile_policy(g, Mr, D, 4 * D, 0);   // fc1's dX GEMM without riders runs on the 160 x 256 x 64 tile
-  BlockPlan p;
-  if (can && dv_env() == 0 && epi_riders_geom(g, Mr, ex)) {
-    p.fc2 = Riders::Epilogue;
-    p.fc1 = Riders::DoneAbove;
-  } else if (can && !cls_only && (dv_env() & 1) && fc1_tile) {
-    p.fc2 = Riders::BothHome;
-    p.fc1 = Riders::ATiles;
-  } else if (can && fc1_side != 0 && fc1_tile && side_stream() != nullptr) {
-    p.fc1 = Riders::Side;
+static int patch_rows(const ImageSource& i, const cara_vit_shape* s, void* patches, void* stream) {
+  switch (i.kind) {
+    case ImageSource::F32Batch: return cara_im2col_patches(i.images, patches, s->B, s->chans, s->img, s->img, s->patch, stream);
+    case ImageSource::U8Batch: return cara_im2col_patches_u8(i.pixels, i.mean, i.stdv, patches, s->B, s->chans, s->img, s->img, s->patch, stream);
+    case ImageSource::U8Rows:
+      return cara_im2col_patches_u8_rows(i.pixels, i.n_split, i.rows, i.mean, i.stdv, patches, i.bad, s->B, s->chans, s->img, s->img, s->patch, stream);
+    case ImageSource::U8RowsCrop:
+      return cara_im2col_patches_u8_rows_crop(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mean, i.stdv, patches, i.bad, s->B, s->chans, s->img,
+                                              s->img, s->patch, stream);
   }
-  if (can && !cls_only && (dv_env() & 2) && g_inside_enabled(0) && tile_policy(g, M, D, 3 * D, 0)) p.qkv = Riders::ATiles;
-  // (dH as fc1's dX GEMM reads it: row-major where that launch runs on the tile, which it does sooner where it carries nothing)
-  p.dh_panels = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, p.fc1 == Riders::Own ? 1 : 0);
-  return p;
+  return CARA_E_ARG;
 }
 
-// The forward behind the three entries: the image is either fp32 (`images`) or resident uint8 pixels with their per-channel
-// mean / std (`pixels`: the batch itself, or with `rows` a whole split of `n_split` images that `rows` indexes); everything
-// behind the patch rows is the same.  `crop` (with `rows` only): the split has Hs x Ws pixels of its own and every sample is read
-// through its box (cara_im2col_patches_u8_rows_crop).
-struct CropBoxes { int Hs, Ws; const int* boxes; };
-static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
-                            const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
-                            const unsigned char* pixels, int n_split, const int64_t* rows, int* bad,
-                            const float* mean, const float* stdv,
-                            const float* droppath, void* workspace, float* logits, void* stream, const CropBoxes* crop = nullptr) {
+// the activations a block's forward saves for its backward, each in the layout the plan gives it
+struct Saved { Act xn1, ao, xn2, h; };
+static Saved saved_acts(const Ctx& cx, const LayerWs& lw, int D, const BlockPlan& p) {
+  return Saved{cx.act(lw.xn1, D, p.xn1), cx.act(lw.ao, p.ldr), cx.act(lw.xn2, D, p.xn2), cx.act(lw.h, 4 * D, p.h)};
+}
+
+static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp, const float* head_w,
+                            const float* head_b, const ImageSource& src, const float* droppath, void* workspace, float* logits, void* stream) {
   Ws W;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !workspace || !logits) return CARA_E_ARG;
-  if (pixels ? (!mean || !stdv) : !images) return CARA_E_ARG;
   char* ws = static_cast<char*>(workspace);
   const int D = g->dim, M = W.M, Rp = g->Rp, B = s->B, N = s->tokens, P = N - 1;
   const float att_scale = 1.0f / sqrtf((float)(D / g->heads));
   cara_pack_layout pl;
   TRY(cara_pack_offsets(g, &pl));
   TRY(cara_factor_prep(g, cp, w->proj_b, w->fc1_b, w->fc2_b, ws + W.pack, stream));
-  const bool dense_qkv = g->cp_length == 2;   // order-2 tensorisation: the QKV linear in the dense-delta form
-  if (dense_qkv) TRY(cara_dense_delta_materialize(g, cp, ws + W.dd, ws + W.ddt, stream));
+  if (g->cp_length == 2) TRY(cara_dense_delta_materialize(g, cp, ws + W.dd, ws + W.ddt, stream));   // (order 2: BlockPlan::dense_qkv)
   // patch embedding: Conv2d(k = s = patch) as a GEMM over im2col rows, then cls + pos_embed
   const int kp = s->chans * s->patch * s->patch;
-  if (pixels && rows && crop)
-    TRY(cara_im2col_patches_u8_rows_crop(pixels, n_split, crop->Hs, crop->Ws, rows, crop->boxes, mean, stdv, ws + W.patches, bad, B, s->chans,
-                                         s->img, s->img, s->patch, stream));
-  else if (pixels && rows)
-    TRY(cara_im2col_patches_u8_rows(pixels, n_split, rows, mean, stdv, ws + W.patches, bad, B, s->chans, s->img, s->img, s->patch, stream));
-  else if (pixels) TRY(cara_im2col_patches_u8(pixels, mean, stdv, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
-  else TRY(cara_im2col_patches(images, ws + W.patches, B, s->chans, s->img, s->img, s->patch, stream));
+  TRY(patch_rows(src, s, ws + W.patches, stream));
   cara_gemm_args a = {};
   a.A = ws + W.patches; a.lda = kp; a.B = w->patch_w; a.ldb = kp; a.M = B * P; a.N = D; a.K = kp;
   a.bias = w->patch_b; a.epi = CARA_EPI_F32; a.C = ws + W.emb; a.ldc = D;
-  Ctx cx{stream, ws + W.gemm_scratch, 0, false};
-  cx.rank = g->rank;
-  with_scratch(a, cx);
+  const Ctx px{stream, ws, &W, s, Rp, W.ldt, g->rank};
+  with_scratch(a, px);
   TRY(cara_gemm_bf16(&a, stream));
-  TRY(cara_assemble_tokens(reinterpret_cast<float*>(ws + W.emb), w->cls, w->pos,
-                           reinterpret_cast<float*>(ws + W.layer[0].x_in), B, P, D, stream));
+  TRY(cara_assemble_tokens(px.f32(W.emb), w->cls, w->pos, px.f32(W.layer[0].x_in), B, P, D, stream));
   for (int l = 0; l < g->depth; ++l) {
+    const BlockPlan p = plan_block(g, s, M, l);
     const LayerWs& lw = W.layer[l];
     Lin lin[4];
     make_lins(g, w, ws + W.pack, pl, l, lin);
-    float* x_in = reinterpret_cast<float*>(ws + lw.x_in);
-    float* x_mid = reinterpret_cast<float*>(ws + lw.x_mid);
-    float* x_out = reinterpret_cast<float*>(ws + (l + 1 < g->depth ? W.layer[l + 1].x_in : W.x_last));
-    const float* dp1 = droppath ? droppath + (size_t)(2 * l) * B : nullptr;
-    const float* dp2 = droppath ? droppath + (size_t)(2 * l + 1) * B : nullptr;
-    // Only the cls token of the LAST block's output reaches the logits (timm takes x[:, 0] after
-    // the final norm), and proj / LayerNorm / fc1 / fc2 act per token: in the last block they run
-    // on the B cls rows only (row stride N*D).  Exact, not an approximation: every other row of
-    // that block's proj/MLP output is dead.  qkv and attention still see all tokens (keys/values).
-    const bool cls_only = (l == g->depth - 1) && cls_shortcut_enabled() && !s->wd_exact;
-    const int Mr = cls_only ? B : M;
-    const int ldr = cls_only ? N * D : D;          // row stride of the residual stream rows used
-    const int rps = cls_only ? 1 : N;              // rows per sample for the DropPath multipliers
+    float *x_in = px.f32(lw.x_in), *x_mid = px.f32(lw.x_mid), *x_out = px.f32(l + 1 < g->depth ? W.layer[l + 1].x_in : W.x_last);
+    const float *dp1 = droppath ? droppath + (size_t)(2 * l) * B : nullptr, *dp2 = droppath ? droppath + (size_t)(2 * l + 1) * B : nullptr;
+    const Ctx cx = px.on(lw, l, p.Mr, !p.cls_only), cx_all = px.on(lw, l, M, true);   // (qkv and attention always run on all token rows)
+    const Saved sv = saved_acts(cx, lw, D, p);
+    auto linear = [&](int i, const Act& X, const cara_gemm_args& e, const Ctx& c, bool have_T = false) {
+      return p.exact ? lin_fwd_exact(lin[i], X, e, c) : lin_fwd(lin[i], X, e, c, have_T);
+    };
     // x = x + drop_path(attn(norm1(x)))
-    const bool ex = s->wd_exact != 0;   // exact weight-dropout mode: plain GEMMs on the merged weights
-    const bool fx = fuse_xu(g) && !ex;
-    // no backward will follow (cara_vit_shape::inference): do not keep what only it reads
-    const bool inference = s->inference != 0 && !ex;
-    cx.layer = l;
-    cx.full = !cls_only;
-    Ctx cx_all = cx;   // qkv and attention always run on all token rows
-    cx_all.full = true;
-    // K-panel-major activations (panel_acts): pa_x for what all M token rows produce (xn1), pa for the Mr rows of
-    // the proj / MLP half of the block (xn2, h)
-    // (order 2: xn1 stays row-major -- the dense dD = xn1^T dY of the backward reads it with transposing LDS reads)
-    // (h stays row-major where fc2 forward / fc1 dX run on the 160 x 256 x 64 tile, which stages whole 128-byte lines of row-major operands)
-    const bool pa_x = panel_acts(M, s, 2) && !dense_qkv, pa = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, 0), pa_n = panel_acts(Mr, s, 2);
     {
       SiteBracket sb(CARA_SITE_LN1_FWD, cx_all);
-      TRY(cara_layernorm_fwd_ex(x_in, D, w->ln1_g + (size_t)l * D, w->ln1_b + (size_t)l * D, ws + lw.xn1,
-                                reinterpret_cast<float*>(ws + lw.mean1), reinterpret_cast<float*>(ws + lw.rstd1), M, D, s->eps,
-                                (fx && !dense_qkv) ? lin[0].Ut : nullptr, g->rank, Rp, ws + lw.T[0], ws + lw.Tt[0], W.ldt, pa_x ? M : 0, stream));
+      TRY(cara_layernorm_fwd_ex(x_in, D, w->ln1_g + (size_t)l * D, w->ln1_b + (size_t)l * D, sv.xn1.p, px.f32(lw.mean1), px.f32(lw.rstd1), M, D, s->eps,
+                                (p.fx && !p.dense_qkv) ? lin[0].Ut : nullptr, g->rank, Rp, ws + lw.T[0], ws + lw.Tt[0], W.ldt, sv.xn1.panels, stream));
     }
     cara_gemm_args e = {};
     e.epi = CARA_EPI_BF16; e.C = ws + lw.qkv;
-    if (ex) TRY(lin_fwd_exact(lin[0], reinterpret_cast<bf16*>(ws + lw.xn1), D, M, Rp, ws, W, s, e, cx_all));
-    else if (dense_qkv) TRY(lin_fwd_dense(lin[0], reinterpret_cast<bf16*>(ws + lw.xn1), D, M, reinterpret_cast<bf16*>(ws + W.dd) + (size_t)l * 3 * D * D, e, cx_all));
-    else TRY(lin_fwd(lin[0], reinterpret_cast<bf16*>(ws + lw.xn1), pa_x ? -M : D, M, Rp, W.ldt, ws, lw, e, cx_all, fx));
+    if (p.dense_qkv) TRY(lin_fwd_dense(lin[0], sv.xn1, e, cx_all));
+    else TRY(linear(0, sv.xn1, e, cx_all, p.fx));
     {
       SiteBracket sb(CARA_SITE_ATTN_FWD, cx_all);
-      // (the last block: only the cls row of the attention output is read -- by proj on the cls rows -- so only the cls query runs)
-      if (cls_only && cls_attention_enabled())
-        TRY(cara_attention_cls_fwd(ws + lw.qkv, ws + lw.ao, reinterpret_cast<float*>(ws + lw.lse), B, N, g->heads, att_scale, stream));
-      else
-        TRY(cara_attention_fwd(ws + lw.qkv, ws + lw.ao, reinterpret_cast<float*>(ws + lw.lse), B, N, g->heads, att_scale, stream));
+      TRY((p.cls_attn ? cara_attention_cls_fwd : cara_attention_fwd)(ws + lw.qkv, ws + lw.ao, px.f32(lw.lse), B, N, g->heads, att_scale, stream));
     }
     e = {};
-    e.epi = CARA_EPI_RESID; e.C = x_mid; e.aux = x_in; e.rowscale = dp1; e.rows_per_sample = rps; e.ldc = ldr;
+    e.epi = CARA_EPI_RESID; e.C = x_mid; e.aux = x_in; e.rowscale = dp1; e.rows_per_sample = p.rps; e.ldc = p.ldr;
 #ifdef CARA_ABLATE_RESID   // timing experiment only: the residual products with a plain bf16 epilogue (wrong results)
     e = {}; e.epi = CARA_EPI_BF16; e.C = ws + lw.u;
 #endif
-    if (ex) TRY(lin_fwd_exact(lin[1], reinterpret_cast<bf16*>(ws + lw.ao), ldr, Mr, Rp, ws, W, s, e, cx));
-    else TRY(lin_fwd(lin[1], reinterpret_cast<bf16*>(ws + lw.ao), ldr, Mr, Rp, W.ldt, ws, lw, e, cx));
+    TRY(linear(1, sv.ao, e, cx));
     // x = x + drop_path(mlp(norm2(x)))
     {
       SiteBracket sb(CARA_SITE_LN2_FWD, cx);
-      TRY(cara_layernorm_fwd_ex(x_mid, ldr, w->ln2_g + (size_t)l * D, w->ln2_b + (size_t)l * D, ws + lw.xn2,
-                                reinterpret_cast<float*>(ws + lw.mean2), reinterpret_cast<float*>(ws + lw.rstd2), Mr, D, s->eps,
-                                fx ? lin[2].Ut : nullptr, g->rank, Rp, ws + lw.T[2], ws + lw.Tt[2], W.ldt, pa_n ? Mr : 0, stream));
+      TRY(cara_layernorm_fwd_ex(x_mid, p.ldr, w->ln2_g + (size_t)l * D, w->ln2_b + (size_t)l * D, sv.xn2.p, px.f32(lw.mean2), px.f32(lw.rstd2), p.Mr, D, s->eps,
+                                p.fx ? lin[2].Ut : nullptr, g->rank, Rp, ws + lw.T[2], ws + lw.Tt[2], W.ldt, sv.xn2.panels, stream));
     }
     e = {};
     // what the backward's fc2 dX epilogue needs: gelu'(u) itself, kept as IEEE half (CARA_EPI_GELU_DG / _MULH), or the pre-activation u
-    e.epi = save_gelu_grad(g, s) ? CARA_EPI_GELU_DG : CARA_EPI_GELU; e.C = ws + lw.h;
-    e.C2 = inference ? nullptr : ws + lw.u;   // (only read by the backward)
-    if (pa) { e.c_panels = Mr; e.ldc = 4 * D; }   // h (and dH in the backward) K-panel-major
-    if (ex) TRY(lin_fwd_exact(lin[2], reinterpret_cast<bf16*>(ws + lw.xn2), D, Mr, Rp, ws, W, s, e, cx));
-    else TRY(lin_fwd(lin[2], reinterpret_cast<bf16*>(ws + lw.xn2), pa_n ? -Mr : D, Mr, Rp, W.ldt, ws, lw, e, cx, fx));
+    e.epi = p.save_gelu_grad ? CARA_EPI_GELU_DG : CARA_EPI_GELU;
+    writes(e, sv.h);
+    e.C2 = p.inference ? nullptr : ws + lw.u;   // (only read by the backward)
+    TRY(linear(2, sv.xn2, e, cx, p.fx));
     e = {};
-    e.epi = CARA_EPI_RESID; e.C = x_out; e.aux = x_mid; e.rowscale = dp2; e.rows_per_sample = rps; e.ldc = ldr;
+    e.epi = CARA_EPI_RESID; e.C = x_out; e.aux = x_mid; e.rowscale = dp2; e.rows_per_sample = p.rps; e.ldc = p.ldr;
 #ifdef CARA_ABLATE_RESID
     e = {}; e.epi = CARA_EPI_BF16; e.C = ws + lw.u;
 #endif
-    if (ex) TRY(lin_fwd_exact(lin[3], reinterpret_cast<bf16*>(ws + lw.h), 4 * D, Mr, Rp, ws, W, s, e, cx));
-    else TRY(lin_fwd(lin[3], reinterpret_cast<bf16*>(ws + lw.h), pa ? -Mr : 4 * D, Mr, Rp, W.ldt, ws, lw, e, cx));
+    TRY(linear(3, sv.h, e, cx));
   }
   // norm -> cls token -> head  (LayerNorm is per token, so only the cls rows are normalised)
   // ... all in fp32, one launch (cara_head_forward): the 16-bit xn and the row statistics are kept for the backward
-  return cara_head_forward(reinterpret_cast<float*>(ws + W.x_last), (long)N * D, w->norm_g, w->norm_b, head_w, head_b, ws + W.clsn,
-                           reinterpret_cast<float*>(ws + W.meanF), reinterpret_cast<float*>(ws + W.rstdF), logits, B, s->num_classes,
-                           D, s->eps, stream);
+  return cara_head_forward(px.f32(W.x_last), (long)N * D, w->norm_g, w->norm_b, head_w, head_b, ws + W.clsn, px.f32(W.meanF), px.f32(W.rstdF), logits, B,
+                           s->num_classes, D, s->eps, stream);
 }
 
 extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                                 const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
                                 const float* droppath, void* workspace, float* logits, void* stream) {
-  return vit_forward_body(g, s, w, cp, head_w, head_b, images, nullptr, 0, nullptr, nullptr, nullptr, nullptr, droppath, workspace,
-                          logits, stream);
+  if (!images) return CARA_E_ARG;
+  const ImageSource src{ImageSource::F32Batch, images};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
 extern "C" int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                                    const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
                                    const float* mean, const float* stdv, const float* droppath, void* workspace, float* logits,
                                    void* stream) {
-  if (!pixels) return CARA_E_ARG;
-  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, 0, nullptr, nullptr, mean, stdv, droppath, workspace, logits,
-                          stream);
+  if (!pixels || !mean || !stdv) return CARA_E_ARG;
+  const ImageSource src{ImageSource::U8Batch, nullptr, pixels, mean, stdv};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
 extern "C" int cara_vit_forward_u8_rows(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                                         const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
                                         int n_split, const int64_t* rows, const float* mean, const float* stdv,
                                         const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
-  if (!pixels || !rows || n_split <= 0) return CARA_E_ARG;
-  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, n_split, rows, bad, mean, stdv, droppath, workspace, logits,
-                          stream);
+  if (!pixels || !rows || n_split <= 0 || !mean || !stdv) return CARA_E_ARG;
+  const ImageSource src{ImageSource::U8Rows, nullptr, pixels, mean, stdv, n_split, rows, bad};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
 extern "C" int cara_vit_forward_u8_rows_crop(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
@@ -1051,10 +1113,9 @@ extern "C" int cara_vit_forward_u8_rows_crop(const cara_geom* g, const cara_vit_
                                              int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const float* mean,
                                              const float* stdv, const float* droppath, void* workspace, float* logits, int* bad,
                                              void* stream) {
-  if (!pixels || !rows || !boxes || n_split <= 0 || Hs <= 0 || Ws <= 0) return CARA_E_ARG;
-  const CropBoxes crop{Hs, Ws, boxes};
-  return vit_forward_body(g, s, w, cp, head_w, head_b, nullptr, pixels, n_split, rows, bad, mean, stdv, droppath, workspace, logits,
-                          stream, &crop);
+  if (!pixels || !rows || !boxes || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
+  const ImageSource src{ImageSource::U8RowsCrop, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
 extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
@@ -1067,110 +1128,74 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
   char* ws = static_cast<char*>(workspace);
   BwdPass pass;
   const SlabFormats& formats = pass.formats;
-  Ctx cx{stream, ws + W.gemm_scratch, 0, false, &pass, g->rank};
+  const Ctx px{stream, ws, &W, s, g->Rp, W.ldt, g->rank, &pass};
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const int D = g->dim, M = W.M, Rp = g->Rp, B = s->B, N = s->tokens;
   const float att_scale = 1.0f / sqrtf((float)(D / g->heads));
   cara_pack_layout pl;
   TRY(cara_pack_offsets(g, &pl));
-  float* dx = reinterpret_cast<float*>(ws + W.dx);
+  BlockPlan plans[64];
+  for (int l = 0; l < g->depth; ++l) plans[l] = plan_block(g, s, M, l);
+  const BlockPlan& last = plans[g->depth - 1];
+  float* dx = px.f32(W.dx);
   const Ws::Bwd& R = W.bwd;
-  bf16* dyb = reinterpret_cast<bf16*>(ws + R.dyb_fc2);   // dY of the last block's fc2
   TRY(head_backward_scaled(dlogits, ws + W.clsn, head_w, dhead_w, dhead_b, ws + W.dclsn, B, s->num_classes, D, s->loss_scale,
                            s->found_inf, stream));
-  // Gradient enters the token stream only through the cls rows.  With the last block on its cls rows (the default) every kernel of that
-  // block reads dx / dyb on those rows only, and its LayerNorm-1 backward -- the first launch that touches every row of dx -- is told
-  // so (cara_layernorm_bwd_rows_in: dx_in on every N-th row): the two buffers need no zeroing (58 MB of memset + 39 MB of zeros read
-  // back, ~18 us per step, r05).  Otherwise (CARA_CLS_SHORTCUT=0, exact weight dropout) the last block runs on all rows: zeros.
-  static const int force_zero = env_once("CARA_BWD_MEMSETS", 0);   // (1: the memsets and the all-rows read back, for A/B runs)
-  const bool last_on_cls = cls_shortcut_enabled() && !s->wd_exact && !force_zero;
-  if (!last_on_cls) {
+  if (!last.dx_on_cls) {   // (the last block reads every row of dx and of its dyb: zeros outside the cls rows)
     if (hipMemsetAsync(dx, 0, (size_t)M * D * 4, hs) != hipSuccess) return CARA_E_LAUNCH;
-    if (hipMemsetAsync(dyb, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
+    if (hipMemsetAsync(ws + R.dyb_fc2, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
   }
   const float* dp_last = droppath ? droppath + (size_t)(2 * (g->depth - 1) + 1) * B : nullptr;
-  TRY(cara_layernorm_bwd(ws + W.dclsn, reinterpret_cast<float*>(ws + W.x_last), (long)N * D, w->norm_g,
-                         reinterpret_cast<float*>(ws + W.meanF), reinterpret_cast<float*>(ws + W.rstdF), nullptr, dx, dyb,
-                         dp_last, 1, B, D, stream));
-  const bool ex = s->wd_exact != 0;
-  const bool fx = fuse_xu(g) && !ex;
-  const bool dense_qkv = g->cp_length == 2;
+  TRY(cara_layernorm_bwd(ws + W.dclsn, px.f32(W.x_last), (long)N * D, w->norm_g, px.f32(W.meanF), px.f32(W.rstdF), nullptr, dx, ws + R.dyb_fc2, dp_last, 1, B,
+                         D, stream));
   bool have_G_fc2 = false;   // G' of this block's fc2 was left by the LayerNorm backward of the block above
   for (int l = g->depth - 1; l >= 0; --l) {
+    const BlockPlan& p = plans[l];
     const LayerWs& lw = W.layer[l];
     Lin lin[4];
     make_lins(g, w, ws + W.pack, pl, l, lin);
     const float* dp1 = droppath ? droppath + (size_t)(2 * l) * B : nullptr;
     const float* dp_prev = (droppath && l > 0) ? droppath + (size_t)(2 * (l - 1) + 1) * B : nullptr;
-    // last block: only the cls rows carry gradient into proj / MLP (see cara_vit_forward)
-    const bool cls_only = (l == g->depth - 1) && cls_shortcut_enabled() && !s->wd_exact;
-    const int Mr = cls_only ? B : M;
-    const int ldr = cls_only ? N * D : D;
-    const int rps = cls_only ? 1 : N;
-    cx.layer = l;
-    cx.full = !cls_only;
-    Ctx cx_all = cx;   // attention and qkv always run on all token rows
-    cx_all.full = true;
-    // (dyb and G'[3] of this block's fc2 were written by the block above / the final norm's backward)
-    bf16* dyp = reinterpret_cast<bf16*>(ws + R.dyb_proj);
-    bf16* dH = reinterpret_cast<bf16*>(ws + R.dH);
-    bf16* dQKV = reinterpret_cast<bf16*>(ws + R.dQKV);
+    const Ctx cx = px.on(lw, l, p.Mr, !p.cls_only), cx_all = px.on(lw, l, M, true);   // (attention and qkv always run on all token rows)
+    // what the forward saved; the dY of the four linears (dyb and G'[3] of fc2 were written by the block above / the final norm's backward)
+    const Saved sv = saved_acts(cx, lw, D, p);
+    const Act dyb = cx.act(R.dyb_fc2, p.ldr, p.dyb_in), dH = cx.act(R.dH, 4 * D, p.dH), dyp = cx.act(R.dyb_proj, p.ldr, p.dyp), dQKV = cx.act(R.dQKV, 3 * D);
+    auto linear = [&](int i, const Act& dY, const Act& X, bool want_dx, const cara_gemm_args& e, bool want_dc, const Ctx& c, Riders where, bool have_G = false) {
+      return p.exact ? lin_bwd_exact(lin[i], dY, X, want_dx, e, want_dc, c) : lin_bwd(lin[i], dY, X, want_dx, e, want_dc, c, where, have_G);
+    };
     // ---- mlp branch: dY = drop_path scale * dx (already in dyb) ----
     cara_gemm_args e = {};
-    e.epi = save_gelu_grad(g, s) ? CARA_EPI_MULH : CARA_EPI_DGELU; e.C = dH; e.aux = ws + lw.u;
-    // K-panel-major activations, as the forward wrote them (xn1: pa_x; xn2, h: pa) and as the kernels here write
-    // theirs: dH and dyp (pa), dyb of the block below (pa_x).  This block's own dyb came from the block above --
-    // panels -- except in the last block, where the final norm's backward left it row-major on the cls rows.
-    // (h as the forward wrote it: row-major where fc2 forward runs on the 160 x 256 x 64 tile; dH: row-major where fc1 dX does)
-    const bool pa_x = panel_acts(M, s, 2) && !dense_qkv, pa = panel_acts(Mr, s, 1) && !tile_policy(g, Mr, D, 4 * D, 0), pa_n = panel_acts(Mr, s, 2);
-    const BlockPlan plan = plan_block(g, s, M, Mr, cls_only);
-    const bool pa_dh = plan.dh_panels;
+    e.epi = p.save_gelu_grad ? CARA_EPI_MULH : CARA_EPI_DGELU; e.aux = ws + lw.u;
+    writes(e, dH);
     pass.epilogue_ran = false;
-    const bool pa_dp = panel_acts(Mr, s, 4), pa_dx = panel_acts(M, s, 4);   // dyp here; dyb of the block below
-    const bool pa_dyb = pa_dx && l < g->depth - 1;
-    if (pa_dh) { e.c_panels = Mr; e.ldc = 4 * D; }
-    if (ex) TRY(lin_bwd_exact(lin[3], dyb, reinterpret_cast<bf16*>(ws + lw.h), Mr, Rp, ws, W, s, true, e, true, cx));
-    else TRY(lin_bwd(lin[3], dyb, pa_dyb ? -M : ldr, reinterpret_cast<bf16*>(ws + lw.h), pa ? -Mr : 4 * D, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx,
-                     plan.fc2, have_G_fc2));
-    const Riders fc1 = (plan.fc1 == Riders::DoneAbove && !pass.epilogue_ran) ? Riders::Own : plan.fc1;   // (the epilogue said no: fc1 carries its own)
+    TRY(linear(3, dyb, sv.h, true, e, true, cx, p.fc2, have_G_fc2));
+    const Riders fc1 = (p.fc1 == Riders::DoneAbove && !pass.epilogue_ran) ? Riders::Own : p.fc1;   // (the epilogue said no: fc1 carries its own)
     have_G_fc2 = false;
     e = {};
     e.epi = CARA_EPI_BF16; e.C = ws + W.dXn;
-    if (ex) TRY(lin_bwd_exact(lin[2], dH, reinterpret_cast<bf16*>(ws + lw.xn2), Mr, Rp, ws, W, s, true, e, true, cx));
-    else TRY(lin_bwd(lin[2], dH, pa_dh ? -Mr : 4 * D, reinterpret_cast<bf16*>(ws + lw.xn2), pa_n ? -Mr : D, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx, fc1));
-    // dyp = dY of this block's proj: its G' = dY Vs comes out of the same kernel (CARA_LN2B_XU=0: out of proj's dX GEMM instead)
-    static const int ln2b_xu = env_once("CARA_LN2B_XU", 1);
-    const bool fxp = fx && (ln2b_xu != 0 || cls_only);
+    TRY(linear(2, dH, sv.xn2, true, e, true, cx, fc1));
+    // dyp = dY of this block's proj: with fxp its G' = dY Vs comes out of the same kernel
     {
       SiteBracket sb(CARA_SITE_LN2_BWD, cx);
-      TRY(cara_layernorm_bwd_ex(ws + W.dXn, reinterpret_cast<float*>(ws + lw.x_mid), ldr, w->ln2_g + (size_t)l * D,
-                                reinterpret_cast<float*>(ws + lw.mean2), reinterpret_cast<float*>(ws + lw.rstd2), dx, dx, dyp, dp1,
-                                rps, Mr, D, fxp ? lin[1].Vst : nullptr, g->rank, Rp, ws + R.G[1], ws + R.Gt[1], W.ldt, pa_dp ? Mr : 0, stream));
+      TRY(cara_layernorm_bwd_ex(ws + W.dXn, px.f32(lw.x_mid), p.ldr, w->ln2_g + (size_t)l * D, px.f32(lw.mean2), px.f32(lw.rstd2), dx, dx, dyp.p, dp1,
+                                p.rps, p.Mr, D, p.fxp ? lin[1].Vst : nullptr, g->rank, Rp, ws + R.G[1], ws + R.Gt[1], W.ldt, dyp.panels, stream));
     }
     // ---- attention branch ----
     e = {};
-    e.epi = CARA_EPI_BF16; e.C = ws + W.dAO; e.ldc = ldr;
-    const bool cls_attn = cls_only && cls_attention_enabled();   // (then only the cls rows of dAO are ever read)
-    if (cls_only && !cls_attn && hipMemsetAsync(ws + W.dAO, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
-    if (ex) TRY(lin_bwd_exact(lin[1], dyp, reinterpret_cast<bf16*>(ws + lw.ao), Mr, Rp, ws, W, s, true, e, true, cx));
-    else TRY(lin_bwd(lin[1], dyp, pa_dp ? -Mr : ldr, reinterpret_cast<bf16*>(ws + lw.ao), ldr, Mr, Rp, W.ldt, ws, W, lw, true, e, true, cx, Riders::Own, fxp));
+    e.epi = CARA_EPI_BF16; e.C = ws + W.dAO; e.ldc = p.ldr;
+    // (with cls_attn only the cls rows of dAO are ever read)
+    if (p.cls_only && !p.cls_attn && hipMemsetAsync(ws + W.dAO, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
+    TRY(linear(1, dyp, sv.ao, true, e, true, cx, Riders::Own, p.fxp));
     {
       SiteBracket sb(CARA_SITE_ATTN_BWD, cx_all);
-      if (cls_attn)
-        TRY(cara_attention_cls_bwd(ws + lw.qkv, ws + lw.ao, ws + W.dAO, reinterpret_cast<float*>(ws + lw.lse), dQKV, B, N,
-                                   g->heads, att_scale, stream));
-      else
-        TRY(cara_attention_bwd(ws + lw.qkv, ws + lw.ao, ws + W.dAO, reinterpret_cast<float*>(ws + lw.lse), dQKV, B, N,
-                               g->heads, att_scale, stream));
+      TRY((p.cls_attn ? cara_attention_cls_bwd : cara_attention_bwd)(ws + lw.qkv, ws + lw.ao, ws + W.dAO, px.f32(lw.lse), dQKV.p, B, N, g->heads, att_scale,
+                                                                     stream));
     }
     e = {};
     e.epi = CARA_EPI_BF16; e.C = ws + W.dXn;
     // block 0 has nothing trainable upstream of it: its dX GEMM and LayerNorm backward are skipped
-    if (ex) TRY(lin_bwd_exact(lin[0], dQKV, reinterpret_cast<bf16*>(ws + lw.xn1), M, Rp, ws, W, s, l > 0, e, false, cx_all));
-    else if (dense_qkv)
-      TRY(lin_bwd_dense(lin[0], dQKV, reinterpret_cast<bf16*>(ws + lw.xn1), M, reinterpret_cast<bf16*>(ws + W.ddt) + (size_t)l * 3 * D * D,
-                        reinterpret_cast<float*>(ws + W.dD) + (size_t)l * 3 * D * D, reinterpret_cast<float*>(ws + W.dd_slabs), l > 0, e, cx_all));
-    else TRY(lin_bwd(lin[0], dQKV, 3 * D, reinterpret_cast<bf16*>(ws + lw.xn1), pa_x ? -M : D, M, Rp, W.ldt, ws, W, lw, l > 0, e, false, cx_all, plan.qkv));
+    if (p.dense_qkv) TRY(lin_bwd_dense(lin[0], dQKV, sv.xn1, l > 0, e, cx_all));
+    else TRY(linear(0, dQKV, sv.xn1, l > 0, e, false, cx_all, p.qkv));
     // the side stream's products read dH and G' of fc2, which the kernels below overwrite: the caller's stream waits for them (they
     // were launched some 300 us ago)
     if (pass.side_join) {
@@ -1183,20 +1208,18 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
       Lin below[4];
       make_lins(g, w, ws + W.pack, pl, l - 1, below);
       SiteBracket sb(CARA_SITE_LN1_BWD, cx_all);
-      TRY(cara_layernorm_bwd_rows_in(ws + W.dXn, reinterpret_cast<float*>(ws + lw.x_in), D, w->ln1_g + (size_t)l * D,
-                                     reinterpret_cast<float*>(ws + lw.mean1), reinterpret_cast<float*>(ws + lw.rstd1), dx, dx, dyb,
-                                     dp_prev, N, M, D, fx ? below[3].Vst : nullptr, g->rank, Rp, ws + R.G[3], ws + R.Gt[3], W.ldt,
-                                     pa_dx ? M : 0, (cls_only && last_on_cls) ? N : 0, stream));   // (last block: dx holds the cls rows only so far)
-      have_G_fc2 = fx;
+      TRY(cara_layernorm_bwd_rows_in(ws + W.dXn, px.f32(lw.x_in), D, w->ln1_g + (size_t)l * D, px.f32(lw.mean1), px.f32(lw.rstd1), dx, dx, dyb.p, dp_prev, N, M,
+                                     D, p.fx ? below[3].Vst : nullptr, g->rank, Rp, ws + R.G[3], ws + R.Gt[3], W.ldt, p.dyb_out, p.dx_in_every, stream));
+      have_G_fc2 = p.fx;
     }
   }
-  TRY(flush_waiting(cx, Rp, W.ldt));   // (block 0's proj dU still waits where its qkv is not lin_bwd's: order 2)
-  if (!ex) {   // (the exact mode wrote dU / dVs / dc of every layer directly)
+  TRY(flush_waiting(px));   // (block 0's proj dU still waits where its qkv is not lin_bwd's: order 2)
+  if (!last.exact) {   // (the exact mode wrote dU / dVs / dc of every layer directly)
     const int ins[4] = {D, D, D, 4 * D}, outs[4] = {3 * D, D, 4 * D, D};
     const int L = g->depth;
     cara_ts_reduce red[CARA_TS_REDUCE_MAX];   // all slab sums of the pass in ONE launch (8 + 6 of them, more where a linear's layers differ in slab format)
     int nred = 0;
-    const int Rc = (Rp == 32 && ts_rank(cx, Rp) <= 16) ? 16 : 0;   // (every product of the pass was told the same rank)
+    const int Rc = (Rp == 32 && ts_rank(px) <= 16) ? 16 : 0;   // (every product of the pass was told the same rank)
     auto push = [&](const cara_ts_reduce& e) -> int {
       if (nred == CARA_TS_REDUCE_MAX) {
         TRY(cara_tskinny_reduce_many(red, nred, stream));
@@ -1206,29 +1229,22 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
       return CARA_OK;
     };
     for (int i = 0; i < 4; ++i) {
-      if (i == 0 && dense_qkv) continue;   // order 2: the QKV linear wrote no skinny slabs (its gradient is dense, below)
-      float* dU = reinterpret_cast<float*>(ws + W.dU[i]);
-      float* dVs = reinterpret_cast<float*>(ws + W.dVs[i]);
-      float* dc = i == 0 ? nullptr : reinterpret_cast<float*>(ws + W.dc[i]);
-      // qkv (i == 0) sees all tokens in every block; proj / fc1 / fc2 of the last block ran on B rows,
+      if (i == 0 && last.dense_qkv) continue;   // order 2: the QKV linear wrote no skinny slabs (its gradient is dense, below)
+      float *dU = px.f32(W.dU[i]), *dVs = px.f32(W.dVs[i]), *dc = i == 0 ? nullptr : px.f32(W.dc[i]);
+      // qkv (i == 0) sees all tokens in every block; proj / fc1 / fc2 of the last block ran on B rows where it is on its cls rows,
       // so that block's slabs have their own chunking
-      const int full = (i == 0 || !cls_shortcut_enabled()) ? L : L - 1;   // (not reached in the exact mode)
+      const int full = (i == 0 || !last.cls_only) ? L : L - 1;
       // runs of layers whose products left the same slab format (one per block / one per wave: SlabFormats)
-      for (int l0 = 0; l0 < full;) {
-        int l1 = l0 + 1;
-        while (l1 < full && formats.U[i][l1] == formats.U[i][l0]) ++l1;
-        TRY(push(cara_ts_reduce{ws + W.slabU[i] + (size_t)l0 * W.strideU[i], W.strideU[i], dU + (size_t)l0 * ins[i] * Rp, nullptr, l1 - l0, M, ins[i], Rp, Rc,
-                                formats.U[i][l0]}));
-        l0 = l1;
-      }
-      for (int l0 = 0; l0 < full;) {
-        int l1 = l0 + 1;
-        while (l1 < full && formats.V[i][l1] == formats.V[i][l0]) ++l1;
-        TRY(push(cara_ts_reduce{ws + W.slabV[i] + (size_t)l0 * W.strideV[i], W.strideV[i], dVs + (size_t)l0 * outs[i] * Rp, dc ? dc + (size_t)l0 * outs[i] : nullptr,
-                                l1 - l0, M, outs[i], Rp, Rc, formats.V[i][l0]}));
-        l0 = l1;
-      }
-      if (i != 0 && cls_shortcut_enabled()) {
+      auto runs = [&](const unsigned short* f, size_t slabs, size_t stride, float* out, float* colsum, int K1) -> int {
+        for (int l0 = 0, l1; l0 < full; l0 = l1) {
+          for (l1 = l0 + 1; l1 < full && f[l1] == f[l0];) ++l1;
+          TRY(push(cara_ts_reduce{ws + slabs + l0 * stride, stride, out + (size_t)l0 * K1 * Rp, colsum ? colsum + (size_t)l0 * K1 : nullptr, l1 - l0, M, K1, Rp, Rc, f[l0]}));
+        }
+        return CARA_OK;
+      };
+      TRY(runs(formats.U[i], W.slabU[i], W.strideU[i], dU, nullptr, ins[i]));
+      TRY(runs(formats.V[i], W.slabV[i], W.strideV[i], dVs, dc, outs[i]));
+      if (i != 0 && last.cls_only) {
         const size_t l = L - 1;
         TRY(push(cara_ts_reduce{ws + W.slabU[i] + l * W.strideU[i], 0, dU + l * ins[i] * Rp, nullptr, 1, B, ins[i], Rp, Rc, 0}));
         TRY(push(cara_ts_reduce{ws + W.slabV[i] + l * W.strideV[i], 0, dVs + l * outs[i] * Rp, dc + l * outs[i], 1, B, outs[i], Rp, Rc, 0}));
@@ -1236,15 +1252,11 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
     }
     TRY(cara_tskinny_reduce_many(red, nred, stream));
   }
-  cara_layer_grads lg;
-  lg.dU_qkv = reinterpret_cast<float*>(ws + W.dU[0]); lg.dVs_qkv = reinterpret_cast<float*>(ws + W.dVs[0]);
-  lg.dU_proj = reinterpret_cast<float*>(ws + W.dU[1]); lg.dVs_proj = reinterpret_cast<float*>(ws + W.dVs[1]);
-  lg.dU_fc1 = reinterpret_cast<float*>(ws + W.dU[2]); lg.dVs_fc1 = reinterpret_cast<float*>(ws + W.dVs[2]);
-  lg.dU_fc2 = reinterpret_cast<float*>(ws + W.dU[3]); lg.dVs_fc2 = reinterpret_cast<float*>(ws + W.dVs[3]);
-  lg.dc_proj = reinterpret_cast<float*>(ws + W.dc[1]); lg.dc_fc1 = reinterpret_cast<float*>(ws + W.dc[2]);
-  lg.dc_fc2 = reinterpret_cast<float*>(ws + W.dc[3]);
+  const cara_layer_grads lg{px.f32(W.dU[0]), px.f32(W.dVs[0]), px.f32(W.dU[1]), px.f32(W.dVs[1]), px.f32(W.dU[2]), px.f32(W.dVs[2]),   // dU, dVs of qkv, proj, fc1
+                            px.f32(W.dU[3]), px.f32(W.dVs[3]), px.f32(W.dc[1]),  px.f32(W.dc[2]),  px.f32(W.dc[3])};                      // ... fc2; dc of proj, fc1, fc2
   TRY(cara_factor_grad_reduce_ex(g, cp, &lg, grads, ws + W.gscratch, s->loss_scale, s->found_inf, stream));
-  if (dense_qkv)   // CP_A1 / CP_A2 / CP_R1 of the order-2 tensorisation, from the dense dD of every (layer, projection)
-    TRY(cara_dense_delta_grad(g, cp, reinterpret_cast<const float*>(ws + W.dD), grads, ws + W.dd_scratch, stream));
+  if (last.dense_qkv)   // CP_A1 / CP_A2 / CP_R1 of the order-2 tensorisation, from the dense dD of every (layer, projection)
+    TRY(cara_dense_delta_grad(g, cp, px.f32(W.dD), grads, ws + W.dd_scratch, stream));
   return CARA_OK;
 }
+
