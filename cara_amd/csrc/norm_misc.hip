@@ -401,6 +401,12 @@ __device__ __forceinline__ CropAxis crop_axis(int o, int n_out, int n_box, bool 
 }
 // normalize_u8x4's operations on a value that is no longer a byte
 __device__ __forceinline__ float normalize_f32(float v, float mu, float sd) { return (v / 255.0f - mu) / sd; }
+// the bilinear value of one output pixel, before normalisation: top / bot = the two source rows at the box's left edge
+__device__ __forceinline__ float crop_value(const uint8_t* top, const uint8_t* bot, const CropAxis& ax, float fy) {
+  const float t0 = (float)top[ax.i0], t1 = (float)top[ax.i1], b0 = (float)bot[ax.i0], b1 = (float)bot[ax.i1];
+  const float t = t0 + ax.f * (t1 - t0), u = b0 + ax.f * (b1 - b0);
+  return t + fy * (u - t);
+}
 __global__ __launch_bounds__(256) void im2col_u8_rows_crop_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
                                                                   const int64_t* __restrict__ rows, const int* __restrict__ boxes,
                                                                   const float* __restrict__ mean, const float* __restrict__ stdv,
@@ -434,11 +440,84 @@ __global__ __launch_bounds__(256) void im2col_u8_rows_crop_kernel(const uint8_t*
   const float mu = mean[c], sd = stdv[c];
   float v[4];
 #pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = normalize_f32(crop_value(top, bot, crop_axis(gx * p + px + j, Wi, w, flip), ay.f), mu, sd);
+  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+}
+
+// im2col_u8_rows_crop_kernel with Mixup / CutMix: mix int32 [B,8] = (partner, cx0, cy0, cw, ch, blend, target, 0).  Sample b is
+// mixed with what sample `partner` would be UNMIXED at the same output position (through rows[partner] and boxes[partner], its
+// flip included): inside the rectangle (cx0, cy0, cw, ch) of the output the pixel is the partner's, outside it a + m (b - a) on the
+// un-normalised 0..255 values, m = the fp32 whose bits `blend` holds -- exact at m == 0, like the axes' a + f (b - a).  Then
+// normalize_f32 and the one rounding to 16 bits.  `target` is the loss's (xent_mix_kernel).  boxes may be NULL: every sample reads
+// its whole image (the host then asks Hs == Hi, Ws == Wi).  The lane layout is the crop kernel's; a pixel loads only the image
+// it needs -- the partner alone inside the rectangle, its own alone outside it when m == 0 -- and a sample that is its own partner
+// checks one source, not two: an identity table costs the crop kernel's loads plus its table row.  Nothing is formed from an unchecked value: zeros, counted once in *bad, for a sample whose own or whose
+// partner's row or box is bad, whose partner is outside [0, B), whose rectangle is not inside the output or whose m is not in [0, 1].
+struct MixSource { const uint8_t* origin; int w, h; bool flip; };   // byte (y0, x0) of channel 0 of the image, and its box
+__device__ __forceinline__ bool mix_source(const uint8_t* img, long n_split, int C, int Hs, int Ws, const int64_t* rows,
+                                           const int* boxes, int b, MixSource* s) {
+  const int64_t r = rows[b];
+  int x0 = 0, y0 = 0, w = Ws, h = Hs, flip = 0;
+  if (boxes) {
+    const int* box = boxes + (size_t)b * 5;
+    x0 = box[0]; y0 = box[1]; w = box[2]; h = box[3]; flip = box[4];
+  }
+  // (the crop kernel's order: x0, y0 >= 0 before Ws - x0, Hs - y0 are formed)
+  if (r < 0 || r >= n_split || w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > Ws - x0 || h > Hs - y0) return false;
+  *s = MixSource{img + (size_t)r * C * Hs * Ws + (size_t)y0 * Ws + x0, w, h, flip != 0};
+  return true;
+}
+__global__ __launch_bounds__(256) void im2col_u8_rows_mix_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                                 const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                                 const int* __restrict__ mix, const float* __restrict__ mean,
+                                                                 const float* __restrict__ stdv, bf16* __restrict__ out,
+                                                                 int* __restrict__ bad, int B, int C, int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const int kcols = C * p * p;
+  const long e = idx * 4;
+  const long row = e / kcols;
+  const int col = (int)(e - row * kcols);
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
+  const int gy = pr / gw, gx = pr % gw;
+  const int* mx = mix + (size_t)b * 8;
+  const int partner = mx[0], cx0 = mx[1], cy0 = mx[2], cw = mx[3], ch = mx[4];
+  const float m = __int_as_float(mx[5]);
+  MixSource own, oth;
+  // (partner is inside [0, B) before rows[partner] / boxes[partner] are formed; cx0, cy0 >= 0 before Wi - cx0, Hi - cy0; a NaN
+  // fails m >= 0)
+  const bool self = partner == b;
+  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) &&
+                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth))) && cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 &&
+                  cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
+  if (!ok) {
+    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
+    const bf16 z = (bf16)0.0f;
+    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
+    return;
+  }
+  if (self) oth = own;
+  const int oy = gy * p + py, ox0 = gx * p + px;
+  const CropAxis ay_own = crop_axis(oy, Hi, own.h, false), ay_oth = crop_axis(oy, Hi, oth.h, false);
+  const size_t chan = (size_t)c * Hs * Ws;
+  const uint8_t *top_own = own.origin + chan + (size_t)ay_own.i0 * Ws, *bot_own = own.origin + chan + (size_t)ay_own.i1 * Ws;
+  const uint8_t *top_oth = oth.origin + chan + (size_t)ay_oth.i0 * Ws, *bot_oth = oth.origin + chan + (size_t)ay_oth.i1 * Ws;
+  const bool row_in = oy >= cy0 && oy - cy0 < ch;
+  const float mu = mean[c], sd = stdv[c];
+  float v[4];
+#pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const CropAxis ax = crop_axis(gx * p + px + j, Wi, w, flip);
-    const float t0 = (float)top[ax.i0], t1 = (float)top[ax.i1], b0 = (float)bot[ax.i0], b1 = (float)bot[ax.i1];
-    const float t = t0 + ax.f * (t1 - t0), u = b0 + ax.f * (b1 - b0);
-    v[j] = normalize_f32(t + ay.f * (u - t), mu, sd);
+    const int ox = ox0 + j;
+    float a;
+    if (row_in && ox >= cx0 && ox - cx0 < cw) {
+      a = crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f);
+    } else {
+      a = crop_value(top_own, bot_own, crop_axis(ox, Wi, own.w, own.flip), ay_own.f);
+      if (m != 0.0f) a = a + m * (crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f) - a);
+    }
+    v[j] = normalize_f32(a, mu, sd);
   }
   *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
 }
@@ -498,6 +577,54 @@ __global__ __launch_bounds__(64) void xent_kernel(const float* __restrict__ logi
     for (int c = lane; c < C; c += 64)
       dlogits[(size_t)b * C + c] = ok ? (__expf(lr[c] - lse) - (c == y ? 1.f : 0.f)) * gsc : qnan;
   if (lane == 0) loss_per[b] = ok ? (lse - lr[y]) * invB : qnan;
+}
+// xent_kernel against a soft target (label smoothing eps; Mixup / CutMix: the partner's label with weight t = the fp32 whose bits
+// mix[b][6] holds; mix NULL: t = 0):  q_c = (1 - eps) ((1 - t) [c == ya] + t [c == yb]) + eps / C,  ya = labels[b], yb =
+// labels[partner],  term_b = (lse_b - sum_c q_c l_c) / B,  dlogits = (softmax - q) gsc.  sum_c q_c l_c = (1 - eps) (l_ya + t (l_yb -
+// l_ya)) + (eps / C) sum_c l_c: one more wave reduction, its sum gathered in the pass that finds the maximum.  The lerp is exact at
+// t == 0 and where ya == yb, 1 - eps is 1 at eps == 0 and the eps / C term is added only where it is not zero: eps == 0 && t == 0
+// gives q == the one-hot and every output bit for bit xent_kernel's.
+// Guards as there: ya or yb outside [0, C), partner outside [0, B) (checked before labels[partner] is formed) or a t that is not
+// in [0, 1] (a NaN fails t >= 0) index nothing and make the sample's term and dlogits row NaN; other samples are unaffected.
+__global__ __launch_bounds__(64) void xent_mix_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                      const int* __restrict__ mix, float eps, float* __restrict__ loss_per,
+                                                      float* __restrict__ dlogits, int B, int C, float dscale,
+                                                      const float* __restrict__ loss_scale) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* lr = logits + (size_t)b * C;
+  float m = -3.0e38f, sl = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    m = fmaxf(m, lr[c]);
+    sl += lr[c];
+  }
+  m = wave_max(m);
+  sl = wave_sum(sl);
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += __expf(lr[c] - m);
+  s = wave_sum(s);
+  const float lse = m + __logf(s);
+  const int partner = mix ? mix[(size_t)b * 8] : b;
+  const float t = mix ? __int_as_float(mix[(size_t)b * 8 + 6]) : 0.f;
+  const int64_t yal = labels[b];
+  const bool pok = partner >= 0 && partner < B;
+  const int64_t ybl = pok ? labels[partner] : -1;
+  const bool ok = yal >= 0 && yal < C && ybl >= 0 && ybl < C && t >= 0.f && t <= 1.f;   // (wave-uniform)
+  const int ya = ok ? (int)yal : 0, yb = ok ? (int)ybl : 0;
+  const float wa = (1.f - eps) * (1.f - t), wb = (1.f - eps) * t, u = eps / (float)C;
+  const float qnan = __builtin_nanf("");
+  const float invB = 1.0f / B;
+  const float gsc = invB * dscale * (loss_scale ? *loss_scale : 1.f);   // (xent_kernel's)
+  if (dlogits)
+    for (int c = lane; c < C; c += 64) {
+      const float q = (c == ya ? wa : 0.f) + (c == yb ? wb : 0.f) + u;
+      dlogits[(size_t)b * C + c] = ok ? (__expf(lr[c] - lse) - q) * gsc : qnan;
+    }
+  if (lane == 0) {
+    const float la = lr[ya];
+    float dot = (1.f - eps) * (la + t * (lr[yb] - la));
+    if (u != 0.f) dot += u * sl;
+    loss_per[b] = ok ? (lse - dot) * invB : qnan;
+  }
 }
 __global__ __launch_bounds__(64) void xent_sum_kernel(const float* __restrict__ loss_per, float* __restrict__ loss, int B,
                                                       float* __restrict__ found_inf) {
@@ -762,6 +889,20 @@ extern "C" int cara_im2col_patches_u8_rows_crop(const unsigned char* pixels, int
   return CARA_OK;
 }
 
+extern "C" int cara_im2col_patches_u8_rows_mix(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                               const int* boxes, const int* mix, const float* mean, const float* stdv, void* patches,
+                                               int* bad, int B, int C, int Hi, int Wi, int p, void* stream) {
+  if (!pixels || !rows || !mix || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 ||
+      (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p)
+    return CARA_E_ARG;
+  if (!boxes && (Hs != Hi || Ws != Wi)) return CARA_E_ARG;   // (without boxes a sample is its whole image, byte for byte)
+  const long total4 = (long)B * C * Hi * Wi / 4;
+  hipLaunchKernelGGL(im2col_u8_rows_mix_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     pixels, (long)n_split, Hs, Ws, rows, boxes, mix, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
 extern "C" int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
                                   void* stream) {
   if (!labels || !rows || !out || n_split <= 0 || B <= 0) return CARA_E_ARG;
@@ -787,6 +928,17 @@ extern "C" int cara_cross_entropy_ex(const float* logits, const int64_t* labels,
   if (!logits || !labels || !loss || B <= 0 || C <= 0 || !(dscale > 0.f)) return CARA_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(xent_kernel, dim3(B), dim3(64), 0, st, logits, labels, loss + 1, dlogits, B, C, dscale, loss_scale);
+  CARA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+extern "C" int cara_cross_entropy_mix(const float* logits, const int64_t* labels, const int* mix, float smoothing, float* loss,
+                                      float* dlogits, int B, int C, float dscale, const float* loss_scale, float* found_inf,
+                                      void* stream) {
+  if (!logits || !labels || !loss || B <= 0 || C <= 0 || !(dscale > 0.f) || !(smoothing >= 0.f && smoothing < 1.f)) return CARA_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(xent_mix_kernel, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, loss + 1, dlogits, B, C, dscale, loss_scale);
   CARA_CHECK_LAUNCH();
   hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
   CARA_CHECK_LAUNCH();

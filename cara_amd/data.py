@@ -80,7 +80,8 @@ class RandomResizedCropFlip:
     and an aspect ratio ``exp(U(log ratio))``, ``w = round(sqrt(area * r))``, ``h = round(sqrt(area / r))``; the first try with
     ``0 < w <= Ws`` and ``0 < h <= Hs`` is taken at a uniform integer offset.  If none fits: the centre crop of the whole image
     clamped to the ratio bounds.  ``size`` is the side the crop is resized to (the model's input); the boxes do not depend on it
-    -- the kernel that reads them resamples to the model's own size.  No colour jitter, mixup / cutmix or antialiasing."""
+    -- the kernel that reads them resamples to the model's own size.  No colour jitter or antialiasing; Mixup / CutMix is
+    ``MixupCutmix`` below."""
 
     TRIES = 10
 
@@ -164,14 +165,140 @@ def resized_crop_reference(pixels_u8: torch.Tensor, rows, boxes, size, dtype=tor
     return out
 
 
-def box_seed(seed: int, epoch: int, rank: int) -> int:
+def box_seed(seed: int, epoch: int, rank: int, stream: int = 0x27D4EB2F) -> int:
     """32-bit seed (torch's host generator keeps no more) of the generator that draws the crop boxes of one rank's epoch: each
     of seed, epoch and rank enters through an odd multiplier, so changing one of them alone always changes the value, and a
-    bijective finaliser (murmur3's) spreads neighbouring values"""
-    x = (int(seed) * 0x9E3779B1 + int(epoch) * 0x85EBCA77 + int(rank) * 0xC2B2AE3D + 0x27D4EB2F) & 0xffffffff
+    bijective finaliser (murmur3's) spreads neighbouring values.  ``stream``: the constant of this random stream (``mix_seed``
+    has another)"""
+    x = (int(seed) * 0x9E3779B1 + int(epoch) * 0x85EBCA77 + int(rank) * 0xC2B2AE3D + int(stream)) & 0xffffffff
     x = ((x ^ (x >> 16)) * 0x85EBCA6B) & 0xffffffff
     x = ((x ^ (x >> 13)) * 0xC2B2AE35) & 0xffffffff
     return x ^ (x >> 16)
+
+
+def mix_seed(seed: int, epoch: int, rank: int) -> int:
+    """``box_seed`` of the stream that draws the Mixup / CutMix tables: another constant, so the same (seed, epoch, rank) gives a
+    generator that is not the boxes'"""
+    return box_seed(seed, epoch, rank, stream=0x165667B1)
+
+
+def _f32_bits(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.float32).contiguous().view(torch.int32)
+
+
+def _bits_f32(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.int32).contiguous().view(torch.float32)
+
+
+def identity_mix(B: int, steps: Optional[int] = None) -> torch.Tensor:
+    """int32 [B, 8] (or [steps, B, 8]) table that mixes nothing: partner = the sample itself, no rectangle, m = t = 0"""
+    t = torch.zeros(B, 8, dtype=torch.int32)
+    t[:, 0] = torch.arange(B, dtype=torch.int32)
+    return t if steps is None else t.expand(steps, B, 8).contiguous()
+
+
+class MixupCutmix:
+    """Mix tables for the resident feed: the published definition of timm's ``Mixup`` in batch mode (``mode="batch"``,
+    ``correct_lam=True``), restated (timm is not installed).  Per batch: with probability ``1 - prob`` the identity table.
+    Otherwise CutMix is chosen if ``rand < switch_prob`` and both alphas are positive (with one positive alpha: that method),
+    ``lam ~ Beta(alpha, alpha)`` of the chosen method, and every sample ``i`` is mixed with ``partner = B - 1 - i`` (timm's
+    ``x.flip(0)``).
+      Mixup:  ``x_i (1 - m) + x_partner m`` with ``m = t = 1 - lam``, no rectangle.
+      CutMix: ``r = sqrt(1 - lam)``, ``ch = int(Hi r)``, ``cw = int(Wi r)``, centre ``(cy, cx)`` a uniform integer in [0, Hi) x
+              [0, Wi), edges ``clip(c -/+ side // 2, 0, Hi or Wi)`` (timm's ``rand_bbox``); the rectangle is the partner's
+              pixels, ``t = area / (Hi Wi)`` of the clipped rectangle (``correct_lam``: lam = 1 - t) and ``m = 0``.
+    The target of sample ``i`` is ``(1 - t) onehot(y_i) + t onehot(y_partner)``, smoothed by the loss (``soft_target``).
+    A row of the table is ``(partner, cx0, cy0, cw, ch, bits of fp32 m, bits of fp32 t, 0)``: include/cara_hip.h,
+    ``cara_im2col_patches_u8_rows_mix``.  ``size`` = Hi or (Hi, Wi): the model's input, in whose pixels the rectangle is."""
+
+    def __init__(self, size, mixup_alpha: float = 0.8, cutmix_alpha: float = 1.0, prob: float = 1.0, switch_prob: float = 0.5):
+        Hi, Wi = (size, size) if isinstance(size, int) else size
+        if int(Hi) <= 0 or int(Wi) <= 0 or mixup_alpha < 0 or cutmix_alpha < 0 or (mixup_alpha == 0 and cutmix_alpha == 0) \
+                or not (0.0 <= prob <= 1.0) or not (0.0 <= switch_prob <= 1.0):
+            raise ValueError("MixupCutmix: size > 0, alphas >= 0 and not both 0, prob and switch_prob in [0, 1]")
+        self.Hi, self.Wi = int(Hi), int(Wi)
+        self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob = float(mixup_alpha), float(cutmix_alpha), float(prob), float(switch_prob)
+
+    def draw(self, B: int, steps: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """int32 [steps, B, 8] on the host.  A fixed number of variates of ``generator`` per batch -- one, the seed of that batch's
+        own generator (the Beta draw rejects a varying number of its variates) -- so batch ``k`` does not depend on ``steps``."""
+        Hi, Wi = self.Hi, self.Wi
+        out = identity_mix(B, steps)
+        for k in range(steps):
+            g = torch.Generator().manual_seed(int(torch.randint(0, 2 ** 31 - 1, (1,), generator=generator)))
+            u = torch.rand(4, generator=g, dtype=torch.float64).tolist()
+            if not u[0] < self.prob:
+                continue
+            cutmix = self.cutmix_alpha > 0 and (self.mixup_alpha == 0 or u[1] < self.switch_prob)
+            alpha = self.cutmix_alpha if cutmix else self.mixup_alpha
+            x, y = torch._standard_gamma(torch.full((2,), alpha, dtype=torch.float64), generator=g).tolist()
+            lam = x / (x + y) if x + y > 0 else 0.5
+            row = out[k]
+            row[:, 0] = B - 1 - torch.arange(B, dtype=torch.int32)
+            if cutmix:
+                r = math.sqrt(1.0 - lam)
+                ch, cw = int(Hi * r), int(Wi * r)
+                cy, cx = min(int(u[2] * Hi), Hi - 1), min(int(u[3] * Wi), Wi - 1)
+                y0, y1 = min(max(cy - ch // 2, 0), Hi), min(max(cy + ch // 2, 0), Hi)
+                x0, x1 = min(max(cx - cw // 2, 0), Wi), min(max(cx + cw // 2, 0), Wi)
+                row[:, 1], row[:, 2], row[:, 3], row[:, 4] = x0, y0, x1 - x0, y1 - y0
+                row[:, 6] = _f32_bits(torch.tensor((x1 - x0) * (y1 - y0) / (Hi * Wi), dtype=torch.float64))
+            else:
+                row[:, 5] = row[:, 6] = _f32_bits(torch.tensor(1.0 - lam, dtype=torch.float64))
+        return out
+
+
+def check_mix(mix: torch.Tensor, B: int, Hi: int, Wi: int) -> None:
+    """ValueError unless ``mix`` is an int32 [..., B, 8] table whose every partner is in [0, B), whose every rectangle lies inside
+    the ``Hi`` x ``Wi`` output and whose every m and t is in [0, 1] (the companion of ``check_boxes``)"""
+    if not torch.is_tensor(mix) or mix.dtype != torch.int32 or mix.ndim < 2 or mix.shape[-1] != 8 or mix.shape[-2] != B:
+        raise ValueError("mix must be an int32 [..., batch, 8] tensor (partner, cx0, cy0, cw, ch, blend bits, target bits, 0)")
+    t = mix.reshape(-1, 8).cpu()
+    w = t.to(torch.int64)
+    m, tg = _bits_f32(t[:, 5]), _bits_f32(t[:, 6])
+    bad = (w[:, 0] < 0) | (w[:, 0] >= B) | (w[:, 1] < 0) | (w[:, 2] < 0) | (w[:, 3] < 0) | (w[:, 4] < 0) | (w[:, 1] + w[:, 3] > Wi) \
+        | (w[:, 2] + w[:, 4] > Hi) | ~((m >= 0) & (m <= 1)) | ~((tg >= 0) & (tg <= 1))
+    if bool(bad.any()):
+        i = int(bad.to(torch.int64).argmax())
+        raise ValueError(f"{int(bad.sum())} mix entry(ies) with a partner outside [0, {B}), a rectangle outside the {Hi} x {Wi} output "
+                         f"or a weight outside [0, 1], the first: {t[i, :5].tolist()} m {float(m[i])} t {float(tg[i])}")
+
+
+def mix_reference(pixels_u8: torch.Tensor, rows, boxes, mix, size, dtype=torch.float64) -> torch.Tensor:
+    """What ``cara_im2col_patches_u8_rows_mix`` samples, before normalisation, in torch ops on the CPU: with ``x =
+    resized_crop_reference(pixels, rows, boxes, size)`` (``boxes`` None: every sample its whole image, which must have the
+    output's size) and row ``i`` of ``mix`` = (p, cx0, cy0, cw, ch, m, t, 0): ``out[i] = x[i] + m (x[p] - x[i])``, then
+    ``out[i][:, cy0:cy0+ch, cx0:cx0+cw] = x[p][...]``.  [B,C,Hi,Wi] of ``dtype``."""
+    Hi, Wi = (size, size) if isinstance(size, int) else size
+    rows = torch.as_tensor(rows).cpu()
+    if boxes is None:
+        if tuple(pixels_u8.shape[2:]) != (Hi, Wi):
+            raise ValueError("without boxes the split must have the output's size")
+        boxes = torch.tensor([[0, 0, Wi, Hi, 0]] * len(rows), dtype=torch.int32)
+    mix = torch.as_tensor(mix).cpu()
+    check_mix(mix, len(rows), Hi, Wi)
+    x = resized_crop_reference(pixels_u8, rows, boxes, (Hi, Wi), dtype)
+    m = _bits_f32(mix[:, 5]).to(dtype)
+    out = torch.empty_like(x)
+    for i, (p, cx0, cy0, cw, ch) in enumerate(mix[:, :5].tolist()):
+        out[i] = x[i] + m[i] * (x[p] - x[i])
+        out[i][:, cy0:cy0 + ch, cx0:cx0 + cw] = x[p][:, cy0:cy0 + ch, cx0:cx0 + cw]
+    return out
+
+
+def soft_target(labels: torch.Tensor, mix, classes: int, smoothing: float = 0.0) -> torch.Tensor:
+    """The target ``cara_cross_entropy_mix`` trains on, float64 [B, classes]: ``q = (1 - eps) ((1 - t) onehot(y) + t
+    onehot(y[partner])) + eps / classes`` -- torch's ``label_smoothing`` of timm's ``mixup_target``.  ``mix`` None: t = 0."""
+    y = labels.detach().cpu().long()
+    B = y.shape[0]
+    eye = torch.eye(classes, dtype=torch.float64)
+    if mix is None:
+        partner, t = torch.arange(B), torch.zeros(B, dtype=torch.float64)
+    else:
+        mix = torch.as_tensor(mix).cpu()
+        partner, t = mix[:, 0].long(), _bits_f32(mix[:, 6]).double()
+    t = t[:, None]
+    return (1.0 - smoothing) * ((1.0 - t) * eye[y] + t * eye[y[partner]]) + smoothing / classes
 
 
 class ResidentSplit:
@@ -232,7 +359,7 @@ class ResidentSplit:
         return epoch_iter
 
     def train_rows(self, batch_size: int = 64, seed: int = 0, rank: Optional[int] = None,
-                   world: Optional[int] = None, augment=None) -> Callable[[int], Iterator[torch.Tensor]]:
+                   world: Optional[int] = None, augment=None, mix=None) -> Callable[[int], Iterator[torch.Tensor]]:
         """``f(epoch)`` -> iterator of int64 [batch_size] index vectors on the device: the indices ``train_batches`` draws
         (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
         and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
@@ -240,7 +367,14 @@ class ResidentSplit:
         ``augment`` (a ``RandomResizedCropFlip``, or anything with its ``draw``): the iterator yields ``(rows, boxes)`` --
         the same index vectors, each with an int32 [batch_size, 5] view of one [steps, batch_size, 5] box upload per epoch
         (``train_step_resident(..., boxes=)``).  The boxes are drawn on the host from a generator seeded by (seed, epoch,
-        rank) and range-checked before the upload, like the indices."""
+        rank) and range-checked before the upload, like the indices.
+        ``mix`` (a ``MixupCutmix``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix)``
+        -- ``boxes`` is None without an ``augment`` -- each with an int32 [batch_size, 8] view of one [steps, batch_size, 8] upload
+        per epoch (``train_step_resident(..., mix=)``), drawn from a generator seeded by (seed, epoch, rank) on a stream of its
+        own (``mix_seed``) and range-checked (``check_mix``) before the upload."""
+        if mix is not None and not (callable(getattr(mix, "draw", None)) and isinstance(getattr(mix, "Hi", None), int)
+                                    and isinstance(getattr(mix, "Wi", None), int)):
+            raise ValueError("mix must be a MixupCutmix (anything with draw(B, steps, generator), Hi and Wi)")
         rank = D.get_rank() if rank is None else rank
         world = D.world_size() if world is None else world
 
@@ -251,18 +385,28 @@ class ResidentSplit:
             table = torch.stack(idx)
             if int(table.min()) < 0 or int(table.max()) >= len(self):
                 raise ValueError(f"epoch {epoch}: a drawn index is outside [0, {len(self)})")
-            if augment is None:
-                table = table.to(self.pixels.device)
-                for step in range(table.shape[0]):
-                    yield table[step]
-                return
-            Hs, Ws = self.pixels.shape[2:]
-            gen = torch.Generator().manual_seed(box_seed(seed, epoch, rank))
-            boxes = augment.draw(Hs, Ws, table.numel(), gen).reshape(*table.shape, 5)
-            check_boxes(boxes, Hs, Ws)
-            table, boxes = table.to(self.pixels.device), boxes.to(self.pixels.device)
+            boxes = mixes = None
+            if augment is not None:
+                Hs, Ws = self.pixels.shape[2:]
+                gen = torch.Generator().manual_seed(box_seed(seed, epoch, rank))
+                boxes = augment.draw(Hs, Ws, table.numel(), gen).reshape(*table.shape, 5)
+                check_boxes(boxes, Hs, Ws)
+                boxes = boxes.to(self.pixels.device)
+            if mix is not None:
+                mixes = mix.draw(table.shape[1], table.shape[0], torch.Generator().manual_seed(mix_seed(seed, epoch, rank)))
+                if not torch.is_tensor(mixes) or tuple(mixes.shape) != (*table.shape, 8):
+                    raise ValueError(f"mix.draw gave {tuple(mixes.shape) if torch.is_tensor(mixes) else type(mixes).__name__}, "
+                                     f"not an int32 {(*table.shape, 8)} table")
+                check_mix(mixes, table.shape[1], mix.Hi, mix.Wi)
+                mixes = mixes.contiguous().to(self.pixels.device)
+            table = table.to(self.pixels.device)
             for step in range(table.shape[0]):
-                yield table[step], boxes[step]
+                if mixes is not None:
+                    yield table[step], (None if boxes is None else boxes[step]), mixes[step]
+                elif boxes is not None:
+                    yield table[step], boxes[step]
+                else:
+                    yield table[step]
         return epoch_iter
 
     def eval_batches(self, batch_size: int = 256) -> Callable[[], Iterator[Tuple[torch.Tensor, torch.Tensor]]]:
@@ -294,7 +438,7 @@ class ResidentSplit:
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
              seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False, augment=None,
-             train_size: Optional[int] = None):
+             train_size: Optional[int] = None, mix=None):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
@@ -304,9 +448,10 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     ``fit(feed="resident")`` takes: the steps read the split's uint8 pixels by index instead of a normalised fp32 batch.
     ``augment`` / ``train_size`` (with ``resident_feed``): the training split is decoded at ``train_size`` (default 224, the
     model's size) and its ``train_rows`` yields ``(rows, boxes)`` drawn by ``augment`` -- "resize 256, random-resized-crop
-    224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size."""
-    if (augment is not None or train_size is not None) and not resident_feed:
-        raise ValueError("augment / train_size belong to the resident feed: pass resident_feed=True")
+    224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size.
+    ``mix`` (with ``resident_feed``; a ``MixupCutmix``): ``train_rows`` yields ``(rows, boxes or None, mix)``."""
+    if (augment is not None or train_size is not None or mix is not None) and not resident_feed:
+        raise ValueError("augment / train_size / mix belong to the resident feed: pass resident_feed=True")
     if train_size is not None and train_size != 224 and augment is None:
         raise ValueError("a training split of another size than the model's is read through crop boxes: pass augment")
     root = root if root is not None else "./data/vtab-1k/" + name
@@ -314,7 +459,7 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers, size=224 if train_size is None else train_size)
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
     if resident_feed:
-        feed = (train, train.train_rows(batch_size, seed=seed) if augment is None else train.train_rows(batch_size, seed=seed, augment=augment))
+        feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix))
     else:
         feed = train.train_batches(batch_size, seed=seed)
     return feed, (test if shard_eval else test.eval_batches(256))

@@ -232,13 +232,13 @@ class CaraEngine:
             return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev)
 
     def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None):
-        """``resident = (split, rows[, boxes])``: the images are rows of a resident uint8 split (``images`` is None then), with
-        ``boxes`` read through a crop box per sample at the model's own input size"""
-        boxes = None
+        """``resident = (split, rows[, boxes[, mix]])``: the images are rows of a resident uint8 split (``images`` is None then),
+        with ``boxes`` read through a crop box per sample at the model's own input size, with ``mix`` mixed by that table"""
+        boxes = mix = None
         if resident is None:
             st = self._state(model, images.shape[0], images.shape[2], dev)
         else:
-            split, rows, boxes = resident if len(resident) == 3 else (*resident, None)
+            split, rows, boxes, mix = (*resident, None, None)[:4]
             st = self._state(model, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
             if st["shape"].chans != 3:
                 raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
@@ -265,6 +265,12 @@ class CaraEngine:
         if resident is None:
             check(self._lib().cara_vit_forward(*args, ptr(images), ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)),
                   "cara_vit_forward")
+        elif mix is not None:
+            mean, std = self._eval_norm(dev)
+            check(self._lib().cara_vit_forward_u8_rows_mix(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
+                                                           split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(mean), ptr(std),
+                                                           ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)),
+                                                           stream(dev)), "cara_vit_forward_u8_rows_mix")
         elif boxes is not None:
             mean, std = self._eval_norm(dev)
             check(self._lib().cara_vit_forward_u8_rows_crop(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
@@ -437,25 +443,35 @@ class CaraEngine:
         if optimizer is not None:
             optimizer.step()
 
-    def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None):
+    @staticmethod
+    def _smoothing(label_smoothing) -> float:
+        if not isinstance(label_smoothing, (int, float)) or not (0.0 <= label_smoothing < 1.0):   # (a NaN fails the comparison)
+            raise CaraError(f"label_smoothing must be a number in [0, 1), not {label_smoothing!r}")
+        return float(label_smoothing)
+
+    def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
+                   label_smoothing: float = 0.0):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
         process group has more than one rank -> ``optimizer.step()``.  Returns the loss (device
         scalar, local to this rank).  ``p.grad`` of every trainable parameter is a view of the flat
-        buffer, so any torch optimizer consumes it unchanged."""
+        buffer, so any torch optimizer consumes it unchanged.
+        ``label_smoothing`` = eps in [0, 1): the loss is torch's ``cross_entropy(label_smoothing=eps)``
+        (``cara_cross_entropy_mix``; 0 runs ``cara_cross_entropy_ex`` as before)."""
+        eps = self._smoothing(label_smoothing)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp),
-                          lambda: labels.contiguous(), optimizer, group, droppath)
+                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps)
 
-    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath):
+    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
-        (called inside the step, on ``dev``)."""
+        (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one."""
         model = self._model()
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
         if not hasattr(model.head, "weight"):
@@ -480,9 +496,14 @@ class CaraEngine:
             from .dist import world_size
             fp16 = self.precision == "fp16"
             gv = self._grad_buffers(model, dev)
-            check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(self._loss_buf), ptr(self._dlogits),
-                                                    B, ncls, C.c_float(1.0 / world_size(group)), ptr(self._amp(dev)) if fp16 else None,
-                                                    ptr(gv["_found_inf"]) if fp16 else None, stream(dev)), "cara_cross_entropy_ex")
+            tail = (B, ncls, C.c_float(1.0 / world_size(group)), ptr(self._amp(dev)) if fp16 else None,
+                    ptr(gv["_found_inf"]) if fp16 else None, stream(dev))
+            if mix is None and smoothing == 0.0:
+                check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(self._loss_buf), ptr(self._dlogits), *tail),
+                      "cara_cross_entropy_ex")
+            else:
+                check(self._lib().cara_cross_entropy_mix(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(self._loss_buf),
+                                                         ptr(self._dlogits), *tail), "cara_cross_entropy_mix")
             self._run_backward(self._dlogits, droppath, hw, cp, prescaled=True)
             self._apply_gradients(optimizer, group, prescaled=True)
         return self._loss_buf[0]
@@ -514,13 +535,18 @@ class CaraEngine:
             raise CaraError("boxes need a model that states its input size (patch_embed.img_size)")
         return img
 
-    def _resident_args(self, split, rows, boxes=None):
+    def _resident_args(self, split, rows, boxes=None, mix=None):
         model = self._model()
         box_msg = "boxes must be a contiguous int32 [batch, 5] tensor (x0, y0, w, h, flip) on the model's device"
+        mix_msg = ("mix must be a contiguous int32 [batch, 8] tensor (partner, cx0, cy0, cw, ch, blend bits, target bits, 0) on the "
+                   "model's device")
         # (what a box table is, before where it lives: a host-made table of the wrong type is refused as such)
         if boxes is not None and (not torch.is_tensor(boxes) or boxes.dtype != torch.int32 or boxes.ndim != 2 or boxes.shape[1] != 5
                                   or not boxes.is_contiguous()):
             raise CaraError(box_msg)
+        if mix is not None and (not torch.is_tensor(mix) or mix.dtype != torch.int32 or mix.ndim != 2 or mix.shape[1] != 8
+                                or not mix.is_contiguous()):
+            raise CaraError(mix_msg)
         dev = model.head.weight.device if hasattr(model.head, "weight") else None
         if dev is None:
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
@@ -536,14 +562,15 @@ class CaraEngine:
             raise CaraError("rows must be a contiguous int64 [batch] tensor on the model's device")
         if boxes is not None and (boxes.device != dev or boxes.shape[0] != rows.shape[0]):
             raise CaraError(box_msg)
+        if mix is not None and (mix.device != dev or mix.shape[0] != rows.shape[0]):
+            raise CaraError(mix_msg)
         return model, dev
 
-    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None):
+    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None):
         model = self._model()
         dev = rows.device
         with torch.cuda.device(dev):
-            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev,
-                                        resident=(split, rows) if boxes is None else (split, rows, boxes))
+            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix))
 
     def _gather_labels(self, split, rows):
         dev, B = rows.device, rows.shape[0]
@@ -557,7 +584,8 @@ class CaraEngine:
                                              stream(dev)), "cara_gather_labels")
         return buf
 
-    def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None):
+    def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
+                            mix=None, label_smoothing: float = 0.0):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -566,21 +594,27 @@ class CaraEngine:
         ``boxes`` (device int32 [batch, 5] = (x0, y0, w, h, flip) in the split's pixels, e.g. ``data.RandomResizedCropFlip.draw``):
         sample ``i`` is the bilinear resize of that box of image ``rows[i]`` to the model's input size, flipped where ``flip`` is
         non-zero (``cara_vit_forward_u8_rows_crop``); the split's pixels may then be [N,3,Hs,Ws] of any size.  A box that is not
-        inside the image is not read either: a zero image, counted like a bad row."""
-        _, dev = self._resident_args(split, rows, boxes)
-        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes),
-                          lambda: self._gather_labels(split, rows), optimizer, group, droppath)
+        inside the image is not read either: a zero image, counted like a bad row.
+        ``mix`` (device int32 [batch, 8], e.g. ``data.MixupCutmix.draw``): Mixup / CutMix by index -- sample ``i`` is blended with,
+        or gets a rectangle of, the unmixed sample ``mix[i][0]`` of the same batch (``cara_vit_forward_u8_rows_mix``; with or without
+        ``boxes``) and is trained on both labels (``cara_cross_entropy_mix``, ``data.soft_target``).  A table entry the kernel
+        refuses -- ``data.check_mix`` -- gives a zero image, counted like a bad row.  ``label_smoothing`` as in ``train_step``.
+        Without either, the step is the one it was."""
+        eps = self._smoothing(label_smoothing)
+        _, dev = self._resident_args(split, rows, boxes, mix)
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix),
+                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps)
 
-    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None):
+    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None):
         """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``
-        as in ``train_step_resident`` (a centre-cropped evaluation by hand)"""
-        model, dev = self._resident_args(split, rows, boxes)
+        and ``mix`` as in ``train_step_resident`` (a centre-cropped evaluation by hand)"""
+        model, dev = self._resident_args(split, rows, boxes, mix)
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
         self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, model.head.weight, model.head.bias, cp, False, boxes)
+            return self._forward_rows(split, rows, droppath, model.head.weight, model.head.bias, cp, False, boxes, mix)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):

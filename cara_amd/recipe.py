@@ -110,28 +110,39 @@ class GraphedTrainStep:
     The resident form ``step(split, rows)`` captures ``train_step_resident``: one graph per (split, shape of ``rows``, mode), whose
     only static input is the index vector -- 8 bytes per sample are copied per step, no image.  ``step(split, (rows, boxes))``
     captures the augmented step (``train_step_resident(..., boxes=)``): one graph per (split, shapes, mode) again, whose static
-    inputs are the index vector and the box table -- both copied before every replay, 28 bytes per sample."""
+    inputs are the index vector and the box table -- both copied before every replay, 28 bytes per sample.
+    ``step(split, (rows, boxes_or_None, mix))`` captures the mixed step (``train_step_resident(..., mix=)``) the same way: the
+    Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.  ``label_smoothing`` is the steps' (all
+    forms); it is part of every graph's key."""
 
-    def __init__(self, engine, optimizer):
+    def __init__(self, engine, optimizer, label_smoothing: float = 0.0):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
         self.eng, self.opt = engine, optimizer
+        self.label_smoothing = engine._smoothing(label_smoothing) if label_smoothing else 0.0
         self._graphs = {}
+
+    def _kw(self):
+        # (a step without smoothing is called exactly as before)
+        return {"label_smoothing": self.label_smoothing} if self.label_smoothing else {}
 
     def __call__(self, x, y, group=None):
         """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector, or
-        ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table"""
+        ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table, or ``(split, (rows, boxes_or_None, mix))``:
+        with a device int32 [batch, 8] mix table too"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
         resident = hasattr(x, "pixels")
         if resident and isinstance(y, (tuple, list)):
-            return self._call_boxes(x, y[0], y[1], group)
-        step = eng.train_step_resident if resident else eng.train_step
+            return self._call_tables(x, y[0], y[1], y[2] if len(y) > 2 else None, group)
+        kw = self._kw()
+        step = (lambda a, b, opt, group=None: eng.train_step_resident(a, b, opt, group=group, **kw)) if resident else \
+            (lambda a, b, opt, group=None: eng.train_step(a, b, opt, group=group, **kw))
         self.opt.advance()
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(x, y, self.opt, group=group)
         # (the split itself is part of a resident key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
-        key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision)
+        key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision, self.label_smoothing)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -161,22 +172,30 @@ class GraphedTrainStep:
         gr.replay()
         return loss
 
-    def _call_boxes(self, split, rows, boxes, group):
-        """the resident form through crop boxes: warm, capture, replay as above, with two static inputs"""
+    def _call_tables(self, split, rows, boxes, mix, group):
+        """the resident form through crop boxes and / or a mix table: warm, capture, replay as above, with two or three static
+        inputs"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
-        eng._resident_args(split, rows, boxes)     # (refused here, not inside a capture)
+        eng._resident_args(split, rows, boxes, mix)     # (refused here, not inside a capture)
         self.opt.advance()
+        tables = [t for t in (boxes, mix) if t is not None]
+
+        def step(rs, ts):
+            ts = list(ts)
+            return eng.train_step_resident(split, rs, self.opt, group=group, boxes=ts.pop(0) if boxes is not None else None,
+                                           **({"mix": ts.pop(0)} if mix is not None else {}), **self._kw())
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
-            return eng.train_step_resident(split, rows, self.opt, group=group, boxes=boxes)
-        key = (("rows+boxes", split, tuple(rows.shape), tuple(boxes.shape)), bool(model.training), eng.precision)
+            return step(rows, tables)
+        key = (("rows+boxes" if mix is None else "rows+boxes+mix", split, tuple(rows.shape), boxes is not None and tuple(boxes.shape),
+                mix is not None and tuple(mix.shape)), bool(model.training), eng.precision, self.label_smoothing)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
-            return eng.train_step_resident(split, rows, self.opt, group=group, boxes=boxes)
+            return step(rows, tables)
         dev = rows.device
         if ent == "warm":
-            rs, bs = rows.clone(), boxes.clone()
+            rs, bs = rows.clone(), tuple(t.clone() for t in tables)
             torch.cuda.synchronize(dev)
             gr = torch.cuda.CUDAGraph()
             gen = eng._device_generator(dev)
@@ -186,12 +205,13 @@ class GraphedTrainStep:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 with torch.cuda.graph(gr, stream=side):
-                    loss = eng.train_step_resident(split, rs, self.opt, group=group, boxes=bs)
+                    loss = step(rs, bs)
             torch.cuda.current_stream(dev).wait_stream(side)
-            ent = self._graphs[key] = (gr, split, (rs, bs), loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
-        gr, _, (rs, bs), loss = ent[:4]
+            ent = self._graphs[key] = (gr, split, (rs, *bs), loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
+        gr, _, (rs, *bs), loss = ent[:4]
         rs.copy_(rows)
-        bs.copy_(boxes)
+        for static, t in zip(bs, tables):
+            static.copy_(t)
         gr.replay()
         return loss
 
@@ -199,7 +219,7 @@ class GraphedTrainStep:
 def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[Callable[[], Iterable]] = None,
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
         on_eval: Optional[Callable[[int, float], None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
-        graph: bool = False, eval_mode: str = "reference", feed: str = "batches"):
+        graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -224,12 +244,17 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     normalised fp32 batch.  An index outside the split is counted on the device, not read; the count is looked at where the
     evaluation epochs read from the device anyway and once more after the last epoch, and a non-zero one raises.
     A ``rows_of`` that yields ``(rows, boxes)`` pairs (``train_rows(..., augment=data.RandomResizedCropFlip(...))``) trains
-    through a crop box per sample (``train_step_resident(..., boxes=)``); a box outside its image is counted like a bad row."""
+    through a crop box per sample (``train_step_resident(..., boxes=)``); a box outside its image is counted like a bad row.
+    One that yields ``(rows, boxes_or_None, mix)`` triples (``train_rows(..., mix=data.MixupCutmix(...))``) trains with Mixup /
+    CutMix by index (``train_step_resident(..., mix=)``); a mix entry the kernel refuses is counted like a bad row too.
+    ``label_smoothing`` in [0, 1): every step's loss is the smoothed cross-entropy (both feeds)."""
     if eval_mode not in ("reference", "sharded"):
         raise CaraError(f"eval_mode must be 'reference' or 'sharded', not {eval_mode!r}")
     if feed not in ("batches", "resident"):
         raise CaraError(f"feed must be 'batches' or 'resident', not {feed!r}")
     from . import dist as cdist
+    eng = model._cara_engine
+    smooth = {"label_smoothing": eng._smoothing(label_smoothing)} if label_smoothing else {}
     model.train()
     params = trainable_parameters(model)
     if cdist.world_size(group) > 1:
@@ -243,8 +268,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     from .optim import AdamW
     opt = AdamW(params, lr=lr, weight_decay=weight_decay, capturable=graph)
     sched = CosineLRScheduler(opt, t_initial=100, warmup_t=10, lr_min=1e-5, warmup_lr_init=1e-6, decay_rate=0.1)
-    eng = model._cara_engine
-    gstep = GraphedTrainStep(eng, opt) if graph else None
+    gstep = GraphedTrainStep(eng, opt, **smooth) if graph else None
     best = 0.0
     if feed == "resident":
         split, rows_of = train_batches
@@ -252,19 +276,24 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
 
         def step(split, rows, opt, group=None):
             if isinstance(rows, (tuple, list)):
+                if len(rows) > 2:
+                    rows, boxes, mix = rows
+                    return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, mix=mix, **smooth)
                 rows, boxes = rows
-                return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes)
-            return eng.train_step_resident(split, rows, opt, group=group)
+                return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **smooth)
+            return eng.train_step_resident(split, rows, opt, group=group, **smooth)
     else:
-        step = eng.train_step
+        def step(x, y, opt, group=None):
+            return eng.train_step(x, y, opt, group=group, **smooth)
 
     def check_rows(upto):
         # (data parallel: a rank that raised alone would leave the others waiting in the next all-reduce.  train_rows range-checks
         # an epoch's indices on the host before it uploads them, on every rank, so only a hand-made feed can get here)
         bad = eng.resident_bad_rows() if feed == "resident" else 0
         if bad:
-            raise CaraError(f"fit: {bad} row index(es) outside the training split (or crop boxes outside their image) reached the "
-                            f"device up to epoch {upto}")
+            raise CaraError(f"fit: {bad} row index(es) outside the training split (or crop boxes outside their image, or mix entries "
+                            f"with a partner outside the batch, a rectangle outside the output or a weight outside [0, 1]) reached "
+                            f"the device up to epoch {upto}")
     for epoch in range(epochs):
         for x, y in train_batches(epoch):
             if gstep is not None:

@@ -321,6 +321,21 @@ int cara_im2col_patches_u8_rows(const unsigned char* pixels, int n_split, const 
 int cara_im2col_patches_u8_rows_crop(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
                                      const int* boxes, const float* mean, const float* std, void* patches, int* bad, int B,
                                      int C, int Hi, int Wi, int p, void* stream);
+/* cara_im2col_patches_u8_rows_crop with Mixup / CutMix by index: mix device int32 [B,8], row b = (partner, cx0, cy0, cw, ch,
+ * blend, target, 0).  partner in [0, B) (b itself allowed): the sample whose UNMIXED value at the same output position -- through
+ * rows[partner] and boxes[partner], its flip included -- is mixed in.  (cx0, cy0, cw, ch): the CutMix rectangle in output pixels;
+ * inside it the pixel is the partner's; cw == 0 or ch == 0: no rectangle.  blend: the bits of an fp32 m in [0, 1]; outside the
+ * rectangle the pixel is a + m (b - a) in fp32 on the un-normalised 0..255 values (a the sample's own bilinear value, b the
+ * partner's; exact at m == 0), then (v / 255 - mean[c]) / std[c] and the one rounding to 16 bits.  target: the bits of an fp32 t,
+ * the weight of the partner's label -- read by cara_cross_entropy_mix only.  The last word is written as 0 and not read.
+ * boxes may be NULL: every sample reads its whole image, and Hs == Hi, Ws == Wi is asked.  A sample gets zero patch rows and
+ * is counted once in *bad (may be NULL) when its own or its partner's row or box is bad (by the rules above), its partner is
+ * outside [0, B), its rectangle is not inside the output (cx0, cy0, cw, ch >= 0, cx0+cw <= Wi, cy0+ch <= Hi) or its m is not in
+ * [0, 1] (a NaN is not); none of these values is used before it is checked.  An identity table (partner = b, the rest 0)
+ * gives bit for bit the patch rows of cara_im2col_patches_u8_rows_crop, or of cara_im2col_patches_u8_rows without boxes.  */
+int cara_im2col_patches_u8_rows_mix(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                    const int* boxes, const int* mix, const float* mean, const float* std, void* patches,
+                                    int* bad, int B, int C, int Hi, int Wi, int p, void* stream);
 /* out[i] = labels[rows[i]] (device int64 [B] each; labels int64 [n_split]); a row outside [0, n_split) is not
  * dereferenced: it gives 0 and is counted in *bad (device int, may be NULL)                                    */
 int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
@@ -341,6 +356,16 @@ int cara_cross_entropy(const float* logits, const int64_t* labels, float* loss, 
  * UNSCALED mean loss.                                                                                                  */
 int cara_cross_entropy_ex(const float* logits, const int64_t* labels, float* loss, float* dlogits,
                           int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream);
+/* cara_cross_entropy_ex against a soft target: label smoothing (smoothing = eps in [0, 1): torch's label_smoothing) and the
+ * partner's label of a Mixup / CutMix table (mix as in cara_im2col_patches_u8_rows_mix: partner = mix[b][0], t = the fp32 whose
+ * bits mix[b][6] holds; mix NULL: t = 0 for every sample) -- timm's mixup_target.  labels are the samples' OWN classes:
+ *   ya = labels[b], yb = labels[partner],  q_c = (1 - eps) ((1 - t) [c == ya] + t [c == yb]) + eps / C,
+ *   loss[1 + b] = (lse_b - sum_c q_c l_c) / B,  loss[0] = their sum (unscaled),  dlogits = (softmax - q) / B * dscale * loss scale.
+ * eps == 0 with t == 0 (with a table or without) gives bit for bit what cara_cross_entropy_ex gives.  ya or yb outside [0, C), a
+ * partner outside [0, B) or a t outside [0, 1] (or NaN) is never used as an index: that sample's term, its dlogits row and
+ * loss[0] are NaN, the other samples unaffected.  smoothing outside [0, 1): CARA_E_ARG, nothing launched.  found_inf is cleared. */
+int cara_cross_entropy_mix(const float* logits, const int64_t* labels, const int* mix, float smoothing, float* loss,
+                           float* dlogits, int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream);
 /* Scoring on the device (test() of vit_cp.py:73-82 without its per-batch host read): for the first n_valid <= B rows of
  * logits fp32 [B,classes] (row stride ldl floats) and labels int64 [B], ADD into `state`, five 64-bit words
  * (cara_eval_state_bytes() = 40 bytes, 8-byte aligned, zeroed by the caller before the first batch):
@@ -568,6 +593,13 @@ int cara_vit_forward_u8_rows_crop(const cara_geom* g, const cara_vit_shape* s, c
                                   int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const float* mean,
                                   const float* std, const float* droppath, void* workspace, float* logits, int* bad,
                                   void* stream);
+/* cara_vit_forward_u8_rows_crop with a Mixup / CutMix table (mix device int32 [B,8], cara_im2col_patches_u8_rows_mix; boxes may
+ * be NULL on a split of the model's size): only the patch rows differ; workspace and backward unchanged.                    */
+int cara_vit_forward_u8_rows_mix(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                 const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                 int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const int* mix,
+                                 const float* mean, const float* std, const float* droppath, void* workspace, float* logits,
+                                 int* bad, void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,

@@ -15,7 +15,11 @@ not part of bench.py.
 --augment runs other legs instead (the lines above are then not printed): the eager resident step as it is, the same step through
 crop boxes (data.RandomResizedCropFlip on a 256-px split of the same images count: "resize 256, random-resized-crop 224"), and the
 two patch-row kernels alone (cara_im2col_patches_u8_rows / cara_im2col_patches_u8_rows_crop at the step's output shape, device
-events around --kernel-launches back-to-back launches), all interleaved round by round."""
+events around --kernel-launches back-to-back launches), all interleaved round by round.
+
+--mix adds to the --augment legs, interleaved with them in the same process: the augmented step with Mixup / CutMix tables
+(data.MixupCutmix) and label smoothing 0.1, and cara_im2col_patches_u8_rows_mix alone on an identity table, a Mixup table and a
+CutMix table."""
 import argparse
 import json
 import os
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"])
     ap.add_argument("--legs", default="eager,graph")
     ap.add_argument("--augment", action="store_true", help="time the augmented resident step and the two patch-row kernels instead")
+    ap.add_argument("--mix", action="store_true", help="the --augment legs plus the mixed step and the mix kernel alone")
     ap.add_argument("--source", type=int, default=256, help="--augment: side of the split the boxes are drawn on")
     ap.add_argument("--kernel-launches", type=int, default=200, help="--augment: launches per timed kernel window")
     args = ap.parse_args()
@@ -73,7 +78,7 @@ def main():
             yield from of_epoch(epoch)
             epoch += 1
 
-    if args.augment:
+    if args.augment or args.mix:
         return augment_legs(args, eng, opt, split, feeder, dev, gd)
     gstep = GraphedTrainStep(eng, opt)
 
@@ -137,7 +142,7 @@ def main():
 
 def augment_legs(args, eng, opt, split, feeder, dev, gd):
     from cara_amd import _lib as L
-    from cara_amd.data import IMAGENET_MEAN, IMAGENET_STD, RandomResizedCropFlip, ResidentSplit
+    from cara_amd.data import IMAGENET_MEAN, IMAGENET_STD, MixupCutmix, RandomResizedCropFlip, ResidentSplit, identity_mix
     S, B = args.source, args.batch
     big = ResidentSplit.from_tensors(torch.randint(0, 256, (args.images, 3, S, S), generator=gd, dtype=torch.uint8, device=dev), split.labels)
     aug = RandomResizedCropFlip(224)
@@ -167,6 +172,25 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
         L.check(lib.cara_im2col_patches_u8_rows_crop(L.ptr(big.pixels), len(big), S, S, L.ptr(rows), L.ptr(boxes), L.ptr(mean), L.ptr(std),
                                                      L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st), "cara_im2col_patches_u8_rows_crop")
     kernels = {"kernel/u8_rows": k_rows, f"kernel/u8_rows_crop{S}": k_crop}
+    if args.mix:
+        def mixed(item):
+            opt.advance()
+            return eng.train_step_resident(big, item[0], opt, boxes=item[1], mix=item[2], label_smoothing=0.1)
+        steps[f"eager/resident+crop{S}+mix"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224))), mixed)
+        rev = B - 1 - torch.arange(B, dtype=torch.int32)
+        half = torch.tensor(0.5).view(torch.int32).item()
+        mixup, cutmix = identity_mix(B), identity_mix(B)
+        mixup[:, 0], mixup[:, 5], mixup[:, 6] = rev, half, half
+        cutmix[:, 0], cutmix[:, 6] = rev, half
+        cutmix[:, 1:5] = torch.tensor([33, 33, 158, 158], dtype=torch.int32)       # half of the 224 x 224 output, on no tile edge
+        for name, t in (("identity", identity_mix(B)), ("mixup", mixup), ("cutmix", cutmix)):
+            t = t.to(dev)
+
+            def k_mix(t=t):
+                L.check(lib.cara_im2col_patches_u8_rows_mix(L.ptr(big.pixels), len(big), S, S, L.ptr(rows), L.ptr(boxes), L.ptr(t), L.ptr(mean),
+                                                            L.ptr(std), L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st),
+                        "cara_im2col_patches_u8_rows_mix")
+            kernels[f"kernel/u8_rows_mix{S}/{name}"] = k_mix
 
     def step_window(name, n):
         feed, step = steps[name]
@@ -203,10 +227,12 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
         for name, ts in table.items():
             res[name] = {unit: [round(t, 4) for t in ts], "median": round(statistics.median(ts), 4), "min": round(min(ts), 4),
                          "max": round(max(ts), 4), "spread": round(max(ts) - min(ts), 4)}
-            print(f"{name:26s} {statistics.median(ts):9.4f} {unit.split('_')[0]} (min {min(ts):.4f}, max {max(ts):.4f})")
+            print(f"{name:32s} {statistics.median(ts):9.4f} {unit.split('_')[0]} (min {min(ts):.4f}, max {max(ts):.4f})")
     a, b = res["eager/resident"], res[f"eager/resident+crop{S}"]
     res["crop_minus_plain_ms"] = round(b["median"] - a["median"], 4)
     res["crop_not_slower_within_plain_spread"] = bool(b["median"] - a["median"] <= a["spread"])
+    if args.mix:
+        res["mix_minus_crop_ms"] = round(res[f"eager/resident+crop{S}+mix"]["median"] - b["median"], 4)
     res["last_loss"] = last
     res["bad_rows"] = eng.resident_bad_rows()
     print(json.dumps(res))
