@@ -303,9 +303,11 @@ def gemm(A, B, out, *, epi, bias=None, A2=None, B2=None, C2=None, aux=None, rows
 
 
 def pack_b_panels(B):
-    """bf16 [N, K] -> its K-panel-major image [K/32, N, 32] (cara_gemm_args::Bp)."""
+    """16-bit [N, K] of the active build's operand type (`using`) -> its K-panel-major image [K/32, N, 32] (cara_gemm_args::Bp)."""
     N, K = B.shape
-    out = torch.empty(K // 32, N, 32, dtype=torch.bfloat16, device=B.device)
+    if B.dtype != act_dtype():
+        raise CaraError(f"pack_b_panels: operand is {B.dtype}, the active build takes {act_dtype()}")
+    out = torch.empty(K // 32, N, 32, dtype=act_dtype(), device=B.device)
     check(lib().cara_pack_b_panels(ptr(B), B.stride(0), N, K, ptr(out), stream()), "cara_pack_b_panels")
     return out
 

@@ -376,7 +376,7 @@ __device__ __forceinline__ void gemm32_body(const cara_gemm_args& p, const int t
     // interior wave tiles: the epilogue's input operand requested a pass group ahead (gemm_epilogue.h)
     const int mw = m0 + wr * (MI * 16), nw = n0 + wc * 64;
     const bool ok = mw + MI * 16 <= p.M && nw + 64 <= p.N && (p.ldc & 7) == 0 && coff == 0 && (EPI != CARA_EPI_MULH || !p.bias) &&
-                    (EPI != CARA_EPI_RESID || !p.rowscale || p.rows_per_sample >= MI * 16) && (!p.bias || (nw & 3) == 0);
+                    (EPI != CARA_EPI_RESID || !p.rowscale || p.rows_per_sample >= MI * 16) && (!p.bias || (EPI == CARA_EPI_RESID && (nw & 3) == 0));   // (only the _RESID form adds a bias)
     if (ok) {   // wave-uniform
       epilogue_interior_aux<EPI, MI, 1>(p, acc, stg, mw, nw, lane);
       STAMP_END();
@@ -610,7 +610,7 @@ __device__ __forceinline__ void gemm32ft_body(const cara_gemm_args& p, const int
   if constexpr (EPI == CARA_EPI_RESID || EPI == CARA_EPI_DGELU) {
     const int mw = m0 + wr * 64, nw = n0 + wc * 64;
     const bool ok = mw + 64 <= p.M && nw + 64 <= p.N && (p.ldc & 7) == 0 &&
-                    (EPI == CARA_EPI_DGELU || !p.rowscale || p.rows_per_sample >= 64) && (!p.bias || (nw & 3) == 0);
+                    (EPI == CARA_EPI_DGELU || !p.rowscale || p.rows_per_sample >= 64) && (!p.bias || (EPI == CARA_EPI_RESID && (nw & 3) == 0));   // (only the _RESID form adds a bias)
     if (ok) {   // wave-uniform
       epilogue_interior_aux<EPI, 4, 2>(p, acc, stg, mw, nw, lane);
       return;

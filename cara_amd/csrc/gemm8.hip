@@ -468,7 +468,7 @@ __device__ __forceinline__ void g8_tile(const cara_gemm_args& p, const int tiles
   }
   float* stg = reinterpret_cast<float*>(wstg);
   if constexpr (EPI == CARA_EPI_RESID || EPI == CARA_EPI_DGELU) {
-    const bool ok = interior && (EPI == CARA_EPI_DGELU || !p.rowscale || p.rows_per_sample >= RT * 16) && (!p.bias || (nw & 3) == 0);
+    const bool ok = interior && (EPI == CARA_EPI_DGELU || !p.rowscale || p.rows_per_sample >= RT * 16) && (!p.bias || (EPI == CARA_EPI_RESID && (nw & 3) == 0));   // (only the _RESID form adds a bias)
     if (ok) {
       epilogue_interior_aux<EPI, RT, 1>(p, acc, stg, mw, nw, lane);
       return;

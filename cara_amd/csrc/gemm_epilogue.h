@@ -533,6 +533,13 @@ __device__ __forceinline__ void epilogue_mulh_riders(const cara_gemm_args& p, co
           o = valid ? o : 0.f;
           hh[k] = valid ? hh[k] : (bf16)0.f;
         }
+#ifdef CARA_F16_OPERANDS
+        // IEEE-half build: without the select of the edge form the compiler folds product + conversion into v_fma_mixlo_f16 (ONE
+        // rounding of the exact product), while the launch without riders (epilogue_interior_aux, epilogue_rows) keeps v_mul_f32 +
+        // v_cvt (two): C differed from that launch where the fp32 product lands on a half tie, and a launch with riders writes the
+        // C of the launch without them, bit for bit (tests/test_gemm_contract_gpu.py).  The product is an fp32 value everywhere:
+        asm volatile("" : "+v"(o));
+#endif
         out[k] = (bf16)o;
       }
       if (valid) *reinterpret_cast<bf16x8*>(c_b + (size_t)(unsigned)((unsigned)r * cstep + off_cp)) = out;

@@ -44,3 +44,14 @@ SMALL_CAPS = {"ln_y": _FAMILY_CAPS, "ln_dyb": 0.02, "head_xn16": _FAMILY_CAPS, "
 
 def logits_ok(r_ref: float, r_model: float) -> bool:
     return r_ref <= LOGITS_ABS and r_ref <= LOGITS_VS_MODEL * max(r_model, MODEL_FLOOR)
+
+# The GEMM family (oracle/gemm_model.py), per 16-bit output kind: the share of a tensor's elements that may be the NEIGHBOUR of the
+# model's rounded value, taken over the elements whose derived term is below a quarter of their own 16-bit step.  Elements above
+# that -- the cancelling rows (|acc| << sum |a b|: gamma(K) sum |a b| is many steps of a sum near zero), the GELU's negative tail
+# (a step of h = -1e-6 is 1e-8, the pre-activation's term 1e-6), sums that happen to land near zero -- have NO cap: the interval
+# alone holds them, as it does the offset LayerNorm rows above.  ONE neighbour case never breaks a cap (M = 1, N = 8: 12 %).
+# Chosen as SMALL_CAPS: the fp32 other-order restatement's largest share over all host cases and both builds
+# (tests/test_gemm_model.py, `python -m tests.test_gemm_model`; table in docs/findings/gemm_contract.md section 2), doubled and rounded
+# up to the next of 0.5 %, 1 %, 2 %; never fitted to a device.  Measured: gelu_h 0.0030 (fp16; bf16 none) -> 1 %; dgelu 0.0010
+# (fp16; bf16 0.0006) -> 0.5 %; bf16, T 0.0001 (fp16), gelu_u, gelu_dg, mulh none -> 0.5 %.
+GEMM_CAPS = {"bf16": 0.005, "gelu_h": 0.01, "gelu_u": 0.005, "gelu_dg": 0.005, "dgelu": 0.005, "mulh": 0.005, "T": 0.005}
