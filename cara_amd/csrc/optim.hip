@@ -9,6 +9,8 @@
 //   p   -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 // The tensors come BY VALUE in the kernel arguments (pointers and sizes of up to 32 tensors, 1.3 KiB): no table in device
 // memory, nothing to upload when a learning rate changes.
+// Beside it: the loss-scale update of the IEEE-half build, and gradient accumulation and global-norm clipping over the step's one
+// flat gradient buffer (cara_grad_accumulate, cara_grad_clip).
 #include "common.h"
 
 namespace {
@@ -76,6 +78,118 @@ __global__ void amp_update_kernel(float* __restrict__ st, const float* __restric
   }
 }
 
+// ---- gradient accumulation and global-norm clipping over ONE flat fp32 buffer (cara_hip.h: cara_grad_accumulate, cara_grad_clip) ----
+// Both are latency-bound launches over 0.5 MB (rank 16) to some tens of MB: 16-byte accesses, few resident workgroups, no atomics.
+
+// dst = a + b (b == NULL: dst = a), one fp32 rounding per element.  Elements [head, head + 4 nvec) go as float4 (the host passes
+// nvec > 0 only when all pointers share dst's residue mod 16), the rest -- at most 3 + 3 elements then, everything otherwise -- one by
+// one.  An element is read and written by the same thread, so dst may be a or b.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* dst, const float* a, const float* b, size_t n, size_t head,
+                                                              size_t nvec) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t v = tid; v < nvec; v += stride) {
+    const size_t i = head + 4 * v;
+    f32x4 x = *reinterpret_cast<const f32x4*>(a + i);
+    if (b) {
+      const f32x4 y = *reinterpret_cast<const f32x4*>(b + i);
+      x += y;
+    }
+    *reinterpret_cast<f32x4*>(dst + i) = x;
+  }
+  const size_t body_end = head + 4 * nvec, nedge = head + (n - body_end);
+  for (size_t e = tid; e < nedge; e += stride) {
+    const size_t i = e < head ? e : body_end + (e - head);
+    dst[i] = b ? a[i] + b[i] : a[i];
+  }
+}
+
+// THE REDUCTION TREE of cara_grad_clip (tests/optim_model.py restates it and derives the test bound from it).
+// A chunk is CLIP_CHUNK = 8192 consecutive elements; 256 threads (4 waves) per workgroup.
+//   1. thread t: acc = 0; for j = 0 .. 7, for c = 0 .. 3: acc = acc + g[8192 chunk + 4 (256 j + t) + c]^2  (elements past n add 0):
+//      one rounding per square, 32 sequential additions (the first one, to 0, is exact: 31);
+//   2. the wave's 64 accumulators: the butterfly of wave_sum, lanes 32, 16, 8, 4, 2, 1 apart: 6 additions;
+//   3. the four wave sums, left to right ((w0 + w1) + w2) + w3: 3 additions                      -> partial[chunk]   (launch 1)
+//   4. thread t of EVERY workgroup of launch 2: acc = 0; for q = t, t + 256, ... < chunks: acc = acc + partial[q]
+//      (ceil(chunks / 256) sequential additions), then steps 2 and 3 again: 6 + 3 additions      -> total, the same bits everywhere
+// Longest path: 31 + 6 + 3 + ceil(chunks / 256) + 6 + 3 additions, one rounding per square before them, one sqrtf after.
+// Every product and sum is a single IEEE operation: these kernels are written with plain operators under `fp contract(off)` (hipcc's
+// default fuses acc + x * x into an fma, through __fmul_rn / __fadd_rn too, and the square would lose its own rounding).
+constexpr int CLIP_CHUNK = 8192;
+constexpr int CLIP_MAX_GRID = 2048;   // launch 2 walks the chunks grid-strided above this many (n > 16.7 M elements)
+
+__device__ __forceinline__ float clip_block_sum(float acc, float* lds) {
+#pragma clang fp contract(off)
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  const float s = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+  __syncthreads();
+  return s;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, size_t n, float* partial) {
+#pragma clang fp contract(off)
+  __shared__ float lds[4];
+  const size_t base = (size_t)blockIdx.x * CLIP_CHUNK;
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const size_t i = base + 4 * ((size_t)j * 256 + threadIdx.x);
+    float x[4] = {0.f, 0.f, 0.f, 0.f};
+    if (VEC && i + 4 <= n) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+      x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (i + c < n) x[c] = g[i + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float sq = x[c] * x[c];
+      acc = acc + sq;
+    }
+  }
+  const float s = clip_block_sum(acc, lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_scale_kernel(float* g, size_t n, size_t chunks, float max_norm, const float* partial,
+                                                         const float* found_inf, float* out) {
+#pragma clang fp contract(off)
+  __shared__ float lds[4];
+  float acc = 0.f;
+  for (size_t q = threadIdx.x; q < chunks; q += 256) acc = acc + partial[q];
+  const float norm = sqrtf(clip_block_sum(acc, lds));
+  // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (norm + 1e-6), clamped to at most 1 (a NaN stays a NaN, as torch.clamp's)
+  const float c = max_norm / (norm + 1e-6f);
+  const bool skip = found_inf && *found_inf != 0.f;   // the step is skipped: Inf x 0 must not put NaNs into the gradients
+  const float coef = skip ? 1.f : (c < 1.f ? c : (c == c ? 1.f : c));
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    out[0] = norm;
+    out[1] = coef;
+  }
+  if (coef == 1.f) return;                            // nothing to scale: the buffer is not written
+  for (size_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
+    const size_t base = chunk * CLIP_CHUNK;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const size_t i = base + 4 * ((size_t)j * 256 + threadIdx.x);
+      if (VEC && i + 4 <= n) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+        v *= coef;
+        *reinterpret_cast<f32x4*>(g + i) = v;
+      } else {
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4)
+          if (i + c4 < n) g[i + c4] = g[i + c4] * coef;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int cara_amp_update(float* state, const float* found_inf, float growth, float backoff, int interval, float max_scale,
@@ -97,6 +211,45 @@ extern "C" int cara_adamw_step(const cara_adamw_args* a, void* stream) {
   }
   if (chunks > 0x7fffffffu) return CARA_E_ARG;
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)chunks), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_grad_accumulate(float* dst, const float* a, const float* b, size_t n, void* stream) {
+  if (!dst || !a || n == 0 || ((uintptr_t)dst | (uintptr_t)a | (uintptr_t)b) % 4 != 0) return CARA_E_ARG;
+  const uintptr_t r = (uintptr_t)dst % 16;
+  size_t head = 0, nvec = 0;
+  if ((uintptr_t)a % 16 == r && (!b || (uintptr_t)b % 16 == r)) {
+    head = ((16 - r) % 16) / 4;
+    if (head > n) head = n;
+    nvec = (n - head) / 4;
+  }
+  const size_t edge = n - 4 * nvec, work = nvec > edge ? nvec : edge;
+  size_t grid = (work + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), dst, a, b, n, head,
+                     nvec);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" size_t cara_grad_clip_scratch_bytes(size_t n) {
+  if (n == 0 || n > ((size_t)1 << 31)) return 0;
+  return ((n + CLIP_CHUNK - 1) / CLIP_CHUNK) * sizeof(float);
+}
+
+extern "C" int cara_grad_clip(float* g, size_t n, float max_norm, float* scratch, const float* found_inf, float* out, void* stream) {
+  if (!g || !scratch || !out || n == 0 || n > ((size_t)1 << 31) || !(max_norm > 0.f) || (uintptr_t)g % 4 != 0) return CARA_E_ARG;
+  const size_t chunks = (n + CLIP_CHUNK - 1) / CLIP_CHUNK;                 // <= 2^18
+  const unsigned grid2 = (unsigned)(chunks < (size_t)CLIP_MAX_GRID ? chunks : (size_t)CLIP_MAX_GRID);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if ((uintptr_t)g % 16 == 0) {
+    hipLaunchKernelGGL(grad_sumsq_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, st, g, n, scratch);
+    hipLaunchKernelGGL(grad_scale_kernel<true>, dim3(grid2), dim3(256), 0, st, g, n, chunks, max_norm, scratch, found_inf, out);
+  } else {   // a buffer that is only 4-byte aligned: the same element-to-thread map and summation order with dword accesses
+    hipLaunchKernelGGL(grad_sumsq_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, st, g, n, scratch);
+    hipLaunchKernelGGL(grad_scale_kernel<false>, dim3(grid2), dim3(256), 0, st, g, n, chunks, max_norm, scratch, found_inf, out);
+  }
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }

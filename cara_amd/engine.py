@@ -412,11 +412,12 @@ class CaraEngine:
         model = self._model()
         return [getattr(model, "CP_" + n) for n in self.cp_fields] + [model.head.weight, model.head.bias]
 
-    def _apply_gradients(self, optimizer=None, group=None, prescaled=False):
+    def _apply_gradients(self, optimizer=None, group=None, prescaled=False, clip_grad=None):
         """Tail of a train step, shared by train_step and the CPU multi-process tests: bind ``p.grad`` of every
         trainable parameter to its view of the flat buffer, ONE all-reduce of that buffer when the group has more than
         one rank -- a plain SUM when the gradients were computed from a dlogits already divided by the world size
-        (``prescaled``: train_step), the mean otherwise -- and ``optimizer.step()``."""
+        (``prescaled``: train_step), the mean otherwise -- the global-norm clip when ``clip_grad`` is given, and
+        ``optimizer.step()``."""
         model = self._model()
         g = self._grad_views
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
@@ -426,6 +427,8 @@ class CaraEngine:
         # the only data-path collective of a step: one RCCL all-reduce over xGMI of the flat buffer
         from .dist import allreduce_mean_, allreduce_sum_
         (allreduce_sum_ if prescaled else allreduce_mean_)(self._flat_grad, group)
+        if clip_grad is not None:   # on the all-reduced buffer: every rank clips the same values by the same coefficient
+            self._clip_flat(clip_grad)
         if self.precision == "fp16" and self._flat_grad.is_cuda:
             found = g["_found_inf"]
             dev = found.device
@@ -449,8 +452,96 @@ class CaraEngine:
             raise CaraError(f"label_smoothing must be a number in [0, 1), not {label_smoothing!r}")
         return float(label_smoothing)
 
+    @staticmethod
+    def _max_norm(clip_grad) -> Optional[float]:
+        """``clip_grad``: None (no clip) or the max_norm of ``clip_grad_norm_``, a number > 0 (``inf`` only measures)"""
+        if clip_grad is None:
+            return None
+        if isinstance(clip_grad, bool) or not isinstance(clip_grad, (int, float)) or not (clip_grad > 0.0):   # (a NaN fails the comparison)
+            raise CaraError(f"clip_grad must be None or a number > 0, not {clip_grad!r}")
+        return float(clip_grad)
+
+    @staticmethod
+    def _window(accumulate):
+        """``accumulate``: None (every step is an optimiser step) or ``(i, k)``: micro-step ``i`` of a window of ``k``, 0 <= i < k"""
+        if accumulate is None:
+            return 0, 1
+        ok = isinstance(accumulate, (tuple, list)) and len(accumulate) == 2 \
+            and all(isinstance(v, int) and not isinstance(v, bool) for v in accumulate)
+        if not ok or not (accumulate[1] >= 1 and 0 <= accumulate[0] < accumulate[1]):
+            raise CaraError(f"accumulate must be (i, k) with integers 0 <= i < k, not {accumulate!r}")
+        return int(accumulate[0]), int(accumulate[1])
+
+    def _enter_window(self, i, k, B):
+        """Order and batch size of the micro-steps of a window, checked before anything is launched: i runs 0, 1, ... k - 1, every
+        micro-batch has the first one's size.  A refused call closes the window: the next one starts at 0."""
+        nxt, k0, B0 = self.__dict__.get("_win") or (0, k, B)
+        self._win = None
+        if i != nxt or (nxt > 0 and (k != k0 or B != B0)):
+            what = f"micro-step {nxt} of {k0} with batch size {B0}" if nxt > 0 else "micro-step 0"
+            raise CaraError(f"accumulate = ({i}, {k}) with batch size {B}: the window expects {what} "
+                            "(micro-steps come in order and share one batch size)")
+        if k > 1 and torch.cuda.is_current_stream_capturing():
+            raise CaraError("accumulate with k > 1 cannot be captured: the window spans several graph replays")
+        if i + 1 < k:
+            self._win = (i + 1, k, B)
+
+    def _accumulate_flat(self, i, k, dev):
+        """micro-step i of k > 1, after its backward: acc = flat (i == 0), acc += flat, and flat = acc + flat at the last one --
+        left to right in fp32, the found-inf word (the last element) along with the gradients"""
+        flat = self._flat_grad
+        acc = self.__dict__.get("_acc_grad")
+        if acc is None or acc.numel() != flat.numel() or acc.device != flat.device:
+            acc = self._acc_grad = torch.empty_like(flat)
+        dst, a, b = (acc, flat, None) if i == 0 else (acc, acc, flat) if i < k - 1 else (flat, acc, flat)
+        check(self._lib().cara_grad_accumulate(ptr(dst), ptr(a), ptr(b), flat.numel(), stream(dev)), "cara_grad_accumulate")
+
+    grad_norm = None   # device float [2] = (global L2 norm before the clip, coefficient applied) of the last clipped step
+
+    def _clip_flat(self, max_norm):
+        """cara_grad_clip over the gradient elements of the flat buffer (the found-inf word behind them stays out of the norm and
+        is, in fp16, what leaves an overflowed step's gradients untouched) -> ``grad_norm``; nothing is read on the host"""
+        flat = self._flat_grad
+        if not flat.is_cuda:
+            raise CaraError("clip_grad runs on the GPU only (no CPU path)")
+        dev, n = flat.device, flat.numel() - 1
+        bufs = self.__dict__.setdefault("_clip_bufs", {})   # per (device, size), never replaced: a captured step holds the addresses
+        got = bufs.get((dev, n))
+        if got is None:
+            nbytes = int(self._lib().cara_grad_clip_scratch_bytes(n))
+            if nbytes == 0:
+                raise CaraError(f"cara_grad_clip takes 1 .. 2^31 elements, not {n}")
+            got = bufs[(dev, n)] = (torch.empty(nbytes // 4, device=dev), torch.zeros(2, device=dev))
+        scratch, out = got
+        found = self._grad_views["_found_inf"] if self.precision == "fp16" else None
+        with torch.cuda.device(dev):
+            check(self._lib().cara_grad_clip(ptr(flat), n, max_norm, ptr(scratch), ptr(found), ptr(out), stream(dev)), "cara_grad_clip")
+        self.grad_norm = out
+        return out
+
+    def clip_grad_norm_(self, max_norm):
+        """``torch.nn.utils.clip_grad_norm_(trainable_parameters(), max_norm)`` for the autograd path (``model(x); loss.backward()``)
+        as two launches and no host read: -> the device tensor ``(norm, coef)``, which is ``grad_norm`` too.  Gradients that are
+        not the views of the flat buffer yet (autograd hands out copies) are moved into it and ``p.grad`` is bound to the views,
+        as after ``train_step``; like those, they are overwritten by the next backward -- ``zero_grad()`` before it.  Under
+        ``precision = "fp16"`` the gradients of an overflowed backward are left as they are.  Inside a train step use
+        ``train_step(..., clip_grad=max_norm)``: the clip then runs behind the all-reduce."""
+        max_norm = self._max_norm(max_norm)
+        if max_norm is None:
+            raise CaraError("clip_grad_norm_ needs a max_norm > 0")
+        params = self.trainable_parameters()
+        if self._flat_grad is None or any(p.grad is None for p in params):
+            raise CaraError("clip_grad_norm_ follows a backward: every trainable parameter must have a gradient")
+        g = self._grad_views
+        with torch.no_grad():
+            for n, p in zip(list(self.cp_fields) + ["head_w", "head_b"], params):
+                if p.grad.data_ptr() != g[n].data_ptr():
+                    g[n].copy_(p.grad)
+                    p.grad = g[n]
+            return self._clip_flat(max_norm)
+
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
-                   label_smoothing: float = 0.0):
+                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -458,7 +549,16 @@ class CaraEngine:
         scalar, local to this rank).  ``p.grad`` of every trainable parameter is a view of the flat
         buffer, so any torch optimizer consumes it unchanged.
         ``label_smoothing`` = eps in [0, 1): the loss is torch's ``cross_entropy(label_smoothing=eps)``
-        (``cara_cross_entropy_mix``; 0 runs ``cara_cross_entropy_ex`` as before)."""
+        (``cara_cross_entropy_mix``; 0 runs ``cara_cross_entropy_ex`` as before).
+        ``accumulate = (i, k)``: micro-step ``i`` of a window of ``k`` micro-batches of one size, called in order.  Each runs
+        forward, loss and backward with the loss divided by ``k`` as well; the flat buffers are summed left to right in fp32 in a
+        second buffer of the same layout (``cara_grad_accumulate``), and only the LAST micro-step runs the tail -- one all-reduce,
+        the clip, the loss-scale update, ``optimizer.step()`` -- on the sum.  Before it nothing is communicated and no parameter,
+        moment or loss scale changes; in fp16 an overflow in any micro-step skips the whole window once.  The returned loss is
+        the micro-batch's own mean.  ``k == 1`` (or None) is the step without a window.  Not under graph capture for ``k > 1``.
+        ``clip_grad = max_norm`` (> 0): ``torch.nn.utils.clip_grad_norm_`` over all trainable tensors behind the all-reduce and
+        before the optimiser (``cara_grad_clip``: two launches, no host read, bitwise the same on every rank); ``grad_norm`` then
+        holds the device tensor (norm before the clip, coefficient)."""
         eps = self._smoothing(label_smoothing)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
@@ -466,13 +566,16 @@ class CaraEngine:
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp),
-                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps)
+                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad)
 
-    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0):
+    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
-        (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one."""
+        (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one.
+        ``accumulate`` and ``clip_grad`` as in ``train_step``."""
         model = self._model()
+        win_i, win_k = self._window(accumulate)
+        max_norm = self._max_norm(clip_grad)
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
         if not hasattr(model.head, "weight"):
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
@@ -480,6 +583,7 @@ class CaraEngine:
         if hw.device != dev or any(t.device != dev for t in cp):
             raise CaraError("model parameters and images must be on the same device")
         self._refuse_fp16_unfactored()
+        self._enter_window(win_i, win_k, B)
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, B, dev)
@@ -491,12 +595,13 @@ class CaraEngine:
                 self._dlogits = torch.empty(B, ncls, device=dev)
             if self._dlogits.shape != logits.shape:
                 self._dlogits = torch.empty(B, ncls, device=dev)
-            # dlogits leaves the cross-entropy already divided by the world size (the all-reduce is then a plain SUM) and, in the
-            # IEEE-half build, multiplied by the loss scale; the same launch clears the step's found-inf word
+            # dlogits leaves the cross-entropy already divided by the world size (the all-reduce is then a plain SUM) -- and by the
+            # micro-steps of an accumulation window -- and, in the IEEE-half build, multiplied by the loss scale; the same launch
+            # clears the step's found-inf word
             from .dist import world_size
             fp16 = self.precision == "fp16"
             gv = self._grad_buffers(model, dev)
-            tail = (B, ncls, C.c_float(1.0 / world_size(group)), ptr(self._amp(dev)) if fp16 else None,
+            tail = (B, ncls, C.c_float(1.0 / (world_size(group) * win_k)), ptr(self._amp(dev)) if fp16 else None,
                     ptr(gv["_found_inf"]) if fp16 else None, stream(dev))
             if mix is None and smoothing == 0.0:
                 check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(self._loss_buf), ptr(self._dlogits), *tail),
@@ -505,7 +610,10 @@ class CaraEngine:
                 check(self._lib().cara_cross_entropy_mix(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(self._loss_buf),
                                                          ptr(self._dlogits), *tail), "cara_cross_entropy_mix")
             self._run_backward(self._dlogits, droppath, hw, cp, prescaled=True)
-            self._apply_gradients(optimizer, group, prescaled=True)
+            if win_k > 1:
+                self._accumulate_flat(win_i, win_k, dev)
+            if win_i == win_k - 1:
+                self._apply_gradients(optimizer, group, prescaled=True, clip_grad=max_norm)
         return self._loss_buf[0]
 
     # ------------------------------------------------------------------ training from a resident uint8 split
@@ -585,7 +693,7 @@ class CaraEngine:
         return buf
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
-                            mix=None, label_smoothing: float = 0.0):
+                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -598,12 +706,13 @@ class CaraEngine:
         ``mix`` (device int32 [batch, 8], e.g. ``data.MixupCutmix.draw``): Mixup / CutMix by index -- sample ``i`` is blended with,
         or gets a rectangle of, the unmixed sample ``mix[i][0]`` of the same batch (``cara_vit_forward_u8_rows_mix``; with or without
         ``boxes``) and is trained on both labels (``cara_cross_entropy_mix``, ``data.soft_target``).  A table entry the kernel
-        refuses -- ``data.check_mix`` -- gives a zero image, counted like a bad row.  ``label_smoothing`` as in ``train_step``.
+        refuses -- ``data.check_mix`` -- gives a zero image, counted like a bad row.  ``label_smoothing``, ``accumulate`` and
+        ``clip_grad`` as in ``train_step``.
         Without either, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
         _, dev = self._resident_args(split, rows, boxes, mix)
         return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix),
-                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps)
+                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None):
         """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``

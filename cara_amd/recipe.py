@@ -113,24 +113,35 @@ class GraphedTrainStep:
     inputs are the index vector and the box table -- both copied before every replay, 28 bytes per sample.
     ``step(split, (rows, boxes_or_None, mix))`` captures the mixed step (``train_step_resident(..., mix=)``) the same way: the
     Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.  ``label_smoothing`` is the steps' (all
-    forms); it is part of every graph's key."""
+    forms); it is part of every graph's key.  ``clip_grad`` likewise: the two launches of ``cara_grad_clip`` are captured with
+    the step (``CaraEngine.train_step(..., clip_grad=)``).  An accumulation window (``accumulate`` with k > 1) spans several
+    replays and is refused."""
 
-    def __init__(self, engine, optimizer, label_smoothing: float = 0.0):
+    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
         self.eng, self.opt = engine, optimizer
         self.label_smoothing = engine._smoothing(label_smoothing) if label_smoothing else 0.0
+        self.clip_grad = engine._max_norm(clip_grad)
         self._graphs = {}
 
     def _kw(self):
-        # (a step without smoothing is called exactly as before)
-        return {"label_smoothing": self.label_smoothing} if self.label_smoothing else {}
+        # (a step without smoothing and without a clip is called exactly as before)
+        kw = {"label_smoothing": self.label_smoothing} if self.label_smoothing else {}
+        if self.clip_grad is not None:
+            kw["clip_grad"] = self.clip_grad
+        return kw
 
-    def __call__(self, x, y, group=None):
+    def _refuse_window(self, accumulate):
+        if self.eng._window(accumulate)[1] > 1:
+            raise CaraError("GraphedTrainStep: accumulate with k > 1 is not supported (the window spans several graph replays)")
+
+    def __call__(self, x, y, group=None, accumulate=None):
         """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector, or
         ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table, or ``(split, (rows, boxes_or_None, mix))``:
         with a device int32 [batch, 8] mix table too"""
         from . import dist as cdist
+        self._refuse_window(accumulate)
         eng, model = self.eng, self.eng._model()
         resident = hasattr(x, "pixels")
         if resident and isinstance(y, (tuple, list)):
@@ -142,7 +153,8 @@ class GraphedTrainStep:
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(x, y, self.opt, group=group)
         # (the split itself is part of a resident key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
-        key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision, self.label_smoothing)
+        key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision, self.label_smoothing,
+               self.clip_grad)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -188,7 +200,7 @@ class GraphedTrainStep:
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(rows, tables)
         key = (("rows+boxes" if mix is None else "rows+boxes+mix", split, tuple(rows.shape), boxes is not None and tuple(boxes.shape),
-                mix is not None and tuple(mix.shape)), bool(model.training), eng.precision, self.label_smoothing)
+                mix is not None and tuple(mix.shape)), bool(model.training), eng.precision, self.label_smoothing, self.clip_grad)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -219,7 +231,8 @@ class GraphedTrainStep:
 def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[Callable[[], Iterable]] = None,
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
         on_eval: Optional[Callable[[int, float], None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
-        graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0):
+        graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
+        accum_steps: int = 1):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -247,7 +260,16 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     through a crop box per sample (``train_step_resident(..., boxes=)``); a box outside its image is counted like a bad row.
     One that yields ``(rows, boxes_or_None, mix)`` triples (``train_rows(..., mix=data.MixupCutmix(...))``) trains with Mixup /
     CutMix by index (``train_step_resident(..., mix=)``); a mix entry the kernel refuses is counted like a bad row too.
-    ``label_smoothing`` in [0, 1): every step's loss is the smoothed cross-entropy (both feeds)."""
+    ``label_smoothing`` in [0, 1): every step's loss is the smoothed cross-entropy (both feeds).
+    ``clip_grad = max_norm``: every optimiser step clips the global gradient norm first (``train_step(..., clip_grad=)``; both
+    feeds, eager and graphed).  ``accum_steps = k`` > 1: ``k`` consecutive batches of an epoch form a window -- one optimiser step,
+    one all-reduce and one scheduler step per window on the sum of their gradients (``train_step(..., accumulate=(i, k))``), an
+    effective batch of ``k`` batches.  The batches of a window are held until it is complete, and a trailing incomplete window at
+    the end of an epoch is DROPPED without being run: ``drop_last`` at window granularity.  Not with ``graph = True``."""
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+        raise CaraError(f"accum_steps must be an integer >= 1, not {accum_steps!r}")
+    if graph and accum_steps > 1:
+        raise CaraError("fit: accum_steps > 1 cannot run with graph = True (an accumulation window spans several graph replays)")
     if eval_mode not in ("reference", "sharded"):
         raise CaraError(f"eval_mode must be 'reference' or 'sharded', not {eval_mode!r}")
     if feed not in ("batches", "resident"):
@@ -255,6 +277,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     from . import dist as cdist
     eng = model._cara_engine
     smooth = {"label_smoothing": eng._smoothing(label_smoothing)} if label_smoothing else {}
+    if clip_grad is not None:
+        smooth["clip_grad"] = eng._max_norm(clip_grad)
     model.train()
     params = trainable_parameters(model)
     if cdist.world_size(group) > 1:
@@ -274,17 +298,17 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         split, rows_of = train_batches
         train_batches = lambda epoch: ((split, rows) for rows in rows_of(epoch))   # noqa: E731
 
-        def step(split, rows, opt, group=None):
+        def step(split, rows, opt, group=None, **win):
             if isinstance(rows, (tuple, list)):
                 if len(rows) > 2:
                     rows, boxes, mix = rows
-                    return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, mix=mix, **smooth)
+                    return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, mix=mix, **smooth, **win)
                 rows, boxes = rows
-                return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **smooth)
-            return eng.train_step_resident(split, rows, opt, group=group, **smooth)
+                return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **smooth, **win)
+            return eng.train_step_resident(split, rows, opt, group=group, **smooth, **win)
     else:
-        def step(x, y, opt, group=None):
-            return eng.train_step(x, y, opt, group=group, **smooth)
+        def step(x, y, opt, group=None, **win):
+            return eng.train_step(x, y, opt, group=group, **smooth, **win)
 
     def check_rows(upto):
         # (data parallel: a rank that raised alone would leave the others waiting in the next all-reduce.  train_rows range-checks
@@ -295,8 +319,16 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
                             f"with a partner outside the batch, a rectangle outside the output or a weight outside [0, 1]) reached "
                             f"the device up to epoch {upto}")
     for epoch in range(epochs):
+        window = []
         for x, y in train_batches(epoch):
-            if gstep is not None:
+            if accum_steps > 1:
+                window.append((x, y))
+                if len(window) < accum_steps:
+                    continue                    # (what is left in `window` when the epoch ends is dropped)
+                for i, (wx, wy) in enumerate(window):
+                    step(wx, wy, opt, group=group, accumulate=(i, accum_steps))
+                window = []
+            elif gstep is not None:
                 gstep(x, y, group=group)
             else:
                 step(x, y, opt, group=group)

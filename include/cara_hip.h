@@ -494,6 +494,22 @@ int cara_adamw_step(const cara_adamw_args* a, void* stream);
  * counter = 0.  torch.amp.GradScaler's rule.  found_inf is left as it is (cara_adamw_args::skip_flag reads it next).    */
 int cara_amp_update(float* state, const float* found_inf, float growth, float backoff, int interval, float max_scale,
                     void* stream);
+/* Gradient accumulation over one flat fp32 buffer: dst[i] = a[i] + b[i], i < n, one fp32 rounding each; b == NULL copies a.
+ * dst may be a or b (an element is read and written by the same thread).  Any n >= 1 and any 4-byte-aligned pointers: 16-byte
+ * accesses where the three pointers share one residue mod 16, dword accesses otherwise.  The engine's flat buffer carries the
+ * found-inf word as its last element; adding it along keeps "some micro-step overflowed" non-zero.  Only enqueues.          */
+int cara_grad_accumulate(float* dst, const float* a, const float* b, size_t n, void* stream);
+/* torch.nn.utils.clip_grad_norm_(norm_type = 2) over one flat fp32 buffer g[n], 1 <= n <= 2^31, in two launches without atomics:
+ * launch 1 writes one partial sum of squares per chunk of 8192 elements into scratch (cara_grad_clip_scratch_bytes(n) bytes;
+ * 0 for an n outside the range); in launch 2 EVERY workgroup adds all partials in the same fixed order (the tree is stated in
+ * cara_amd/csrc/optim.hip), so each holds the identical total, forms norm = sqrtf(total) and coef = min(1, max_norm /
+ * (norm + 1e-6f)) and multiplies its own chunks by coef; workgroup 0 writes out[0] = norm, out[1] = coef (device float[2]).
+ * Bitwise reproducible run to run, and equal on all ranks that hold equal buffers.  coef == 1: g is not written at all.
+ * found_inf (device float or NULL) != 0: g is left untouched and out[1] = 1 -- the step is skipped anyway (cara_amp_update,
+ * cara_adamw_args::skip_flag) and Inf x 0 must not put NaNs into the gradients.  A NaN norm gives a NaN coef (torch.clamp's rule).
+ * max_norm > 0; +inf only measures.  Both launches only enqueue on `stream` and capture into a hipGraph.               */
+size_t cara_grad_clip_scratch_bytes(size_t n);
+int cara_grad_clip(float* g, size_t n, float max_norm, float* scratch, const float* found_inf, float* out, void* stream);
 
 /* ---- exact weight-space dropout mode (the reference's train-mode arithmetic, cara.py:35,57,81,92) ---- */
 /* keep(o,i) of linear `linear_id` = (cara_weight_dropout_hash(o*in + i, seed, linear_id) >> 8) >= p * 2^24
