@@ -10,7 +10,8 @@
 // The tensors come BY VALUE in the kernel arguments (pointers and sizes of up to 32 tensors, 1.3 KiB): no table in device
 // memory, nothing to upload when a learning rate changes.
 // Beside it: the loss-scale update of the IEEE-half build, and gradient accumulation and global-norm clipping over the step's one
-// flat gradient buffer (cara_grad_accumulate, cara_grad_clip).
+// flat gradient buffer (cara_grad_accumulate, cara_grad_clip), and the moving average of the trainable tensors, AdamW's scheme again
+// (cara_ema_update).
 #include "common.h"
 
 namespace {
@@ -190,7 +191,90 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(float* g, size_t n, siz
   }
 }
 
+// ---- exponential moving average of the trainable tensors (cara_hip.h: cara_ema_update) ----
+// adamw_kernel's scheme once more: pointers and sizes of up to 32 tensors BY VALUE in the kernel arguments (784 bytes), a prefix walk,
+// 1024-element chunks -- one launch over the 14 tensors of a step, no table in device memory.
+struct ema_table {
+  float* e[CARA_ADAMW_MAX_TENSORS];
+  const float* p[CARA_ADAMW_MAX_TENSORS];
+  size_t n[CARA_ADAMW_MAX_TENSORS];
+  int ntensors;
+  float weight;              // 1 - decay, used when weight_dev is NULL
+  const float* weight_dev;   // the capturable form: the weight lives in device memory
+};
+
+// torch.lerp's two-branch definition, every operation a single IEEE fp32 operation (no fma: see the clip kernels above)
+__device__ __forceinline__ float ema_lerp(float e, float p, float w, float one_minus_w) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  if (w < 0.5f) {
+    const float s = w * d;
+    return e + s;
+  }
+  const float s = d * one_minus_w;
+  return p - s;
+}
+
+__global__ __launch_bounds__(256) void ema_kernel(const ema_table a) {
+#pragma clang fp contract(off)
+  int t = 0, first = 0;
+  for (; t < a.ntensors && t < CARA_ADAMW_MAX_TENSORS; ++t) {
+    const int nchunk = (int)((a.n[t] + ADAMW_CHUNK - 1) / ADAMW_CHUNK);
+    if ((int)blockIdx.x < first + nchunk) break;
+    first += nchunk;
+  }
+  if (t >= a.ntensors || t >= CARA_ADAMW_MAX_TENSORS) return;
+  const float w = a.weight_dev ? *a.weight_dev : a.weight;
+  if (!(w >= 0.f && w <= 1.f)) return;   // a device weight outside [0, 1], or a NaN: nothing is written
+  const float omw = 1.f - w;             // exact for w in [0.5, 1], the only range that reads it
+  float* e = a.e[t];
+  const float* p = a.p[t];
+  const size_t n = a.n[t];
+  const size_t base = (size_t)((int)blockIdx.x - first) * ADAMW_CHUNK;
+  if ((((uintptr_t)e | (uintptr_t)p) & 15) == 0) {   // both 16-byte aligned: one float4 per thread (the chunk base is a multiple of 4)
+    const size_t i = base + 4 * (size_t)threadIdx.x;
+    if (i + 4 <= n) {
+      f32x4 ev = *reinterpret_cast<const f32x4*>(e + i);
+      const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) ev[c] = ema_lerp(ev[c], pv[c], w, omw);
+      *reinterpret_cast<f32x4*>(e + i) = ev;
+    } else {
+      for (size_t k = i; k < n; ++k) e[k] = ema_lerp(e[k], p[k], w, omw);   // the tensor's last 1 .. 3 elements
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const size_t i = base + (size_t)j * 256 + threadIdx.x;
+    if (i < n) e[i] = ema_lerp(e[i], p[i], w, omw);
+  }
+}
+
 }  // namespace
+
+extern "C" int cara_ema_update(int ntensors, float* const* ema, const float* const* param, const size_t* n, float weight,
+                               const float* weight_dev, void* stream) {
+  if (!ema || !param || !n || ntensors < 1 || ntensors > CARA_ADAMW_MAX_TENSORS) return CARA_E_ARG;
+  if (weight_dev ? (uintptr_t)weight_dev % 4 != 0 : !(weight >= 0.f && weight <= 1.f)) return CARA_E_ARG;   // (a NaN fails the comparison)
+  ema_table a = {};
+  size_t chunks = 0;
+  for (int t = 0; t < ntensors; ++t) {
+    if (!ema[t] || !param[t] || n[t] == 0 || ((uintptr_t)ema[t] | (uintptr_t)param[t]) % 4 != 0 || ema[t] == param[t]) return CARA_E_ARG;
+    if (n[t] > (size_t)0x7fffffffu * ADAMW_CHUNK) return CARA_E_ARG;
+    a.e[t] = ema[t];
+    a.p[t] = param[t];
+    a.n[t] = n[t];
+    chunks += (n[t] + ADAMW_CHUNK - 1) / ADAMW_CHUNK;
+  }
+  if (chunks > 0x7fffffffu) return CARA_E_ARG;
+  a.ntensors = ntensors;
+  a.weight = weight;
+  a.weight_dev = weight_dev;
+  hipLaunchKernelGGL(ema_kernel, dim3((unsigned)chunks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
 
 extern "C" int cara_amp_update(float* state, const float* found_inf, float growth, float backoff, int interval, float max_scale,
                                void* stream) {

@@ -412,6 +412,35 @@ class CaraEngine:
         model = self._model()
         return [getattr(model, "CP_" + n) for n in self.cp_fields] + [model.head.weight, model.head.bias]
 
+    ema = None   # the average recipe.fit(ema_decay=) trains with, left here for the caller
+
+    def make_ema(self, decay: float = 0.9998, warmup: bool = False, capturable: bool = False):
+        """``ema.ParamEma`` over ``trainable_parameters()`` (the frozen backbone does not move): hand it to ``train_step(..., ema=)``
+        and score it with ``evaluate(..., weights=)``.  ``capturable = True`` for ``GraphedTrainStep``."""
+        from .ema import ParamEma
+        return ParamEma(self.trainable_parameters(), decay, warmup=warmup, capturable=capturable)
+
+    def _check_ema(self, ema, dev, what):
+        """``ema`` is None or a ParamEma whose shadows match trainable_parameters() one by one, on ``dev``"""
+        if ema is None:
+            return
+        from .ema import ParamEma
+        params = self.trainable_parameters()
+        if not isinstance(ema, ParamEma) or len(ema.tensors) != len(params):
+            raise CaraError(f"{what} must be a ParamEma over this model's trainable parameters (CaraEngine.make_ema)")
+        for s, p in zip(ema.tensors, params):
+            if s.shape != p.shape or s.device != dev or s.dtype != torch.float32 or not s.is_contiguous():
+                raise CaraError(f"{what}: a shadow tensor is {tuple(s.shape)} on {s.device}, the model's parameter {tuple(p.shape)} on "
+                                f"{dev} (CaraEngine.make_ema builds a matching one)")
+
+    def _forward_weights(self, model, dev, weights):
+        """-> (cp tensors, head weight, head bias) a forward reads: the model's own, or the shadows of ``weights``"""
+        if weights is None:
+            return [getattr(model, "CP_" + n) for n in self.cp_fields], model.head.weight, model.head.bias
+        self._check_ema(weights, dev, "weights")
+        k = len(self.cp_fields)
+        return list(weights.tensors[:k]), weights.tensors[k], weights.tensors[k + 1]
+
     def _apply_gradients(self, optimizer=None, group=None, prescaled=False, clip_grad=None):
         """Tail of a train step, shared by train_step and the CPU multi-process tests: bind ``p.grad`` of every
         trainable parameter to its view of the flat buffer, ONE all-reduce of that buffer when the group has more than
@@ -541,7 +570,7 @@ class CaraEngine:
             return self._clip_flat(max_norm)
 
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
-                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None):
+                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -558,7 +587,9 @@ class CaraEngine:
         the micro-batch's own mean.  ``k == 1`` (or None) is the step without a window.  Not under graph capture for ``k > 1``.
         ``clip_grad = max_norm`` (> 0): ``torch.nn.utils.clip_grad_norm_`` over all trainable tensors behind the all-reduce and
         before the optimiser (``cara_grad_clip``: two launches, no host read, bitwise the same on every rank); ``grad_norm`` then
-        holds the device tensor (norm before the clip, coefficient)."""
+        holds the device tensor (norm before the clip, coefficient).
+        ``ema`` (a ``ParamEma`` of ``make_ema``): its one-launch update runs last in the tail, behind ``optimizer.step()`` -- with a
+        window, at its last micro-step only.  A step skipped for an fp16 overflow updates the average too (cara_amd/ema.py)."""
         eps = self._smoothing(label_smoothing)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
@@ -566,14 +597,18 @@ class CaraEngine:
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp),
-                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad)
+                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema)
 
-    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None):
+    def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None,
+              ema=None):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
         (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one.
-        ``accumulate`` and ``clip_grad`` as in ``train_step``."""
+        ``accumulate``, ``clip_grad`` and ``ema`` as in ``train_step``."""
         model = self._model()
+        self._check_ema(ema, dev, "ema")
+        if ema is not None and not ema.capturable and torch.cuda.is_current_stream_capturing():
+            raise CaraError("a captured step needs make_ema(..., capturable=True): the weight would be frozen into the graph")
         win_i, win_k = self._window(accumulate)
         max_norm = self._max_norm(clip_grad)
         cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
@@ -614,6 +649,8 @@ class CaraEngine:
                 self._accumulate_flat(win_i, win_k, dev)
             if win_i == win_k - 1:
                 self._apply_gradients(optimizer, group, prescaled=True, clip_grad=max_norm)
+                if ema is not None:
+                    ema.update()
         return self._loss_buf[0]
 
     # ------------------------------------------------------------------ training from a resident uint8 split
@@ -693,7 +730,7 @@ class CaraEngine:
         return buf
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
-                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None):
+                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -706,24 +743,24 @@ class CaraEngine:
         ``mix`` (device int32 [batch, 8], e.g. ``data.MixupCutmix.draw``): Mixup / CutMix by index -- sample ``i`` is blended with,
         or gets a rectangle of, the unmixed sample ``mix[i][0]`` of the same batch (``cara_vit_forward_u8_rows_mix``; with or without
         ``boxes``) and is trained on both labels (``cara_cross_entropy_mix``, ``data.soft_target``).  A table entry the kernel
-        refuses -- ``data.check_mix`` -- gives a zero image, counted like a bad row.  ``label_smoothing``, ``accumulate`` and
-        ``clip_grad`` as in ``train_step``.
+        refuses -- ``data.check_mix`` -- gives a zero image, counted like a bad row.  ``label_smoothing``, ``accumulate``,
+        ``clip_grad`` and ``ema`` as in ``train_step``.
         Without either, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
         _, dev = self._resident_args(split, rows, boxes, mix)
         return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix),
-                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad)
+                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema)
 
-    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None):
+    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None):
         """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``
-        and ``mix`` as in ``train_step_resident`` (a centre-cropped evaluation by hand)"""
+        and ``mix`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
         model, dev = self._resident_args(split, rows, boxes, mix)
-        cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
+        cp, hw, hb = self._forward_weights(model, dev, weights)
         self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, model.head.weight, model.head.bias, cp, False, boxes, mix)
+            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):
@@ -763,15 +800,15 @@ class CaraEngine:
         """bytes held by the evaluation workspaces (diagnostics: tools/eval_bench.py)"""
         return sum(st["ws"].numel() for st in self.__dict__.get("_eval_ws", {}).values())
 
-    def _eval_forward(self, model, x, dev):
+    def _eval_forward(self, model, x, dev, weights=None):
         """logits of one evaluation batch: uint8 pixels -> cara_vit_forward_u8, fp32 images -> cara_vit_forward, both on the
         inference-sized workspace.  The returned tensor is the workspace entry's own: valid until the next batch."""
         if x.ndim != 4 or x.shape[2] != x.shape[3]:
             raise CaraError("images must be [B, C, H, H]")
         st = self._eval_state(model, x.shape[0], x.shape[2], dev)
-        cp = [getattr(model, "CP_" + n) for n in self.cp_fields]
+        cp, hw, hb = weights if weights is not None else self._forward_weights(model, dev, None)
         cps = self._cp_ptrs([t.detach().contiguous() for t in cp])
-        hw, hb = model.head.weight.detach().contiguous(), model.head.bias.detach().contiguous()
+        hw, hb = hw.detach().contiguous(), hb.detach().contiguous()
         lib, args = self._lib(), (C.byref(st["geom"]), C.byref(st["shape"]), C.byref(self._ingested[1]), C.byref(cps), ptr(hw), ptr(hb))
         if x.dtype == torch.uint8:
             if st["shape"].chans != 3:
@@ -784,7 +821,7 @@ class CaraEngine:
                   "cara_vit_forward")
         return st["logits"]
 
-    def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None) -> dict:
+    def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None, weights=None) -> dict:
         """Top-1 / top-5 accuracy and mean cross-entropy of a whole split, on the device and sharded over the ranks of
         ``group``: ``test()`` of vit_cp.py:73-82 without its host read per batch.  -> ``dict(top1, top5, loss, n)``, the
         same on every rank; ``n`` is the number of images scored by all ranks together.
@@ -794,7 +831,9 @@ class CaraEngine:
         rank's part already.  Each batch is one forward on an inference-sized workspace held beside the training workspace
         and one ``cara_eval_accumulate`` launch into a 40-byte device state; nothing is read back inside the loop.  Then
         one SUM all-reduce of the state and one read-back.  Like the reference's ``test()`` it leaves the model in eval mode.
-        ``debug_hook(logits, labels, n_valid)`` (tests) sees every batch's logits; they are overwritten by the next batch."""
+        ``debug_hook(logits, labels, n_valid)`` (tests) sees every batch's logits; they are overwritten by the next batch.
+        ``weights`` (a ``ParamEma`` of ``make_ema``): the pass scores the averaged weights -- the same forward on the same workspace
+        is handed the shadow tensors as its CP and head pointers; nothing is copied and the model's parameters are not touched."""
         from . import dist as cdist
         model = self._model()
         model.eval()
@@ -812,6 +851,7 @@ class CaraEngine:
         else:
             batches = split_or_batches() if callable(split_or_batches) else split_or_batches
         lib = self._lib()
+        use = self._forward_weights(model, dev, weights)
         with torch.no_grad(), torch.cuda.device(dev):
             state = torch.zeros(int(lib.cara_eval_state_bytes()) // 8, dtype=torch.int64, device=dev)
             for item in batches:
@@ -819,7 +859,7 @@ class CaraEngine:
                 n_valid = int(item[2]) if len(item) > 2 else y.shape[0]
                 if x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]:
                     raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
-                logits = self._eval_forward(model, x, dev)
+                logits = self._eval_forward(model, x, dev, use)
                 check(lib.cara_eval_accumulate(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
                                                logits.shape[1], ptr(state), stream(dev)), "cara_eval_accumulate")
                 if debug_hook is not None:

@@ -81,10 +81,20 @@ def checkpoint_name(dataset: str, acc: float, seed: int, directory: str = ".") -
     return os.path.join(directory, f"vit_{dataset}_{round(acc, 5)}_seed_{seed}.pt")
 
 
-def save_checkpoint(model, path: str) -> None:
+def save_checkpoint(model, path: str, weights=None) -> None:
     """vit_cp.py:66: ``th.save(vit.state_dict(), name)`` -- the WHOLE state dict (frozen backbone, 12 CP_* tensors,
-    head), keys of timm 0.4.12, tensors on the CPU so that the file loads anywhere."""
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
+    head), keys of timm 0.4.12, tensors on the CPU so that the file loads anywhere.
+    ``weights`` (a ``ParamEma``, e.g. ``CaraEngine.make_ema``): the same keys, with the entry of every averaged parameter taken
+    from its shadow -- ``load_checkpoint`` then gives the model that ``evaluate(..., weights=)`` scored."""
+    sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    if weights is not None:
+        names = {id(p): n for n, p in model.named_parameters()}
+        for p, s in zip(weights.params, weights.tensors):
+            n = names.get(id(p))
+            if n is None or n not in sd or sd[n].shape != s.shape:
+                raise CaraError("save_checkpoint: weights must average parameters of this model (CaraEngine.make_ema)")
+            sd[n] = s.detach().cpu()
+    torch.save(sd, path)
 
 
 def load_checkpoint(model, path: str) -> None:
@@ -115,22 +125,32 @@ class GraphedTrainStep:
     Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.  ``label_smoothing`` is the steps' (all
     forms); it is part of every graph's key.  ``clip_grad`` likewise: the two launches of ``cara_grad_clip`` are captured with
     the step (``CaraEngine.train_step(..., clip_grad=)``).  An accumulation window (``accumulate`` with k > 1) spans several
-    replays and is refused."""
+    replays and is refused.  ``ema`` (``CaraEngine.make_ema(..., capturable=True)``): the average's launch is captured behind the
+    optimiser's; its weight lives in device memory and ``ema.advance()`` runs before every step, as ``optimizer.advance()`` does."""
 
-    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None):
+    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
-        self.eng, self.opt = engine, optimizer
+        if ema is not None and not getattr(ema, "capturable", False):
+            raise CaraError("GraphedTrainStep needs CaraEngine.make_ema(..., capturable=True)")
+        self.eng, self.opt, self.ema = engine, optimizer, ema
         self.label_smoothing = engine._smoothing(label_smoothing) if label_smoothing else 0.0
         self.clip_grad = engine._max_norm(clip_grad)
         self._graphs = {}
 
     def _kw(self):
-        # (a step without smoothing and without a clip is called exactly as before)
+        # (a step without smoothing, without a clip and without an average is called exactly as before)
         kw = {"label_smoothing": self.label_smoothing} if self.label_smoothing else {}
         if self.clip_grad is not None:
             kw["clip_grad"] = self.clip_grad
+        if self.ema is not None:
+            kw["ema"] = self.ema
         return kw
+
+    def _advance(self):
+        self.opt.advance()
+        if self.ema is not None:
+            self.ema.advance()
 
     def _refuse_window(self, accumulate):
         if self.eng._window(accumulate)[1] > 1:
@@ -149,7 +169,7 @@ class GraphedTrainStep:
         kw = self._kw()
         step = (lambda a, b, opt, group=None: eng.train_step_resident(a, b, opt, group=group, **kw)) if resident else \
             (lambda a, b, opt, group=None: eng.train_step(a, b, opt, group=group, **kw))
-        self.opt.advance()
+        self._advance()
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(x, y, self.opt, group=group)
         # (the split itself is part of a resident key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
@@ -190,7 +210,7 @@ class GraphedTrainStep:
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
         eng._resident_args(split, rows, boxes, mix)     # (refused here, not inside a capture)
-        self.opt.advance()
+        self._advance()
         tables = [t for t in (boxes, mix) if t is not None]
 
         def step(rs, ts):
@@ -230,9 +250,9 @@ class GraphedTrainStep:
 
 def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[Callable[[], Iterable]] = None,
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
-        on_eval: Optional[Callable[[int, float], None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
+        on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
-        accum_steps: int = 1):
+        accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -265,7 +285,15 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     feeds, eager and graphed).  ``accum_steps = k`` > 1: ``k`` consecutive batches of an epoch form a window -- one optimiser step,
     one all-reduce and one scheduler step per window on the sum of their gradients (``train_step(..., accumulate=(i, k))``), an
     effective batch of ``k`` batches.  The batches of a window are held until it is complete, and a trailing incomplete window at
-    the end of an epoch is DROPPED without being run: ``drop_last`` at window granularity.  Not with ``graph = True``."""
+    the end of an epoch is DROPPED without being run: ``drop_last`` at window granularity.  Not with ``graph = True``.
+    ``ema_decay = d``: an exponential moving average of the trainable tensors (``CaraEngine.make_ema(d, warmup=ema_warmup)``, built
+    after the broadcast; one more launch per optimiser step, every feed, eager and graphed).  The evaluation epochs then score
+    BOTH the raw parameters and the average -- ``eval_mode = "sharded"`` hands the shadows to ``CaraEngine.evaluate(weights=)``,
+    ``"reference"`` runs the module forward with every averaged parameter's ``.data`` swapped for its shadow and restored
+    afterwards -- and call ``on_eval(epoch, raw_accuracy, averaged_accuracy)``; the AVERAGED accuracy is the one that is compared,
+    returned and named in the checkpoint file, and ``save_best`` writes the averaged weights (``save_checkpoint(weights=)``).
+    The average is left in ``model._cara_engine.ema``.  ``ema_decay = None``: nothing of this runs and ``on_eval(epoch, accuracy)``
+    is called as before."""
     if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
         raise CaraError(f"accum_steps must be an integer >= 1, not {accum_steps!r}")
     if graph and accum_steps > 1:
@@ -292,6 +320,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     from .optim import AdamW
     opt = AdamW(params, lr=lr, weight_decay=weight_decay, capturable=graph)
     sched = CosineLRScheduler(opt, t_initial=100, warmup_t=10, lr_min=1e-5, warmup_lr_init=1e-6, decay_rate=0.1)
+    ema = None
+    if ema_decay is not None:
+        ema = eng.ema = eng.make_ema(ema_decay, warmup=ema_warmup, capturable=graph)
+        smooth["ema"] = ema
     gstep = GraphedTrainStep(eng, opt, **smooth) if graph else None
     best = 0.0
     if feed == "resident":
@@ -343,6 +375,13 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
                     acc = eng.evaluate(test_batches, group=group)["top1"]
                 else:
                     acc = evaluate(model, test_batches())
+                raw = acc
+                if ema is not None:
+                    if eval_mode == "sharded":
+                        acc = eng.evaluate(test_batches, group=group, weights=ema)["top1"]
+                    else:
+                        with ema.swapped_in():
+                            acc = evaluate(model, test_batches())
                 if acc > best and save_best is not None and cdist.get_rank(group) == 0:
                     import os
                     old = save_best.get("path")
@@ -350,10 +389,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
                         os.remove(old)
                     save_best["path"] = checkpoint_name(save_best.get("dataset", "task"), acc, save_best.get("seed", seed),
                                                         save_best.get("dir", "."))
-                    save_checkpoint(model, save_best["path"])
+                    save_checkpoint(model, save_best["path"], weights=ema)
                 best = max(best, acc)
                 if on_eval:
-                    on_eval(epoch, acc)
+                    on_eval(epoch, acc) if ema is None else on_eval(epoch, raw, acc)
                 if not reference_eval_quirk:
                     model.train()
     check_rows(epochs - 1)   # one host read per fit: the epochs after the last evaluation, or a fit shorter than 11 epochs

@@ -510,6 +510,20 @@ int cara_grad_accumulate(float* dst, const float* a, const float* b, size_t n, v
  * max_norm > 0; +inf only measures.  Both launches only enqueue on `stream` and capture into a hipGraph.               */
 size_t cara_grad_clip_scratch_bytes(size_t n);
 int cara_grad_clip(float* g, size_t n, float max_norm, float* scratch, const float* found_inf, float* out, void* stream);
+/* Exponential moving average of up to CARA_ADAMW_MAX_TENSORS fp32 tensors in ONE launch: ema[i][j] moves towards param[i][j] by
+ * weight = 1 - decay, j < n[i].  ema, param and n are HOST arrays of ntensors entries (1 <= ntensors <= CARA_ADAMW_MAX_TENSORS), read
+ * during the call and carried by value in the kernel arguments: no table in device memory.  weight_dev == NULL: the by-value weight is
+ * used; otherwise the kernel reads that device float (a launch captured into a hipGraph then follows a decay that warms up).
+ * Per element, in fp32, every operation a single IEEE operation (no fma) -- torch.lerp's definition:
+ *   w <  0.5:  e = e + w * (p - e)
+ *   otherwise: e = p - (p - e) * (1 - w)
+ * so p == e gives e back and w == 1 gives p, bitwise (-0 at w < 0.5 comes back as +0).  16-byte accesses for a tensor whose two
+ * pointers are both 16-byte aligned, dword accesses otherwise: the same bits.  param is never written.
+ * CARA_E_ARG, nothing launched: a null array or entry, n[i] == 0, a pointer that is not 4-byte aligned, ema[i] == param[i], ntensors
+ * out of range, weight_dev == NULL with !(0 <= weight <= 1) (a NaN too).  A device weight outside [0, 1] or NaN: the kernel
+ * writes nothing.  Only enqueues.                                                                                              */
+int cara_ema_update(int ntensors, float* const* ema, const float* const* param, const size_t* n, float weight,
+                    const float* weight_dev, void* stream);
 
 /* ---- exact weight-space dropout mode (the reference's train-mode arithmetic, cara.py:35,57,81,92) ---- */
 /* keep(o,i) of linear `linear_id` = (cara_weight_dropout_hash(o*in + i, seed, linear_id) >> 8) >= p * 2^24
