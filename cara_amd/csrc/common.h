@@ -140,6 +140,18 @@ __device__ __forceinline__ f32x4 mfma_16x16x16(bf16x4 a, bf16x4 b, f32x4 c) {
 #endif
 }
 
+// the project's counter hash: lowbias32 finaliser over (element index, seed, stream id) -- the exact weight dropout's keep mask
+// (stream = the linear's id) and the erase noise of the resident feed; bit-exactly mirrored in tests (numpy uint32)
+__host__ __device__ __forceinline__ unsigned keep_hash(unsigned idx, unsigned seed, unsigned lin) {
+  unsigned h = idx * 0x9E3779B1u ^ (seed + lin * 0x85EBCA77u);
+  h ^= h >> 16;
+  h *= 0x7FEB352Du;
+  h ^= h >> 15;
+  h *= 0x846CA68Bu;
+  h ^= h >> 16;
+  return h;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

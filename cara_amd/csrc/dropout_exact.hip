@@ -22,16 +22,7 @@
 
 namespace {
 
-// lowbias32 finaliser over (element index, seed, linear id); bit-exactly mirrored in tests (numpy uint32)
-__host__ __device__ __forceinline__ unsigned keep_hash(unsigned idx, unsigned seed, unsigned lin) {
-  unsigned h = idx * 0x9E3779B1u ^ (seed + lin * 0x85EBCA77u);
-  h ^= h >> 16;
-  h *= 0x7FEB352Du;
-  h ^= h >> 15;
-  h *= 0x846CA68Bu;
-  h ^= h >> 16;
-  return h;
-}
+// (keep_hash: common.h)
 // keep with probability 1 - p: compare the top 24 bits with p * 2^24
 __device__ __forceinline__ float keep_scale(unsigned idx, unsigned seed, unsigned lin, unsigned thresh, float inv_keep) {
   return (keep_hash(idx, seed, lin) >> 8) >= thresh ? inv_keep : 0.f;

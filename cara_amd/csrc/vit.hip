@@ -978,14 +978,16 @@ extern "C" int cara_head_backward(const float* dlogits, const void* xn, const fl
 // The image of a forward: an fp32 batch, or resident uint8 pixels with their per-channel mean / std -- the batch itself, or a whole
 // split of n_split images that `rows` indexes, each sample read whole or through its box out of the split's own Hs x Ws pixels
 // (cara_im2col_patches_u8_rows_crop), and mixed with a partner sample where a Mixup / CutMix table says so
-// (cara_im2col_patches_u8_rows_mix; its boxes may be NULL).  Each entry checks and sets the fields of its kind; everything behind the patch rows is the same.
+// (cara_im2col_patches_u8_rows_mix; its boxes may be NULL), and colour-jittered / erased where an aug table says so
+// (cara_im2col_patches_u8_rows_aug).  Each entry checks and sets the fields of its kind; everything behind the patch rows is the same.
 struct ImageSource {
-  enum Kind { F32Batch, U8Batch, U8Rows, U8RowsCrop, U8RowsMix } kind;
+  enum Kind { F32Batch, U8Batch, U8Rows, U8RowsCrop, U8RowsMix, U8RowsAug } kind;
   const float* images;                                      // F32Batch
   const unsigned char* pixels; const float *mean, *stdv;   // the three U8 kinds
   int n_split; const int64_t* rows; int* bad;               // U8Rows, U8RowsCrop, U8RowsMix
   int Hs, Ws; const int* boxes;                             // U8RowsCrop, U8RowsMix
-  const int* mix;                                           // U8RowsMix
+  const int* mix;                                           // U8RowsMix, U8RowsAug (may be NULL there, like its boxes)
+  const int* aug; void* stat;                               // U8RowsAug: the jitter / erase table and its statistic scratch
 };
 static int patch_rows(const ImageSource& i, const cara_vit_shape* s, void* patches, void* stream) {
   switch (i.kind) {
@@ -999,6 +1001,9 @@ static int patch_rows(const ImageSource& i, const cara_vit_shape* s, void* patch
     case ImageSource::U8RowsMix:
       return cara_im2col_patches_u8_rows_mix(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mix, i.mean, i.stdv, patches, i.bad, s->B, s->chans,
                                              s->img, s->img, s->patch, stream);
+    case ImageSource::U8RowsAug:
+      return cara_im2col_patches_u8_rows_aug(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mix, i.aug, i.stat, i.mean, i.stdv, patches, i.bad,
+                                             s->B, s->chans, s->img, s->img, s->patch, stream);
   }
   return CARA_E_ARG;
 }
@@ -1130,6 +1135,16 @@ extern "C" int cara_vit_forward_u8_rows_mix(const cara_geom* g, const cara_vit_s
                                             int* bad, void* stream) {
   if (!pixels || !rows || !mix || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
   const ImageSource src{ImageSource::U8RowsMix, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
+}
+
+extern "C" int cara_vit_forward_u8_rows_aug(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                            const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                            int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const int* mix,
+                                            const int* aug, void* stat_scratch, const float* mean, const float* stdv,
+                                            const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
+  if (!pixels || !rows || !aug || !stat_scratch || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
+  const ImageSource src{ImageSource::U8RowsAug, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix, aug, stat_scratch};
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 

@@ -80,8 +80,8 @@ class RandomResizedCropFlip:
     and an aspect ratio ``exp(U(log ratio))``, ``w = round(sqrt(area * r))``, ``h = round(sqrt(area / r))``; the first try with
     ``0 < w <= Ws`` and ``0 < h <= Hs`` is taken at a uniform integer offset.  If none fits: the centre crop of the whole image
     clamped to the ratio bounds.  ``size`` is the side the crop is resized to (the model's input); the boxes do not depend on it
-    -- the kernel that reads them resamples to the model's own size.  No colour jitter or antialiasing; Mixup / CutMix is
-    ``MixupCutmix`` below."""
+    -- the kernel that reads them resamples to the model's own size.  No antialiasing; Mixup / CutMix is ``MixupCutmix`` and
+    colour jitter / Random Erasing ``ColorJitterErase`` below."""
 
     TRIES = 10
 
@@ -301,6 +301,183 @@ def soft_target(labels: torch.Tensor, mix, classes: int, smoothing: float = 0.0)
     return (1.0 - smoothing) * ((1.0 - t) * eye[y] + t * eye[y[partner]]) + smoothing / classes
 
 
+def aug_seed(seed: int, epoch: int, rank: int) -> int:
+    """``box_seed`` of the stream that draws the colour-jitter / erase tables (a third constant)"""
+    return box_seed(seed, epoch, rank, stream=0x2545F491)
+
+
+AUG_NONE, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION = 0, 1, 2, 3
+AUG_ERASE_STREAM = 0x45524153                 # the counter hash's stream of the erase noise (norm_misc.hip)
+GRAY_WEIGHTS = (0.2989, 0.587, 0.114)         # torchvision's rgb_to_grayscale; the kernel holds them as fp32
+
+
+def identity_aug(B: int, steps: Optional[int] = None) -> torch.Tensor:
+    """int32 [B, 16] (or [steps, B, 16]) table that changes nothing: no colour op, no erase rectangle"""
+    return torch.zeros((B, 16) if steps is None else (steps, B, 16), dtype=torch.int32)
+
+
+class ColorJitterErase:
+    """Colour-jitter / Random-Erasing tables for the resident feed, restated from the published definitions (neither torchvision
+    nor timm is installed).
+    torchvision's ``ColorJitter(brightness, contrast, saturation)`` (no hue): per sample a factor uniform in
+    ``[max(0, 1 - j), 1 + j]`` for every ``j > 0`` and a uniform random order of the three ops; each op is ``_blend``:
+    ``clamp(f x + (1 - f) d)`` with ``d`` = 0 (brightness), the image's mean gray (contrast) or the pixel's gray (saturation).
+    timm's ``RandomErasing(probability, min_area, max_area, min_aspect, max_aspect, mode, max_count=1)``: with probability
+    ``erase_prob``, up to ten attempts of ``area = Hi Wi U(erase_scale)``, ``aspect = exp(U(log erase_ratio))``, ``h =
+    round(sqrt(area aspect))``, ``w = round(sqrt(area / aspect))``; the first with ``w < Wi`` and ``h < Hi`` is taken at a uniform
+    integer offset (``top`` in [0, Hi - h], ``left`` in [0, Wi - w]); none fits: nothing erased.  ``erase_mode``: "pixel" (a standard
+    normal per element of the normalised image) or "const" (zeros).
+    A row of the table is ``(op0, f0 bits, op1, f1 bits, op2, f2 bits, ex0, ey0, ew, eh, emode, eseed, 0, 0, 0, 0)``:
+    include/cara_hip.h, ``cara_im2col_patches_u8_rows_aug``.  ``size`` = Hi or (Hi, Wi): the model's input."""
+
+    TRIES = 10
+
+    def __init__(self, size, brightness: float = 0.4, contrast: float = 0.4, saturation: float = 0.4, erase_prob: float = 0.25,
+                 erase_scale=(0.02, 1.0 / 3.0), erase_ratio=(0.3, 3.3), erase_mode: str = "pixel"):
+        Hi, Wi = (size, size) if isinstance(size, int) else size
+        if int(Hi) <= 0 or int(Wi) <= 0 or min(brightness, contrast, saturation) < 0 or not (0.0 <= erase_prob <= 1.0) \
+                or not (0 < erase_scale[0] <= erase_scale[1] <= 1) or not (0 < erase_ratio[0] <= erase_ratio[1]) \
+                or erase_mode not in ("pixel", "const"):
+            raise ValueError("ColorJitterErase: size > 0, jitters >= 0, erase_prob in [0, 1], 0 < erase_scale[0] <= erase_scale[1] <= 1, "
+                             "0 < erase_ratio[0] <= erase_ratio[1], erase_mode 'pixel' or 'const'")
+        self.Hi, self.Wi = int(Hi), int(Wi)
+        self.jitter = (float(brightness), float(contrast), float(saturation))
+        self.erase_prob, self.erase_mode = float(erase_prob), erase_mode
+        self.erase_scale, self.erase_ratio = (float(erase_scale[0]), float(erase_scale[1])), (float(erase_ratio[0]), float(erase_ratio[1]))
+
+    def draw(self, B: int, steps: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """int32 [steps, B, 16] on the host.  One variate of ``generator`` per batch -- the seed of that batch's own generator, as
+        in ``MixupCutmix.draw`` -- so batch ``k`` does not depend on ``steps``."""
+        Hi, Wi, T = self.Hi, self.Wi, self.TRIES
+        out = identity_aug(B, steps)
+        for k in range(steps):
+            g = torch.Generator().manual_seed(int(torch.randint(0, 2 ** 31 - 1, (1,), generator=generator)))
+            uf = torch.rand(B, 3, generator=g, dtype=torch.float64)
+            order = torch.rand(B, 3, generator=g, dtype=torch.float64).argsort(1)      # a uniform permutation per sample
+            ue = torch.rand(B, T, 4, generator=g, dtype=torch.float64)
+            coin = torch.rand(B, generator=g, dtype=torch.float64)
+            seeds = torch.randint(0, 2 ** 32, (B,), generator=g, dtype=torch.int64)
+            row = out[k]
+            j = torch.tensor(self.jitter, dtype=torch.float64)
+            lo = (1.0 - j).clamp(min=0.0)
+            f = lo + (1.0 + j - lo) * uf                                                # [B, 3]: brightness, contrast, saturation
+            ops = torch.where(j > 0, torch.arange(1, 4), torch.zeros(3, dtype=torch.int64)).expand(B, 3)
+            row[:, 0:6:2] = ops.gather(1, order).to(torch.int32)
+            row[:, 1:6:2] = torch.where(ops.gather(1, order) > 0, _f32_bits(f.gather(1, order)), torch.zeros(B, 3, dtype=torch.int32))
+            area = Hi * Wi * (self.erase_scale[0] + (self.erase_scale[1] - self.erase_scale[0]) * ue[..., 0])
+            la, lb = math.log(self.erase_ratio[0]), math.log(self.erase_ratio[1])
+            aspect = torch.exp(la + (lb - la) * ue[..., 1])
+            h = torch.round(torch.sqrt(area * aspect)).to(torch.int64)
+            w = torch.round(torch.sqrt(area / aspect)).to(torch.int64)
+            fits = (w < Wi) & (h < Hi) & (w > 0) & (h > 0)
+            first = fits.to(torch.int64).argmax(1)
+            pick = lambda t: t.gather(1, first[:, None])[:, 0]   # noqa: E731
+            w, h = pick(w), pick(h)
+            top = torch.floor(pick(ue[..., 2]) * (Hi - h + 1).clamp(min=1)).to(torch.int64).clamp(min=0)
+            left = torch.floor(pick(ue[..., 3]) * (Wi - w + 1).clamp(min=1)).to(torch.int64).clamp(min=0)
+            on = fits.any(1) & (coin < self.erase_prob)
+            zero = torch.zeros(B, dtype=torch.int64)
+            row[:, 6] = torch.where(on, torch.minimum(left, Wi - w), zero).to(torch.int32)
+            row[:, 7] = torch.where(on, torch.minimum(top, Hi - h), zero).to(torch.int32)
+            row[:, 8] = torch.where(on, w, zero).to(torch.int32)
+            row[:, 9] = torch.where(on, h, zero).to(torch.int32)
+            row[:, 10] = 1 if self.erase_mode == "pixel" else 0
+            row[:, 11] = torch.where(seeds >= 2 ** 31, seeds - 2 ** 32, seeds).to(torch.int32)
+        return out
+
+
+def check_aug(aug: torch.Tensor, B: int, Hi: int, Wi: int) -> None:
+    """ValueError unless ``aug`` is an int32 [..., B, 16] table the kernel accepts: every op in [0, 3], no non-zero op twice in a row,
+    every factor of a non-zero op finite and >= 0, every erase rectangle inside the ``Hi`` x ``Wi`` output, every emode 0 or 1,
+    the last four words 0 (the companion of ``check_mix``)"""
+    if not torch.is_tensor(aug) or aug.dtype != torch.int32 or aug.ndim < 2 or aug.shape[-1] != 16 or aug.shape[-2] != B:
+        raise ValueError("aug must be an int32 [..., batch, 16] tensor (op0, f0, op1, f1, op2, f2, ex0, ey0, ew, eh, emode, eseed, 0, 0, 0, 0)")
+    t = aug.reshape(-1, 16).cpu()
+    w = t.to(torch.int64)
+    ops, f = w[:, 0:6:2], _bits_f32(t[:, 1:6:2])
+    bad = ((ops < 0) | (ops > 3)).any(1)
+    for code in (1, 2, 3):
+        bad |= (ops == code).sum(1) > 1
+    bad |= ((ops != 0) & ~((f >= 0) & torch.isfinite(f))).any(1)
+    bad |= (w[:, 6] < 0) | (w[:, 7] < 0) | (w[:, 8] < 0) | (w[:, 9] < 0) | (w[:, 6] + w[:, 8] > Wi) | (w[:, 7] + w[:, 9] > Hi)
+    bad |= ((w[:, 10] != 0) & (w[:, 10] != 1)) | (w[:, 12:] != 0).any(1)
+    if bool(bad.any()):
+        i = int(bad.to(torch.int64).argmax())
+        raise ValueError(f"{int(bad.sum())} aug entry(ies) with an unknown or repeated op, a factor that is negative or not finite, an erase "
+                         f"rectangle outside the {Hi} x {Wi} output, an emode outside {{0, 1}} or a non-zero pad word, the first: "
+                         f"{t[i].tolist()}")
+
+
+def erase_noise(index, eseed: int):
+    """(u1, arg, z): the pixel-mode erase value of element ``index`` (its position in [B,C,Hi,Wi], any integer array) in the kernel's
+    formula: two draws of the counter hash, ``u1 = ((h1 >> 8) + 1) 2^-24``, ``u2 = (h2 >> 8) 2^-24`` (exact), ``arg`` = the fp32
+    product ``6.2831855f u2``; ``z = sqrt(-2 log(u1)) cos(arg)`` in float64 on those fp32 arguments.  numpy arrays."""
+    import numpy as np
+    from .dropout import keep_hash_np
+    i = np.asarray(index).astype(np.uint32)
+    seed = int(eseed) & 0xffffffff
+    h1 = keep_hash_np(i * np.uint32(2), seed, AUG_ERASE_STREAM)
+    h2 = keep_hash_np(i * np.uint32(2) + np.uint32(1), seed, AUG_ERASE_STREAM)
+    u1 = ((h1 >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    u2 = (h2 >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    arg = np.float32(6.2831855) * u2
+    return u1, arg, np.sqrt(-2.0 * np.log(u1)) * np.cos(arg.astype(np.float64))
+
+
+def color_chain_reference(x: torch.Tensor, row) -> torch.Tensor:
+    """the colour chain of one table row on one unmixed image ``x`` [3,Hi,Wi] on the 0..255 scale, in ``x``'s dtype: each slot
+    ``clamp(f x + (1 - f) d, 0, 255)`` with the fp32 factor and the fp32 gray weights the kernel holds"""
+    wr, wg, wb = (float(torch.tensor(v, dtype=torch.float32)) for v in GRAY_WEIGHTS)
+    gray = lambda t: wr * t[0] + wg * t[1] + wb * t[2]   # noqa: E731
+    row = torch.as_tensor(row).to(torch.int32)
+    for k in range(3):
+        op = int(row[2 * k])
+        if op == AUG_NONE:
+            continue
+        f = float(_bits_f32(row[2 * k + 1:2 * k + 2])[0])
+        d = 0.0 if op == AUG_BRIGHTNESS else (gray(x).mean() if op == AUG_CONTRAST else gray(x)[None])
+        x = (f * x + (1.0 - f) * d).clamp(0.0, 255.0)
+    return x
+
+
+def aug_reference(pixels_u8: torch.Tensor, rows, boxes, mix, aug, size, dtype=torch.float64) -> torch.Tensor:
+    """What ``cara_im2col_patches_u8_rows_aug`` computes before its one rounding to 16 bits, in torch ops on the CPU: the
+    NORMALISED image [B,3,Hi,Wi] of ``dtype``.  ``y[i] = color_chain_reference(resized_crop_reference(...)[i], aug[i])``; the mix of
+    ``mix_reference`` on ``y`` (``mix`` None: none; ``boxes`` None: whole images of the output's size); ``(v / 255 - mean) / std``; the
+    erase rectangle of ``aug[i]`` filled with 0 or with ``erase_noise``.  Named functions are evaluated in float64 on the fp32
+    arguments the kernel's formula gives them."""
+    Hi, Wi = (size, size) if isinstance(size, int) else size
+    rows = torch.as_tensor(rows).cpu()
+    B = len(rows)
+    if boxes is None:
+        if tuple(pixels_u8.shape[2:]) != (Hi, Wi):
+            raise ValueError("without boxes the split must have the output's size")
+        boxes = torch.tensor([[0, 0, Wi, Hi, 0]] * B, dtype=torch.int32)
+    mix = identity_mix(B) if mix is None else torch.as_tensor(mix).cpu()
+    aug = torch.as_tensor(aug).cpu()
+    check_mix(mix, B, Hi, Wi)
+    check_aug(aug, B, Hi, Wi)
+    if pixels_u8.shape[1] != 3:
+        raise ValueError("the colour ops are defined on three channels")
+    x = resized_crop_reference(pixels_u8, rows, boxes, (Hi, Wi), dtype)
+    y = torch.stack([color_chain_reference(x[i], aug[i]) for i in range(B)])
+    m = _bits_f32(mix[:, 5]).to(dtype)
+    out = torch.empty_like(y)
+    for i, (p, cx0, cy0, cw, ch) in enumerate(mix[:, :5].tolist()):
+        out[i] = y[i] + m[i] * (y[p] - y[i])
+        out[i][:, cy0:cy0 + ch, cx0:cx0 + cw] = y[p][:, cy0:cy0 + ch, cx0:cx0 + cw]
+    mean = torch.tensor(IMAGENET_MEAN, dtype=torch.float32).to(dtype).view(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, dtype=torch.float32).to(dtype).view(1, 3, 1, 1)
+    out = (out / 255.0 - mean) / std
+    index = torch.arange(B * 3 * Hi * Wi).view(B, 3, Hi, Wi)
+    for i, (ex0, ey0, ew, eh, emode, eseed) in enumerate(aug[:, 6:12].tolist()):
+        if ew == 0 or eh == 0:
+            continue
+        sl = (slice(None), slice(ey0, ey0 + eh), slice(ex0, ex0 + ew))
+        out[i][sl] = torch.from_numpy(erase_noise(index[i][sl].numpy(), eseed)[2]).to(dtype) if emode else 0.0
+    return out
+
+
 class ResidentSplit:
     """One file list decoded once and kept on ``device`` as the resized uint8 pixels ``pixels`` [N,3,size,size]
     (150 KB per image: the 73k-image dsprites test split is 11 GB, not 44) plus ``labels`` int64 [N]; a batch is
@@ -359,7 +536,7 @@ class ResidentSplit:
         return epoch_iter
 
     def train_rows(self, batch_size: int = 64, seed: int = 0, rank: Optional[int] = None,
-                   world: Optional[int] = None, augment=None, mix=None) -> Callable[[int], Iterator[torch.Tensor]]:
+                   world: Optional[int] = None, augment=None, mix=None, color=None) -> Callable[[int], Iterator[torch.Tensor]]:
         """``f(epoch)`` -> iterator of int64 [batch_size] index vectors on the device: the indices ``train_batches`` draws
         (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
         and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
@@ -371,7 +548,13 @@ class ResidentSplit:
         ``mix`` (a ``MixupCutmix``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix)``
         -- ``boxes`` is None without an ``augment`` -- each with an int32 [batch_size, 8] view of one [steps, batch_size, 8] upload
         per epoch (``train_step_resident(..., mix=)``), drawn from a generator seeded by (seed, epoch, rank) on a stream of its
-        own (``mix_seed``) and range-checked (``check_mix``) before the upload."""
+        own (``mix_seed``) and range-checked (``check_mix``) before the upload.
+        ``color`` (a ``ColorJitterErase``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix,
+        aug)`` -- ``boxes`` and ``mix`` None where not asked for -- each with an int32 [batch_size, 16] view of one upload per epoch
+        (``train_step_resident(..., aug=)``), drawn on a third stream (``aug_seed``) and checked (``check_aug``) before the upload."""
+        if color is not None and not (callable(getattr(color, "draw", None)) and isinstance(getattr(color, "Hi", None), int)
+                                      and isinstance(getattr(color, "Wi", None), int)):
+            raise ValueError("color must be a ColorJitterErase (anything with draw(B, steps, generator), Hi and Wi)")
         if mix is not None and not (callable(getattr(mix, "draw", None)) and isinstance(getattr(mix, "Hi", None), int)
                                     and isinstance(getattr(mix, "Wi", None), int)):
             raise ValueError("mix must be a MixupCutmix (anything with draw(B, steps, generator), Hi and Wi)")
@@ -385,7 +568,7 @@ class ResidentSplit:
             table = torch.stack(idx)
             if int(table.min()) < 0 or int(table.max()) >= len(self):
                 raise ValueError(f"epoch {epoch}: a drawn index is outside [0, {len(self)})")
-            boxes = mixes = None
+            boxes = mixes = augs = None
             if augment is not None:
                 Hs, Ws = self.pixels.shape[2:]
                 gen = torch.Generator().manual_seed(box_seed(seed, epoch, rank))
@@ -399,9 +582,18 @@ class ResidentSplit:
                                      f"not an int32 {(*table.shape, 8)} table")
                 check_mix(mixes, table.shape[1], mix.Hi, mix.Wi)
                 mixes = mixes.contiguous().to(self.pixels.device)
+            if color is not None:
+                augs = color.draw(table.shape[1], table.shape[0], torch.Generator().manual_seed(aug_seed(seed, epoch, rank)))
+                if not torch.is_tensor(augs) or tuple(augs.shape) != (*table.shape, 16):
+                    raise ValueError(f"color.draw gave {tuple(augs.shape) if torch.is_tensor(augs) else type(augs).__name__}, "
+                                     f"not an int32 {(*table.shape, 16)} table")
+                check_aug(augs, table.shape[1], color.Hi, color.Wi)
+                augs = augs.contiguous().to(self.pixels.device)
             table = table.to(self.pixels.device)
             for step in range(table.shape[0]):
-                if mixes is not None:
+                if augs is not None:
+                    yield table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]), augs[step]
+                elif mixes is not None:
                     yield table[step], (None if boxes is None else boxes[step]), mixes[step]
                 elif boxes is not None:
                     yield table[step], boxes[step]
@@ -438,7 +630,7 @@ class ResidentSplit:
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
              seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False, augment=None,
-             train_size: Optional[int] = None, mix=None):
+             train_size: Optional[int] = None, mix=None, color=None):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
@@ -449,9 +641,10 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     ``augment`` / ``train_size`` (with ``resident_feed``): the training split is decoded at ``train_size`` (default 224, the
     model's size) and its ``train_rows`` yields ``(rows, boxes)`` drawn by ``augment`` -- "resize 256, random-resized-crop
     224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size.
-    ``mix`` (with ``resident_feed``; a ``MixupCutmix``): ``train_rows`` yields ``(rows, boxes or None, mix)``."""
-    if (augment is not None or train_size is not None or mix is not None) and not resident_feed:
-        raise ValueError("augment / train_size / mix belong to the resident feed: pass resident_feed=True")
+    ``mix`` (with ``resident_feed``; a ``MixupCutmix``): ``train_rows`` yields ``(rows, boxes or None, mix)``.
+    ``color`` (with ``resident_feed``; a ``ColorJitterErase``): ``train_rows`` yields ``(rows, boxes or None, mix or None, aug)``."""
+    if (augment is not None or train_size is not None or mix is not None or color is not None) and not resident_feed:
+        raise ValueError("augment / train_size / mix / color belong to the resident feed: pass resident_feed=True")
     if train_size is not None and train_size != 224 and augment is None:
         raise ValueError("a training split of another size than the model's is read through crop boxes: pass augment")
     root = root if root is not None else "./data/vtab-1k/" + name
@@ -459,7 +652,8 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers, size=224 if train_size is None else train_size)
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
     if resident_feed:
-        feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix))
+        feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix,
+                                        **({"color": color} if color is not None else {})))
     else:
         feed = train.train_batches(batch_size, seed=seed)
     return feed, (test if shard_eval else test.eval_batches(256))

@@ -232,13 +232,14 @@ class CaraEngine:
             return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev)
 
     def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None):
-        """``resident = (split, rows[, boxes[, mix]])``: the images are rows of a resident uint8 split (``images`` is None then),
-        with ``boxes`` read through a crop box per sample at the model's own input size, with ``mix`` mixed by that table"""
-        boxes = mix = None
+        """``resident = (split, rows[, boxes[, mix[, aug]]])``: the images are rows of a resident uint8 split (``images`` is None
+        then), with ``boxes`` read through a crop box per sample at the model's own input size, with ``mix`` mixed by that table, with
+        ``aug`` colour-jittered and erased by that one"""
+        boxes = mix = aug = None
         if resident is None:
             st = self._state(model, images.shape[0], images.shape[2], dev)
         else:
-            split, rows, boxes, mix = (*resident, None, None)[:4]
+            split, rows, boxes, mix, aug = (*resident, None, None, None)[:5]
             st = self._state(model, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
             if st["shape"].chans != 3:
                 raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
@@ -265,6 +266,13 @@ class CaraEngine:
         if resident is None:
             check(self._lib().cara_vit_forward(*args, ptr(images), ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)),
                   "cara_vit_forward")
+        elif aug is not None:
+            mean, std = self._eval_norm(dev)
+            check(self._lib().cara_vit_forward_u8_rows_aug(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
+                                                           split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(aug),
+                                                           ptr(self._aug_stat(dev, rows.shape[0])), ptr(mean), ptr(std), ptr(droppath),
+                                                           ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)), stream(dev)),
+                  "cara_vit_forward_u8_rows_aug")
         elif mix is not None:
             mean, std = self._eval_norm(dev)
             check(self._lib().cara_vit_forward_u8_rows_mix(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
@@ -680,7 +688,16 @@ class CaraEngine:
             raise CaraError("boxes need a model that states its input size (patch_embed.img_size)")
         return img
 
-    def _resident_args(self, split, rows, boxes=None, mix=None):
+    def _aug_stat(self, dev, B):
+        """the jitter kernels' statistic scratch (``cara_aug_stat_bytes``): one buffer per (device, batch size), never replaced -- a
+        captured step holds its address (68 bytes per sample)"""
+        bufs = self.__dict__.setdefault("_aug_stat_bufs", {})
+        buf = bufs.get((dev, B))
+        if buf is None:
+            buf = bufs[(dev, B)] = torch.empty(int(self._lib().cara_aug_stat_bytes(B)) // 4, dtype=torch.float32, device=dev)
+        return buf
+
+    def _resident_args(self, split, rows, boxes=None, mix=None, aug=None):
         model = self._model()
         box_msg = "boxes must be a contiguous int32 [batch, 5] tensor (x0, y0, w, h, flip) on the model's device"
         mix_msg = ("mix must be a contiguous int32 [batch, 8] tensor (partner, cx0, cy0, cw, ch, blend bits, target bits, 0) on the "
@@ -692,6 +709,11 @@ class CaraEngine:
         if mix is not None and (not torch.is_tensor(mix) or mix.dtype != torch.int32 or mix.ndim != 2 or mix.shape[1] != 8
                                 or not mix.is_contiguous()):
             raise CaraError(mix_msg)
+        aug_msg = ("aug must be a contiguous int32 [batch, 16] tensor (op0, f0, op1, f1, op2, f2, ex0, ey0, ew, eh, emode, eseed, 0, 0, 0, "
+                   "0) on the model's device")
+        if aug is not None and (not torch.is_tensor(aug) or aug.dtype != torch.int32 or aug.ndim != 2 or aug.shape[1] != 16
+                                or not aug.is_contiguous()):
+            raise CaraError(aug_msg)
         dev = model.head.weight.device if hasattr(model.head, "weight") else None
         if dev is None:
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
@@ -709,13 +731,15 @@ class CaraEngine:
             raise CaraError(box_msg)
         if mix is not None and (mix.device != dev or mix.shape[0] != rows.shape[0]):
             raise CaraError(mix_msg)
+        if aug is not None and (aug.device != dev or aug.shape[0] != rows.shape[0]):
+            raise CaraError(aug_msg)
         return model, dev
 
-    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None):
+    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None, aug=None):
         model = self._model()
         dev = rows.device
         with torch.cuda.device(dev):
-            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix))
+            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix, aug))
 
     def _gather_labels(self, split, rows):
         dev, B = rows.device, rows.shape[0]
@@ -730,7 +754,7 @@ class CaraEngine:
         return buf
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
-                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None):
+                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -745,22 +769,26 @@ class CaraEngine:
         ``boxes``) and is trained on both labels (``cara_cross_entropy_mix``, ``data.soft_target``).  A table entry the kernel
         refuses -- ``data.check_mix`` -- gives a zero image, counted like a bad row.  ``label_smoothing``, ``accumulate``,
         ``clip_grad`` and ``ema`` as in ``train_step``.
-        Without either, the step is the one it was."""
+        ``aug`` (device int32 [batch, 16], e.g. ``data.ColorJitterErase.draw``): colour jitter and Random Erasing by index -- each
+        sample's brightness / contrast / saturation chain on its unmixed crop (the partner's own chain on the partner), then the
+        mix, the normalisation and the erase rectangle (``cara_vit_forward_u8_rows_aug``; with or without ``boxes`` and ``mix``).
+        A table entry the kernel refuses -- ``data.check_aug`` -- gives a zero image, counted like a bad row.
+        Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
-        _, dev = self._resident_args(split, rows, boxes, mix)
-        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix),
+        _, dev = self._resident_args(split, rows, boxes, mix, aug)
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix, aug),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema)
 
-    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None):
-        """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``
-        and ``mix`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
-        model, dev = self._resident_args(split, rows, boxes, mix)
+    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None):
+        """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``,
+        ``mix`` and ``aug`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
+        model, dev = self._resident_args(split, rows, boxes, mix, aug)
         cp, hw, hb = self._forward_weights(model, dev, weights)
         self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix)
+            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix, aug)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):

@@ -122,7 +122,9 @@ class GraphedTrainStep:
     captures the augmented step (``train_step_resident(..., boxes=)``): one graph per (split, shapes, mode) again, whose static
     inputs are the index vector and the box table -- both copied before every replay, 28 bytes per sample.
     ``step(split, (rows, boxes_or_None, mix))`` captures the mixed step (``train_step_resident(..., mix=)``) the same way: the
-    Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.  ``label_smoothing`` is the steps' (all
+    Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.
+    ``step(split, (rows, boxes_or_None, mix_or_None, aug))`` captures the jittered step (``train_step_resident(..., aug=)``): the
+    colour-jitter / erase table is copied per replay too, 64 bytes per sample.  ``label_smoothing`` is the steps' (all
     forms); it is part of every graph's key.  ``clip_grad`` likewise: the two launches of ``cara_grad_clip`` are captured with
     the step (``CaraEngine.train_step(..., clip_grad=)``).  An accumulation window (``accumulate`` with k > 1) spans several
     replays and is refused.  ``ema`` (``CaraEngine.make_ema(..., capturable=True)``): the average's launch is captured behind the
@@ -159,13 +161,14 @@ class GraphedTrainStep:
     def __call__(self, x, y, group=None, accumulate=None):
         """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector, or
         ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table, or ``(split, (rows, boxes_or_None, mix))``:
-        with a device int32 [batch, 8] mix table too"""
+        with a device int32 [batch, 8] mix table too, or ``(split, (rows, boxes_or_None, mix_or_None, aug))``: with a device int32
+        [batch, 16] colour-jitter / erase table"""
         from . import dist as cdist
         self._refuse_window(accumulate)
         eng, model = self.eng, self.eng._model()
         resident = hasattr(x, "pixels")
         if resident and isinstance(y, (tuple, list)):
-            return self._call_tables(x, y[0], y[1], y[2] if len(y) > 2 else None, group)
+            return self._call_tables(x, y[0], y[1], y[2] if len(y) > 2 else None, group, **({"aug": y[3]} if len(y) > 3 else {}))
         kw = self._kw()
         step = (lambda a, b, opt, group=None: eng.train_step_resident(a, b, opt, group=group, **kw)) if resident else \
             (lambda a, b, opt, group=None: eng.train_step(a, b, opt, group=group, **kw))
@@ -204,23 +207,25 @@ class GraphedTrainStep:
         gr.replay()
         return loss
 
-    def _call_tables(self, split, rows, boxes, mix, group):
-        """the resident form through crop boxes and / or a mix table: warm, capture, replay as above, with two or three static
-        inputs"""
+    def _call_tables(self, split, rows, boxes, mix, group, aug=None):
+        """the resident form through crop boxes and / or a mix table and / or an aug table: warm, capture, replay as above, with two
+        to four static inputs"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
-        eng._resident_args(split, rows, boxes, mix)     # (refused here, not inside a capture)
+        eng._resident_args(split, rows, boxes, mix, *(() if aug is None else (aug,)))     # (refused here, not inside a capture)
         self._advance()
-        tables = [t for t in (boxes, mix) if t is not None]
+        tables = [t for t in (boxes, mix, aug) if t is not None]
 
         def step(rs, ts):
             ts = list(ts)
             return eng.train_step_resident(split, rs, self.opt, group=group, boxes=ts.pop(0) if boxes is not None else None,
-                                           **({"mix": ts.pop(0)} if mix is not None else {}), **self._kw())
+                                           **({"mix": ts.pop(0)} if mix is not None else {}),
+                                           **({"aug": ts.pop(0)} if aug is not None else {}), **self._kw())
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(rows, tables)
         key = (("rows+boxes" if mix is None else "rows+boxes+mix", split, tuple(rows.shape), boxes is not None and tuple(boxes.shape),
-                mix is not None and tuple(mix.shape)), bool(model.training), eng.precision, self.label_smoothing, self.clip_grad)
+                mix is not None and tuple(mix.shape), *(() if aug is None else (("aug", tuple(aug.shape)),))), bool(model.training),
+               eng.precision, self.label_smoothing, self.clip_grad)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -280,6 +285,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     through a crop box per sample (``train_step_resident(..., boxes=)``); a box outside its image is counted like a bad row.
     One that yields ``(rows, boxes_or_None, mix)`` triples (``train_rows(..., mix=data.MixupCutmix(...))``) trains with Mixup /
     CutMix by index (``train_step_resident(..., mix=)``); a mix entry the kernel refuses is counted like a bad row too.
+    One that yields ``(rows, boxes_or_None, mix_or_None, aug)`` (``train_rows(..., color=data.ColorJitterErase(...))``) trains with
+    colour jitter and Random Erasing by index too (``train_step_resident(..., aug=)``).
     ``label_smoothing`` in [0, 1): every step's loss is the smoothed cross-entropy (both feeds).
     ``clip_grad = max_norm``: every optimiser step clips the global gradient norm first (``train_step(..., clip_grad=)``; both
     feeds, eager and graphed).  ``accum_steps = k`` > 1: ``k`` consecutive batches of an epoch form a window -- one optimiser step,
@@ -332,6 +339,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
 
         def step(split, rows, opt, group=None, **win):
             if isinstance(rows, (tuple, list)):
+                if len(rows) > 3:
+                    rows, boxes, mix, aug = rows
+                    return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **({} if mix is None else {"mix": mix}), aug=aug,
+                                                   **smooth, **win)
                 if len(rows) > 2:
                     rows, boxes, mix = rows
                     return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, mix=mix, **smooth, **win)
@@ -348,7 +359,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         bad = eng.resident_bad_rows() if feed == "resident" else 0
         if bad:
             raise CaraError(f"fit: {bad} row index(es) outside the training split (or crop boxes outside their image, or mix entries "
-                            f"with a partner outside the batch, a rectangle outside the output or a weight outside [0, 1]) reached "
+                            f"with a partner outside the batch, a rectangle outside the output or a weight outside [0, 1], or aug entries "
+                            f"data.check_aug refuses) reached "
                             f"the device up to epoch {upto}")
     for epoch in range(epochs):
         window = []

@@ -336,6 +336,37 @@ int cara_im2col_patches_u8_rows_crop(const unsigned char* pixels, int n_split, i
 int cara_im2col_patches_u8_rows_mix(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
                                     const int* boxes, const int* mix, const float* mean, const float* std, void* patches,
                                     int* bad, int B, int C, int Hi, int Wi, int p, void* stream);
+/* cara_im2col_patches_u8_rows_mix with colour jitter and Random Erasing by index: aug device int32 [B,16], row b =
+ *   (op0, f0, op1, f1, op2, f2, ex0, ey0, ew, eh, emode, eseed, 0, 0, 0, 0)
+ * op: 0 none, 1 brightness, 2 contrast, 3 saturation -- a non-zero code at most once per row, in any order; f: the bits of a finite
+ * fp32 factor >= 0 (not read where op == 0); (ex0, ey0, ew, eh): the erase rectangle in output pixels, ew == 0 or eh == 0: none;
+ * emode: 0 const, 1 pixel; eseed: any 32 bits; the last four words 0.  All of it in fp32, every product and sum one IEEE operation
+ * (no contraction), on the un-normalised 0..255 values; u = the sample's own unmixed bilinear value (as above):
+ *   each slot in order:  v <- min(max(f v + (1 - f) d, 0), 255), 1 - f rounded once;  brightness d = 0;  saturation d = gray =
+ *   (0.2989 r + 0.587 g) + 0.114 b of that pixel's three channel values at that point of the chain;  contrast d = M_b, the mean of gray
+ *   over all Hi x Wi output pixels of sample b as they stand before the contrast slot (torchvision's _blend on float tensors,
+ *   rescaled to 0..255: exact at f == 1, d clamped at f == 0).  M_b comes from a pre-pass through a fixed tree: 16 workgroups of 256
+ *   threads per sample; thread t of workgroup k adds gray of the pixels q = 256 k + t, + 4096, ... < Hi Wi (q = oy Wi + ox) in
+ *   sequence; the wave's 64 sums by a butterfly (lanes 32, 16, 8, 4, 2, 1 apart); the four wave sums left to right; the 16 workgroup
+ *   sums left to right; one division by (float)(Hi Wi).
+ *   Then the mix step exactly as in cara_im2col_patches_u8_rows_mix, the partner's value being the partner's unmixed value after its
+ *   own chain (its row of aug, its M); then (v / 255 - mean[c]) / std[c]; then the erase: inside the rectangle the normalised value
+ *   becomes 0 (const) or z (pixel):  i = ((b C + c) Hi + oy) Wi + ox;  h1 = cara_weight_dropout_hash(2 i, eseed, 0x45524153), h2 =
+ *   ...(2 i + 1, ...);  u1 = ((h1 >> 8) + 1) 2^-24 in (0, 1], u2 = (h2 >> 8) 2^-24 in [0, 1) (exact);
+ *   z = sqrtf(-2 logf(u1)) cosf(6.2831855f u2) -- roundings: logf, sqrtf, the product 6.2831855f u2, cosf, the last product (the
+ *   product with -2 is exact);  then the one rounding to the build's 16-bit type.
+ * mix and boxes may each be NULL (no partner; whole images, Hs == Hi and Ws == Wi asked).  aug NULL: the call without a table
+ * (the launches of _rows_mix, _rows_crop or _rows).  stat_scratch: cara_aug_stat_bytes(B) bytes of device memory, 4-byte aligned
+ * (fp32 stat [B], then the tree's partial sums); a sample without a contrast op loads no pixel in the pre-pass and its stat word
+ * is neither written nor read.  C must be 3 and 2 B C Hi Wi <= 2^32: CARA_E_ARG otherwise, nothing launched.  A sample gets zero
+ * patch rows and is counted once in *bad by the rules of _rows_mix and where its own OR ITS PARTNER's aug row has an op outside
+ * [0, 3], a repeated op, a factor that is negative, infinite or NaN, a rectangle not inside the output (ew, eh, ex0, ey0 >= 0, ew <=
+ * Wi - ex0, eh <= Hi - ey0, in this order), an emode outside {0, 1} or a non-zero pad word.  An all-zero aug table gives bit for bit
+ * the patch rows of the call without it.                                                                                        */
+size_t cara_aug_stat_bytes(int B);
+int cara_im2col_patches_u8_rows_aug(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                    const int* boxes, const int* mix, const int* aug, void* stat_scratch, const float* mean,
+                                    const float* std, void* patches, int* bad, int B, int C, int Hi, int Wi, int p, void* stream);
 /* out[i] = labels[rows[i]] (device int64 [B] each; labels int64 [n_split]); a row outside [0, n_split) is not
  * dereferenced: it gives 0 and is counted in *bad (device int, may be NULL)                                    */
 int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
@@ -630,6 +661,14 @@ int cara_vit_forward_u8_rows_mix(const cara_geom* g, const cara_vit_shape* s, co
                                  int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const int* mix,
                                  const float* mean, const float* std, const float* droppath, void* workspace, float* logits,
                                  int* bad, void* stream);
+/* cara_vit_forward_u8_rows_mix with a colour-jitter / erase table (aug device int32 [B,16] and stat_scratch of
+ * cara_aug_stat_bytes(B) bytes, cara_im2col_patches_u8_rows_aug; mix and boxes may each be NULL): only the patch rows differ;
+ * workspace and backward unchanged.                                                                                          */
+int cara_vit_forward_u8_rows_aug(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
+                                 const cara_cp* cp, const float* head_w, const float* head_b, const unsigned char* pixels,
+                                 int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const int* mix,
+                                 const int* aug, void* stat_scratch, const float* mean, const float* std, const float* droppath,
+                                 void* workspace, float* logits, int* bad, void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,

@@ -19,7 +19,11 @@ events around --kernel-launches back-to-back launches), all interleaved round by
 
 --mix adds to the --augment legs, interleaved with them in the same process: the augmented step with Mixup / CutMix tables
 (data.MixupCutmix) and label smoothing 0.1, and cara_im2col_patches_u8_rows_mix alone on an identity table, a Mixup table and a
-CutMix table."""
+CutMix table.
+
+--aug adds to the --mix legs: the mixed step with an all-zero colour table, with colour jitter alone and with jitter and Random
+Erasing (data.ColorJitterErase), and cara_im2col_patches_u8_rows_aug alone (its two pre-pass launches included) on an all-zero
+table, a jitter table and a jitter + erase table, each over the identity mix table."""
 import argparse
 import json
 import os
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--legs", default="eager,graph")
     ap.add_argument("--augment", action="store_true", help="time the augmented resident step and the two patch-row kernels instead")
     ap.add_argument("--mix", action="store_true", help="the --augment legs plus the mixed step and the mix kernel alone")
+    ap.add_argument("--aug", action="store_true", help="the --mix legs plus the jittered / erased steps and the aug kernels alone")
     ap.add_argument("--source", type=int, default=256, help="--augment: side of the split the boxes are drawn on")
     ap.add_argument("--kernel-launches", type=int, default=200, help="--augment: launches per timed kernel window")
     args = ap.parse_args()
@@ -78,6 +83,8 @@ def main():
             yield from of_epoch(epoch)
             epoch += 1
 
+    if args.aug:
+        args.mix = True
     if args.augment or args.mix:
         return augment_legs(args, eng, opt, split, feeder, dev, gd)
     gstep = GraphedTrainStep(eng, opt)
@@ -191,6 +198,27 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
                                                             L.ptr(std), L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st),
                         "cara_im2col_patches_u8_rows_mix")
             kernels[f"kernel/u8_rows_mix{S}/{name}"] = k_mix
+    if args.aug:
+        from cara_amd.data import ColorJitterErase, identity_aug
+        zero_color = type("ZeroColor", (), {"Hi": 224, "Wi": 224, "draw": staticmethod(lambda B_, steps, generator: identity_aug(B_, steps))})()
+        jitter, full = ColorJitterErase(224, erase_prob=0.0), ColorJitterErase(224)
+
+        def jittered(item):
+            opt.advance()
+            return eng.train_step_resident(big, item[0], opt, boxes=item[1], mix=item[2], aug=item[3], label_smoothing=0.1)
+        for name, c in (("aug0", zero_color), ("jitter", jitter), ("jitter+erase", full)):
+            steps[f"eager/resident+crop{S}+mix+{name}"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224), color=c)), jittered)
+        ident = identity_mix(B).to(dev)
+        stat = torch.empty(int(lib.cara_aug_stat_bytes(B)) // 4, device=dev)
+        gk = torch.Generator().manual_seed(9)
+        for name, t in (("zero", identity_aug(B)), ("jitter", jitter.draw(B, 1, gk)[0]), ("jitter+erase", ColorJitterErase(224, erase_prob=1.0).draw(B, 1, gk)[0])):
+            t = t.contiguous().to(dev)
+
+            def k_aug(t=t):
+                L.check(lib.cara_im2col_patches_u8_rows_aug(L.ptr(big.pixels), len(big), S, S, L.ptr(rows), L.ptr(boxes), L.ptr(ident), L.ptr(t),
+                                                            L.ptr(stat), L.ptr(mean), L.ptr(std), L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st),
+                        "cara_im2col_patches_u8_rows_aug")
+            kernels[f"kernel/u8_rows_aug{S}/{name}"] = k_aug
 
     def step_window(name, n):
         feed, step = steps[name]
