@@ -749,6 +749,230 @@ __global__ __launch_bounds__(256) void im2col_u8_rows_aug_kernel(const uint8_t* 
   *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
 }
 
+// Patch dropout: the five patch-row kernels above on a kept subset of the patches.  keep int32 [B,K]: output row b K + j is the row
+// of patch pr = keep[b][j] of sample b.  Each sibling is its kernel with the row decomposed as (b, j) and pr read from the table;
+// from pr on -- (gy, gx), the pixel's position in the full Hi x Wi output, every table lookup, the erase index -- the text is that
+// kernel's, so a kept row is bit for bit the row it writes.  A sample the kernel calls bad: K zero rows, counted once (the lane of
+// j == 0, col == 0); otherwise an entry outside [0, gh gw) is never used: a zero row, counted by the lane that writes its first element.
+struct KeptRow { int b, j, col; long e; };
+__device__ __forceinline__ KeptRow kept_row(long idx, int K, int kcols) {
+  const long e = idx * 4;
+  const long row = e / kcols;
+  return KeptRow{(int)(row / K), (int)(row % K), (int)(e - row * kcols), e};
+}
+__device__ __forceinline__ void zero_row4(bf16* __restrict__ out, long e) {
+  const bf16 z = (bf16)0.0f;
+  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
+}
+__global__ __launch_bounds__(256) void im2col_keep_kernel(const float* __restrict__ img, const int* __restrict__ keep, int K,
+                                                          bf16* __restrict__ out, int* __restrict__ bad, int B, int C, int Hi, int Wi,
+                                                          int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const KeptRow kr = kept_row(idx, K, C * p * p);
+  const long e = kr.e;
+  const int col = kr.col, b = kr.b;
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int pr = keep[(size_t)b * K + kr.j];
+  if (pr < 0 || pr >= gh * gw) {
+    if (bad && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int gy = pr / gw, gx = pr % gw;
+  const float4 v = *reinterpret_cast<const float4*>(img + (((size_t)b * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
+  bf16x4 o = {(bf16)v.x, (bf16)v.y, (bf16)v.z, (bf16)v.w};
+  *reinterpret_cast<bf16x4*>(out + e) = o;
+}
+__global__ __launch_bounds__(256) void im2col_u8_rows_keep_kernel(const uint8_t* __restrict__ img, long n_split,
+                                                                  const int64_t* __restrict__ rows, const int* __restrict__ keep, int K,
+                                                                  const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                  bf16* __restrict__ out, int* __restrict__ bad, int B, int C, int Hi,
+                                                                  int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const KeptRow kr = kept_row(idx, K, C * p * p);
+  const long e = kr.e;
+  const int col = kr.col, b = kr.b;
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int64_t r = rows[b];
+  if (r < 0 || r >= n_split) {
+    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int pr = keep[(size_t)b * K + kr.j];
+  if (pr < 0 || pr >= gh * gw) {
+    if (bad && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int gy = pr / gw, gx = pr % gw;
+  const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)r * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
+  *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
+}
+__global__ __launch_bounds__(256) void im2col_u8_rows_crop_keep_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                                       const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                                       const int* __restrict__ keep, int K,
+                                                                       const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                       bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
+                                                                       int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const KeptRow kr = kept_row(idx, K, C * p * p);
+  const long e = kr.e;
+  const int col = kr.col, b = kr.b;
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int64_t r = rows[b];
+  const int* box = boxes + (size_t)b * 5;
+  const int x0 = box[0], y0 = box[1], w = box[2], h = box[3];
+  const bool flip = box[4] != 0;
+  if (r < 0 || r >= n_split || w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > Ws - x0 || h > Hs - y0) {
+    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int pr = keep[(size_t)b * K + kr.j];
+  if (pr < 0 || pr >= gh * gw) {
+    if (bad && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int gy = pr / gw, gx = pr % gw;
+  const CropAxis ay = crop_axis(gy * p + py, Hi, h, false);
+  const uint8_t* plane = img + ((size_t)r * C + c) * Hs * Ws;
+  const uint8_t* top = plane + (size_t)(y0 + ay.i0) * Ws + x0;
+  const uint8_t* bot = plane + (size_t)(y0 + ay.i1) * Ws + x0;
+  const float mu = mean[c], sd = stdv[c];
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = normalize_f32(crop_value(top, bot, crop_axis(gx * p + px + j, Wi, w, flip), ay.f), mu, sd);
+  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+}
+__global__ __launch_bounds__(256) void im2col_u8_rows_mix_keep_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                                      const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                                      const int* __restrict__ mix, const int* __restrict__ keep, int K,
+                                                                      const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                      bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
+                                                                      int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const KeptRow kr = kept_row(idx, K, C * p * p);
+  const long e = kr.e;
+  const int col = kr.col, b = kr.b;
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  const int* mx = mix + (size_t)b * 8;
+  const int partner = mx[0], cx0 = mx[1], cy0 = mx[2], cw = mx[3], ch = mx[4];
+  const float m = __int_as_float(mx[5]);
+  MixSource own, oth;
+  const bool self = partner == b;
+  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) &&
+                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth))) && cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 &&
+                  cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
+  if (!ok) {
+    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int pr = keep[(size_t)b * K + kr.j];
+  if (pr < 0 || pr >= gh * gw) {
+    if (bad && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int gy = pr / gw, gx = pr % gw;
+  if (self) oth = own;
+  const int oy = gy * p + py, ox0 = gx * p + px;
+  const CropAxis ay_own = crop_axis(oy, Hi, own.h, false), ay_oth = crop_axis(oy, Hi, oth.h, false);
+  const size_t chan = (size_t)c * Hs * Ws;
+  const uint8_t *top_own = own.origin + chan + (size_t)ay_own.i0 * Ws, *bot_own = own.origin + chan + (size_t)ay_own.i1 * Ws;
+  const uint8_t *top_oth = oth.origin + chan + (size_t)ay_oth.i0 * Ws, *bot_oth = oth.origin + chan + (size_t)ay_oth.i1 * Ws;
+  const bool row_in = oy >= cy0 && oy - cy0 < ch;
+  const float mu = mean[c], sd = stdv[c];
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ox = ox0 + j;
+    float a;
+    if (row_in && ox >= cx0 && ox - cx0 < cw) {
+      a = crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f);
+    } else {
+      a = crop_value(top_own, bot_own, crop_axis(ox, Wi, own.w, own.flip), ay_own.f);
+      if (m != 0.0f) a = mix_blend(a, m, crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f));
+    }
+    v[j] = normalize_f32(a, mu, sd);
+  }
+  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+}
+__global__ __launch_bounds__(256) void im2col_u8_rows_aug_keep_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                                      const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                                      const int* __restrict__ mix, const int* __restrict__ aug,
+                                                                      const float* __restrict__ stat, const int* __restrict__ keep, int K,
+                                                                      const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                      bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
+                                                                      int Hi, int Wi, int p, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const int gw = Wi / p, gh = Hi / p;
+  const KeptRow kr = kept_row(idx, K, C * p * p);
+  const long e = kr.e;
+  const int col = kr.col, b = kr.b;
+  const int c = col / (p * p), py = (col / p) % p, px = col % p;
+  int partner = b, cx0 = 0, cy0 = 0, cw = 0, ch = 0;
+  float m = 0.0f;
+  if (mix) {
+    const int* mx = mix + (size_t)b * 8;
+    partner = mx[0]; cx0 = mx[1]; cy0 = mx[2]; cw = mx[3]; ch = mx[4];
+    m = __int_as_float(mx[5]);
+  }
+  MixSource own, oth;
+  AugRow own_a, oth_a;
+  const bool self = partner == b;
+  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) && aug_row(aug, b, Hi, Wi, &own_a) &&
+                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth) &&
+                            aug_row(aug, partner, Hi, Wi, &oth_a))) &&
+                  cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 && cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
+  if (!ok) {
+    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int pr = keep[(size_t)b * K + kr.j];
+  if (pr < 0 || pr >= gh * gw) {
+    if (bad && col == 0) atomicAdd(bad, 1);
+    zero_row4(out, e);
+    return;
+  }
+  const int gy = pr / gw, gx = pr % gw;
+  if (self) { oth = own; oth_a = own_a; }
+  const float M_own = own_a.contrast_at < 3 ? stat[b] : 0.0f, M_oth = oth_a.contrast_at < 3 ? stat[partner] : 0.0f;
+  const int oy = gy * p + py, ox0 = gx * p + px;
+  const AugSource s_own = aug_source(own, oy, Hi, Hs, Ws), s_oth = aug_source(oth, oy, Hi, Hs, Ws);
+  const bool row_in = oy >= cy0 && oy - cy0 < ch;
+  const bool erow_in = oy >= own_a.ey0 && oy - own_a.ey0 < own_a.eh;
+  const float mu = mean[c], sd = stdv[c];
+  const unsigned i0 = (((unsigned)b * (unsigned)C + (unsigned)c) * (unsigned)Hi + (unsigned)oy) * (unsigned)Wi + (unsigned)ox0;
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ox = ox0 + j;
+    float a;
+    if (row_in && ox >= cx0 && ox - cx0 < cw) {
+      a = aug_value(s_oth, oth_a, M_oth, c, ox, Wi);
+    } else {
+      a = aug_value(s_own, own_a, M_own, c, ox, Wi);
+      if (m != 0.0f) a = mix_blend(a, m, aug_value(s_oth, oth_a, M_oth, c, ox, Wi));
+    }
+    v[j] = normalize_f32(a, mu, sd);
+    if (erow_in && ox >= own_a.ex0 && ox - own_a.ex0 < own_a.ew) v[j] = own_a.emode ? aug_noise(i0 + (unsigned)j, own_a.eseed) : 0.0f;
+  }
+  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+}
+
 // out[i] = labels[rows[i]]; a row outside [0, n_split) is not dereferenced: it gives 0 and is counted in *bad (may be NULL)
 __global__ __launch_bounds__(256) void gather_labels_kernel(const int64_t* __restrict__ labels, long n_split,
                                                             const int64_t* __restrict__ rows, int64_t* __restrict__ out,
@@ -774,6 +998,28 @@ __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__
   float4 s = (t == 0) ? *reinterpret_cast<const float4*>(cls + d)
                       : *reinterpret_cast<const float4*>(emb + ((size_t)b * P + (t - 1)) * D + d);
   s.x += pv.x; s.y += pv.y; s.z += pv.z; s.w += pv.w;
+  *reinterpret_cast<float4*>(x + e) = s;
+}
+
+// assemble_kernel behind a patch dropout: token 1 + j of sample b is kept patch keep[b][j], whose position row is 1 + keep[b][j] of
+// the full table pos [1 + P, D].  An entry outside [0, P) reads no position row: the token is emb's row alone.
+__global__ __launch_bounds__(256) void assemble_keep_kernel(const float* __restrict__ emb, const float* __restrict__ cls,
+                                                            const float* __restrict__ pos, const int* __restrict__ keep,
+                                                            float* __restrict__ x, int B, int K, int P, int D, long total4) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total4) return;
+  const long e = idx * 4;
+  const int d = (int)(e % D);
+  const long tok = e / D;
+  const int t = (int)(tok % (K + 1)), b = (int)(tok / (K + 1));
+  const int pr = t == 0 ? -1 : keep[(size_t)b * K + (t - 1)];
+  const bool has_pos = t == 0 || (pr >= 0 && pr < P);
+  float4 s = (t == 0) ? *reinterpret_cast<const float4*>(cls + d)
+                      : *reinterpret_cast<const float4*>(emb + ((size_t)b * K + (t - 1)) * D + d);
+  if (has_pos) {
+    const float4 pv = *reinterpret_cast<const float4*>(pos + (size_t)(t == 0 ? 0 : 1 + pr) * D + d);
+    s.x += pv.x; s.y += pv.y; s.z += pv.z; s.w += pv.w;
+  }
   *reinterpret_cast<float4*>(x + e) = s;
 }
 
@@ -1164,6 +1410,60 @@ extern "C" int cara_im2col_patches_u8_rows_aug(const unsigned char* pixels, int 
   return CARA_OK;
 }
 
+// Patch dropout: the entries above on a kept subset (keep int32 [B,K], 1 <= K <= gh gw).  B K rows are written, nothing beyond.
+extern "C" int cara_im2col_patches_keep(const float* img, const int* keep, int K, void* patches, int* bad, int B, int C, int Hi, int Wi,
+                                        int p, void* stream) {
+  if (!img || !keep || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p || (Wi & 3)) return CARA_E_ARG;
+  if (K < 1 || K > (Hi / p) * (Wi / p)) return CARA_E_ARG;
+  const long total4 = (long)B * K * C * p * p / 4;
+  hipLaunchKernelGGL(im2col_keep_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     img, keep, K, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_im2col_patches_u8_rows_keep(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                                const int* boxes, const int* mix, const int* aug, void* stat_scratch, const int* keep,
+                                                int K, const float* mean, const float* stdv, void* patches, int* bad, int B, int C,
+                                                int Hi, int Wi, int p, void* stream) {
+  // (the checks of cara_im2col_patches_u8_rows_aug and of the entry it hands a call without a table to, in their order)
+  if (!pixels || !rows || !keep || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 ||
+      (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p)
+    return CARA_E_ARG;
+  if (K < 1 || K > (Hi / p) * (Wi / p)) return CARA_E_ARG;
+  if (!boxes && (Hs != Hi || Ws != Wi)) return CARA_E_ARG;   // (without boxes a sample is its whole image, byte for byte)
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long total4 = (long)B * K * C * p * p / 4;
+  const dim3 grid((unsigned)((total4 + 255) / 256)), block(256);
+  if (aug) {
+    if (C != 3) return CARA_E_ARG;
+    if (!stat_scratch || (reinterpret_cast<uintptr_t>(stat_scratch) & 3)) return CARA_E_ARG;
+    if (2ull * (unsigned long long)B * C * Hi * Wi > (1ull << 32)) return CARA_E_ARG;
+    float* stat = static_cast<float*>(stat_scratch);
+    float* partial = stat + B;
+    // the contrast pre-pass of the call without keep, unchanged: M_b is the mean over the whole image, kept or not
+    hipLaunchKernelGGL(aug_gray_mean_kernel, dim3((unsigned)B * AUG_GROUPS), dim3(256), 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, aug,
+                       partial, B, C, Hi, Wi);
+    CARA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(aug_gray_mean_reduce_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, aug, partial, stat, B, Hi, Wi);
+    CARA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(im2col_u8_rows_aug_keep_kernel, grid, block, 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, mix, aug, stat, keep, K,
+                       mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  } else if (mix) {
+    hipLaunchKernelGGL(im2col_u8_rows_mix_keep_kernel, grid, block, 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, mix, keep, K, mean, stdv,
+                       (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  } else if (boxes) {
+    hipLaunchKernelGGL(im2col_u8_rows_crop_keep_kernel, grid, block, 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, keep, K, mean, stdv,
+                       (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
+  } else {
+    if ((Wi & 3) || (reinterpret_cast<uintptr_t>(pixels) & 3)) return CARA_E_ARG;   // (dword loads, as cara_im2col_patches_u8_rows)
+    hipLaunchKernelGGL(im2col_u8_rows_keep_kernel, grid, block, 0, st, pixels, (long)n_split, rows, keep, K, mean, stdv, (bf16*)patches, bad,
+                       B, C, Hi, Wi, p, total4);
+  }
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
 extern "C" int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
                                   void* stream) {
   if (!labels || !rows || !out || n_split <= 0 || B <= 0) return CARA_E_ARG;
@@ -1179,6 +1479,16 @@ extern "C" int cara_assemble_tokens(const float* emb, const float* cls, const fl
   const long total4 = (long)B * (P + 1) * D / 4;
   hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      emb, cls, pos, x, B, P, D, total4);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_assemble_tokens_keep(const float* emb, const float* cls, const float* pos, const int* keep, float* x, int B, int K,
+                                         int P, int D, void* stream) {
+  if (!emb || !cls || !pos || !keep || !x || B <= 0 || K <= 0 || K > P || D <= 0 || (D & 3)) return CARA_E_ARG;
+  const long total4 = (long)B * (K + 1) * D / 4;
+  hipLaunchKernelGGL(assemble_keep_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     emb, cls, pos, keep, x, B, K, P, D, total4);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }

@@ -80,7 +80,9 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   if (!(g->Rp == 32 || g->Rp == 64) || g->rank > g->Rp || s->B <= 0 || s->tokens <= 1) return false;
   // (no token limit of the kernels' own: attention streams K / V above 608 tokens; row counts and row indices are int)
   if (s->tokens > (1 << 20) || (long long)s->B * s->tokens >= (1ll << 31)) return false;
-  if (s->img % s->patch || (s->img / s->patch) * (s->img / s->patch) + 1 != s->tokens) return false;
+  // (a patch dropout runs the blocks on 1 + K of the grid's tokens, 1 <= K <= grid: every per-token region below is sized by
+  // `tokens`; which entries take fewer tokens than the grid has is theirs to say, vit_forward_body)
+  if (s->img % s->patch || s->tokens > (s->img / s->patch) * (s->img / s->patch) + 1) return false;
   if ((s->chans * s->patch * s->patch) % 64 || g->dim % 256) return false;
   const size_t D = g->dim, M = (size_t)s->B * s->tokens, Rp = g->Rp;
   const size_t ldt = (M + 31) / 32 * 32;
@@ -988,8 +990,16 @@ struct ImageSource {
   int Hs, Ws; const int* boxes;                             // U8RowsCrop, U8RowsMix
   const int* mix;                                           // U8RowsMix, U8RowsAug (may be NULL there, like its boxes)
   const int* aug; void* stat;                               // U8RowsAug: the jitter / erase table and its statistic scratch
+  const int* keep;                                          // F32Batch, U8RowsAug: the kept patches [B, tokens - 1] of a patch dropout, or NULL
 };
 static int patch_rows(const ImageSource& i, const cara_vit_shape* s, void* patches, void* stream) {
+  if (i.keep) {   // (U8RowsAug with a kept subset: boxes, mix and aug may each be NULL)
+    if (i.kind == ImageSource::F32Batch)
+      return cara_im2col_patches_keep(i.images, i.keep, s->tokens - 1, patches, i.bad, s->B, s->chans, s->img, s->img, s->patch, stream);
+    if (i.kind != ImageSource::U8RowsAug) return CARA_E_ARG;
+    return cara_im2col_patches_u8_rows_keep(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mix, i.aug, i.stat, i.keep, s->tokens - 1, i.mean,
+                                            i.stdv, patches, i.bad, s->B, s->chans, s->img, s->img, s->patch, stream);
+  }
   switch (i.kind) {
     case ImageSource::F32Batch: return cara_im2col_patches(i.images, patches, s->B, s->chans, s->img, s->img, s->patch, stream);
     case ImageSource::U8Batch: return cara_im2col_patches_u8(i.pixels, i.mean, i.stdv, patches, s->B, s->chans, s->img, s->img, s->patch, stream);
@@ -1018,6 +1028,9 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
                             const float* head_b, const ImageSource& src, const float* droppath, void* workspace, float* logits, void* stream) {
   Ws W;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !workspace || !logits) return CARA_E_ARG;
+  // an entry without a keep table writes the grid's patch rows, all of them: fewer tokens than that is the keep entries' alone
+  const int grid = (s->img / s->patch) * (s->img / s->patch);
+  if (!src.keep && s->tokens != grid + 1) return CARA_E_ARG;
   char* ws = static_cast<char*>(workspace);
   const int D = g->dim, M = W.M, Rp = g->Rp, B = s->B, N = s->tokens, P = N - 1;
   const float att_scale = 1.0f / sqrtf((float)(D / g->heads));
@@ -1034,7 +1047,8 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
   const Ctx px{stream, ws, &W, s, Rp, W.ldt, g->rank};
   with_scratch(a, px);
   TRY(cara_gemm_bf16(&a, stream));
-  TRY(cara_assemble_tokens(px.f32(W.emb), w->cls, w->pos, px.f32(W.layer[0].x_in), B, P, D, stream));
+  if (src.keep) TRY(cara_assemble_tokens_keep(px.f32(W.emb), w->cls, w->pos, src.keep, px.f32(W.layer[0].x_in), B, P, grid, D, stream));
+  else TRY(cara_assemble_tokens(px.f32(W.emb), w->cls, w->pos, px.f32(W.layer[0].x_in), B, P, D, stream));
   for (int l = 0; l < g->depth; ++l) {
     const BlockPlan p = plan_block(g, s, M, l);
     const LayerWs& lw = W.layer[l];
@@ -1145,6 +1159,26 @@ extern "C" int cara_vit_forward_u8_rows_aug(const cara_geom* g, const cara_vit_s
                                             const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
   if (!pixels || !rows || !aug || !stat_scratch || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
   const ImageSource src{ImageSource::U8RowsAug, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix, aug, stat_scratch};
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
+}
+
+extern "C" int cara_vit_forward_keep(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp,
+                                     const float* head_w, const float* head_b, const float* images, const int* keep,
+                                     const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
+  if (!images || !keep) return CARA_E_ARG;
+  ImageSource src{ImageSource::F32Batch, images};
+  src.bad = bad;
+  src.keep = keep;
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
+}
+
+extern "C" int cara_vit_forward_u8_rows_keep(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp,
+                                             const float* head_w, const float* head_b, const unsigned char* pixels, int n_split, int Hs,
+                                             int Ws, const int64_t* rows, const int* boxes, const int* mix, const int* aug,
+                                             void* stat_scratch, const int* keep, const float* mean, const float* stdv,
+                                             const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
+  if (!pixels || !rows || !keep || (aug && !stat_scratch) || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
+  const ImageSource src{ImageSource::U8RowsAug, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix, aug, stat_scratch, keep};
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 

@@ -478,6 +478,76 @@ def aug_reference(pixels_u8: torch.Tensor, rows, boxes, mix, aug, size, dtype=to
     return out
 
 
+def keep_seed(seed: int, epoch: int, rank: int) -> int:
+    """``box_seed`` of the stream that draws the patch-dropout tables (a fourth constant)"""
+    return box_seed(seed, epoch, rank, stream=0x5BD1E995)
+
+
+def identity_keep(B: int, P: int, steps: Optional[int] = None) -> torch.Tensor:
+    """int32 [B, P] (or [steps, B, P]) table that keeps every patch in its place"""
+    t = torch.arange(P, dtype=torch.int32).expand(B, P).contiguous()
+    return t if steps is None else t.expand(steps, B, P).contiguous()
+
+
+class PatchDropout:
+    """Keep tables for a patch dropout: the published definition of timm's ``PatchDropout`` (the FLIP trick), restated (timm is
+    not installed).  On a grid of ``P`` patches ``K = max(1, int(P * (1 - prob)))`` are kept per sample: each sample independently
+    keeps the first ``K`` entries of ``argsort(randn(P))``, sorted ascending with ``ordered=True`` (timm's default is unordered).
+    The kept tokens are gathered behind the position embedding, so token ``1 + j`` of sample ``b`` is patch ``keep[b][j]`` with
+    ITS row of ``pos_embed``; the cls token stays.  Training steps only: an evaluation sees every patch.
+    ``size`` / ``patch`` (optional): the model's input and patch size, from which ``grid`` = P follows -- what ``train_rows`` and
+    ``recipe.fit`` ask for, in the way ``MixupCutmix`` carries ``Hi`` / ``Wi``; or pass ``grid=`` itself."""
+
+    def __init__(self, prob: float, ordered: bool = False, size=None, patch: int = 16, grid: Optional[int] = None):
+        if not isinstance(prob, (int, float)) or not (0.0 <= prob < 1.0):   # (a NaN fails the comparison)
+            raise ValueError("PatchDropout: prob must be a number in [0, 1)")
+        self.prob, self.ordered = float(prob), bool(ordered)
+        if grid is None and size is not None:
+            Hi, Wi = (size, size) if isinstance(size, int) else size
+            if int(patch) <= 0 or int(Hi) <= 0 or int(Wi) <= 0 or Hi % patch or Wi % patch:
+                raise ValueError("PatchDropout: size must be a positive multiple of patch")
+            grid = (int(Hi) // int(patch)) * (int(Wi) // int(patch))
+        if grid is not None and int(grid) < 1:
+            raise ValueError("PatchDropout: grid must be >= 1")
+        self.grid = None if grid is None else int(grid)
+
+    def num_keep(self, P: int) -> int:
+        return max(1, int(P * (1.0 - self.prob)))
+
+    def draw(self, P: int, B: int, steps: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """int32 [steps, B, K] on the host, from one ``randn`` of ``generator`` for the whole table"""
+        K = self.num_keep(P)
+        noise = torch.randn(steps * B * P, generator=generator).reshape(steps, B, P)
+        keep = torch.argsort(noise, dim=-1)[..., :K]
+        if self.ordered:
+            keep = keep.sort(dim=-1).values
+        return keep.to(torch.int32).contiguous()
+
+
+def check_keep(keep: torch.Tensor, B: int, P: int) -> None:
+    """ValueError unless ``keep`` is an int32 [..., B, K] table, 1 <= K <= P, whose every entry is in [0, P) and whose rows hold no
+    patch twice (the companion of ``check_boxes``; the device checks the range only)"""
+    if not torch.is_tensor(keep) or keep.dtype != torch.int32 or keep.ndim < 2 or keep.shape[-2] != B or not (1 <= keep.shape[-1] <= P):
+        raise ValueError(f"keep must be an int32 [..., batch, K] tensor of patch indices, batch = {B}, 1 <= K <= {P}")
+    t = keep.reshape(-1, keep.shape[-1]).cpu().to(torch.int64)
+    bad = (t < 0) | (t >= P)
+    if bool(bad.any()):
+        raise ValueError(f"{int(bad.sum())} keep entry(ies) outside [0, {P}), the first: {int(t[bad][0])}")
+    s = t.sort(dim=-1).values
+    dup = (s[:, 1:] == s[:, :-1]).any(dim=-1)
+    if bool(dup.any()):
+        i = int(dup.to(torch.int64).argmax())
+        raise ValueError(f"{int(dup.sum())} keep row(s) hold a patch twice, the first: {t[i].tolist()}")
+
+
+def keep_reference(tokens_or_rows: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+    """Host gather for the tests: ``tokens_or_rows`` [B, P, ...] (patch rows, or patch tokens with their positions added) ->
+    [B, K, ...], entry ``[b, j]`` = ``tokens_or_rows[b, keep[b][j]]``"""
+    idx = keep.to(tokens_or_rows.device, torch.int64)
+    B, K = idx.shape
+    return tokens_or_rows[torch.arange(B, device=idx.device).reshape(B, 1).expand(B, K), idx]
+
+
 class ResidentSplit:
     """One file list decoded once and kept on ``device`` as the resized uint8 pixels ``pixels`` [N,3,size,size]
     (150 KB per image: the 73k-image dsprites test split is 11 GB, not 44) plus ``labels`` int64 [N]; a batch is
@@ -536,7 +606,8 @@ class ResidentSplit:
         return epoch_iter
 
     def train_rows(self, batch_size: int = 64, seed: int = 0, rank: Optional[int] = None,
-                   world: Optional[int] = None, augment=None, mix=None, color=None) -> Callable[[int], Iterator[torch.Tensor]]:
+                   world: Optional[int] = None, augment=None, mix=None, color=None,
+                   patch_drop=None) -> Callable[[int], Iterator[torch.Tensor]]:
         """``f(epoch)`` -> iterator of int64 [batch_size] index vectors on the device: the indices ``train_batches`` draws
         (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
         and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
@@ -551,7 +622,13 @@ class ResidentSplit:
         own (``mix_seed``) and range-checked (``check_mix``) before the upload.
         ``color`` (a ``ColorJitterErase``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix,
         aug)`` -- ``boxes`` and ``mix`` None where not asked for -- each with an int32 [batch_size, 16] view of one upload per epoch
-        (``train_step_resident(..., aug=)``), drawn on a third stream (``aug_seed``) and checked (``check_aug``) before the upload."""
+        (``train_step_resident(..., aug=)``), drawn on a third stream (``aug_seed``) and checked (``check_aug``) before the upload.
+        ``patch_drop`` (a ``PatchDropout`` that knows its ``grid``, or anything with its ``draw`` and ``grid``): the iterator yields
+        ``(rows, boxes, mix, aug, keep)`` -- None for the tables not asked for -- each with an int32 [batch_size, K] view of one
+        [steps, batch_size, K] upload per epoch (``train_step_resident(..., keep=)``), drawn on a fourth stream (``keep_seed``) and
+        checked (``check_keep``) before the upload."""
+        if patch_drop is not None and not (callable(getattr(patch_drop, "draw", None)) and isinstance(getattr(patch_drop, "grid", None), int)):
+            raise ValueError("patch_drop must be a PatchDropout with its grid (PatchDropout(prob, size=, patch=) or grid=)")
         if color is not None and not (callable(getattr(color, "draw", None)) and isinstance(getattr(color, "Hi", None), int)
                                       and isinstance(getattr(color, "Wi", None), int)):
             raise ValueError("color must be a ColorJitterErase (anything with draw(B, steps, generator), Hi and Wi)")
@@ -568,7 +645,15 @@ class ResidentSplit:
             table = torch.stack(idx)
             if int(table.min()) < 0 or int(table.max()) >= len(self):
                 raise ValueError(f"epoch {epoch}: a drawn index is outside [0, {len(self)})")
-            boxes = mixes = augs = None
+            boxes = mixes = augs = keeps = None
+            if patch_drop is not None:
+                keeps = patch_drop.draw(patch_drop.grid, table.shape[1], table.shape[0],
+                                        torch.Generator().manual_seed(keep_seed(seed, epoch, rank)))
+                if not torch.is_tensor(keeps) or keeps.ndim != 3 or tuple(keeps.shape[:2]) != tuple(table.shape):
+                    raise ValueError(f"patch_drop.draw gave {tuple(keeps.shape) if torch.is_tensor(keeps) else type(keeps).__name__}, "
+                                     f"not an int32 {(*table.shape, 'K')} table")
+                check_keep(keeps, table.shape[1], patch_drop.grid)
+                keeps = keeps.contiguous().to(self.pixels.device)
             if augment is not None:
                 Hs, Ws = self.pixels.shape[2:]
                 gen = torch.Generator().manual_seed(box_seed(seed, epoch, rank))
@@ -591,7 +676,10 @@ class ResidentSplit:
                 augs = augs.contiguous().to(self.pixels.device)
             table = table.to(self.pixels.device)
             for step in range(table.shape[0]):
-                if augs is not None:
+                if keeps is not None:
+                    yield (table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]),
+                           (None if augs is None else augs[step]), keeps[step])
+                elif augs is not None:
                     yield table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]), augs[step]
                 elif mixes is not None:
                     yield table[step], (None if boxes is None else boxes[step]), mixes[step]
@@ -630,7 +718,7 @@ class ResidentSplit:
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
              seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False, augment=None,
-             train_size: Optional[int] = None, mix=None, color=None):
+             train_size: Optional[int] = None, mix=None, color=None, patch_drop=None):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
@@ -642,9 +730,11 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     model's size) and its ``train_rows`` yields ``(rows, boxes)`` drawn by ``augment`` -- "resize 256, random-resized-crop
     224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size.
     ``mix`` (with ``resident_feed``; a ``MixupCutmix``): ``train_rows`` yields ``(rows, boxes or None, mix)``.
-    ``color`` (with ``resident_feed``; a ``ColorJitterErase``): ``train_rows`` yields ``(rows, boxes or None, mix or None, aug)``."""
-    if (augment is not None or train_size is not None or mix is not None or color is not None) and not resident_feed:
-        raise ValueError("augment / train_size / mix / color belong to the resident feed: pass resident_feed=True")
+    ``color`` (with ``resident_feed``; a ``ColorJitterErase``): ``train_rows`` yields ``(rows, boxes or None, mix or None, aug)``.
+    ``patch_drop`` (with ``resident_feed``; a ``PatchDropout`` with its grid): ``train_rows`` yields the 5-tuple ending in ``keep``."""
+    if (augment is not None or train_size is not None or mix is not None or color is not None or patch_drop is not None) \
+            and not resident_feed:
+        raise ValueError("augment / train_size / mix / color / patch_drop belong to the resident feed: pass resident_feed=True")
     if train_size is not None and train_size != 224 and augment is None:
         raise ValueError("a training split of another size than the model's is read through crop boxes: pass augment")
     root = root if root is not None else "./data/vtab-1k/" + name
@@ -653,7 +743,8 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
     if resident_feed:
         feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix,
-                                        **({"color": color} if color is not None else {})))
+                                        **({"color": color} if color is not None else {}),
+                                        **({"patch_drop": patch_drop} if patch_drop is not None else {})))
     else:
         feed = train.train_batches(batch_size, seed=seed)
     return feed, (test if shard_eval else test.eval_batches(256))

@@ -184,7 +184,27 @@ class CaraEngine:
         self._ingest_sig = self._signature(model)
 
     # ------------------------------------------------------------------ per-shape state
-    def _state(self, model, B, img, dev):
+    def _pos_rows(self, need, dev):
+        """The token assembly adds row ``t`` of ``pos_embed`` to token ``t`` (row ``1 + keep[b][j]`` behind a patch dropout) and is not
+        told how many rows there are.  Images of another size than the model's own -- a resident split read without boxes -- ask for
+        ``need`` = grid + 1 rows; where the model has fewer, the kernels get a copy padded with zero rows (those tokens carry no
+        position), so that nothing is read past the end of the parameter.  Said once per engine."""
+        t, w = self._ingested
+        have = t["pos"].shape[0]
+        if have >= need:
+            return
+        if not self.__dict__.get("_warned_pos"):
+            self._warned_pos = True
+            import warnings
+            warnings.warn(f"cara_amd: images of {need - 1} patches on a model whose pos_embed has {have - 1}: the patches beyond get no "
+                          "position embedding (resize the model, or read the split through crop boxes of the model's size)", stacklevel=4)
+        pad = torch.zeros(need, t["pos"].shape[1], dtype=torch.float32, device=dev)
+        pad[:have].copy_(t["pos"])
+        t["pos"] = pad
+        w.pos = ptr(pad)
+
+    def _state(self, model, B, img, dev, tokens=None):
+        """``tokens``: 1 + K of a step behind a patch dropout; None = the grid's (img / patch)^2 + 1"""
         if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
             self._ingest(model, dev)
             self._ws.clear()
@@ -194,16 +214,20 @@ class CaraEngine:
             raise CaraError(f"weight_dropout must be 'off' or 'exact', not {self.weight_dropout!r}")
         if exact and self.cp_length == 2:
             raise CaraError("cp_length 2 (dense QKV deltas) runs with weight_dropout = 'off' only")
-        key = (B, img, ncls, str(dev), exact, self._operands(), self._slot)
+        pe = model.patch_embed
+        self._pos_rows((img // pe.proj.kernel_size[0]) ** 2 + 1, dev)
+        if tokens is None:
+            tokens = (img // pe.proj.kernel_size[0]) ** 2 + 1
+        # (the token count is part of the key: a kept step and a full step of the same batch have workspaces of their own)
+        key = (B, img, ncls, str(dev), exact, self._operands(), self._slot, tokens)
         st = self._ws.get(key)
         if st is None:
-            pe = model.patch_embed
             geom = L.Geom(len(model.blocks), model.embed_dim, model.blocks[0].attn.num_heads, self.rank, self.Rp, self.scale,
                           self.cp_length)
             # (sized with the exact-mode regions when that mode is selected; a call with wd_exact = 0 on the same
             # workspace -- eval -- simply does not touch them)
             patch = pe.proj.kernel_size[0]
-            shape = L.VitShape(B, img, patch, pe.proj.in_channels, (img // patch) ** 2 + 1, ncls,
+            shape = L.VitShape(B, img, patch, pe.proj.in_channels, tokens, ncls,
                                float(model.norm.eps), 1 if exact else 0, float(self.weight_dropout_p), 0)
             nbytes = self._lib().cara_vit_workspace_bytes(C.byref(geom), C.byref(shape))
             if nbytes == 0:
@@ -222,25 +246,38 @@ class CaraEngine:
         return L.cp_ptrs(self.cp_fields, cp)
 
     # ------------------------------------------------------------------ forward / backward
-    def _run_forward(self, images, droppath, head_w, head_b, cp, need_backward=True):
+    def _run_forward(self, images, droppath, head_w, head_b, cp, need_backward=True, keep=None):
         model = self._model()
         if images.ndim != 4 or images.shape[2] != images.shape[3]:
             raise CaraError("images must be [B, C, H, H]")
         images = images.contiguous().float()
         dev = images.device
         with torch.cuda.device(dev):   # the library enqueues on the stream it is given and launches on the current device
-            return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev)
+            return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev, keep=keep)
 
-    def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None):
+    def _check_keep(self, keep, B, img, dev):
+        """``keep`` of a patch dropout (``data.PatchDropout.draw``, one step's [batch, K] view), refused before anything is enqueued"""
+        model = self._model()
+        P = (img // model.patch_embed.proj.kernel_size[0]) ** 2
+        if not torch.is_tensor(keep) or keep.dtype != torch.int32 or keep.ndim != 2 or keep.shape[0] != B or not keep.is_contiguous() \
+                or keep.device != dev or not (1 <= keep.shape[1] <= P):
+            raise CaraError(f"keep must be a contiguous int32 [batch, K] tensor of patch indices on the model's device, 1 <= K <= {P} "
+                            "(data.PatchDropout.draw, data.check_keep)")
+
+    def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None, keep=None):
         """``resident = (split, rows[, boxes[, mix[, aug]]])``: the images are rows of a resident uint8 split (``images`` is None
         then), with ``boxes`` read through a crop box per sample at the model's own input size, with ``mix`` mixed by that table, with
-        ``aug`` colour-jittered and erased by that one"""
+        ``aug`` colour-jittered and erased by that one.  ``keep`` (device int32 [batch, K]): the patch tokens a patch dropout keeps;
+        the blocks then run on 1 + K tokens, on a workspace of that size"""
         boxes = mix = aug = None
         if resident is None:
-            st = self._state(model, images.shape[0], images.shape[2], dev)
+            B, img = images.shape[0], images.shape[2]
         else:
             split, rows, boxes, mix, aug = (*resident, None, None, None)[:5]
-            st = self._state(model, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
+            B, img = rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model)
+        # (keep was checked by the caller -- train_step, train_step_resident, forward_resident -- before anything was enqueued)
+        st = self._state(model, B, img, dev, None if keep is None else 1 + keep.shape[1])
+        if resident is not None:
             if st["shape"].chans != 3:
                 raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
         # weight-space dropout is a train-mode thing (nn.Dropout is the identity in eval); the backward of this
@@ -263,7 +300,17 @@ class CaraEngine:
         logits = torch.empty_like(st["logits"])
         args = (C.byref(st["geom"]), C.byref(st["shape"]), C.byref(self._ingested[1]), C.byref(cps),
                 ptr(head_w.detach().contiguous()), ptr(head_b.detach().contiguous()))
-        if resident is None:
+        if keep is not None and resident is None:
+            check(self._lib().cara_vit_forward_keep(*args, ptr(images), ptr(keep), ptr(droppath), ptr(st["ws"]), ptr(logits),
+                                                    ptr(self._bad_rows(dev)), stream(dev)), "cara_vit_forward_keep")
+        elif keep is not None:
+            mean, std = self._eval_norm(dev)
+            check(self._lib().cara_vit_forward_u8_rows_keep(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
+                                                            split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(aug),
+                                                            ptr(self._aug_stat(dev, rows.shape[0])) if aug is not None else None,
+                                                            ptr(keep), ptr(mean), ptr(std), ptr(droppath), ptr(st["ws"]), ptr(logits),
+                                                            ptr(self._bad_rows(dev)), stream(dev)), "cara_vit_forward_u8_rows_keep")
+        elif resident is None:
             check(self._lib().cara_vit_forward(*args, ptr(images), ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)),
                   "cara_vit_forward")
         elif aug is not None:
@@ -578,7 +625,7 @@ class CaraEngine:
             return self._clip_flat(max_norm)
 
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
-                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None):
+                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, keep=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -597,14 +644,19 @@ class CaraEngine:
         before the optimiser (``cara_grad_clip``: two launches, no host read, bitwise the same on every rank); ``grad_norm`` then
         holds the device tensor (norm before the clip, coefficient).
         ``ema`` (a ``ParamEma`` of ``make_ema``): its one-launch update runs last in the tail, behind ``optimizer.step()`` -- with a
-        window, at its last micro-step only.  A step skipped for an fp16 overflow updates the average too (cara_amd/ema.py)."""
+        window, at its last micro-step only.  A step skipped for an fp16 overflow updates the average too (cara_amd/ema.py).
+        ``keep`` (device int32 [batch, K], e.g. one step of ``data.PatchDropout.draw``): patch dropout -- sample ``i`` trains on
+        its cls token and the K patch tokens ``keep[i]``, each with its own row of the position embedding
+        (``cara_vit_forward_keep``); the blocks run on 1 + K tokens.  None runs the step it was."""
         eps = self._smoothing(label_smoothing)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
+        if keep is not None:
+            self._check_keep(keep, images.shape[0], images.shape[-1], dev)
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
-        return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp),
+        return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp, keep=keep),
                           lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema)
 
     def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None,
@@ -735,11 +787,12 @@ class CaraEngine:
             raise CaraError(aug_msg)
         return model, dev
 
-    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None, aug=None):
+    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None, aug=None, keep=None):
         model = self._model()
         dev = rows.device
         with torch.cuda.device(dev):
-            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix, aug))
+            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix, aug),
+                                        keep=keep)
 
     def _gather_labels(self, split, rows):
         dev, B = rows.device, rows.shape[0]
@@ -754,7 +807,7 @@ class CaraEngine:
         return buf
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
-                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None):
+                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -773,22 +826,30 @@ class CaraEngine:
         sample's brightness / contrast / saturation chain on its unmixed crop (the partner's own chain on the partner), then the
         mix, the normalisation and the erase rectangle (``cara_vit_forward_u8_rows_aug``; with or without ``boxes`` and ``mix``).
         A table entry the kernel refuses -- ``data.check_aug`` -- gives a zero image, counted like a bad row.
+        ``keep`` (device int32 [batch, K], e.g. ``data.PatchDropout.draw``): patch dropout as in ``train_step`` -- only the kept
+        patches' rows are built, each bit for bit the row the step without ``keep`` builds (``cara_vit_forward_u8_rows_keep``; with
+        or without the other tables).  An entry outside the grid gives a zero patch row without a position, counted like a bad row.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
-        _, dev = self._resident_args(split, rows, boxes, mix, aug)
-        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix, aug),
+        model, dev = self._resident_args(split, rows, boxes, mix, aug)
+        if keep is not None:
+            self._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix, aug, keep),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema)
 
-    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None):
+    def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
+                         keep=None):
         """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``,
-        ``mix`` and ``aug`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
+        ``mix``, ``aug`` and ``keep`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
         model, dev = self._resident_args(split, rows, boxes, mix, aug)
+        if keep is not None:
+            self._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
         cp, hw, hb = self._forward_weights(model, dev, weights)
         self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix, aug)
+            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix, aug, keep)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):
@@ -797,6 +858,7 @@ class CaraEngine:
         if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
             self._ingest(model, dev)
         ews = self.__dict__.setdefault("_eval_ws", {})
+        self._pos_rows((img // model.patch_embed.proj.kernel_size[0]) ** 2 + 1, dev)
         ncls = model.head.out_features
         key = (B, img, ncls, str(dev), self._operands())
         st = ews.get(key)

@@ -110,6 +110,9 @@ def evaluate_only(model, path: str, test_batches: Iterable) -> float:
     return evaluate(model, test_batches)
 
 
+KEEP_AHEAD = 64   # steps of keep tables per draw of fit(patch_drop=)
+
+
 class GraphedTrainStep:
     """``CaraEngine.train_step`` captured into a hipGraph and replayed (``cara_vit_forward`` / ``cara_vit_backward`` only enqueue
     work on the caller's stream, include/cara_hip.h; the optimiser must be ``cara_amd.optim.AdamW(capturable=True)``: its step count
@@ -158,33 +161,42 @@ class GraphedTrainStep:
         if self.eng._window(accumulate)[1] > 1:
             raise CaraError("GraphedTrainStep: accumulate with k > 1 is not supported (the window spans several graph replays)")
 
-    def __call__(self, x, y, group=None, accumulate=None):
+    def __call__(self, x, y, group=None, accumulate=None, keep=None):
         """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector, or
         ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table, or ``(split, (rows, boxes_or_None, mix))``:
         with a device int32 [batch, 8] mix table too, or ``(split, (rows, boxes_or_None, mix_or_None, aug))``: with a device int32
-        [batch, 16] colour-jitter / erase table"""
+        [batch, 16] colour-jitter / erase table, or ``(split, (rows, boxes_or_None, mix_or_None, aug_or_None, keep))``: with a device
+        int32 [batch, K] patch-dropout table.  ``keep=`` hands that table to the ``(images, labels)`` and ``(split, rows)`` forms.
+        The table is one more static input, copied before every replay (4 K bytes per sample); its shape is part of the graph's key,
+        so another K captures another graph."""
         from . import dist as cdist
         self._refuse_window(accumulate)
         eng, model = self.eng, self.eng._model()
         resident = hasattr(x, "pixels")
-        if resident and isinstance(y, (tuple, list)):
-            return self._call_tables(x, y[0], y[1], y[2] if len(y) > 2 else None, group, **({"aug": y[3]} if len(y) > 3 else {}))
+        if resident and (isinstance(y, (tuple, list)) or keep is not None):
+            y = (*y, None, None, None, None)[:5] if isinstance(y, (tuple, list)) else (y, None, None, None, None)
+            kp = y[4] if y[4] is not None else keep
+            return self._call_tables(x, y[0], y[1], y[2], group, **({} if y[3] is None else {"aug": y[3]}), **({} if kp is None else {"keep": kp}))
         kw = self._kw()
-        step = (lambda a, b, opt, group=None: eng.train_step_resident(a, b, opt, group=group, **kw)) if resident else \
-            (lambda a, b, opt, group=None: eng.train_step(a, b, opt, group=group, **kw))
+        if keep is not None:   # (refused here, not inside a capture)
+            if x.ndim != 4 or x.shape[2] != x.shape[3]:
+                raise CaraError("images must be [B, C, H, H]")
+            eng._check_keep(keep, x.shape[0], x.shape[2], x.device)
+        step = (lambda a, b, opt, group=None, k=None: eng.train_step_resident(a, b, opt, group=group, **kw)) if resident else \
+            (lambda a, b, opt, group=None, k=None: eng.train_step(a, b, opt, group=group, **kw, **({} if k is None else {"keep": k})))
         self._advance()
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
-            return step(x, y, self.opt, group=group)
+            return step(x, y, self.opt, group=group, k=keep)
         # (the split itself is part of a resident key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
         key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision, self.label_smoothing,
-               self.clip_grad)
+               self.clip_grad, *(() if keep is None else (("keep", tuple(keep.shape)),)))
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
-            return step(x, y, self.opt, group=group)
+            return step(x, y, self.opt, group=group, k=keep)
         dev = y.device
         if ent == "warm":
-            xs, ys = (x if resident else x.clone()), y.clone()
+            xs, ys, ks = (x if resident else x.clone()), y.clone(), (None if keep is None else keep.clone())
             torch.cuda.synchronize(dev)
             gr = torch.cuda.CUDAGraph()
             gen = eng._device_generator(dev)
@@ -194,37 +206,43 @@ class GraphedTrainStep:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 with torch.cuda.graph(gr, stream=side):
-                    loss = step(xs, ys, self.opt, group=group)
+                    loss = step(xs, ys, self.opt, group=group, k=ks)
             torch.cuda.current_stream(dev).wait_stream(side)
             # (the last element keeps what the engine would replace at an eager step of another batch size in between -- its dlogits
             # buffer and the workspace of this shape -- as ``loss`` keeps its loss buffer: the graph holds their addresses)
-            ent = self._graphs[key] = (gr, xs, ys, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
+            ent = self._graphs[key] = (gr, xs, ys, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]), ks)
             # (the capture itself ran nothing: fall through to the replay, which is this call's step)
         gr, xs, ys, loss = ent[:4]
         if not resident:
             xs.copy_(x)
         ys.copy_(y)
+        if keep is not None:
+            ent[5].copy_(keep)
         gr.replay()
         return loss
 
-    def _call_tables(self, split, rows, boxes, mix, group, aug=None):
-        """the resident form through crop boxes and / or a mix table and / or an aug table: warm, capture, replay as above, with two
-        to four static inputs"""
+    def _call_tables(self, split, rows, boxes, mix, group, aug=None, keep=None):
+        """the resident form through crop boxes and / or a mix table and / or an aug table and / or a keep table: warm, capture,
+        replay as above, with one to five static inputs"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
         eng._resident_args(split, rows, boxes, mix, *(() if aug is None else (aug,)))     # (refused here, not inside a capture)
+        if keep is not None:
+            eng._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else eng._model_img(model), rows.device)
         self._advance()
-        tables = [t for t in (boxes, mix, aug) if t is not None]
+        tables = [t for t in (boxes, mix, aug, keep) if t is not None]
 
         def step(rs, ts):
             ts = list(ts)
             return eng.train_step_resident(split, rs, self.opt, group=group, boxes=ts.pop(0) if boxes is not None else None,
                                            **({"mix": ts.pop(0)} if mix is not None else {}),
-                                           **({"aug": ts.pop(0)} if aug is not None else {}), **self._kw())
+                                           **({"aug": ts.pop(0)} if aug is not None else {}),
+                                           **({"keep": ts.pop(0)} if keep is not None else {}), **self._kw())
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(rows, tables)
         key = (("rows+boxes" if mix is None else "rows+boxes+mix", split, tuple(rows.shape), boxes is not None and tuple(boxes.shape),
-                mix is not None and tuple(mix.shape), *(() if aug is None else (("aug", tuple(aug.shape)),))), bool(model.training),
+                mix is not None and tuple(mix.shape), *(() if aug is None else (("aug", tuple(aug.shape)),)),
+                *(() if keep is None else (("keep", tuple(keep.shape)),))), bool(model.training),
                eng.precision, self.label_smoothing, self.clip_grad)
         ent = self._graphs.get(key)
         if ent is None:
@@ -257,7 +275,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
-        accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False):
+        accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -300,7 +318,17 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     afterwards -- and call ``on_eval(epoch, raw_accuracy, averaged_accuracy)``; the AVERAGED accuracy is the one that is compared,
     returned and named in the checkpoint file, and ``save_best`` writes the averaged weights (``save_checkpoint(weights=)``).
     The average is left in ``model._cara_engine.ema``.  ``ema_decay = None``: nothing of this runs and ``on_eval(epoch, accuracy)``
-    is called as before."""
+    is called as before.
+    ``patch_drop`` (a ``data.PatchDropout``; the ``"batches"`` feed): every training step runs on the kept patch tokens of a table
+    drawn on the host from a generator seeded by (seed, epoch, rank) on the stream of ``data.keep_seed`` -- one generator per epoch,
+    drawn ``KEEP_AHEAD`` steps at a time (the feed does not say how many batches an epoch has), checked (``data.check_keep``) and
+    uploaded once per draw; each step gets a [batch, K] view (``train_step(..., keep=)``).  Every micro-batch of an accumulation
+    window has its own rows, every rank its own stream, and the graphed step takes the table as a static input.  The evaluation
+    epochs see every patch.  The resident feed carries its table itself: ``train_rows(..., patch_drop=)``."""
+    if patch_drop is not None and feed != "batches":
+        raise CaraError("fit: patch_drop is the 'batches' feed's; the resident feed carries its table itself (train_rows(..., patch_drop=))")
+    if patch_drop is not None and not callable(getattr(patch_drop, "draw", None)):
+        raise CaraError("fit: patch_drop must be a data.PatchDropout (anything with draw(P, B, steps, generator))")
     if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
         raise CaraError(f"accum_steps must be an integer >= 1, not {accum_steps!r}")
     if graph and accum_steps > 1:
@@ -339,6 +367,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
 
         def step(split, rows, opt, group=None, **win):
             if isinstance(rows, (tuple, list)):
+                if len(rows) > 4:   # (train_rows(..., patch_drop=): None for the tables not asked for)
+                    rows, boxes, mix, aug, keep = rows
+                    tables = {k: v for k, v in (("boxes", boxes), ("mix", mix), ("aug", aug), ("keep", keep)) if v is not None}
+                    return eng.train_step_resident(split, rows, opt, group=group, **tables, **smooth, **win)
                 if len(rows) > 3:
                     rows, boxes, mix, aug = rows
                     return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **({} if mix is None else {"mix": mix}), aug=aug,
@@ -352,6 +384,28 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     else:
         def step(x, y, opt, group=None, **win):
             return eng.train_step(x, y, opt, group=group, **smooth, **win)
+    drawn = {"epoch": None}
+
+    def keep_of(epoch, x):
+        """the next step's [batch, K] view of the epoch's keep table ({} without a patch dropout)"""
+        if patch_drop is None:
+            return {}
+        from .data import check_keep, keep_seed
+        if x.ndim != 4 or x.shape[2] != x.shape[3]:
+            raise CaraError("images must be [B, C, H, H]")
+        B, P = x.shape[0], (x.shape[2] // model.patch_embed.proj.kernel_size[0]) ** 2
+        if getattr(patch_drop, "grid", None) not in (None, P):
+            raise CaraError(f"fit: patch_drop was built for a grid of {patch_drop.grid} patches, the images have {P}")
+        if drawn["epoch"] != epoch:
+            drawn.update(epoch=epoch, gen=torch.Generator().manual_seed(keep_seed(seed, epoch, cdist.get_rank(group))), table=None, next=0)
+        t = drawn["table"]
+        if t is None or drawn["next"] >= t.shape[0] or t.shape[1] != B:
+            t = patch_drop.draw(P, B, KEEP_AHEAD, drawn["gen"])
+            check_keep(t, B, P)
+            t = drawn["table"] = t.contiguous().to(x.device)
+            drawn["next"] = 0
+        drawn["next"] += 1
+        return {"keep": t[drawn["next"] - 1]}
 
     def check_rows(upto):
         # (data parallel: a rank that raised alone would leave the others waiting in the next all-reduce.  train_rows range-checks
@@ -360,22 +414,23 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         if bad:
             raise CaraError(f"fit: {bad} row index(es) outside the training split (or crop boxes outside their image, or mix entries "
                             f"with a partner outside the batch, a rectangle outside the output or a weight outside [0, 1], or aug entries "
-                            f"data.check_aug refuses) reached "
+                            f"data.check_aug refuses, or keep entries outside the patch grid) reached "
                             f"the device up to epoch {upto}")
     for epoch in range(epochs):
         window = []
         for x, y in train_batches(epoch):
+            kept = keep_of(epoch, x) if feed == "batches" else {}
             if accum_steps > 1:
-                window.append((x, y))
+                window.append((x, y, kept))
                 if len(window) < accum_steps:
                     continue                    # (what is left in `window` when the epoch ends is dropped)
-                for i, (wx, wy) in enumerate(window):
-                    step(wx, wy, opt, group=group, accumulate=(i, accum_steps))
+                for i, (wx, wy, wk) in enumerate(window):
+                    step(wx, wy, opt, group=group, accumulate=(i, accum_steps), **wk)
                 window = []
             elif gstep is not None:
-                gstep(x, y, group=group)
+                gstep(x, y, group=group, **kept)
             else:
-                step(x, y, opt, group=group)
+                step(x, y, opt, group=group, **kept)
             if sched is not None:
                 sched.step(epoch)
         if epoch % 10 == 0 and epoch != 0:

@@ -367,6 +367,21 @@ size_t cara_aug_stat_bytes(int B);
 int cara_im2col_patches_u8_rows_aug(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
                                     const int* boxes, const int* mix, const int* aug, void* stat_scratch, const float* mean,
                                     const float* std, void* patches, int* bad, int B, int C, int Hi, int Wi, int p, void* stream);
+/* Patch dropout (timm's PatchDropout): the patch rows of a kept subset only.  keep device int32 [B,K], 1 <= K <= P = (Hi/p) (Wi/p),
+ * entries in [0, P) (patch index gy (Wi/p) + gx), any order; the host refuses duplicates within a sample, the device does not look.
+ * Output row b K + j is the patch row of patch keep[b][j] of sample b: patches bf16 [B*K, C*p*p].  Everything a row holds is a
+ * function of its pixels' positions in the FULL Hi x Wi output image, so a kept row is bit for bit the row of the same patch that
+ * the call without keep writes -- cara_im2col_patches for the first entry; for the second cara_im2col_patches_u8_rows_aug with the
+ * same tables, each of boxes / mix / aug NULL or not under that entry's rules (the contrast pre-pass is that entry's, unchanged: it
+ * still reduces the whole image; the erase noise keeps its element index i in [B,C,Hi,Wi]).  A keep entry outside [0, P) is never
+ * used as an index: its row is zeros and *bad (may be NULL) is incremented once per such entry.  A sample that the rules above call
+ * bad (row, box, mix or aug entry) gets K zero rows and is counted once; its keep entries are not counted again.                  */
+int cara_im2col_patches_keep(const float* img, const int* keep, int K, void* patches, int* bad, int B, int C, int Hi, int Wi,
+                             int p, void* stream);
+int cara_im2col_patches_u8_rows_keep(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                     const int* boxes, const int* mix, const int* aug, void* stat_scratch, const int* keep, int K,
+                                     const float* mean, const float* std, void* patches, int* bad, int B, int C, int Hi, int Wi,
+                                     int p, void* stream);
 /* out[i] = labels[rows[i]] (device int64 [B] each; labels int64 [n_split]); a row outside [0, n_split) is not
  * dereferenced: it gives 0 and is counted in *bad (device int, may be NULL)                                    */
 int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
@@ -374,6 +389,12 @@ int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, 
 /* x fp32 [B,1+P,D]: row 0 = cls + pos[0]; row 1+i = emb[b*P+i] + pos[1+i]                      */
 int cara_assemble_tokens(const float* emb, const float* cls, const float* pos, float* x, int B,
                          int P, int D, void* stream);
+/* cara_assemble_tokens behind a patch dropout: emb fp32 [B*K, D] holds the kept patches' embeddings (row b K + j = patch keep[b][j]),
+ * pos fp32 [1+P, D] the full position embedding.  x fp32 [B,1+K,D]: row 0 = cls + pos[0]; row 1+j = emb[b*K+j] + pos[1 + keep[b][j]],
+ * one fp32 add -- with keep[b][j] = j and K == P bit for bit cara_assemble_tokens.  For an entry outside [0, P) pos is not
+ * dereferenced and the row is emb's alone.  (P is an argument because the range of keep is not otherwise known here.)              */
+int cara_assemble_tokens_keep(const float* emb, const float* cls, const float* pos, const int* keep, float* x, int B, int K,
+                              int P, int D, void* stream);
 /* loss[0] = mean cross-entropy over B (loss must hold 1 + B floats: [1..B] is scratch);
  * dlogits (optional) = (softmax - onehot)/B ; logits fp32 [B,C]   (vit_cp.py:47)
  * A label outside [0, C) is never used as an index: that sample's term loss[1 + b], its dlogits row and loss[0] are NaN. */
@@ -669,6 +690,23 @@ int cara_vit_forward_u8_rows_aug(const cara_geom* g, const cara_vit_shape* s, co
                                  int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes, const int* mix,
                                  const int* aug, void* stat_scratch, const float* mean, const float* std, const float* droppath,
                                  void* workspace, float* logits, int* bad, void* stream);
+/* Patch dropout: the forward on a kept subset of the patch tokens.  cara_vit_shape::tokens may be anything in [2, (img/patch)^2 + 1]
+ * for cara_vit_workspace_bytes, cara_vit_backward and the two entries below; every per-token region is sized by it, and at tokens ==
+ * (img/patch)^2 + 1 every size is what it was.  The entries above take tokens == (img/patch)^2 + 1 only (CARA_E_ARG otherwise, nothing
+ * launched: they write all patch rows).  keep device int32 [B,K] with K == tokens - 1 (CARA_E_ARG otherwise), bad may be NULL:
+ * the patch rows come from cara_im2col_patches_keep / cara_im2col_patches_u8_rows_keep (boxes, mix, aug each NULL or not; stat_scratch
+ * with aug), the tokens from cara_assemble_tokens_keep; the blocks, the final norm and the head see 1 + K tokens and know nothing of
+ * the subset -- the launches of a model whose grid has K patches, on a workspace of cara_vit_workspace_bytes for this shape; a
+ * cara_vit_backward with the same shape may follow (the patch embedding and pos are frozen: the backward reaches nothing in front of
+ * the blocks).  With keep[b][j] = j, K = (img/patch)^2, logits and every gradient are bit for bit those of the entry without keep.    */
+int cara_vit_forward_keep(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp,
+                          const float* head_w, const float* head_b, const float* images, const int* keep, const float* droppath,
+                          void* workspace, float* logits, int* bad, void* stream);
+int cara_vit_forward_u8_rows_keep(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp,
+                                  const float* head_w, const float* head_b, const unsigned char* pixels, int n_split, int Hs, int Ws,
+                                  const int64_t* rows, const int* boxes, const int* mix, const int* aug, void* stat_scratch,
+                                  const int* keep, const float* mean, const float* std, const float* droppath, void* workspace,
+                                  float* logits, int* bad, void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,
