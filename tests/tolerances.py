@@ -55,3 +55,14 @@ def logits_ok(r_ref: float, r_model: float) -> bool:
 # up to the next of 0.5 %, 1 %, 2 %; never fitted to a device.  Measured: gelu_h 0.0030 (fp16; bf16 none) -> 1 %; dgelu 0.0010
 # (fp16; bf16 0.0006) -> 0.5 %; bf16, T 0.0001 (fp16), gelu_u, gelu_dg, mulh none -> 0.5 %.
 GEMM_CAPS = {"bf16": 0.005, "gelu_h": 0.01, "gelu_u": 0.005, "gelu_dg": 0.005, "dgelu": 0.005, "mulh": 0.005, "T": 0.005}
+
+# The adapter-side kernels (oracle/adapter_model.py), per 16-bit output kind, under the same rule as GEMM_CAPS (the share is taken
+# over the elements whose derived term is below a quarter of their own 16-bit step; one neighbour case never breaks a cap).
+# "pack": the entries of cara_factor_prep's pack that are products of one to five fp32 numbers (Vs_*, U_fc2; the copies U_qkv,
+# U_proj, U_fc1 are held bitwise), all layers of one matrix taken as one tensor.  Their derived term gamma(5) |v| = 3e-7 |v| is at most 1 / 13000 of
+# a bf16 step (2^-8 |v| or more) and 1 / 1600 of an fp16 step (2^-11 |v| or more), so every element is capped and a neighbour needs v within that of a rounding boundary.
+# Started from SMALL_CAPS' 2 % and kept there: the fp32 other-order restatement (tests/test_adapter_model.py,
+# `python -m tests.test_adapter_model`; table in docs/findings/adapter_contract.md section 2) uses at most 0.0002 of a tensor over
+# all eight geometries, both draws and both builds (fp16: Vs_qkv of the order-5 geometry (5, 40, 5, 17); bf16: Vs_fc2 of the order-2
+# geometry; every other matrix 0.0001 or none), a hundredth of it; never fitted to a device.
+ADAPTER_CAPS = {"pack": 0.02}
