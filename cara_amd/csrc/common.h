@@ -65,6 +65,24 @@ int cara_layernorm_bwd_rows_in(const void* dy, const float* x, long ldx, const f
 // norm_misc.hip's argument check and dispatch, and vit.hip's plan (fuse only what the kernels take).
 bool cara_layernorm_takes(int C, bool fused);
 
+// One patch-row call of the feed (feed.hip): where the images are, which tables shape them, which rows are written.  Library-internal
+// (the cara_im2col_patches* entries and vit.hip's forward fill one), not part of include/cara_hip.h.  A pointer left NULL is a
+// feature not asked for; what is set picks the kernel.  A new feed feature is a field here and a parameter of a kernel body.
+struct cara_feed {
+  const float* images;                       // an fp32 batch [B,C,Hi,Wi] -- or:
+  const unsigned char* pixels;               // uint8 pixels, the batch [B,C,Hs,Ws] or (rows set) a whole split [n_split,C,Hs,Ws],
+  const float *mean, *stdv;                  //   with their per-channel mean / std
+  int n_split; const int64_t* rows;          // sample b is image rows[b] of the split
+  int* bad;                                  // counts refused samples and keep entries (may be NULL)
+  int Hs, Ws; const int* boxes;              // the source's size; a crop box [B,5] per sample (NULL: Hs == Hi, Ws == Wi, whole images)
+  const int* mix;                            // Mixup / CutMix table [B,8]
+  const int* aug; void* stat;                // colour jitter / erase table [B,16] and its scratch (cara_aug_stat_bytes)
+  const int* keep; int K;                    // patch dropout: the kept patches [B,K] (NULL: all gh gw rows of a sample)
+  int B, C, Hi, Wi, p;                       // the output: B samples of C x Hi x Wi in p x p patches
+};
+// checks a descriptor, picks its kernel and launches it (behind the contrast pre-pass where aug is set) -> patches [B (K or gh gw), C p p]
+int cara_feed_patch_rows(const cara_feed& f, void* patches, void* stream);
+
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 

@@ -307,684 +307,6 @@ __global__ __launch_bounds__(XU ? XU_WAVES * 64 : 256) void ln_bwd_kernel(const 
   }
 }
 
-// images fp32 [B,C,Hi,Wi] -> patch rows bf16 [B*gh*gw, C*p*p], column = (c*p + py)*p + px
-// (the flattening of Conv2d weight [D, C, p, p]); p == 16: one 16-float image row segment per
-// 4 lanes.
-__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, bf16* __restrict__ out,
-                                                     int B, int C, int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;  // one float4 of a patch row
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const int kcols = C * p * p;
-  const long e = idx * 4;
-  const long row = e / kcols;
-  const int col = (int)(e - row * kcols);
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
-  const int gy = pr / gw, gx = pr % gw;
-  const float4 v = *reinterpret_cast<const float4*>(img + (((size_t)b * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
-  bf16x4 o = {(bf16)v.x, (bf16)v.y, (bf16)v.z, (bf16)v.w};
-  *reinterpret_cast<bf16x4*>(out + e) = o;
-}
-
-// The same patch rows straight from resident uint8 pixels [B,C,Hi,Wi]: ToTensor + Normalize of vtab.py:92-94 in the fp32
-// operation order of data.normalize_u8 -- u / 255, - mean[c], / std[c], two correctly rounded divisions (no reciprocal
-// multiply: the build has no fast-math flag) -- then the one rounding to the build's 16-bit type that im2col_kernel applies
-// to the fp32 image.  The fp32 image tensor is never written.  Four pixels (one dword) per lane.
-__device__ __forceinline__ bf16x4 normalize_u8x4(unsigned u, float mu, float sd) {
-  const float v0 = ((float)(u & 255u) / 255.0f - mu) / sd;
-  const float v1 = ((float)((u >> 8) & 255u) / 255.0f - mu) / sd;
-  const float v2 = ((float)((u >> 16) & 255u) / 255.0f - mu) / sd;
-  const float v3 = ((float)(u >> 24) / 255.0f - mu) / sd;
-  return bf16x4{(bf16)v0, (bf16)v1, (bf16)v2, (bf16)v3};
-}
-__global__ __launch_bounds__(256) void im2col_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ mean,
-                                                        const float* __restrict__ stdv, bf16* __restrict__ out,
-                                                        int B, int C, int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const int kcols = C * p * p;
-  const long e = idx * 4;
-  const long row = e / kcols;
-  const int col = (int)(e - row * kcols);
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
-  const int gy = pr / gw, gx = pr % gw;
-  const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)b * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
-  *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
-}
-
-// im2col_u8_kernel over rows of a whole resident split [n_split,C,Hi,Wi] chosen by an index vector: the patch rows of sample b
-// come from image rows[b] (any order, duplicates allowed).  An index outside [0, n_split) is never dereferenced: that sample's
-// patch rows are zeros, and the lane that writes their first dword counts the sample in *bad (may be NULL).
-__global__ __launch_bounds__(256) void im2col_u8_rows_kernel(const uint8_t* __restrict__ img, long n_split,
-                                                             const int64_t* __restrict__ rows, const float* __restrict__ mean,
-                                                             const float* __restrict__ stdv, bf16* __restrict__ out,
-                                                             int* __restrict__ bad, int B, int C, int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const int kcols = C * p * p;
-  const long e = idx * 4;
-  const long row = e / kcols;
-  const int col = (int)(e - row * kcols);
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
-  const int gy = pr / gw, gx = pr % gw;
-  const int64_t r = rows[b];
-  if (r < 0 || r >= n_split) {
-    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
-    const bf16 z = (bf16)0.0f;
-    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
-    return;
-  }
-  const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)r * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
-  *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
-}
-
-// im2col_u8_rows_kernel through a crop box per sample: pixels [n_split,C,Hs,Ws] of any size, boxes int32 [B,5] = (x0, y0, w, h,
-// flip) in source pixels.  Output pixel (oy, ox) is the bilinear sample (half-pixel centres, no antialiasing filter: what
-// F.interpolate(crop, (Hi,Wi), "bilinear", align_corners=False) gives) of the box at ox' = flip ? Wi-1-ox : ox, with indices
-// clamped inside the box.  Each axis is evaluated as a + f * (b - a): the same polynomial as (1-f) a + f b, and exact where
-// f == 0 or a == b -- a box of the output's size gives the source bytes themselves and a 1x1 box a constant image, bit for
-// bit what normalize_u8x4 gives for that byte.  A lane keeps four adjacent output pixels of one patch row (one 8-byte store;
-// the row pair iy0 / iy1 and fy are shared) and fetches its source with byte loads: the box starts at any byte and Ws need
-// not be a multiple of 4, so no dword of the source is aligned; neighbouring lanes read neighbouring bytes of the same two
-// source rows.  A row outside [0, n_split) or a box not inside the source is never dereferenced: zeros, counted once in *bad.
-struct CropAxis { int i0, i1; float f; };
-__device__ __forceinline__ CropAxis crop_axis(int o, int n_out, int n_box, bool flip) {
-  const int of = flip ? n_out - 1 - o : o;
-  const float s = fmaxf(((float)of + 0.5f) * ((float)n_box / (float)n_out) - 0.5f, 0.0f);
-  const int i0 = min((int)s, n_box - 1);
-  return CropAxis{i0, min(i0 + 1, n_box - 1), s - (float)i0};
-}
-// normalize_u8x4's operations on a value that is no longer a byte
-__device__ __forceinline__ float normalize_f32(float v, float mu, float sd) { return (v / 255.0f - mu) / sd; }
-// the bilinear value of one output pixel, before normalisation: top / bot = the two source rows at the box's left edge
-__device__ __forceinline__ float crop_value(const uint8_t* top, const uint8_t* bot, const CropAxis& ax, float fy) {
-  const float t0 = (float)top[ax.i0], t1 = (float)top[ax.i1], b0 = (float)bot[ax.i0], b1 = (float)bot[ax.i1];
-  const float t = t0 + ax.f * (t1 - t0), u = b0 + ax.f * (b1 - b0);
-  return t + fy * (u - t);
-}
-__global__ __launch_bounds__(256) void im2col_u8_rows_crop_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                                  const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                                  const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                  bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
-                                                                  int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const int kcols = C * p * p;
-  const long e = idx * 4;
-  const long row = e / kcols;
-  const int col = (int)(e - row * kcols);
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
-  const int gy = pr / gw, gx = pr % gw;
-  const int64_t r = rows[b];
-  const int* box = boxes + (size_t)b * 5;
-  const int x0 = box[0], y0 = box[1], w = box[2], h = box[3];
-  const bool flip = box[4] != 0;
-  // (x0, y0 >= 0 is checked before Ws - x0, Hs - y0 are formed: no overflow for any int)
-  if (r < 0 || r >= n_split || w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > Ws - x0 || h > Hs - y0) {
-    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
-    const bf16 z = (bf16)0.0f;
-    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
-    return;
-  }
-  const CropAxis ay = crop_axis(gy * p + py, Hi, h, false);
-  const uint8_t* plane = img + ((size_t)r * C + c) * Hs * Ws;
-  const uint8_t* top = plane + (size_t)(y0 + ay.i0) * Ws + x0;
-  const uint8_t* bot = plane + (size_t)(y0 + ay.i1) * Ws + x0;
-  const float mu = mean[c], sd = stdv[c];
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = normalize_f32(crop_value(top, bot, crop_axis(gx * p + px + j, Wi, w, flip), ay.f), mu, sd);
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-
-// im2col_u8_rows_crop_kernel with Mixup / CutMix: mix int32 [B,8] = (partner, cx0, cy0, cw, ch, blend, target, 0).  Sample b is
-// mixed with what sample `partner` would be UNMIXED at the same output position (through rows[partner] and boxes[partner], its
-// flip included): inside the rectangle (cx0, cy0, cw, ch) of the output the pixel is the partner's, outside it a + m (b - a) on the
-// un-normalised 0..255 values, m = the fp32 whose bits `blend` holds -- exact at m == 0, like the axes' a + f (b - a).  Then
-// normalize_f32 and the one rounding to 16 bits.  `target` is the loss's (xent_mix_kernel).  boxes may be NULL: every sample reads
-// its whole image (the host then asks Hs == Hi, Ws == Wi).  The lane layout is the crop kernel's; a pixel loads only the image
-// it needs -- the partner alone inside the rectangle, its own alone outside it when m == 0 -- and a sample that is its own partner
-// checks one source, not two: an identity table costs the crop kernel's loads plus its table row.  Nothing is formed from an unchecked value: zeros, counted once in *bad, for a sample whose own or whose
-// partner's row or box is bad, whose partner is outside [0, B), whose rectangle is not inside the output or whose m is not in [0, 1].
-struct MixSource { const uint8_t* origin; int w, h; bool flip; };   // byte (y0, x0) of channel 0 of the image, and its box
-__device__ __forceinline__ bool mix_source(const uint8_t* img, long n_split, int C, int Hs, int Ws, const int64_t* rows,
-                                           const int* boxes, int b, MixSource* s) {
-  const int64_t r = rows[b];
-  int x0 = 0, y0 = 0, w = Ws, h = Hs, flip = 0;
-  if (boxes) {
-    const int* box = boxes + (size_t)b * 5;
-    x0 = box[0]; y0 = box[1]; w = box[2]; h = box[3]; flip = box[4];
-  }
-  // (the crop kernel's order: x0, y0 >= 0 before Ws - x0, Hs - y0 are formed)
-  if (r < 0 || r >= n_split || w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > Ws - x0 || h > Hs - y0) return false;
-  *s = MixSource{img + (size_t)r * C * Hs * Ws + (size_t)y0 * Ws + x0, w, h, flip != 0};
-  return true;
-}
-// the Mixup blend, one expression for the mix kernel and the jitter kernel (crop_value's argument)
-__device__ __forceinline__ float mix_blend(float a, float m, float b) { return a + m * (b - a); }
-__global__ __launch_bounds__(256) void im2col_u8_rows_mix_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                                 const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                                 const int* __restrict__ mix, const float* __restrict__ mean,
-                                                                 const float* __restrict__ stdv, bf16* __restrict__ out,
-                                                                 int* __restrict__ bad, int B, int C, int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const int kcols = C * p * p;
-  const long e = idx * 4;
-  const long row = e / kcols;
-  const int col = (int)(e - row * kcols);
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
-  const int gy = pr / gw, gx = pr % gw;
-  const int* mx = mix + (size_t)b * 8;
-  const int partner = mx[0], cx0 = mx[1], cy0 = mx[2], cw = mx[3], ch = mx[4];
-  const float m = __int_as_float(mx[5]);
-  MixSource own, oth;
-  // (partner is inside [0, B) before rows[partner] / boxes[partner] are formed; cx0, cy0 >= 0 before Wi - cx0, Hi - cy0; a NaN
-  // fails m >= 0)
-  const bool self = partner == b;
-  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) &&
-                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth))) && cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 &&
-                  cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
-  if (!ok) {
-    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
-    const bf16 z = (bf16)0.0f;
-    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
-    return;
-  }
-  if (self) oth = own;
-  const int oy = gy * p + py, ox0 = gx * p + px;
-  const CropAxis ay_own = crop_axis(oy, Hi, own.h, false), ay_oth = crop_axis(oy, Hi, oth.h, false);
-  const size_t chan = (size_t)c * Hs * Ws;
-  const uint8_t *top_own = own.origin + chan + (size_t)ay_own.i0 * Ws, *bot_own = own.origin + chan + (size_t)ay_own.i1 * Ws;
-  const uint8_t *top_oth = oth.origin + chan + (size_t)ay_oth.i0 * Ws, *bot_oth = oth.origin + chan + (size_t)ay_oth.i1 * Ws;
-  const bool row_in = oy >= cy0 && oy - cy0 < ch;
-  const float mu = mean[c], sd = stdv[c];
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int ox = ox0 + j;
-    float a;
-    if (row_in && ox >= cx0 && ox - cx0 < cw) {
-      a = crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f);
-    } else {
-      a = crop_value(top_own, bot_own, crop_axis(ox, Wi, own.w, own.flip), ay_own.f);
-      if (m != 0.0f) a = mix_blend(a, m, crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f));
-    }
-    v[j] = normalize_f32(a, mu, sd);
-  }
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-
-// im2col_u8_rows_mix_kernel with colour jitter and Random Erasing by index: aug int32 [B,16], row b =
-//   (op0, f0, op1, f1, op2, f2, ex0, ey0, ew, eh, emode, eseed, 0, 0, 0, 0)
-// op: 0 none, 1 brightness, 2 contrast, 3 saturation, each non-zero code at most once in a row, any order (torchvision's
-// ColorJitter draws a permutation); f: the bits of a finite fp32 factor >= 0 (not read where op == 0); (ex0, ey0, ew, eh): the erase
-// rectangle in output pixels (ew == 0 or eh == 0: none); emode 0 const, 1 pixel; eseed any 32 bits; the last four words 0.
-// All arithmetic below is fp32, every product and sum a single IEEE operation (plain operators under `fp contract(off)`), on the
-// un-normalised 0..255 values.  With u = a sample's own unmixed bilinear value (crop_value, shared with the crop and mix kernels):
-//   slot k = 0, 1, 2 in order:   v <- min(max(f v + (1 - f) d, 0), 255)       two products, one sum, and 1 - f rounded once
-//     brightness: d = 0;   saturation: d = gray = (0.2989 r + 0.587 g) + 0.114 b of THAT pixel's three channel values as they
-//     stand at that slot (three products, two sums, left to right);   contrast: d = M_b, the mean of gray over all Hi x Wi output
-//     pixels of sample b's image as it stands before the contrast slot (aug_gray_mean_kernel).
-//   torchvision's _blend on float tensors, rescaled to 0..255: exact at f == 1 (1 v + 0 d = v), d clamped at f == 0.
-//   Then the mix kernel's step, exactly: inside the CutMix rectangle the partner's value, outside it a + m (b - a) -- the partner's
-//   value being the partner's unmixed value after ITS OWN chain (its table row, its M).  Then normalize_f32.
-//   Then the erase: inside (ex0, ey0, ew, eh) the normalised value is replaced by 0 (const) or by a standard normal z (pixel: timm's
-//   RandomErasing(mode="pixel"), one rectangle):  i = ((b C + c) Hi + oy) Wi + ox, the element's index in [B,C,Hi,Wi];
-//     h1 = keep_hash(2 i, eseed, AUG_ERASE_STREAM),  h2 = keep_hash(2 i + 1, eseed, AUG_ERASE_STREAM);
-//     u1 = ((h1 >> 8) + 1) 2^-24 in (0, 1],  u2 = (h2 >> 8) 2^-24 in [0, 1)                    (both exact)
-//     z = sqrtf(-2 logf(u1)) cosf(6.2831855f u2): roundings at logf, the product with -2 (exact), sqrtf, the product 2 pi u2, cosf
-//     and the last product.  The host refuses 2 B C Hi Wi > 2^32.
-//   Then the one rounding to the build's 16-bit type.
-// Strict rule, check_mix's manner: nothing overflows and nothing is formed from an unchecked value.  An op outside [0, 3], a
-// repeated op, a factor that is negative, infinite or NaN, a rectangle not inside the output (ew, eh >= 0, ex0, ey0 >= 0, ew <= Wi -
-// ex0, eh <= Hi - ey0: the CutMix order), emode outside {0, 1} or a non-zero pad word: zero patch rows, counted once in *bad -- also
-// where the PARTNER's row fails.  mix may be NULL (no partner), boxes may be NULL (as in the mix kernel).  C == 3 (the host refuses
-// any other count).  Lane layout: the mix kernel's (four adjacent pixels of one channel, one 8-byte store); a lane loads the other
-// two channels only where a saturation slot is present, and a sample whose row is all zero does the mix kernel's loads plus its
-// 64-byte table row.
-constexpr int AUG_GROUPS = 16;                        // workgroups per sample in aug_gray_mean_kernel (fixed: part of the tree)
-constexpr unsigned AUG_ERASE_STREAM = 0x45524153u;    // keep_hash stream of the erase noise
-struct AugRow { int op[3]; float f[3]; int ex0, ey0, ew, eh, emode; unsigned eseed; int contrast_at; bool sat; };
-__device__ __forceinline__ bool aug_row(const int* aug, int b, int Hi, int Wi, AugRow* a) {
-  const int* r = aug + (size_t)b * 16;
-  bool ok = true;
-  int seen = 0;
-  a->contrast_at = 3;
-  a->sat = false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int op = r[2 * k];
-    float f = 0.0f;
-    if (op < 0 || op > 3) ok = false;
-    else if (op != 0) {
-      f = __int_as_float(r[2 * k + 1]);
-      if ((seen >> op) & 1) ok = false;
-      seen |= 1 << op;
-      if (!(f >= 0.0f && f <= 3.402823466e38f)) ok = false;   // (a NaN fails f >= 0)
-      if (op == 2) a->contrast_at = k;
-      if (op == 3) a->sat = true;
-    }
-    a->op[k] = op;
-    a->f[k] = f;
-  }
-  a->ex0 = r[6]; a->ey0 = r[7]; a->ew = r[8]; a->eh = r[9]; a->emode = r[10]; a->eseed = (unsigned)r[11];
-  // (ex0, ey0 >= 0 before Wi - ex0, Hi - ey0 are formed)
-  return ok && a->ew >= 0 && a->eh >= 0 && a->ex0 >= 0 && a->ey0 >= 0 && a->ew <= Wi - a->ex0 && a->eh <= Hi - a->ey0 &&
-         (a->emode == 0 || a->emode == 1) && (r[12] | r[13] | r[14] | r[15]) == 0;
-}
-__device__ __forceinline__ float aug_gray(float r, float g, float b) {
-#pragma clang fp contract(off)
-  return (0.2989f * r + 0.587f * g) + 0.114f * b;
-}
-__device__ __forceinline__ float aug_blend(float v, float d, float f, float omf) {
-#pragma clang fp contract(off)
-  return fminf(fmaxf(f * v + omf * d, 0.0f), 255.0f);
-}
-// slots [0, upto) of a row on one pixel: THREE: on its three channel values; otherwise on r alone (no saturation slot among them)
-template <bool THREE>
-__device__ __forceinline__ void aug_chain(float& r, float& g, float& b, const AugRow& a, int upto, float M) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int op = a.op[k];
-    if (k >= upto || op == 0) continue;
-    const float f = a.f[k], omf = 1.0f - f;
-    const float d = op == 3 ? aug_gray(r, g, b) : (op == 2 ? M : 0.0f);
-    r = aug_blend(r, d, f, omf);
-    if (THREE) {
-      g = aug_blend(g, d, f, omf);
-      b = aug_blend(b, d, f, omf);
-    }
-  }
-}
-__device__ __forceinline__ float aug_noise(unsigned i, unsigned seed) {
-#pragma clang fp contract(off)
-  const unsigned h1 = keep_hash(2u * i, seed, AUG_ERASE_STREAM), h2 = keep_hash(2u * i + 1u, seed, AUG_ERASE_STREAM);
-  const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-8f, u2 = (float)(h2 >> 8) * 5.9604644775390625e-8f;
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
-}
-// the two source rows of channel 0 that one output row of a sample reads, and what crop_axis needs for its columns
-struct AugSource { const uint8_t *top, *bot; size_t plane; float fy; int w; bool flip; };
-__device__ __forceinline__ AugSource aug_source(const MixSource& s, int oy, int Hi, int Hs, int Ws) {
-  const CropAxis ay = crop_axis(oy, Hi, s.h, false);
-  return AugSource{s.origin + (size_t)ay.i0 * Ws, s.origin + (size_t)ay.i1 * Ws, (size_t)Hs * Ws, ay.f, s.w, s.flip};
-}
-// channel c of output column ox after the sample's own chain
-__device__ __forceinline__ float aug_value(const AugSource& s, const AugRow& a, float M, int c, int ox, int Wi) {
-  const CropAxis ax = crop_axis(ox, Wi, s.w, s.flip);
-  if (a.sat) {
-    float r = crop_value(s.top, s.bot, ax, s.fy), g = crop_value(s.top + s.plane, s.bot + s.plane, ax, s.fy),
-          b = crop_value(s.top + 2 * s.plane, s.bot + 2 * s.plane, ax, s.fy);
-    aug_chain<true>(r, g, b, a, 3, M);
-    return c == 0 ? r : (c == 1 ? g : b);
-  }
-  float v = crop_value(s.top + c * s.plane, s.bot + c * s.plane, ax, s.fy), g = 0.0f, b = 0.0f;
-  aug_chain<false>(v, g, b, a, 3, M);
-  return v;
-}
-
-// The pre-pass of the contrast slot: M_b = the mean of gray over the Hi x Wi output pixels of sample b after the slots that precede
-// its contrast slot, through a FIXED tree (docs/findings/optimizer_side.md section 2's manner; no atomics).  AUG_GROUPS workgroups
-// of 256 threads per sample, whatever the image size:
-//   1. thread t of workgroup k: acc = 0; for q = 256 k + t, + 256 AUG_GROUPS, ... < Hi Wi: acc = acc + gray(pixel q), q = oy Wi + ox;
-//   2. the wave's 64 accumulators by wave_sum's butterfly (lanes 32, 16, 8, 4, 2, 1 apart): 6 additions;
-//   3. the four wave sums left to right: 3 additions                                       -> partial[b][k]
-//   4. aug_gray_mean_reduce_kernel, one thread per sample: the AUG_GROUPS partials left to right (15 additions), then one division
-//      by (float)(Hi Wi)                                                                    -> stat[b]
-// A sample whose row is bad or has no contrast slot loads no pixel and writes nothing; one whose source is bad writes zero partials
-// (the patch-row kernel never reads its stat).  scratch: stat fp32 [B], then partial fp32 [B][AUG_GROUPS] (cara_aug_stat_bytes).
-__global__ __launch_bounds__(256) void aug_gray_mean_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                            const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                            const int* __restrict__ aug, float* __restrict__ partial, int B, int C,
-                                                            int Hi, int Wi) {
-#pragma clang fp contract(off)
-  __shared__ float lds[4];
-  const int b = blockIdx.x / AUG_GROUPS, k = blockIdx.x % AUG_GROUPS;
-  AugRow a;
-  if (!aug_row(aug, b, Hi, Wi, &a) || a.contrast_at == 3) return;
-  MixSource s;
-  if (!mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &s)) {
-    if (threadIdx.x == 0) partial[(size_t)b * AUG_GROUPS + k] = 0.0f;
-    return;
-  }
-  float acc = 0.0f;
-  const int n = Hi * Wi;
-  for (int q = k * 256 + (int)threadIdx.x; q < n; q += 256 * AUG_GROUPS) {
-    const int oy = q / Wi, ox = q - oy * Wi;
-    const AugSource src = aug_source(s, oy, Hi, Hs, Ws);
-    const CropAxis ax = crop_axis(ox, Wi, src.w, src.flip);
-    float r = crop_value(src.top, src.bot, ax, src.fy), g = crop_value(src.top + src.plane, src.bot + src.plane, ax, src.fy),
-          bl = crop_value(src.top + 2 * src.plane, src.bot + 2 * src.plane, ax, src.fy);
-    aug_chain<true>(r, g, bl, a, a.contrast_at, 0.0f);
-    acc = acc + aug_gray(r, g, bl);
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[(size_t)b * AUG_GROUPS + k] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-__global__ __launch_bounds__(64) void aug_gray_mean_reduce_kernel(const int* __restrict__ aug, const float* __restrict__ partial,
-                                                                  float* __restrict__ stat, int B, int Hi, int Wi) {
-#pragma clang fp contract(off)
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  AugRow a;
-  if (!aug_row(aug, b, Hi, Wi, &a) || a.contrast_at == 3) return;
-  const float* p = partial + (size_t)b * AUG_GROUPS;
-  float t = p[0];
-  for (int k = 1; k < AUG_GROUPS; ++k) t = t + p[k];
-  stat[b] = t / (float)(Hi * Wi);
-}
-
-__global__ __launch_bounds__(256) void im2col_u8_rows_aug_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                                 const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                                 const int* __restrict__ mix, const int* __restrict__ aug,
-                                                                 const float* __restrict__ stat, const float* __restrict__ mean,
-                                                                 const float* __restrict__ stdv, bf16* __restrict__ out,
-                                                                 int* __restrict__ bad, int B, int C, int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const int kcols = C * p * p;
-  const long e = idx * 4;
-  const long row = e / kcols;
-  const int col = (int)(e - row * kcols);
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int b = (int)(row / (gh * gw)), pr = (int)(row % (gh * gw));
-  const int gy = pr / gw, gx = pr % gw;
-  int partner = b, cx0 = 0, cy0 = 0, cw = 0, ch = 0;
-  float m = 0.0f;
-  if (mix) {
-    const int* mx = mix + (size_t)b * 8;
-    partner = mx[0]; cx0 = mx[1]; cy0 = mx[2]; cw = mx[3]; ch = mx[4];
-    m = __int_as_float(mx[5]);
-  }
-  MixSource own, oth;
-  AugRow own_a, oth_a;
-  // (the mix kernel's order, each sample's table row checked beside its source; partner inside [0, B) before anything of it is formed)
-  const bool self = partner == b;
-  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) && aug_row(aug, b, Hi, Wi, &own_a) &&
-                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth) &&
-                            aug_row(aug, partner, Hi, Wi, &oth_a))) &&
-                  cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 && cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
-  if (!ok) {
-    if (bad && pr == 0 && col == 0) atomicAdd(bad, 1);
-    const bf16 z = (bf16)0.0f;
-    *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
-    return;
-  }
-  if (self) { oth = own; oth_a = own_a; }
-  // (a statistic is read only where its sample has a contrast slot: the pre-pass wrote exactly those)
-  const float M_own = own_a.contrast_at < 3 ? stat[b] : 0.0f, M_oth = oth_a.contrast_at < 3 ? stat[partner] : 0.0f;
-  const int oy = gy * p + py, ox0 = gx * p + px;
-  const AugSource s_own = aug_source(own, oy, Hi, Hs, Ws), s_oth = aug_source(oth, oy, Hi, Hs, Ws);
-  const bool row_in = oy >= cy0 && oy - cy0 < ch;
-  const bool erow_in = oy >= own_a.ey0 && oy - own_a.ey0 < own_a.eh;
-  const float mu = mean[c], sd = stdv[c];
-  const unsigned i0 = (((unsigned)b * (unsigned)C + (unsigned)c) * (unsigned)Hi + (unsigned)oy) * (unsigned)Wi + (unsigned)ox0;
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int ox = ox0 + j;
-    float a;
-    if (row_in && ox >= cx0 && ox - cx0 < cw) {
-      a = aug_value(s_oth, oth_a, M_oth, c, ox, Wi);
-    } else {
-      a = aug_value(s_own, own_a, M_own, c, ox, Wi);
-      if (m != 0.0f) a = mix_blend(a, m, aug_value(s_oth, oth_a, M_oth, c, ox, Wi));
-    }
-    v[j] = normalize_f32(a, mu, sd);
-    if (erow_in && ox >= own_a.ex0 && ox - own_a.ex0 < own_a.ew) v[j] = own_a.emode ? aug_noise(i0 + (unsigned)j, own_a.eseed) : 0.0f;
-  }
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-
-// Patch dropout: the five patch-row kernels above on a kept subset of the patches.  keep int32 [B,K]: output row b K + j is the row
-// of patch pr = keep[b][j] of sample b.  Each sibling is its kernel with the row decomposed as (b, j) and pr read from the table;
-// from pr on -- (gy, gx), the pixel's position in the full Hi x Wi output, every table lookup, the erase index -- the text is that
-// kernel's, so a kept row is bit for bit the row it writes.  A sample the kernel calls bad: K zero rows, counted once (the lane of
-// j == 0, col == 0); otherwise an entry outside [0, gh gw) is never used: a zero row, counted by the lane that writes its first element.
-struct KeptRow { int b, j, col; long e; };
-__device__ __forceinline__ KeptRow kept_row(long idx, int K, int kcols) {
-  const long e = idx * 4;
-  const long row = e / kcols;
-  return KeptRow{(int)(row / K), (int)(row % K), (int)(e - row * kcols), e};
-}
-__device__ __forceinline__ void zero_row4(bf16* __restrict__ out, long e) {
-  const bf16 z = (bf16)0.0f;
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{z, z, z, z};
-}
-__global__ __launch_bounds__(256) void im2col_keep_kernel(const float* __restrict__ img, const int* __restrict__ keep, int K,
-                                                          bf16* __restrict__ out, int* __restrict__ bad, int B, int C, int Hi, int Wi,
-                                                          int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const KeptRow kr = kept_row(idx, K, C * p * p);
-  const long e = kr.e;
-  const int col = kr.col, b = kr.b;
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int pr = keep[(size_t)b * K + kr.j];
-  if (pr < 0 || pr >= gh * gw) {
-    if (bad && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int gy = pr / gw, gx = pr % gw;
-  const float4 v = *reinterpret_cast<const float4*>(img + (((size_t)b * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
-  bf16x4 o = {(bf16)v.x, (bf16)v.y, (bf16)v.z, (bf16)v.w};
-  *reinterpret_cast<bf16x4*>(out + e) = o;
-}
-__global__ __launch_bounds__(256) void im2col_u8_rows_keep_kernel(const uint8_t* __restrict__ img, long n_split,
-                                                                  const int64_t* __restrict__ rows, const int* __restrict__ keep, int K,
-                                                                  const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                  bf16* __restrict__ out, int* __restrict__ bad, int B, int C, int Hi,
-                                                                  int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const KeptRow kr = kept_row(idx, K, C * p * p);
-  const long e = kr.e;
-  const int col = kr.col, b = kr.b;
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int64_t r = rows[b];
-  if (r < 0 || r >= n_split) {
-    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int pr = keep[(size_t)b * K + kr.j];
-  if (pr < 0 || pr >= gh * gw) {
-    if (bad && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int gy = pr / gw, gx = pr % gw;
-  const unsigned u = *reinterpret_cast<const unsigned*>(img + (((size_t)r * C + c) * Hi + gy * p + py) * Wi + gx * p + px);
-  *reinterpret_cast<bf16x4*>(out + e) = normalize_u8x4(u, mean[c], stdv[c]);
-}
-__global__ __launch_bounds__(256) void im2col_u8_rows_crop_keep_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                                       const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                                       const int* __restrict__ keep, int K,
-                                                                       const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                       bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
-                                                                       int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const KeptRow kr = kept_row(idx, K, C * p * p);
-  const long e = kr.e;
-  const int col = kr.col, b = kr.b;
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int64_t r = rows[b];
-  const int* box = boxes + (size_t)b * 5;
-  const int x0 = box[0], y0 = box[1], w = box[2], h = box[3];
-  const bool flip = box[4] != 0;
-  if (r < 0 || r >= n_split || w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > Ws - x0 || h > Hs - y0) {
-    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int pr = keep[(size_t)b * K + kr.j];
-  if (pr < 0 || pr >= gh * gw) {
-    if (bad && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int gy = pr / gw, gx = pr % gw;
-  const CropAxis ay = crop_axis(gy * p + py, Hi, h, false);
-  const uint8_t* plane = img + ((size_t)r * C + c) * Hs * Ws;
-  const uint8_t* top = plane + (size_t)(y0 + ay.i0) * Ws + x0;
-  const uint8_t* bot = plane + (size_t)(y0 + ay.i1) * Ws + x0;
-  const float mu = mean[c], sd = stdv[c];
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = normalize_f32(crop_value(top, bot, crop_axis(gx * p + px + j, Wi, w, flip), ay.f), mu, sd);
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-__global__ __launch_bounds__(256) void im2col_u8_rows_mix_keep_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                                      const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                                      const int* __restrict__ mix, const int* __restrict__ keep, int K,
-                                                                      const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                      bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
-                                                                      int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const KeptRow kr = kept_row(idx, K, C * p * p);
-  const long e = kr.e;
-  const int col = kr.col, b = kr.b;
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  const int* mx = mix + (size_t)b * 8;
-  const int partner = mx[0], cx0 = mx[1], cy0 = mx[2], cw = mx[3], ch = mx[4];
-  const float m = __int_as_float(mx[5]);
-  MixSource own, oth;
-  const bool self = partner == b;
-  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) &&
-                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth))) && cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 &&
-                  cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
-  if (!ok) {
-    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int pr = keep[(size_t)b * K + kr.j];
-  if (pr < 0 || pr >= gh * gw) {
-    if (bad && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int gy = pr / gw, gx = pr % gw;
-  if (self) oth = own;
-  const int oy = gy * p + py, ox0 = gx * p + px;
-  const CropAxis ay_own = crop_axis(oy, Hi, own.h, false), ay_oth = crop_axis(oy, Hi, oth.h, false);
-  const size_t chan = (size_t)c * Hs * Ws;
-  const uint8_t *top_own = own.origin + chan + (size_t)ay_own.i0 * Ws, *bot_own = own.origin + chan + (size_t)ay_own.i1 * Ws;
-  const uint8_t *top_oth = oth.origin + chan + (size_t)ay_oth.i0 * Ws, *bot_oth = oth.origin + chan + (size_t)ay_oth.i1 * Ws;
-  const bool row_in = oy >= cy0 && oy - cy0 < ch;
-  const float mu = mean[c], sd = stdv[c];
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int ox = ox0 + j;
-    float a;
-    if (row_in && ox >= cx0 && ox - cx0 < cw) {
-      a = crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f);
-    } else {
-      a = crop_value(top_own, bot_own, crop_axis(ox, Wi, own.w, own.flip), ay_own.f);
-      if (m != 0.0f) a = mix_blend(a, m, crop_value(top_oth, bot_oth, crop_axis(ox, Wi, oth.w, oth.flip), ay_oth.f));
-    }
-    v[j] = normalize_f32(a, mu, sd);
-  }
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-__global__ __launch_bounds__(256) void im2col_u8_rows_aug_keep_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                                      const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                                      const int* __restrict__ mix, const int* __restrict__ aug,
-                                                                      const float* __restrict__ stat, const int* __restrict__ keep, int K,
-                                                                      const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                                      bf16* __restrict__ out, int* __restrict__ bad, int B, int C,
-                                                                      int Hi, int Wi, int p, long total4) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total4) return;
-  const int gw = Wi / p, gh = Hi / p;
-  const KeptRow kr = kept_row(idx, K, C * p * p);
-  const long e = kr.e;
-  const int col = kr.col, b = kr.b;
-  const int c = col / (p * p), py = (col / p) % p, px = col % p;
-  int partner = b, cx0 = 0, cy0 = 0, cw = 0, ch = 0;
-  float m = 0.0f;
-  if (mix) {
-    const int* mx = mix + (size_t)b * 8;
-    partner = mx[0]; cx0 = mx[1]; cy0 = mx[2]; cw = mx[3]; ch = mx[4];
-    m = __int_as_float(mx[5]);
-  }
-  MixSource own, oth;
-  AugRow own_a, oth_a;
-  const bool self = partner == b;
-  const bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &own) && aug_row(aug, b, Hi, Wi, &own_a) &&
-                  (self || (partner >= 0 && partner < B && mix_source(img, n_split, C, Hs, Ws, rows, boxes, partner, &oth) &&
-                            aug_row(aug, partner, Hi, Wi, &oth_a))) &&
-                  cw >= 0 && ch >= 0 && cx0 >= 0 && cy0 >= 0 && cw <= Wi - cx0 && ch <= Hi - cy0 && m >= 0.0f && m <= 1.0f;
-  if (!ok) {
-    if (bad && kr.j == 0 && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int pr = keep[(size_t)b * K + kr.j];
-  if (pr < 0 || pr >= gh * gw) {
-    if (bad && col == 0) atomicAdd(bad, 1);
-    zero_row4(out, e);
-    return;
-  }
-  const int gy = pr / gw, gx = pr % gw;
-  if (self) { oth = own; oth_a = own_a; }
-  const float M_own = own_a.contrast_at < 3 ? stat[b] : 0.0f, M_oth = oth_a.contrast_at < 3 ? stat[partner] : 0.0f;
-  const int oy = gy * p + py, ox0 = gx * p + px;
-  const AugSource s_own = aug_source(own, oy, Hi, Hs, Ws), s_oth = aug_source(oth, oy, Hi, Hs, Ws);
-  const bool row_in = oy >= cy0 && oy - cy0 < ch;
-  const bool erow_in = oy >= own_a.ey0 && oy - own_a.ey0 < own_a.eh;
-  const float mu = mean[c], sd = stdv[c];
-  const unsigned i0 = (((unsigned)b * (unsigned)C + (unsigned)c) * (unsigned)Hi + (unsigned)oy) * (unsigned)Wi + (unsigned)ox0;
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int ox = ox0 + j;
-    float a;
-    if (row_in && ox >= cx0 && ox - cx0 < cw) {
-      a = aug_value(s_oth, oth_a, M_oth, c, ox, Wi);
-    } else {
-      a = aug_value(s_own, own_a, M_own, c, ox, Wi);
-      if (m != 0.0f) a = mix_blend(a, m, aug_value(s_oth, oth_a, M_oth, c, ox, Wi));
-    }
-    v[j] = normalize_f32(a, mu, sd);
-    if (erow_in && ox >= own_a.ex0 && ox - own_a.ex0 < own_a.ew) v[j] = own_a.emode ? aug_noise(i0 + (unsigned)j, own_a.eseed) : 0.0f;
-  }
-  *reinterpret_cast<bf16x4*>(out + e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-}
-
-// out[i] = labels[rows[i]]; a row outside [0, n_split) is not dereferenced: it gives 0 and is counted in *bad (may be NULL)
-__global__ __launch_bounds__(256) void gather_labels_kernel(const int64_t* __restrict__ labels, long n_split,
-                                                            const int64_t* __restrict__ rows, int64_t* __restrict__ out,
-                                                            int B, int* __restrict__ bad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const int64_t r = rows[i];
-  const bool ok = r >= 0 && r < n_split;
-  if (!ok && bad) atomicAdd(bad, 1);
-  out[i] = ok ? labels[r] : 0;
-}
-
 __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__ emb, const float* __restrict__ cls,
                                                        const float* __restrict__ pos, float* __restrict__ x,
                                                        int B, int P, int D, long total4) {
@@ -1314,163 +636,6 @@ int cara_layernorm_bwd_rows_in(const void* dy, const float* x, long ldx, const f
   const XuArgs a = Vst ? XuArgs{static_cast<const bf16*>(Vst), rank, Rp, static_cast<bf16*>(G), static_cast<bf16*>(Gt), ldt}
                        : XuArgs{nullptr, 0, 0, nullptr, nullptr, 0};
   return ln_bwd_launch(dy, x, ldx, gamma, mean, rstd, dx_in, dx_out, dyb, rowscale, rows_per_sample, M, C, a, stream, dyb_panels, dx_in_every);
-}
-
-extern "C" int cara_im2col_patches(const float* img, void* patches, int B, int C, int Hi, int Wi, int p, void* stream) {
-  if (!img || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi % p || Wi % p || (Wi & 3)) return CARA_E_ARG;
-  const long total4 = (long)B * C * Hi * Wi / 4;
-  hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     img, (bf16*)patches, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" int cara_im2col_patches_u8(const unsigned char* pixels, const float* mean, const float* stdv, void* patches, int B, int C,
-                                      int Hi, int Wi, int p, void* stream) {
-  if (!pixels || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi % p || Wi % p || (Wi & 3)) return CARA_E_ARG;
-  if (reinterpret_cast<uintptr_t>(pixels) & 3) return CARA_E_ARG;   // (dword loads: rows are Wi % 4 == 0 bytes apart)
-  const long total4 = (long)B * C * Hi * Wi / 4;
-  hipLaunchKernelGGL(im2col_u8_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     pixels, mean, stdv, (bf16*)patches, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" int cara_im2col_patches_u8_rows(const unsigned char* pixels, int n_split, const int64_t* rows, const float* mean,
-                                           const float* stdv, void* patches, int* bad, int B, int C, int Hi, int Wi, int p,
-                                           void* stream) {
-  if (!pixels || !rows || n_split <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi % p || Wi % p || (Wi & 3))
-    return CARA_E_ARG;
-  if (reinterpret_cast<uintptr_t>(pixels) & 3) return CARA_E_ARG;   // (with p % 4 == 0 and Wi % 4 == 0 every image starts dword-aligned)
-  const long total4 = (long)B * C * Hi * Wi / 4;
-  hipLaunchKernelGGL(im2col_u8_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     pixels, (long)n_split, rows, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" int cara_im2col_patches_u8_rows_crop(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
-                                                const int* boxes, const float* mean, const float* stdv, void* patches, int* bad,
-                                                int B, int C, int Hi, int Wi, int p, void* stream) {
-  if (!pixels || !rows || !boxes || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 ||
-      (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p)
-    return CARA_E_ARG;
-  const long total4 = (long)B * C * Hi * Wi / 4;
-  hipLaunchKernelGGL(im2col_u8_rows_crop_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     pixels, (long)n_split, Hs, Ws, rows, boxes, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" int cara_im2col_patches_u8_rows_mix(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
-                                               const int* boxes, const int* mix, const float* mean, const float* stdv, void* patches,
-                                               int* bad, int B, int C, int Hi, int Wi, int p, void* stream) {
-  if (!pixels || !rows || !mix || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 ||
-      (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p)
-    return CARA_E_ARG;
-  if (!boxes && (Hs != Hi || Ws != Wi)) return CARA_E_ARG;   // (without boxes a sample is its whole image, byte for byte)
-  const long total4 = (long)B * C * Hi * Wi / 4;
-  hipLaunchKernelGGL(im2col_u8_rows_mix_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     pixels, (long)n_split, Hs, Ws, rows, boxes, mix, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" size_t cara_aug_stat_bytes(int B) { return B > 0 ? (size_t)B * (1 + AUG_GROUPS) * sizeof(float) : 0; }
-
-extern "C" int cara_im2col_patches_u8_rows_aug(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
-                                               const int* boxes, const int* mix, const int* aug, void* stat_scratch, const float* mean,
-                                               const float* stdv, void* patches, int* bad, int B, int C, int Hi, int Wi, int p,
-                                               void* stream) {
-  if (!aug) {   // no table: the launches of the call without one
-    if (mix) return cara_im2col_patches_u8_rows_mix(pixels, n_split, Hs, Ws, rows, boxes, mix, mean, stdv, patches, bad, B, C, Hi, Wi, p, stream);
-    if (boxes) return cara_im2col_patches_u8_rows_crop(pixels, n_split, Hs, Ws, rows, boxes, mean, stdv, patches, bad, B, C, Hi, Wi, p, stream);
-    if (Hs != Hi || Ws != Wi) return CARA_E_ARG;
-    return cara_im2col_patches_u8_rows(pixels, n_split, rows, mean, stdv, patches, bad, B, C, Hi, Wi, p, stream);
-  }
-  if (!pixels || !rows || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || p <= 0 || (p & 3) || Hi <= 0 ||
-      Wi <= 0 || Hi % p || Wi % p)
-    return CARA_E_ARG;
-  if (C != 3) return CARA_E_ARG;                              // (the colour ops are defined on three channels)
-  if (!stat_scratch || (reinterpret_cast<uintptr_t>(stat_scratch) & 3)) return CARA_E_ARG;
-  if (!boxes && (Hs != Hi || Ws != Wi)) return CARA_E_ARG;   // (without boxes a sample is its whole image, byte for byte)
-  if (2ull * (unsigned long long)B * C * Hi * Wi > (1ull << 32)) return CARA_E_ARG;   // (the noise's two counters per element are 32-bit)
-  float* stat = static_cast<float*>(stat_scratch);
-  float* partial = stat + B;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(aug_gray_mean_kernel, dim3((unsigned)B * AUG_GROUPS), dim3(256), 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, aug,
-                     partial, B, C, Hi, Wi);
-  CARA_CHECK_LAUNCH();
-  hipLaunchKernelGGL(aug_gray_mean_reduce_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, aug, partial, stat, B, Hi, Wi);
-  CARA_CHECK_LAUNCH();
-  const long total4 = (long)B * C * Hi * Wi / 4;
-  hipLaunchKernelGGL(im2col_u8_rows_aug_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, pixels, (long)n_split, Hs, Ws,
-                     rows, boxes, mix, aug, stat, mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-// Patch dropout: the entries above on a kept subset (keep int32 [B,K], 1 <= K <= gh gw).  B K rows are written, nothing beyond.
-extern "C" int cara_im2col_patches_keep(const float* img, const int* keep, int K, void* patches, int* bad, int B, int C, int Hi, int Wi,
-                                        int p, void* stream) {
-  if (!img || !keep || !patches || B <= 0 || C <= 0 || p <= 0 || (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p || (Wi & 3)) return CARA_E_ARG;
-  if (K < 1 || K > (Hi / p) * (Wi / p)) return CARA_E_ARG;
-  const long total4 = (long)B * K * C * p * p / 4;
-  hipLaunchKernelGGL(im2col_keep_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     img, keep, K, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" int cara_im2col_patches_u8_rows_keep(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
-                                                const int* boxes, const int* mix, const int* aug, void* stat_scratch, const int* keep,
-                                                int K, const float* mean, const float* stdv, void* patches, int* bad, int B, int C,
-                                                int Hi, int Wi, int p, void* stream) {
-  // (the checks of cara_im2col_patches_u8_rows_aug and of the entry it hands a call without a table to, in their order)
-  if (!pixels || !rows || !keep || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv || !patches || B <= 0 || C <= 0 || p <= 0 ||
-      (p & 3) || Hi <= 0 || Wi <= 0 || Hi % p || Wi % p)
-    return CARA_E_ARG;
-  if (K < 1 || K > (Hi / p) * (Wi / p)) return CARA_E_ARG;
-  if (!boxes && (Hs != Hi || Ws != Wi)) return CARA_E_ARG;   // (without boxes a sample is its whole image, byte for byte)
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long total4 = (long)B * K * C * p * p / 4;
-  const dim3 grid((unsigned)((total4 + 255) / 256)), block(256);
-  if (aug) {
-    if (C != 3) return CARA_E_ARG;
-    if (!stat_scratch || (reinterpret_cast<uintptr_t>(stat_scratch) & 3)) return CARA_E_ARG;
-    if (2ull * (unsigned long long)B * C * Hi * Wi > (1ull << 32)) return CARA_E_ARG;
-    float* stat = static_cast<float*>(stat_scratch);
-    float* partial = stat + B;
-    // the contrast pre-pass of the call without keep, unchanged: M_b is the mean over the whole image, kept or not
-    hipLaunchKernelGGL(aug_gray_mean_kernel, dim3((unsigned)B * AUG_GROUPS), dim3(256), 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, aug,
-                       partial, B, C, Hi, Wi);
-    CARA_CHECK_LAUNCH();
-    hipLaunchKernelGGL(aug_gray_mean_reduce_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, aug, partial, stat, B, Hi, Wi);
-    CARA_CHECK_LAUNCH();
-    hipLaunchKernelGGL(im2col_u8_rows_aug_keep_kernel, grid, block, 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, mix, aug, stat, keep, K,
-                       mean, stdv, (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  } else if (mix) {
-    hipLaunchKernelGGL(im2col_u8_rows_mix_keep_kernel, grid, block, 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, mix, keep, K, mean, stdv,
-                       (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  } else if (boxes) {
-    hipLaunchKernelGGL(im2col_u8_rows_crop_keep_kernel, grid, block, 0, st, pixels, (long)n_split, Hs, Ws, rows, boxes, keep, K, mean, stdv,
-                       (bf16*)patches, bad, B, C, Hi, Wi, p, total4);
-  } else {
-    if ((Wi & 3) || (reinterpret_cast<uintptr_t>(pixels) & 3)) return CARA_E_ARG;   // (dword loads, as cara_im2col_patches_u8_rows)
-    hipLaunchKernelGGL(im2col_u8_rows_keep_kernel, grid, block, 0, st, pixels, (long)n_split, rows, keep, K, mean, stdv, (bf16*)patches, bad,
-                       B, C, Hi, Wi, p, total4);
-  }
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
-}
-
-extern "C" int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
-                                  void* stream) {
-  if (!labels || !rows || !out || n_split <= 0 || B <= 0) return CARA_E_ARG;
-  hipLaunchKernelGGL(gather_labels_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     labels, (long)n_split, rows, out, B, bad);
-  CARA_CHECK_LAUNCH();
-  return CARA_OK;
 }
 
 extern "C" int cara_assemble_tokens(const float* emb, const float* cls, const float* pos, float* x, int B, int P,

@@ -977,45 +977,17 @@ extern "C" int cara_head_backward(const float* dlogits, const void* xn, const fl
   return head_backward_scaled(dlogits, xn, head_w, dhead_w, dhead_b, dxn, B, classes, D, nullptr, nullptr, stream);
 }
 
-// The image of a forward: an fp32 batch, or resident uint8 pixels with their per-channel mean / std -- the batch itself, or a whole
-// split of n_split images that `rows` indexes, each sample read whole or through its box out of the split's own Hs x Ws pixels
-// (cara_im2col_patches_u8_rows_crop), and mixed with a partner sample where a Mixup / CutMix table says so
-// (cara_im2col_patches_u8_rows_mix; its boxes may be NULL), and colour-jittered / erased where an aug table says so
-// (cara_im2col_patches_u8_rows_aug).  Each entry checks and sets the fields of its kind; everything behind the patch rows is the same.
-struct ImageSource {
-  enum Kind { F32Batch, U8Batch, U8Rows, U8RowsCrop, U8RowsMix, U8RowsAug } kind;
-  const float* images;                                      // F32Batch
-  const unsigned char* pixels; const float *mean, *stdv;   // the three U8 kinds
-  int n_split; const int64_t* rows; int* bad;               // U8Rows, U8RowsCrop, U8RowsMix
-  int Hs, Ws; const int* boxes;                             // U8RowsCrop, U8RowsMix
-  const int* mix;                                           // U8RowsMix, U8RowsAug (may be NULL there, like its boxes)
-  const int* aug; void* stat;                               // U8RowsAug: the jitter / erase table and its statistic scratch
-  const int* keep;                                          // F32Batch, U8RowsAug: the kept patches [B, tokens - 1] of a patch dropout, or NULL
-};
-static int patch_rows(const ImageSource& i, const cara_vit_shape* s, void* patches, void* stream) {
-  if (i.keep) {   // (U8RowsAug with a kept subset: boxes, mix and aug may each be NULL)
-    if (i.kind == ImageSource::F32Batch)
-      return cara_im2col_patches_keep(i.images, i.keep, s->tokens - 1, patches, i.bad, s->B, s->chans, s->img, s->img, s->patch, stream);
-    if (i.kind != ImageSource::U8RowsAug) return CARA_E_ARG;
-    return cara_im2col_patches_u8_rows_keep(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mix, i.aug, i.stat, i.keep, s->tokens - 1, i.mean,
-                                            i.stdv, patches, i.bad, s->B, s->chans, s->img, s->img, s->patch, stream);
-  }
-  switch (i.kind) {
-    case ImageSource::F32Batch: return cara_im2col_patches(i.images, patches, s->B, s->chans, s->img, s->img, s->patch, stream);
-    case ImageSource::U8Batch: return cara_im2col_patches_u8(i.pixels, i.mean, i.stdv, patches, s->B, s->chans, s->img, s->img, s->patch, stream);
-    case ImageSource::U8Rows:
-      return cara_im2col_patches_u8_rows(i.pixels, i.n_split, i.rows, i.mean, i.stdv, patches, i.bad, s->B, s->chans, s->img, s->img, s->patch, stream);
-    case ImageSource::U8RowsCrop:
-      return cara_im2col_patches_u8_rows_crop(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mean, i.stdv, patches, i.bad, s->B, s->chans, s->img,
-                                              s->img, s->patch, stream);
-    case ImageSource::U8RowsMix:
-      return cara_im2col_patches_u8_rows_mix(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mix, i.mean, i.stdv, patches, i.bad, s->B, s->chans,
-                                             s->img, s->img, s->patch, stream);
-    case ImageSource::U8RowsAug:
-      return cara_im2col_patches_u8_rows_aug(i.pixels, i.n_split, i.Hs, i.Ws, i.rows, i.boxes, i.mix, i.aug, i.stat, i.mean, i.stdv, patches, i.bad,
-                                             s->B, s->chans, s->img, s->img, s->patch, stream);
-  }
-  return CARA_E_ARG;
+// The image of a forward is a cara_feed (common.h; the patch rows are feed.hip's): an fp32 batch, or resident uint8 pixels with
+// their per-channel mean / std -- the batch itself, or a whole split of n_split images that `rows` indexes, each sample read whole or
+// through its box, mixed with a partner, colour-jittered / erased, all of its patches or a kept subset.  Each entry checks and sets
+// the fields it has arguments for; the body adds the shape's, and everything behind the patch rows is the same.
+// (a source of Hs x Ws images; an entry without a size of its own reads the shape's img x img images.  Fields are set by name: a
+// field added to cara_feed must not shift an initialiser.)
+static int img_of(const cara_vit_shape* s) { return s ? s->img : 0; }
+static cara_feed source_of(int Hs, int Ws) {
+  cara_feed f = {};
+  f.Hs = Hs; f.Ws = Ws;
+  return f;
 }
 
 // the activations a block's forward saves for its backward, each in the layout the plan gives it
@@ -1025,7 +997,7 @@ static Saved saved_acts(const Ctx& cx, const LayerWs& lw, int D, const BlockPlan
 }
 
 static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp, const float* head_w,
-                            const float* head_b, const ImageSource& src, const float* droppath, void* workspace, float* logits, void* stream) {
+                            const float* head_b, const cara_feed& src, const float* droppath, void* workspace, float* logits, void* stream) {
   Ws W;
   if (!layout(g, s, &W) || !w || !cp || !head_w || !head_b || !workspace || !logits) return CARA_E_ARG;
   // an entry without a keep table writes the grid's patch rows, all of them: fewer tokens than that is the keep entries' alone
@@ -1040,7 +1012,10 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
   if (g->cp_length == 2) TRY(cara_dense_delta_materialize(g, cp, ws + W.dd, ws + W.ddt, stream));   // (order 2: BlockPlan::dense_qkv)
   // patch embedding: Conv2d(k = s = patch) as a GEMM over im2col rows, then cls + pos_embed
   const int kp = s->chans * s->patch * s->patch;
-  TRY(patch_rows(src, s, ws + W.patches, stream));
+  cara_feed feed = src;
+  feed.K = src.keep ? P : 0;
+  feed.B = B; feed.C = s->chans; feed.Hi = feed.Wi = s->img; feed.p = s->patch;
+  TRY(cara_feed_patch_rows(feed, ws + W.patches, stream));
   cara_gemm_args a = {};
   a.A = ws + W.patches; a.lda = kp; a.B = w->patch_w; a.ldb = kp; a.M = B * P; a.N = D; a.K = kp;
   a.bias = w->patch_b; a.epi = CARA_EPI_F32; a.C = ws + W.emb; a.ldc = D;
@@ -1110,7 +1085,8 @@ extern "C" int cara_vit_forward(const cara_geom* g, const cara_vit_shape* s, con
                                 const cara_cp* cp, const float* head_w, const float* head_b, const float* images,
                                 const float* droppath, void* workspace, float* logits, void* stream) {
   if (!images) return CARA_E_ARG;
-  const ImageSource src{ImageSource::F32Batch, images};
+  cara_feed src = source_of(img_of(s), img_of(s));
+  src.images = images;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1119,7 +1095,8 @@ extern "C" int cara_vit_forward_u8(const cara_geom* g, const cara_vit_shape* s, 
                                    const float* mean, const float* stdv, const float* droppath, void* workspace, float* logits,
                                    void* stream) {
   if (!pixels || !mean || !stdv) return CARA_E_ARG;
-  const ImageSource src{ImageSource::U8Batch, nullptr, pixels, mean, stdv};
+  cara_feed src = source_of(img_of(s), img_of(s));
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1128,7 +1105,8 @@ extern "C" int cara_vit_forward_u8_rows(const cara_geom* g, const cara_vit_shape
                                         int n_split, const int64_t* rows, const float* mean, const float* stdv,
                                         const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
   if (!pixels || !rows || n_split <= 0 || !mean || !stdv) return CARA_E_ARG;
-  const ImageSource src{ImageSource::U8Rows, nullptr, pixels, mean, stdv, n_split, rows, bad};
+  cara_feed src = source_of(img_of(s), img_of(s));
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1138,7 +1116,9 @@ extern "C" int cara_vit_forward_u8_rows_crop(const cara_geom* g, const cara_vit_
                                              const float* stdv, const float* droppath, void* workspace, float* logits, int* bad,
                                              void* stream) {
   if (!pixels || !rows || !boxes || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
-  const ImageSource src{ImageSource::U8RowsCrop, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes};
+  cara_feed src = source_of(Hs, Ws);
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
+  src.boxes = boxes;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1148,7 +1128,9 @@ extern "C" int cara_vit_forward_u8_rows_mix(const cara_geom* g, const cara_vit_s
                                             const float* mean, const float* stdv, const float* droppath, void* workspace, float* logits,
                                             int* bad, void* stream) {
   if (!pixels || !rows || !mix || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
-  const ImageSource src{ImageSource::U8RowsMix, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix};
+  cara_feed src = source_of(Hs, Ws);
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
+  src.boxes = boxes; src.mix = mix;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1158,7 +1140,9 @@ extern "C" int cara_vit_forward_u8_rows_aug(const cara_geom* g, const cara_vit_s
                                             const int* aug, void* stat_scratch, const float* mean, const float* stdv,
                                             const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
   if (!pixels || !rows || !aug || !stat_scratch || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
-  const ImageSource src{ImageSource::U8RowsAug, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix, aug, stat_scratch};
+  cara_feed src = source_of(Hs, Ws);
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
+  src.boxes = boxes; src.mix = mix; src.aug = aug; src.stat = stat_scratch;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1166,9 +1150,8 @@ extern "C" int cara_vit_forward_keep(const cara_geom* g, const cara_vit_shape* s
                                      const float* head_w, const float* head_b, const float* images, const int* keep,
                                      const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
   if (!images || !keep) return CARA_E_ARG;
-  ImageSource src{ImageSource::F32Batch, images};
-  src.bad = bad;
-  src.keep = keep;
+  cara_feed src = source_of(img_of(s), img_of(s));
+  src.images = images; src.bad = bad; src.keep = keep;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 
@@ -1178,7 +1161,9 @@ extern "C" int cara_vit_forward_u8_rows_keep(const cara_geom* g, const cara_vit_
                                              void* stat_scratch, const int* keep, const float* mean, const float* stdv,
                                              const float* droppath, void* workspace, float* logits, int* bad, void* stream) {
   if (!pixels || !rows || !keep || (aug && !stat_scratch) || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
-  const ImageSource src{ImageSource::U8RowsAug, nullptr, pixels, mean, stdv, n_split, rows, bad, Hs, Ws, boxes, mix, aug, stat_scratch, keep};
+  cara_feed src = source_of(Hs, Ws);
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
+  src.boxes = boxes; src.mix = mix; src.aug = aug; src.stat = stat_scratch; src.keep = keep;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 

@@ -307,7 +307,7 @@ def aug_seed(seed: int, epoch: int, rank: int) -> int:
 
 
 AUG_NONE, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION = 0, 1, 2, 3
-AUG_ERASE_STREAM = 0x45524153                 # the counter hash's stream of the erase noise (norm_misc.hip)
+AUG_ERASE_STREAM = 0x45524153                 # the counter hash's stream of the erase noise (feed.hip)
 GRAY_WEIGHTS = (0.2989, 0.587, 0.114)         # torchvision's rgb_to_grayscale; the kernel holds them as fp32
 
 

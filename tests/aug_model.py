@@ -20,7 +20,7 @@ import torch
 
 U = 2.0 ** -24
 F = np.float32
-GROUPS = 16                                   # AUG_GROUPS of norm_misc.hip: workgroups per sample, part of the tree
+GROUPS = 16                                   # AUG_GROUPS of feed.hip: workgroups per sample, part of the tree
 WR, WG, WB = F(0.2989), F(0.587), F(0.114)
 
 

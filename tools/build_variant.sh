@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../cara_amd/csrc"
 mkdir -p build_$name
 OBJS=""
 pids=()
-for s in lib gemm gemm8 skinny norm_misc attention factors dropout_exact dense_delta optim linear vit; do
+for s in lib gemm gemm8 skinny norm_misc feed attention factors dropout_exact dense_delta optim linear vit; do
   o=build_$name/$s.o
   OBJS="$OBJS $o"
   extra=""; [ $s = attention ] && extra="-fno-slp-vectorize"   # (as cara_amd/csrc/build.sh)
