@@ -77,10 +77,11 @@ struct cara_feed {
   int Hs, Ws; const int* boxes;              // the source's size; a crop box [B,5] per sample (NULL: Hs == Hi, Ws == Wi, whole images)
   const int* mix;                            // Mixup / CutMix table [B,8]
   const int* aug; void* stat;                // colour jitter / erase table [B,16] and its scratch (cara_aug_stat_bytes)
+  const int* ra; void* ra_stat;              // RandAugment table [B,16] and its scratch (cara_ra_stat_bytes)
   const int* keep; int K;                    // patch dropout: the kept patches [B,K] (NULL: all gh gw rows of a sample)
   int B, C, Hi, Wi, p;                       // the output: B samples of C x Hi x Wi in p x p patches
 };
-// checks a descriptor, picks its kernel and launches it (behind the contrast pre-pass where aug is set) -> patches [B (K or gh gw), C p p]
+// checks a descriptor, picks its kernel and launches it (behind the histogram pre-pass where ra is set and the contrast pre-pass where aug is) -> patches [B (K or gh gw), C p p]
 int cara_feed_patch_rows(const cara_feed& f, void* patches, void* stream);
 
 #define GLOBAL_AS __attribute__((address_space(1)))

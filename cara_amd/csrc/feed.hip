@@ -1,11 +1,14 @@
 // The training feed's patch rows (gfx950 only): images -> rows bf16 [B*gh*gw, C*p*p] of the patch-embedding GEMM, column =
 // (c*p + py)*p + px (the flattening of Conv2d weight [D, C, p, p]), from an fp32 batch or straight from resident uint8 pixels --
-// whole images or a crop box per sample, Mixup / CutMix, colour jitter and Random Erasing by index, all rows or a kept subset.
+// whole images or a crop box per sample, RandAugment's affine and lookup ops, Mixup / CutMix, colour jitter and Random Erasing by
+// index, all rows or a kept subset.
 // One call is one cara_feed (common.h); cara_feed_patch_rows checks it and launches one of TWO kernel bodies:
 //   aligned_rows_kernel<T, KEEP>        the source is the output's size and dword-aligned: one float4 / one dword per lane
-//   box_rows_kernel<MIX, AUG, KEEP>     the source is read through a box: byte loads for four adjacent pixels, one 8-byte store
+//   box_rows<MIX, AUG, RA, KEEP>        the source is read through a box: byte loads for four adjacent pixels, one 8-byte store
 // What a body CAN meet is a template parameter, so an instantiation carries nothing of a feature it does not have (the crop form no
-// partner, the mix form no jitter row); what a lane is (feed_lane: its row, its sample, its refusal) is one text for all of them.
+// partner, the mix form no jitter row, none but the RA forms a RandAugment row); what a lane is (feed_lane: its row, its sample, its
+// refusal) is one text for all of them.  box_rows is entered through box_rows_kernel<MIX, AUG, KEEP> (RA = false: the kernels'
+// names are what they were, so a host trace of a call without the ra table is the one it was) and box_rows_ra_kernel<AUG, KEEP>.
 // The next feed feature is a field of cara_feed and a parameter of a body, not a sibling kernel.
 #include <type_traits>
 
@@ -182,18 +185,185 @@ __device__ __forceinline__ float aug_noise(unsigned i, unsigned seed) {
   const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-8f, u2 = (float)(h2 >> 8) * 5.9604644775390625e-8f;
   return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
 }
-// channel c of output column ox after the sample's own chain
-__device__ __forceinline__ float aug_value(const RowSource& s, const AugRow& a, float M, int c, int ox, int Wi) {
-  const CropAxis ax = crop_axis(ox, Wi, s.w, s.flip);
+// channel c of one output pixel after the sample's own chain; base(ch) = channel ch of that pixel before the chain
+template <class Base>
+__device__ __forceinline__ float aug_value(Base&& base, const AugRow& a, float M, int c) {
   if (a.sat) {
-    float r = crop_value(s.top, s.bot, ax, s.fy), g = crop_value(s.top + s.plane, s.bot + s.plane, ax, s.fy),
-          b = crop_value(s.top + 2 * s.plane, s.bot + 2 * s.plane, ax, s.fy);
+    float r = base(0), g = base(1), b = base(2);
     aug_chain<true>(r, g, b, a, 3, M);
     return c == 0 ? r : (c == 1 ? g : b);
   }
-  float v = crop_value(s.top + c * s.plane, s.bot + c * s.plane, ax, s.fy), g = 0.0f, b = 0.0f;
+  float v = base(c), g = 0.0f, b = 0.0f;
   aug_chain<false>(v, g, b, a, 3, M);
   return v;
+}
+
+// RandAugment by index: ra int32 [B,16], row b =
+//   (op0, arg0, op1, arg1, op2, arg2, m00, m01, m02, m10, m11, m12, fill, 0, 0, 0)
+// op: a lookup slot on the quantised value q, applied in the order 0, 1, 2:
+//   0 none (arg 0);   1 posterize, arg = bits kept 0..8: q & ~((1 << (8 - arg)) - 1);   2 solarize, arg = threshold 0..256:
+//   q < arg ? q : 255 - q;   3 solarize-add, arg 0..255: q < 128 ? min(q + arg, 255) : q;   4 invert: 255 - q (arg 0);
+//   5 autocontrast, 6 equalize (arg 0): the sample's channel table, at most one of the two in a row (ra_table_kernel).
+// m..: the bits of six finite fp32 numbers of magnitude <= 32768, the output-to-input affine;  fill = 0x00RRGGBB.
+// All arithmetic below is fp32, every product and sum a single IEEE operation (plain operators under `fp contract(off)`).  Output
+// pixel (ox, oy), x = ox + 0.5, y = oy + 0.5:   u = (m00 x + m01 y) + m02,   v = (m10 x + m11 y) + m12.
+//   Unless 0 <= u < Wi and 0 <= v < Hi (a NaN fails; nothing is converted to an integer before the test) the value is the fill byte
+//   of the channel.  Inside, the sample's box (w x h, flip) is sampled at the continuous position:
+//     uf = flip ? Wi - u : u,  s = max(uf (w / Wi) - 0.5, 0),  i0 = min((int)s, w - 1),  i1 = min(i0 + 1, w - 1),  f = s - i0;
+//     the same for v with h / Hi and no flip;  then t + fy (b - t) of the two rows' a + f (b - a).
+//   A row whose matrix words are the bits of (1, 0, 0, 0, 1, 0) takes crop_axis / crop_value instead: bit for bit the value of the
+//   call without the table, with that code's contraction.
+//   Where the row has a lookup slot: q = (int)rintf(value) (half to even; the value is in [0, 255]), the slots on q, and (float)q
+//   goes on -- the fill pixels too.  A row without one does not quantise.
+//   Then the jitter chain of the aug row where there is one, the mix, normalize_f32, the erase, the one rounding to 16 bits: the
+//   value above stands where crop_value stood.
+// The statistic slot: h_c[256] = the histogram of q, as it stands before that slot, over ALL Hi x Wi output pixels of the sample's
+// channel c (fill pixels count; patch dropout does not change it).  Integers: no order of summation matters.
+//   ra_hist_kernel: RA_GROUPS workgroups of 256 threads per sample, LDS atomics into int [3][256], stored whole as the workgroup's
+//     partial (nothing of the scratch is read before it is written: its earlier content does not matter);
+//   ra_table_kernel: one workgroup per (sample, channel), thread i = bin i: h[i] = the sum of the partials, then
+//     autocontrast: lo, hi = first and last non-zero bin; hi <= lo: identity; else lut[i] = clamp((255 (i - lo)) / (hi - lo), 0, 255)
+//       in integer division, 0 below lo;
+//     equalize: z = h[hi], step = (sum h - z) / 255; hi <= lo or step == 0: identity; else lut[i] = min(255, (step / 2 +
+//       sum_{j < i} h[j]) / step).
+// scratch: lut uint8 [B][3][256], then partial int32 [B][RA_GROUPS][3][256] (cara_ra_stat_bytes).  A sample without a statistic slot
+// or with a bad row loads no pixel and writes nothing; one whose source is bad writes zero partials (an identity table nobody reads).
+// Strict rule: an op outside [0, 6], an argument outside its range, two statistic slots, a matrix word that is not finite or larger
+// than 32768 in magnitude, a fill with a non-zero top byte or a non-zero pad word make the row bad.  C == 3.
+constexpr int RA_GROUPS = 8;                          // workgroups per sample in ra_hist_kernel
+struct RaRow { int slot[3]; float m[6]; int fill, stat_at, stat_op; bool ident, lookup; };   // slot = op | arg << 4
+__device__ __forceinline__ bool ra_row(const int* ra, int b, RaRow* r) {
+  const int* w = ra + (size_t)b * 16;
+  bool ok = true;
+  r->stat_at = 3;
+  r->stat_op = 0;
+  r->lookup = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int op = w[2 * k], arg = w[2 * k + 1];
+    const int top = op == 1 ? 8 : (op == 2 ? 256 : (op == 3 ? 255 : 0));
+    if (op < 0 || op > 6 || arg < 0 || arg > top) ok = false;
+    if (op == 5 || op == 6) {
+      if (r->stat_at != 3) ok = false;
+      r->stat_at = k;
+      r->stat_op = op;
+    }
+    if (op != 0) r->lookup = true;
+    r->slot[k] = op | (arg << 4);   // (used only where ok)
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    r->m[i] = __int_as_float(w[6 + i]);
+    if (!(fabsf(r->m[i]) <= 32768.0f)) ok = false;   // (a NaN fails)
+  }
+  r->ident = w[6] == 0x3f800000 && w[7] == 0 && w[8] == 0 && w[9] == 0 && w[10] == 0x3f800000 && w[11] == 0;
+  r->fill = w[12];
+  return ok && ((unsigned)r->fill >> 24) == 0 && (w[13] | w[14] | w[15]) == 0;
+}
+// lookup slots [0, upto) on a quantised value; lut: the sample's table of that channel (read at the statistic slot alone)
+__device__ __forceinline__ int ra_slots(int q, const RaRow& r, const uint8_t* lut, int upto) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int op = r.slot[k] & 15, arg = r.slot[k] >> 4;
+    if (k >= upto || op == 0) continue;
+    if (op == 1) q &= ~((1 << (8 - arg)) - 1);
+    else if (op == 2) q = q < arg ? q : 255 - q;
+    else if (op == 3) q = q < 128 ? min(q + arg, 255) : q;
+    else if (op == 4) q = 255 - q;
+    else q = lut[q];
+  }
+  return q;
+}
+// the continuous position's bilinear value (or the fill byte) of channel c of output pixel (ox, oy); plane = Hs Ws
+__device__ __forceinline__ float ra_geometry(const MixSource& s, const RaRow& r, int c, int ox, int oy, int Hi, int Wi, int Ws, size_t plane) {
+#pragma clang fp contract(off)
+  const float x = (float)ox + 0.5f, y = (float)oy + 0.5f;
+  const float u = (r.m[0] * x + r.m[1] * y) + r.m[2];
+  const float v = (r.m[3] * x + r.m[4] * y) + r.m[5];
+  if (!(u >= 0.0f && u < (float)Wi && v >= 0.0f && v < (float)Hi)) return (float)((r.fill >> (16 - 8 * c)) & 255);
+  const float uf = s.flip ? (float)Wi - u : u;
+  const float sx = fmaxf(uf * ((float)s.w / (float)Wi) - 0.5f, 0.0f), sy = fmaxf(v * ((float)s.h / (float)Hi) - 0.5f, 0.0f);
+  const int x0 = min((int)sx, s.w - 1), x1 = min(x0 + 1, s.w - 1), y0 = min((int)sy, s.h - 1), y1 = min(y0 + 1, s.h - 1);
+  const float fx = sx - (float)x0, fy = sy - (float)y0;
+  const uint8_t *top = s.origin + c * plane + (size_t)y0 * Ws, *bot = s.origin + c * plane + (size_t)y1 * Ws;
+  const float t0 = (float)top[x0], t1 = (float)top[x1], b0 = (float)bot[x0], b1 = (float)bot[x1];
+  const float t = t0 + fx * (t1 - t0), bb = b0 + fx * (b1 - b0);
+  return t + fy * (bb - t);
+}
+// channel c of output pixel (ox, oy) of a sample after its ra row: the geometry, then the lookup slots [0, upto).  ident(c): that
+// channel by crop_value (the call without the table); lut: the sample's tables [3][256]
+template <class Ident>
+__device__ __forceinline__ float ra_value(const MixSource& s, const RaRow& r, const uint8_t* lut, int c, int ox, int oy, int Hi, int Wi,
+                                          int Ws, size_t plane, int upto, Ident&& ident) {
+  float v = r.ident ? ident(c) : ra_geometry(s, r, c, ox, oy, Hi, Wi, Ws, plane);
+  if (r.lookup) v = (float)ra_slots(min(max((int)rintf(v), 0), 255), r, lut + c * 256, upto);
+  return v;
+}
+// ra_value where no lane keeps a row pair: the pre-passes, one pixel at a time
+__device__ __forceinline__ float ra_pixel(const MixSource& s, const RaRow& r, const uint8_t* lut, int c, int ox, int oy, int Hi, int Wi,
+                                          int Hs, int Ws, int upto) {
+  return ra_value(s, r, lut, c, ox, oy, Hi, Wi, Ws, (size_t)Hs * Ws, upto, [&](int ch) {
+    const RowSource src = row_source(s, oy, Hi, Hs, Ws);
+    return crop_value(src.top + ch * src.plane, src.bot + ch * src.plane, crop_axis(ox, Wi, src.w, src.flip), src.fy);
+  });
+}
+
+__global__ __launch_bounds__(256) void ra_hist_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                      const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                      const int* __restrict__ ra, int* __restrict__ partial, int B, int C, int Hi, int Wi) {
+  __shared__ int h[3 * 256];
+  const int b = blockIdx.x / RA_GROUPS, k = blockIdx.x % RA_GROUPS;
+  RaRow r;
+  if (!ra_row(ra, b, &r) || r.stat_at == 3) return;
+  int* out = partial + ((size_t)b * RA_GROUPS + k) * (3 * 256);
+  MixSource s;
+  const bool src_ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &s);
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) h[i] = 0;
+  __syncthreads();
+  if (src_ok) {
+    const int n = Hi * Wi;
+    for (int q = k * 256 + (int)threadIdx.x; q < n; q += 256 * RA_GROUPS) {
+      const int oy = q / Wi, ox = q - oy * Wi;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        // (the row has a lookup slot: ra_value quantised, and slots keep [0, 255])
+        const int v = (int)ra_pixel(s, r, nullptr, c, ox, oy, Hi, Wi, Hs, Ws, r.stat_at);
+        atomicAdd(&h[c * 256 + min(max(v, 0), 255)], 1);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) out[i] = h[i];
+}
+__global__ __launch_bounds__(256) void ra_table_kernel(const int* __restrict__ ra, const int* __restrict__ partial,
+                                                       uint8_t* __restrict__ lut, int B) {
+  __shared__ int h[256];
+  __shared__ int lo, hi;
+  const int b = blockIdx.x / 3, c = blockIdx.x % 3, i = threadIdx.x;
+  RaRow r;
+  if (!ra_row(ra, b, &r) || r.stat_at == 3) return;
+  int mine = 0;
+  for (int k = 0; k < RA_GROUPS; ++k) mine += partial[((size_t)b * RA_GROUPS + k) * (3 * 256) + c * 256 + i];
+  h[i] = mine;
+  if (i == 0) { lo = 256; hi = -1; }
+  __syncthreads();
+  if (mine != 0) { atomicMin(&lo, i); atomicMax(&hi, i); }
+  __syncthreads();
+  int v = i;
+  if (hi > lo) {
+    if (r.stat_op == 5) {
+      v = i < lo ? 0 : min(255 * (i - lo) / (hi - lo), 255);
+    } else {
+      int before = 0, total = 0;
+      for (int j = 0; j < 256; ++j) {
+        if (j == i) before = total;
+        total += h[j];
+      }
+      const int step = (total - h[hi]) / 255;
+      if (step != 0) v = min(255, (step / 2 + before) / step);
+    }
+  }
+  lut[((size_t)b * 3 + c) * 256 + i] = (uint8_t)v;
 }
 
 // The pre-pass of the contrast slot: M_b = the mean of gray over the Hi x Wi output pixels of sample b after the slots that precede
@@ -207,17 +377,22 @@ __device__ __forceinline__ float aug_value(const RowSource& s, const AugRow& a, 
 // A sample whose row is bad or has no contrast slot loads no pixel and writes nothing; one whose source is bad writes zero partials
 // (the patch-row kernel never reads its stat).  scratch: stat fp32 [B], then partial fp32 [B][AUG_GROUPS] (cara_aug_stat_bytes).
 // M_b is the mean over the whole image, whether its patches are all kept or not.
-__global__ __launch_bounds__(256) void aug_gray_mean_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
-                                                            const int64_t* __restrict__ rows, const int* __restrict__ boxes,
-                                                            const int* __restrict__ aug, float* __restrict__ partial, int B, int C,
-                                                            int Hi, int Wi) {
+// RA (aug_gray_mean_ra_kernel): the three channel values are the sample's values after its ra row (ra_pixel, behind ra_table_kernel);
+// a bad ra row writes zero partials like a bad source.
+template <bool RA>
+__device__ __forceinline__ void aug_gray_mean(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws, const int64_t* __restrict__ rows,
+                                              const int* __restrict__ boxes, const int* __restrict__ aug, const int* __restrict__ ra,
+                                              const uint8_t* __restrict__ lut, float* __restrict__ partial, int B, int C, int Hi, int Wi) {
 #pragma clang fp contract(off)
   __shared__ float lds[4];
   const int b = blockIdx.x / AUG_GROUPS, k = blockIdx.x % AUG_GROUPS;
   AugRow a;
   if (!aug_row(aug, b, Hi, Wi, &a) || a.contrast_at == 3) return;
   MixSource s;
-  if (!mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &s)) {
+  RaRow rr;
+  bool ok = mix_source(img, n_split, C, Hs, Ws, rows, boxes, b, &s);
+  if constexpr (RA) ok = ra_row(ra, b, &rr) && ok;
+  if (!ok) {
     if (threadIdx.x == 0) partial[(size_t)b * AUG_GROUPS + k] = 0.0f;
     return;
   }
@@ -225,10 +400,19 @@ __global__ __launch_bounds__(256) void aug_gray_mean_kernel(const uint8_t* __res
   const int n = Hi * Wi;
   for (int q = k * 256 + (int)threadIdx.x; q < n; q += 256 * AUG_GROUPS) {
     const int oy = q / Wi, ox = q - oy * Wi;
-    const RowSource src = row_source(s, oy, Hi, Hs, Ws);
-    const CropAxis ax = crop_axis(ox, Wi, src.w, src.flip);
-    float r = crop_value(src.top, src.bot, ax, src.fy), g = crop_value(src.top + src.plane, src.bot + src.plane, ax, src.fy),
-          bl = crop_value(src.top + 2 * src.plane, src.bot + 2 * src.plane, ax, src.fy);
+    float r, g, bl;
+    if constexpr (RA) {
+      const uint8_t* t = lut + (size_t)b * (3 * 256);
+      r = ra_pixel(s, rr, t, 0, ox, oy, Hi, Wi, Hs, Ws, 3);
+      g = ra_pixel(s, rr, t, 1, ox, oy, Hi, Wi, Hs, Ws, 3);
+      bl = ra_pixel(s, rr, t, 2, ox, oy, Hi, Wi, Hs, Ws, 3);
+    } else {
+      const RowSource src = row_source(s, oy, Hi, Hs, Ws);
+      const CropAxis ax = crop_axis(ox, Wi, src.w, src.flip);
+      r = crop_value(src.top, src.bot, ax, src.fy);
+      g = crop_value(src.top + src.plane, src.bot + src.plane, ax, src.fy);
+      bl = crop_value(src.top + 2 * src.plane, src.bot + 2 * src.plane, ax, src.fy);
+    }
     aug_chain<true>(r, g, bl, a, a.contrast_at, 0.0f);
     acc = acc + aug_gray(r, g, bl);
   }
@@ -236,6 +420,19 @@ __global__ __launch_bounds__(256) void aug_gray_mean_kernel(const uint8_t* __res
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partial[(size_t)b * AUG_GROUPS + k] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+__global__ __launch_bounds__(256) void aug_gray_mean_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                            const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                            const int* __restrict__ aug, float* __restrict__ partial, int B, int C,
+                                                            int Hi, int Wi) {
+  aug_gray_mean<false>(img, n_split, Hs, Ws, rows, boxes, aug, nullptr, nullptr, partial, B, C, Hi, Wi);
+}
+__global__ __launch_bounds__(256) void aug_gray_mean_ra_kernel(const uint8_t* __restrict__ img, long n_split, int Hs, int Ws,
+                                                               const int64_t* __restrict__ rows, const int* __restrict__ boxes,
+                                                               const int* __restrict__ aug, const int* __restrict__ ra,
+                                                               const uint8_t* __restrict__ lut, float* __restrict__ partial, int B, int C,
+                                                               int Hi, int Wi) {
+  aug_gray_mean<true>(img, n_split, Hs, Ws, rows, boxes, aug, ra, lut, partial, B, C, Hi, Wi);
 }
 __global__ __launch_bounds__(64) void aug_gray_mean_reduce_kernel(const int* __restrict__ aug, const float* __restrict__ partial,
                                                                   float* __restrict__ stat, int B, int Hi, int Wi) {
@@ -314,37 +511,48 @@ __global__ __launch_bounds__(256) void aligned_rows_kernel(const cara_feed f, bf
   }
 }
 
-// The box body.  MIX: a mix table may be present; AUG: an aug table is (and a mix table may be).  What a sample is checked for
-// and carries follows from AUG alone: its source, and its jitter row beside it.
-template <bool AUG> struct FeedSample { MixSource box; };
-template <> struct FeedSample<true> { MixSource box; AugRow a; };
-template <bool AUG>
-__device__ __forceinline__ bool feed_sample(const cara_feed& f, int b, FeedSample<AUG>* s) {
+// The box body.  MIX: a mix table may be present; AUG: an aug table is (and a mix table may be); RA: an ra table is (and the other
+// two may be).  What a sample is checked for and carries follows from AUG and RA: its source, its jitter row and its ra row.
+struct NoRow {};
+template <bool AUG, bool RA>
+struct FeedSample { MixSource box; std::conditional_t<AUG, AugRow, NoRow> a; std::conditional_t<RA, RaRow, NoRow> r; };
+template <bool AUG, bool RA>
+__device__ __forceinline__ bool feed_sample(const cara_feed& f, int b, FeedSample<AUG, RA>* s) {
   if (!mix_source(f.pixels, f.n_split, f.C, f.Hs, f.Ws, f.rows, f.boxes, b, &s->box)) return false;
+  if constexpr (RA) {
+    if (!ra_row(f.ra, b, &s->r)) return false;
+  }
   if constexpr (AUG) return aug_row(f.aug, b, f.Hi, f.Wi, &s->a);
   else return true;
 }
-// channel c of output column ox of a sample, un-normalised and unmixed
-template <bool AUG>
-__device__ __forceinline__ float feed_value(const RowSource& s, const FeedSample<AUG>& smp, float M, int c, int ox, int Wi) {
-  if constexpr (AUG) return aug_value(s, smp.a, M, c, ox, Wi);
-  else return crop_value(s.top + c * s.plane, s.bot + c * s.plane, crop_axis(ox, Wi, s.w, s.flip), s.fy);
+// channel c of output pixel (ox, oy) of a sample, un-normalised and unmixed; lut: the sample's ra tables (RA alone)
+template <bool AUG, bool RA>
+__device__ __forceinline__ float feed_value(const cara_feed& f, const RowSource& s, const FeedSample<AUG, RA>& smp, const uint8_t* lut, float M,
+                                            int c, int ox, int oy) {
+  const CropAxis ax = crop_axis(ox, f.Wi, s.w, s.flip);
+  auto crop = [&](int ch) { return crop_value(s.top + ch * s.plane, s.bot + ch * s.plane, ax, s.fy); };
+  auto base = [&](int ch) {
+    if constexpr (RA) return ra_value(smp.box, smp.r, lut, ch, ox, oy, f.Hi, f.Wi, f.Ws, s.plane, 3, crop);
+    else return crop(ch);
+  };
+  if constexpr (AUG) return aug_value(base, smp.a, M, c);
+  else return base(c);
 }
 // A lane keeps four adjacent output pixels of one channel of one patch row (the row pair and fy are shared).  A sample is refused
-// -- zeros, counted once -- where its own or its partner's row, box or jitter row is bad, its partner is outside [0, B) (checked
-// before anything of the partner's is formed), its rectangle is not inside the output or its m is not in [0, 1].
-template <bool MIX, bool AUG, bool KEEP>
-__global__ __launch_bounds__(256) void box_rows_kernel(const cara_feed f, bf16* __restrict__ out, long total4) {
-  static_assert(MIX || !AUG, "the jitter form is the mix form's extension");
+// -- zeros, counted once -- where its own or its partner's row, box, jitter row or ra row is bad, its partner is outside [0, B)
+// (checked before anything of the partner's is formed), its rectangle is not inside the output or its m is not in [0, 1].
+template <bool MIX, bool AUG, bool RA, bool KEEP>
+__device__ __forceinline__ void box_rows(const cara_feed& f, bf16* __restrict__ out, long total4) {
+  static_assert(MIX || !(AUG || RA), "the jitter and ra forms are the mix form's extensions");
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total4) return;
   const int Hi = f.Hi, Wi = f.Wi;
   FeedLane L;
-  MixRow mr;                   // (these three are set by the check below, which feed_lane calls once; oth only where the
-  FeedSample<AUG> own, oth;    // sample has a partner that is not itself)
+  MixRow mr;                       // (these three are set by the check below, which feed_lane calls once; oth only where the
+  FeedSample<AUG, RA> own, oth;    // sample has a partner that is not itself)
   if (!feed_lane<KEEP>(f, out, idx, [&](int b) {
-        mr = mix_row<MIX, AUG>(f.mix, b);
-        // (each sample's jitter row is checked beside its source; a sample that is its own partner checks one source)
+        mr = mix_row<MIX, AUG || RA>(f.mix, b);
+        // (each sample's jitter and ra rows are checked beside its source; a sample that is its own partner checks one source)
         return feed_sample(f, b, &own) &&
                (mr.partner == b || (mr.partner >= 0 && mr.partner < f.B && feed_sample(f, mr.partner, &oth))) && mix_row_ok(mr, Hi, Wi);
       }, &L))
@@ -363,6 +571,12 @@ __global__ __launch_bounds__(256) void box_rows_kernel(const cara_feed f, bf16* 
     erow_in = oy >= own.a.ey0 && oy - own.a.ey0 < own.a.eh;
     i0 = (((unsigned)b * (unsigned)f.C + (unsigned)c) * (unsigned)Hi + (unsigned)oy) * (unsigned)Wi + (unsigned)L.ox;
   }
+  // (a table is read only at a statistic slot: ra_table_kernel wrote exactly those samples')
+  const uint8_t *lut_own = nullptr, *lut_oth = nullptr;
+  if constexpr (RA) {
+    lut_own = static_cast<const uint8_t*>(f.ra_stat) + (size_t)b * (3 * 256);
+    lut_oth = static_cast<const uint8_t*>(f.ra_stat) + (size_t)mr.partner * (3 * 256);
+  }
   const bool row_in = oy >= mr.cy0 && oy - mr.cy0 < mr.ch;
   const float mu = f.mean[c], sd = f.stdv[c];
   float v[4];
@@ -371,12 +585,12 @@ __global__ __launch_bounds__(256) void box_rows_kernel(const cara_feed f, bf16* 
     const int ox = L.ox + j;
     float a;
     if constexpr (!MIX) {
-      a = feed_value(s_own, own, M_own, c, ox, Wi);
+      a = feed_value(f, s_own, own, lut_own, M_own, c, ox, oy);
     } else if (row_in && ox >= mr.cx0 && ox - mr.cx0 < mr.cw) {
-      a = feed_value(s_oth, oth, M_oth, c, ox, Wi);
+      a = feed_value(f, s_oth, oth, lut_oth, M_oth, c, ox, oy);
     } else {
-      a = feed_value(s_own, own, M_own, c, ox, Wi);
-      if (mr.m != 0.0f) a = mix_blend(a, mr.m, feed_value(s_oth, oth, M_oth, c, ox, Wi));
+      a = feed_value(f, s_own, own, lut_own, M_own, c, ox, oy);
+      if (mr.m != 0.0f) a = mix_blend(a, mr.m, feed_value(f, s_oth, oth, lut_oth, M_oth, c, ox, oy));
     }
     v[j] = normalize_f32(a, mu, sd);
     if constexpr (AUG) {
@@ -384,6 +598,14 @@ __global__ __launch_bounds__(256) void box_rows_kernel(const cara_feed f, bf16* 
     }
   }
   *reinterpret_cast<bf16x4*>(out + L.e) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
+}
+template <bool MIX, bool AUG, bool KEEP>
+__global__ __launch_bounds__(256) void box_rows_kernel(const cara_feed f, bf16* __restrict__ out, long total4) {
+  box_rows<MIX, AUG, false, KEEP>(f, out, total4);
+}
+template <bool AUG, bool KEEP>
+__global__ __launch_bounds__(256) void box_rows_ra_kernel(const cara_feed f, bf16* __restrict__ out, long total4) {
+  box_rows<true, AUG, true, KEEP>(f, out, total4);
 }
 
 // out[i] = labels[rows[i]]; a row outside [0, n_split) is not dereferenced: it gives 0 and is counted in *bad (may be NULL)
@@ -402,6 +624,7 @@ __global__ __launch_bounds__(256) void gather_labels_kernel(const int64_t* __res
 using FeedKernel = void (*)(cara_feed, bf16*, long);
 template <bool KEEP>
 FeedKernel feed_kernel(const cara_feed& f) {
+  if (f.ra) return f.aug ? box_rows_ra_kernel<true, KEEP> : box_rows_ra_kernel<false, KEEP>;
   if (f.aug) return box_rows_kernel<true, true, KEEP>;
   if (f.mix) return box_rows_kernel<true, false, KEEP>;
   if (f.boxes) return box_rows_kernel<false, false, KEEP>;
@@ -425,7 +648,7 @@ int cara_feed_patch_rows(const cara_feed& f, void* patches, void* stream) {
   if (!f.boxes && (f.Hs != f.Hi || f.Ws != f.Wi)) return CARA_E_ARG;   // (without boxes a sample is its whole image, byte for byte)
   const int grid_rows = (f.Hi / f.p) * (f.Wi / f.p);
   if (f.keep && (f.K < 1 || f.K > grid_rows)) return CARA_E_ARG;
-  const bool box = f.boxes || f.mix || f.aug;
+  const bool box = f.boxes || f.mix || f.aug || f.ra;
   if (f.images) {
     if (f.pixels || f.rows || box) return CARA_E_ARG;
   } else {
@@ -435,14 +658,31 @@ int cara_feed_patch_rows(const cara_feed& f, void* patches, void* stream) {
   // (dword loads: with p % 4 == 0 and Wi % 4 == 0 every image, row and patch segment starts dword-aligned)
   if (!box && ((f.Wi & 3) || (reinterpret_cast<uintptr_t>(f.pixels) & 3))) return CARA_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  uint8_t* lut = static_cast<uint8_t*>(f.ra_stat);
+  // (every refusal before the first launch)
+  if (f.ra && (f.C != 3 || !f.ra_stat || (reinterpret_cast<uintptr_t>(f.ra_stat) & 3))) return CARA_E_ARG;   // (fill is three bytes, the tables per channel of three)
   if (f.aug) {
     if (f.C != 3) return CARA_E_ARG;                              // (the colour ops are defined on three channels)
     if (!f.stat || (reinterpret_cast<uintptr_t>(f.stat) & 3)) return CARA_E_ARG;
     if (2ull * (unsigned long long)f.B * f.C * f.Hi * f.Wi > (1ull << 32)) return CARA_E_ARG;   // (the noise's two counters per element are 32-bit)
+  }
+  if (f.ra) {
+    int* partial = reinterpret_cast<int*>(lut + (size_t)f.B * (3 * 256));
+    hipLaunchKernelGGL(ra_hist_kernel, dim3((unsigned)f.B * RA_GROUPS), dim3(256), 0, st, f.pixels, (long)f.n_split, f.Hs, f.Ws, f.rows, f.boxes,
+                       f.ra, partial, f.B, f.C, f.Hi, f.Wi);
+    CARA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ra_table_kernel, dim3((unsigned)f.B * 3), dim3(256), 0, st, f.ra, partial, lut, f.B);
+    CARA_CHECK_LAUNCH();
+  }
+  if (f.aug) {
     float* stat = static_cast<float*>(f.stat);
     float* partial = stat + f.B;
-    hipLaunchKernelGGL(aug_gray_mean_kernel, dim3((unsigned)f.B * AUG_GROUPS), dim3(256), 0, st, f.pixels, (long)f.n_split, f.Hs, f.Ws, f.rows,
-                       f.boxes, f.aug, partial, f.B, f.C, f.Hi, f.Wi);
+    if (f.ra)
+      hipLaunchKernelGGL(aug_gray_mean_ra_kernel, dim3((unsigned)f.B * AUG_GROUPS), dim3(256), 0, st, f.pixels, (long)f.n_split, f.Hs, f.Ws,
+                         f.rows, f.boxes, f.aug, f.ra, lut, partial, f.B, f.C, f.Hi, f.Wi);
+    else
+      hipLaunchKernelGGL(aug_gray_mean_kernel, dim3((unsigned)f.B * AUG_GROUPS), dim3(256), 0, st, f.pixels, (long)f.n_split, f.Hs, f.Ws, f.rows,
+                         f.boxes, f.aug, partial, f.B, f.C, f.Hi, f.Wi);
     CARA_CHECK_LAUNCH();
     hipLaunchKernelGGL(aug_gray_mean_reduce_kernel, dim3((unsigned)((f.B + 63) / 64)), dim3(64), 0, st, f.aug, partial, stat, f.B, f.Hi, f.Wi);
     CARA_CHECK_LAUNCH();
@@ -526,6 +766,21 @@ extern "C" int cara_im2col_patches_u8_rows_keep(const unsigned char* pixels, int
   f.Hs = Hs; f.Ws = Ws; f.boxes = boxes; f.mix = mix; f.aug = aug; f.stat = stat_scratch; f.keep = keep; f.K = K;
   return cara_feed_patch_rows(f, patches, stream);
 }
+
+// RandAugment by index: every table but `rows` may be NULL; without `ra` the launches of the _keep / _aug entries
+extern "C" int cara_im2col_patches_u8_rows_ra(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows,
+                                              const int* boxes, const int* mix, const int* aug, void* stat_scratch, const int* ra,
+                                              void* ra_scratch, const int* keep, int K, const float* mean, const float* stdv,
+                                              void* patches, int* bad, int B, int C, int Hi, int Wi, int p, void* stream) {
+  if (!rows) return CARA_E_ARG;
+  cara_feed f = whole_images(B, C, Hi, Wi, p);
+  f.pixels = pixels; f.mean = mean; f.stdv = stdv; f.n_split = n_split; f.rows = rows; f.bad = bad;
+  f.Hs = Hs; f.Ws = Ws; f.boxes = boxes; f.mix = mix; f.aug = aug; f.stat = stat_scratch; f.ra = ra; f.ra_stat = ra_scratch;
+  f.keep = keep; f.K = keep ? K : 0;
+  return cara_feed_patch_rows(f, patches, stream);
+}
+
+extern "C" size_t cara_ra_stat_bytes(int B) { return B > 0 ? (size_t)B * (3 * 256) * (1 + RA_GROUPS * sizeof(int)) : 0; }
 
 extern "C" int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
                                   void* stream) {

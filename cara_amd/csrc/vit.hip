@@ -979,7 +979,7 @@ extern "C" int cara_head_backward(const float* dlogits, const void* xn, const fl
 
 // The image of a forward is a cara_feed (common.h; the patch rows are feed.hip's): an fp32 batch, or resident uint8 pixels with
 // their per-channel mean / std -- the batch itself, or a whole split of n_split images that `rows` indexes, each sample read whole or
-// through its box, mixed with a partner, colour-jittered / erased, all of its patches or a kept subset.  Each entry checks and sets
+// through its box, RandAugmented, mixed with a partner, colour-jittered / erased, all of its patches or a kept subset.  Each entry checks and sets
 // the fields it has arguments for; the body adds the shape's, and everything behind the patch rows is the same.
 // (a source of Hs x Ws images; an entry without a size of its own reads the shape's img x img images.  Fields are set by name: a
 // field added to cara_feed must not shift an initialiser.)
@@ -1164,6 +1164,19 @@ extern "C" int cara_vit_forward_u8_rows_keep(const cara_geom* g, const cara_vit_
   cara_feed src = source_of(Hs, Ws);
   src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
   src.boxes = boxes; src.mix = mix; src.aug = aug; src.stat = stat_scratch; src.keep = keep;
+  return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
+}
+
+extern "C" int cara_vit_forward_u8_rows_ra(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp,
+                                           const float* head_w, const float* head_b, const unsigned char* pixels, int n_split, int Hs,
+                                           int Ws, const int64_t* rows, const int* boxes, const int* mix, const int* aug,
+                                           void* stat_scratch, const int* ra, void* ra_scratch, const int* keep, const float* mean,
+                                           const float* stdv, const float* droppath, void* workspace, float* logits, int* bad,
+                                           void* stream) {
+  if (!pixels || !rows || !ra || !ra_scratch || (aug && !stat_scratch) || n_split <= 0 || Hs <= 0 || Ws <= 0 || !mean || !stdv) return CARA_E_ARG;
+  cara_feed src = source_of(Hs, Ws);
+  src.pixels = pixels; src.mean = mean; src.stdv = stdv; src.n_split = n_split; src.rows = rows; src.bad = bad;
+  src.boxes = boxes; src.mix = mix; src.aug = aug; src.stat = stat_scratch; src.ra = ra; src.ra_stat = ra_scratch; src.keep = keep;
   return vit_forward_body(g, s, w, cp, head_w, head_b, src, droppath, workspace, logits, stream);
 }
 

@@ -461,6 +461,12 @@ def aug_reference(pixels_u8: torch.Tensor, rows, boxes, mix, aug, size, dtype=to
         raise ValueError("the colour ops are defined on three channels")
     x = resized_crop_reference(pixels_u8, rows, boxes, (Hi, Wi), dtype)
     y = torch.stack([color_chain_reference(x[i], aug[i]) for i in range(B)])
+    return _mix_normalize_erase(y, mix, aug, Hi, Wi, dtype)
+
+
+def _mix_normalize_erase(y: torch.Tensor, mix, aug, Hi: int, Wi: int, dtype) -> torch.Tensor:
+    """the tail of ``aug_reference`` (and ``ra_reference``) on the unmixed images ``y`` [B,3,Hi,Wi] after their own chains"""
+    B = y.shape[0]
     m = _bits_f32(mix[:, 5]).to(dtype)
     out = torch.empty_like(y)
     for i, (p, cx0, cy0, cw, ch) in enumerate(mix[:, :5].tolist()):
@@ -476,6 +482,274 @@ def aug_reference(pixels_u8: torch.Tensor, rows, boxes, mix, aug, size, dtype=to
         sl = (slice(None), slice(ey0, ey0 + eh), slice(ex0, ex0 + ew))
         out[i][sl] = torch.from_numpy(erase_noise(index[i][sl].numpy(), eseed)[2]).to(dtype) if emode else 0.0
     return out
+
+
+def ra_seed(seed: int, epoch: int, rank: int) -> int:
+    """``box_seed`` of the stream that draws the RandAugment tables (a fifth constant)"""
+    return box_seed(seed, epoch, rank, stream=0x3C6EF372)
+
+
+RA_NONE, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_INVERT, RA_AUTOCONTRAST, RA_EQUALIZE = range(7)
+RA_ARG_MAX = (0, 8, 256, 255, 0, 0, 0)        # the largest argument of each lookup op
+RA_MATRIX_MAX = 32768.0
+RA_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
+          "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+_RA_LOOKUP = {"Posterize": RA_POSTERIZE, "Solarize": RA_SOLARIZE, "SolarizeAdd": RA_SOLARIZE_ADD, "Invert": RA_INVERT,
+              "AutoContrast": RA_AUTOCONTRAST, "Equalize": RA_EQUALIZE}
+_RA_JITTER = {"Color": AUG_SATURATION, "Contrast": AUG_CONTRAST, "Brightness": AUG_BRIGHTNESS}
+_RA_GEOMETRIC = ("Rotate", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+
+
+def identity_ra(B: int, steps: Optional[int] = None) -> torch.Tensor:
+    """int32 [B, 16] (or [steps, B, 16]) table that changes nothing: no lookup op, the identity matrix (1, 0, 0, 0, 1, 0), fill 0"""
+    t = torch.zeros((B, 16) if steps is None else (steps, B, 16), dtype=torch.int32)
+    t[..., 6] = t[..., 10] = 0x3f800000
+    return t
+
+
+def ra_level_arg(op: str, level: float, sign: int = 1, increasing: bool = True):
+    """the argument of one op at level L in [0, 10] (timm's ``_LEVEL_DENOM`` = 10), restated: Rotate -> degrees ``+-30 L/10``; ShearX /
+    ShearY -> ``+-0.3 L/10``; TranslateXRel / TranslateYRel -> ``+-0.45 L/10`` of the size; Posterize -> bits kept ``4 - int(4 L/10)``
+    (not increasing: ``int(4 L/10)``); Solarize -> threshold ``256 - int(256 L/10)`` (not increasing: ``int(256 L/10)``); SolarizeAdd ->
+    ``int(110 L/10)``; Color / Contrast / Brightness -> factor ``max(0.1, 1 +- 0.9 L/10)`` (not increasing: ``0.1 + 1.8 L/10``);
+    AutoContrast, Equalize, Invert -> None"""
+    x = float(level) / 10.0
+    if op == "Rotate":
+        return sign * 30.0 * x
+    if op in ("ShearX", "ShearY"):
+        return sign * 0.3 * x
+    if op in ("TranslateXRel", "TranslateYRel"):
+        return sign * 0.45 * x
+    if op == "Posterize":
+        return 4 - int(4 * x) if increasing else int(4 * x)
+    if op == "Solarize":
+        return 256 - int(256 * x) if increasing else min(256, int(256 * x))
+    if op == "SolarizeAdd":
+        return min(255, int(110 * x))
+    if op in _RA_JITTER:
+        return max(0.1, 1.0 + sign * 0.9 * x) if increasing else 0.1 + 1.8 * x
+    if op in ("AutoContrast", "Equalize", "Invert"):
+        return None
+    raise ValueError(f"unknown RandAugment op {op!r} (one of {RA_OPS})")
+
+
+def ra_op_matrix(op: str, arg: float, Hi: int, Wi: int):
+    """the 3 x 3 float64 output-to-input matrix of one geometric op on a ``Hi`` x ``Wi`` image, in PIL's ``Image.transform(AFFINE)``
+    convention (evaluated at pixel centres): Rotate by ``arg`` degrees about (Wi / 2, Hi / 2) as ``Image.rotate`` builds it; ShearX
+    (1, arg, 0; 0, 1, 0); ShearY (1, 0, 0; arg, 1, 0); TranslateXRel (1, 0, arg Wi; 0, 1, 0); TranslateYRel (1, 0, 0; 0, 1, arg Hi)"""
+    import numpy as np
+    m = np.eye(3)
+    if op == "Rotate":
+        t = -math.radians(arg)
+        c, s, cx, cy = math.cos(t), math.sin(t), Wi / 2.0, Hi / 2.0
+        m[0] = (c, s, cx - (c * cx + s * cy))
+        m[1] = (-s, c, cy - (-s * cx + c * cy))
+    elif op == "ShearX":
+        m[0, 1] = arg
+    elif op == "ShearY":
+        m[1, 0] = arg
+    elif op == "TranslateXRel":
+        m[0, 2] = arg * Wi
+    elif op == "TranslateYRel":
+        m[1, 2] = arg * Hi
+    else:
+        raise ValueError(f"{op!r} is no geometric op")
+    return m
+
+
+class RandAugment:
+    """RandAugment tables for the resident feed (timm's ``rand-m9-mstd0.5-inc1``), restated from the published definitions (timm is
+    not installed): per sample ``n`` ops drawn uniformly (with replacement) from ``ops``, each applied with probability ``prob`` at the
+    level ``clip(N(m, mstd), 0, 10)`` through ``ra_level_arg`` (a fair sign where the map says +-).
+    ``draw`` gives two tables: ``ra`` int32 [steps, B, 16], rows ``(op0, arg0, op1, arg1, op2, arg2, m00, m01, m02, m10, m11, m12,
+    fill, 0, 0, 0)`` of ``cara_im2col_patches_u8_rows_ra`` (include/cara_hip.h), and ``slots`` int32 [steps, B, 6], the jitter slots
+    ``(op0, f0, op1, f1, op2, f2)`` of the ``aug`` row.  The geometric ops of a sample compose in drawn order into ONE output-to-input
+    matrix (float64, rounded once to fp32): one resampling, not one per op.  Posterize, Solarize, SolarizeAdd, Invert, AutoContrast
+    and Equalize fill the lookup slots in drawn order; Color / Contrast / Brightness become the saturation / contrast / brightness
+    slots of the aug row.
+    Known departures from PIL's order of application: (1) the geometry always comes first, whatever was drawn; (2) the jitter slots
+    run after the lookup slots; (3) the fill pixels pass through the lookup slots (PIL fills after them when the geometric op comes
+    last); (4) a second AutoContrast / Equalize of a sample is dropped (one statistic slot per row), and so is a repeated Color /
+    Contrast / Brightness (``check_aug``: a jitter op at most once per row).  Not built: Sharpness, PIL's random choice of
+    interpolation (always bilinear).  ``size`` = Hi or (Hi, Wi): the model's input.  ``n`` <= 3: a row has three slots of each kind."""
+
+    def __init__(self, size, n: int = 2, m: float = 9, mstd: float = 0.5, prob: float = 0.5, increasing: bool = True,
+                 fill=(124, 116, 104), ops=None):
+        Hi, Wi = (size, size) if isinstance(size, int) else size
+        ops = tuple(RA_OPS if ops is None else ops)
+        if int(Hi) <= 0 or int(Wi) <= 0 or not (1 <= int(n) <= 3) or not (0 <= m <= 10) or mstd < 0 or not (0.0 <= prob <= 1.0) \
+                or len(fill) != 3 or any(not (0 <= int(v) <= 255) for v in fill) or not ops or any(o not in RA_OPS for o in ops):
+            raise ValueError(f"RandAugment: size > 0, 1 <= n <= 3, 0 <= m <= 10, mstd >= 0, prob in [0, 1], fill three bytes, ops from {RA_OPS}")
+        self.Hi, self.Wi, self.n, self.m, self.mstd, self.prob = int(Hi), int(Wi), int(n), float(m), float(mstd), float(prob)
+        self.increasing, self.ops = bool(increasing), ops
+        self.fill = (int(fill[0]) << 16) | (int(fill[1]) << 8) | int(fill[2])
+
+    def row(self, drawn):
+        """(ra row, jitter slots) as two lists of ints from ``[(op name, level, sign), ...]`` in drawn order (the applied ops only)"""
+        import numpy as np
+        mat, lookup, jitter = np.eye(3), [], []
+        for op, level, sign in drawn:
+            arg = ra_level_arg(op, level, sign, self.increasing)
+            if op in _RA_GEOMETRIC:
+                mat = mat @ ra_op_matrix(op, arg, self.Hi, self.Wi)     # (the later op maps the output first)
+            elif op in _RA_LOOKUP:
+                code = _RA_LOOKUP[op]
+                if code >= RA_AUTOCONTRAST and any(c >= RA_AUTOCONTRAST for c, _ in lookup):
+                    continue
+                lookup.append((code, 0 if arg is None else int(arg)))
+            elif all(c != _RA_JITTER[op] for c, _ in jitter):
+                jitter.append((_RA_JITTER[op], int(np.array([arg], dtype=np.float32).view(np.int32)[0])))
+        lookup += [(0, 0)] * (3 - len(lookup))
+        jitter += [(0, 0)] * (3 - len(jitter))
+        words = [int(w) for w in np.ascontiguousarray(mat[:2].astype(np.float32)).view(np.int32).reshape(-1)]
+        return [v for s in lookup for v in s] + words + [self.fill, 0, 0, 0], [v for s in jitter for v in s]
+
+    def draw(self, B: int, steps: int, generator: Optional[torch.Generator] = None):
+        """(ra int32 [steps, B, 16], slots int32 [steps, B, 6]) on the host.  One variate of ``generator`` per batch -- the seed of that
+        batch's own generator, as in ``MixupCutmix.draw`` -- so batch ``k`` does not depend on ``steps``."""
+        ra, slots = identity_ra(B, steps), torch.zeros(steps, B, 6, dtype=torch.int32)
+        for k in range(steps):
+            g = torch.Generator().manual_seed(int(torch.randint(0, 2 ** 31 - 1, (1,), generator=generator)))
+            which = torch.randint(0, len(self.ops), (B, self.n), generator=g).tolist()
+            coin = torch.rand(B, self.n, generator=g, dtype=torch.float64).tolist()
+            level = (self.m + self.mstd * torch.randn(B, self.n, generator=g, dtype=torch.float64)).clamp_(0.0, 10.0).tolist()
+            sign = torch.rand(B, self.n, generator=g, dtype=torch.float64).tolist()
+            rows = [self.row([(self.ops[which[b][j]], level[b][j], 1 if sign[b][j] < 0.5 else -1) for j in range(self.n) if coin[b][j] < self.prob])
+                    for b in range(B)]
+            ra[k] = torch.tensor([r for r, _ in rows], dtype=torch.int32)
+            slots[k] = torch.tensor([s for _, s in rows], dtype=torch.int32)
+        return ra, slots
+
+
+def check_ra(ra: torch.Tensor, B: int) -> None:
+    """ValueError unless ``ra`` is an int32 [..., B, 16] table the kernel accepts: every op in [0, 6], every argument in its op's range
+    (``RA_ARG_MAX``; 0 for no op), at most one statistic op (autocontrast, equalize) in a row, every matrix word a finite fp32 of
+    magnitude <= 32768, fill <= 0xFFFFFF, the last three words 0 (the companion of ``check_aug``)"""
+    if not torch.is_tensor(ra) or ra.dtype != torch.int32 or ra.ndim < 2 or ra.shape[-1] != 16 or ra.shape[-2] != B:
+        raise ValueError("ra must be an int32 [..., batch, 16] tensor (op0, arg0, op1, arg1, op2, arg2, m00, m01, m02, m10, m11, m12, fill, 0, 0, 0)")
+    t = ra.reshape(-1, 16).cpu()
+    w = t.to(torch.int64)
+    ops, args, m = w[:, 0:6:2], w[:, 1:6:2], _bits_f32(t[:, 6:12])
+    bad = ((ops < 0) | (ops > 6)).any(1)
+    top = torch.tensor(RA_ARG_MAX)[ops.clamp(0, 6)]
+    bad |= ((args < 0) | (args > top)).any(1)
+    bad |= (ops >= RA_AUTOCONTRAST).sum(1) > 1
+    bad |= (~(m.abs() <= RA_MATRIX_MAX)).any(1)
+    bad |= (w[:, 12] < 0) | (w[:, 12] > 0xFFFFFF) | (w[:, 13:] != 0).any(1)
+    if bool(bad.any()):
+        i = int(bad.to(torch.int64).argmax())
+        raise ValueError(f"{int(bad.sum())} ra entry(ies) with an unknown op, an argument outside its range, two statistic ops, a matrix "
+                         f"word that is not finite or above {RA_MATRIX_MAX:g} in magnitude, a fill above 0xFFFFFF or a non-zero pad word, "
+                         f"the first: {t[i].tolist()}")
+
+
+def ra_lut(hist, op: int):
+    """the 256-entry table of a statistic op from a 256-bin histogram (integers): autocontrast -- lo, hi the first / last non-zero
+    bin, identity if hi <= lo, else ``clamp(255 (i - lo) // (hi - lo), 0, 255)`` and 0 below lo; equalize -- ``step = (sum h - h[hi])
+    // 255``, identity if hi <= lo or step == 0, else ``min(255, (step // 2 + sum_{j<i} h[j]) // step)``.  numpy int64 [256]."""
+    import numpy as np
+    h = np.asarray(hist, dtype=np.int64)
+    i = np.arange(256, dtype=np.int64)
+    nz = np.nonzero(h)[0]
+    if len(nz) < 2:
+        return i
+    lo, hi = int(nz[0]), int(nz[-1])
+    if op == RA_AUTOCONTRAST:
+        return np.where(i < lo, 0, np.clip((255 * (i - lo)) // (hi - lo), 0, 255))
+    step = (int(h.sum()) - int(h[hi])) // 255
+    if step == 0:
+        return i
+    before = np.concatenate([[0], np.cumsum(h)[:-1]])
+    return np.minimum(255, (step // 2 + before) // step)
+
+
+def ra_lookup_reference(q, row):
+    """the lookup slots of one ra row on the quantised image ``q`` (integer array [3,Hi,Wi]) -> (image, tables or None): the
+    statistic slot's tables are int64 [3, 256], of the histograms as they stand before that slot"""
+    import numpy as np
+    q = np.asarray(q).astype(np.int64)
+    tables = None
+    for k in range(3):
+        op, arg = int(row[2 * k]), int(row[2 * k + 1])
+        if op == RA_POSTERIZE:
+            q = q & ~((1 << (8 - arg)) - 1)
+        elif op == RA_SOLARIZE:
+            q = np.where(q < arg, q, 255 - q)
+        elif op == RA_SOLARIZE_ADD:
+            q = np.where(q < 128, np.minimum(q + arg, 255), q)
+        elif op == RA_INVERT:
+            q = 255 - q
+        elif op in (RA_AUTOCONTRAST, RA_EQUALIZE):
+            tables = np.stack([ra_lut(np.bincount(q[c].reshape(-1), minlength=256), op) for c in range(3)])
+            q = np.stack([tables[c][q[c]] for c in range(3)])
+    return q, tables
+
+
+def ra_geometry_reference(pixels_u8: torch.Tensor, r: int, box, row, Hi: int, Wi: int, dtype=torch.float64) -> torch.Tensor:
+    """the geometry of one ra row on image ``r`` of the split through ``box`` = (x0, y0, w, h, flip): [3,Hi,Wi] of ``dtype`` on the
+    0..255 scale, in the kernel's formula with the fp32 matrix words the row holds -- ``u = m00 x + m01 y + m02``, ``v = m10 x + m11 y +
+    m12`` at ``x = ox + 0.5``, ``y = oy + 0.5``; the fill byte unless ``0 <= u < Wi`` and ``0 <= v < Hi``; inside, ``uf = flip ? Wi - u : u``,
+    ``s = max(uf w / Wi - 0.5, 0)``, ``i0 = min(int(s), w - 1)``, ``i1 = min(i0 + 1, w - 1)``, ``f = s - i0``, the same for v, bilinear"""
+    x0, y0, w, h, flip = (int(v) for v in box)
+    row = torch.as_tensor(row).to(torch.int32)
+    m = _bits_f32(row[6:12]).to(dtype)
+    src = pixels_u8[r, :, y0:y0 + h, x0:x0 + w].to(dtype)
+    y, x = torch.meshgrid(torch.arange(Hi, dtype=dtype) + 0.5, torch.arange(Wi, dtype=dtype) + 0.5, indexing="ij")
+    u = m[0] * x + m[1] * y + m[2]
+    v = m[3] * x + m[4] * y + m[5]
+    inside = (u >= 0) & (u < Wi) & (v >= 0) & (v < Hi)
+    uf = Wi - u if flip else u
+
+    def axis(t, n_box, n_out):
+        s = (t * n_box / n_out - 0.5).clamp(min=0)
+        s = torch.where(inside, s, torch.zeros_like(s))
+        i0 = s.to(torch.int64).clamp(max=n_box - 1)
+        return i0, (i0 + 1).clamp(max=n_box - 1), s - i0.to(dtype)
+    ix0, ix1, fx = axis(uf, w, Wi)
+    iy0, iy1, fy = axis(v, h, Hi)
+    top = (1 - fx) * src[:, iy0, ix0] + fx * src[:, iy0, ix1]
+    bot = (1 - fx) * src[:, iy1, ix0] + fx * src[:, iy1, ix1]
+    val = (1 - fy) * top + fy * bot
+    fill = int(row[12])
+    fills = torch.tensor([(fill >> 16) & 255, (fill >> 8) & 255, fill & 255], dtype=dtype).view(3, 1, 1)
+    return torch.where(inside[None], val, fills.expand_as(val))
+
+
+def ra_reference(pixels_u8: torch.Tensor, rows, boxes, mix, aug, ra, size, dtype=torch.float64, parts: bool = False):
+    """What ``cara_im2col_patches_u8_rows_ra`` computes before its one rounding to 16 bits, in torch / numpy ops on the CPU: the
+    NORMALISED image [B,3,Hi,Wi] of ``dtype``.  Per sample ``ra_geometry_reference``; where the row has a lookup slot, ``rint`` (half to
+    even) and ``ra_lookup_reference``; then ``color_chain_reference`` with the ``aug`` row (``aug`` None: none), the mix (``mix`` None:
+    none), the normalisation and the erase of ``aug_reference``.  ``parts``: also the unquantised geometry values and the statistic
+    tables, ``(out, geometry [B,3,Hi,Wi], [tables or None] * B)``."""
+    Hi, Wi = (size, size) if isinstance(size, int) else size
+    rows = torch.as_tensor(rows).cpu()
+    B = len(rows)
+    px = pixels_u8.cpu()
+    if boxes is None:
+        if tuple(px.shape[2:]) != (Hi, Wi):
+            raise ValueError("without boxes the split must have the output's size")
+        boxes = torch.tensor([[0, 0, Wi, Hi, 0]] * B, dtype=torch.int32)
+    boxes = torch.as_tensor(boxes).cpu()
+    mix = identity_mix(B) if mix is None else torch.as_tensor(mix).cpu()
+    aug = identity_aug(B) if aug is None else torch.as_tensor(aug).cpu()
+    ra = torch.as_tensor(ra).cpu()
+    check_boxes(boxes, px.shape[2], px.shape[3])
+    check_mix(mix, B, Hi, Wi)
+    check_aug(aug, B, Hi, Wi)
+    check_ra(ra, B)
+    if px.shape[1] != 3:
+        raise ValueError("the RandAugment ops are defined on three channels")
+    geo = torch.stack([ra_geometry_reference(px, int(rows[i]), boxes[i].tolist(), ra[i], Hi, Wi, dtype) for i in range(B)])
+    y, tables = [], []
+    for i in range(B):
+        v, t = geo[i], None
+        if bool((ra[i, 0:6:2] != 0).any()):
+            q, t = ra_lookup_reference(torch.round(v).clamp(0, 255).to(torch.int64).numpy(), ra[i].tolist())
+            v = torch.from_numpy(q).to(dtype)
+        tables.append(t)
+        y.append(color_chain_reference(v, aug[i]))
+    out = _mix_normalize_erase(torch.stack(y), mix, aug, Hi, Wi, dtype)
+    return (out, geo, tables) if parts else out
 
 
 def keep_seed(seed: int, epoch: int, rank: int) -> int:
@@ -607,7 +881,7 @@ class ResidentSplit:
 
     def train_rows(self, batch_size: int = 64, seed: int = 0, rank: Optional[int] = None,
                    world: Optional[int] = None, augment=None, mix=None, color=None,
-                   patch_drop=None) -> Callable[[int], Iterator[torch.Tensor]]:
+                   patch_drop=None, rand=None) -> Callable[[int], Iterator[torch.Tensor]]:
         """``f(epoch)`` -> iterator of int64 [batch_size] index vectors on the device: the indices ``train_batches`` draws
         (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
         and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
@@ -626,7 +900,17 @@ class ResidentSplit:
         ``patch_drop`` (a ``PatchDropout`` that knows its ``grid``, or anything with its ``draw`` and ``grid``): the iterator yields
         ``(rows, boxes, mix, aug, keep)`` -- None for the tables not asked for -- each with an int32 [batch_size, K] view of one
         [steps, batch_size, K] upload per epoch (``train_step_resident(..., keep=)``), drawn on a fourth stream (``keep_seed``) and
-        checked (``check_keep``) before the upload."""
+        checked (``check_keep``) before the upload.
+        ``rand`` (a ``RandAugment``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix, aug, keep,
+        ra)`` -- None for the tables not asked for, except ``aug``, which carries the jitter slots ``rand`` drew -- each with an int32
+        [batch_size, 16] view of one upload per epoch (``train_step_resident(..., ra=)``), drawn on a fifth stream (``ra_seed``) and
+        checked (``check_ra``, ``check_aug``) before the upload.  With ``color`` too, ``color`` must only erase (its three jitters 0): as
+        in timm, auto-augment replaces colour jitter."""
+        if rand is not None and not (callable(getattr(rand, "draw", None)) and isinstance(getattr(rand, "Hi", None), int)
+                                     and isinstance(getattr(rand, "Wi", None), int)):
+            raise ValueError("rand must be a RandAugment (anything with draw(B, steps, generator), Hi and Wi)")
+        if rand is not None and color is not None and any(float(j) != 0.0 for j in getattr(color, "jitter", (1.0,))):
+            raise ValueError("rand replaces colour jitter: pass a color that only erases (brightness = contrast = saturation = 0)")
         if patch_drop is not None and not (callable(getattr(patch_drop, "draw", None)) and isinstance(getattr(patch_drop, "grid", None), int)):
             raise ValueError("patch_drop must be a PatchDropout with its grid (PatchDropout(prob, size=, patch=) or grid=)")
         if color is not None and not (callable(getattr(color, "draw", None)) and isinstance(getattr(color, "Hi", None), int)
@@ -674,9 +958,24 @@ class ResidentSplit:
                                      f"not an int32 {(*table.shape, 16)} table")
                 check_aug(augs, table.shape[1], color.Hi, color.Wi)
                 augs = augs.contiguous().to(self.pixels.device)
+            ras = None
+            if rand is not None:
+                ras, slots = rand.draw(table.shape[1], table.shape[0], torch.Generator().manual_seed(ra_seed(seed, epoch, rank)))
+                if not torch.is_tensor(ras) or tuple(ras.shape) != (*table.shape, 16) or not torch.is_tensor(slots) \
+                        or tuple(slots.shape) != (*table.shape, 6):
+                    raise ValueError(f"rand.draw did not give an int32 {(*table.shape, 16)} table and int32 {(*table.shape, 6)} jitter slots")
+                check_ra(ras, table.shape[1])
+                ras = ras.contiguous().to(self.pixels.device)
+                host = identity_aug(table.shape[1], table.shape[0]) if augs is None else augs.cpu().clone()
+                host[..., :6] = slots
+                check_aug(host, table.shape[1], rand.Hi, rand.Wi)
+                augs = host.contiguous().to(self.pixels.device)
             table = table.to(self.pixels.device)
             for step in range(table.shape[0]):
-                if keeps is not None:
+                if ras is not None:
+                    yield (table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]), augs[step],
+                           (None if keeps is None else keeps[step]), ras[step])
+                elif keeps is not None:
                     yield (table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]),
                            (None if augs is None else augs[step]), keeps[step])
                 elif augs is not None:
@@ -718,7 +1017,7 @@ class ResidentSplit:
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
              seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False, augment=None,
-             train_size: Optional[int] = None, mix=None, color=None, patch_drop=None):
+             train_size: Optional[int] = None, mix=None, color=None, patch_drop=None, rand=None):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
@@ -731,10 +1030,11 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size.
     ``mix`` (with ``resident_feed``; a ``MixupCutmix``): ``train_rows`` yields ``(rows, boxes or None, mix)``.
     ``color`` (with ``resident_feed``; a ``ColorJitterErase``): ``train_rows`` yields ``(rows, boxes or None, mix or None, aug)``.
-    ``patch_drop`` (with ``resident_feed``; a ``PatchDropout`` with its grid): ``train_rows`` yields the 5-tuple ending in ``keep``."""
-    if (augment is not None or train_size is not None or mix is not None or color is not None or patch_drop is not None) \
-            and not resident_feed:
-        raise ValueError("augment / train_size / mix / color / patch_drop belong to the resident feed: pass resident_feed=True")
+    ``patch_drop`` (with ``resident_feed``; a ``PatchDropout`` with its grid): ``train_rows`` yields the 5-tuple ending in ``keep``.
+    ``rand`` (with ``resident_feed``; a ``RandAugment``): ``train_rows`` yields the 6-tuple ending in ``ra``."""
+    if (augment is not None or train_size is not None or mix is not None or color is not None or patch_drop is not None
+            or rand is not None) and not resident_feed:
+        raise ValueError("augment / train_size / mix / color / patch_drop / rand belong to the resident feed: pass resident_feed=True")
     if train_size is not None and train_size != 224 and augment is None:
         raise ValueError("a training split of another size than the model's is read through crop boxes: pass augment")
     root = root if root is not None else "./data/vtab-1k/" + name
@@ -744,7 +1044,8 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     if resident_feed:
         feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix,
                                         **({"color": color} if color is not None else {}),
-                                        **({"patch_drop": patch_drop} if patch_drop is not None else {})))
+                                        **({"patch_drop": patch_drop} if patch_drop is not None else {}),
+                                        **({"rand": rand} if rand is not None else {})))
     else:
         feed = train.train_batches(batch_size, seed=seed)
     return feed, (test if shard_eval else test.eval_batches(256))

@@ -265,15 +265,15 @@ class CaraEngine:
                             "(data.PatchDropout.draw, data.check_keep)")
 
     def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None, keep=None):
-        """``resident = (split, rows[, boxes[, mix[, aug]]])``: the images are rows of a resident uint8 split (``images`` is None
+        """``resident = (split, rows[, boxes[, mix[, aug[, ra]]]])``: the images are rows of a resident uint8 split (``images`` is None
         then), with ``boxes`` read through a crop box per sample at the model's own input size, with ``mix`` mixed by that table, with
-        ``aug`` colour-jittered and erased by that one.  ``keep`` (device int32 [batch, K]): the patch tokens a patch dropout keeps;
+        ``aug`` colour-jittered and erased by that one, with ``ra`` RandAugmented by that one.  ``keep`` (device int32 [batch, K]): the patch tokens a patch dropout keeps;
         the blocks then run on 1 + K tokens, on a workspace of that size"""
-        boxes = mix = aug = None
+        boxes = mix = aug = ra = None
         if resident is None:
             B, img = images.shape[0], images.shape[2]
         else:
-            split, rows, boxes, mix, aug = (*resident, None, None, None)[:5]
+            split, rows, boxes, mix, aug, ra = (*resident, None, None, None, None)[:6]
             B, img = rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model)
         # (keep was checked by the caller -- train_step, train_step_resident, forward_resident -- before anything was enqueued)
         st = self._state(model, B, img, dev, None if keep is None else 1 + keep.shape[1])
@@ -303,6 +303,14 @@ class CaraEngine:
         if keep is not None and resident is None:
             check(self._lib().cara_vit_forward_keep(*args, ptr(images), ptr(keep), ptr(droppath), ptr(st["ws"]), ptr(logits),
                                                     ptr(self._bad_rows(dev)), stream(dev)), "cara_vit_forward_keep")
+        elif ra is not None:
+            mean, std = self._eval_norm(dev)
+            check(self._lib().cara_vit_forward_u8_rows_ra(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
+                                                          split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(aug),
+                                                          ptr(self._aug_stat(dev, rows.shape[0])) if aug is not None else None,
+                                                          ptr(ra), ptr(self._ra_stat(dev, rows.shape[0])), ptr(keep), ptr(mean), ptr(std),
+                                                          ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)), stream(dev)),
+                  "cara_vit_forward_u8_rows_ra")
         elif keep is not None:
             mean, std = self._eval_norm(dev)
             check(self._lib().cara_vit_forward_u8_rows_keep(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
@@ -749,7 +757,15 @@ class CaraEngine:
             buf = bufs[(dev, B)] = torch.empty(int(self._lib().cara_aug_stat_bytes(B)) // 4, dtype=torch.float32, device=dev)
         return buf
 
-    def _resident_args(self, split, rows, boxes=None, mix=None, aug=None):
+    def _ra_stat(self, dev, B):
+        """the RandAugment pre-pass' scratch (``cara_ra_stat_bytes``: byte tables and partial histograms), kept like ``_aug_stat``'s"""
+        bufs = self.__dict__.setdefault("_ra_stat_bufs", {})
+        buf = bufs.get((dev, B))
+        if buf is None:
+            buf = bufs[(dev, B)] = torch.empty(int(self._lib().cara_ra_stat_bytes(B)) // 4, dtype=torch.int32, device=dev)
+        return buf
+
+    def _resident_args(self, split, rows, boxes=None, mix=None, aug=None, ra=None):
         model = self._model()
         box_msg = "boxes must be a contiguous int32 [batch, 5] tensor (x0, y0, w, h, flip) on the model's device"
         mix_msg = ("mix must be a contiguous int32 [batch, 8] tensor (partner, cx0, cy0, cw, ch, blend bits, target bits, 0) on the "
@@ -766,6 +782,11 @@ class CaraEngine:
         if aug is not None and (not torch.is_tensor(aug) or aug.dtype != torch.int32 or aug.ndim != 2 or aug.shape[1] != 16
                                 or not aug.is_contiguous()):
             raise CaraError(aug_msg)
+        ra_msg = ("ra must be a contiguous int32 [batch, 16] tensor (op0, arg0, op1, arg1, op2, arg2, m00, m01, m02, m10, m11, m12, fill, 0, "
+                  "0, 0) on the model's device")
+        if ra is not None and (not torch.is_tensor(ra) or ra.dtype != torch.int32 or ra.ndim != 2 or ra.shape[1] != 16
+                               or not ra.is_contiguous()):
+            raise CaraError(ra_msg)
         dev = model.head.weight.device if hasattr(model.head, "weight") else None
         if dev is None:
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
@@ -785,13 +806,15 @@ class CaraEngine:
             raise CaraError(mix_msg)
         if aug is not None and (aug.device != dev or aug.shape[0] != rows.shape[0]):
             raise CaraError(aug_msg)
+        if ra is not None and (ra.device != dev or ra.shape[0] != rows.shape[0]):
+            raise CaraError(ra_msg)
         return model, dev
 
-    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None, aug=None, keep=None):
+    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None, aug=None, keep=None, ra=None):
         model = self._model()
         dev = rows.device
         with torch.cuda.device(dev):
-            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix, aug),
+            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix, aug, ra),
                                         keep=keep)
 
     def _gather_labels(self, split, rows):
@@ -807,7 +830,7 @@ class CaraEngine:
         return buf
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
-                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None):
+                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None, ra=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -829,19 +852,23 @@ class CaraEngine:
         ``keep`` (device int32 [batch, K], e.g. ``data.PatchDropout.draw``): patch dropout as in ``train_step`` -- only the kept
         patches' rows are built, each bit for bit the row the step without ``keep`` builds (``cara_vit_forward_u8_rows_keep``; with
         or without the other tables).  An entry outside the grid gives a zero patch row without a position, counted like a bad row.
+        ``ra`` (device int32 [batch, 16], e.g. ``data.RandAugment.draw``): RandAugment by index -- each sample's crop is sampled through
+        its 2x3 affine with a fill colour and passes its lookup slots (posterize, solarize, solarize-add, invert, autocontrast,
+        equalize) before the jitter chain, the mix and the rest (``cara_vit_forward_u8_rows_ra``; with or without the other tables).
+        A table entry the kernel refuses -- ``data.check_ra`` -- gives a zero image, counted like a bad row.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
-        model, dev = self._resident_args(split, rows, boxes, mix, aug)
+        model, dev = self._resident_args(split, rows, boxes, mix, aug, ra)
         if keep is not None:
             self._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
-        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix, aug, keep),
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix, aug, keep, ra),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
-                         keep=None):
+                         keep=None, ra=None):
         """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``,
-        ``mix``, ``aug`` and ``keep`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
-        model, dev = self._resident_args(split, rows, boxes, mix, aug)
+        ``mix``, ``aug``, ``keep`` and ``ra`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
+        model, dev = self._resident_args(split, rows, boxes, mix, aug, ra)
         if keep is not None:
             self._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
         cp, hw, hb = self._forward_weights(model, dev, weights)
@@ -849,7 +876,7 @@ class CaraEngine:
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix, aug, keep)
+            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix, aug, keep, ra)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):

@@ -127,7 +127,9 @@ class GraphedTrainStep:
     ``step(split, (rows, boxes_or_None, mix))`` captures the mixed step (``train_step_resident(..., mix=)``) the same way: the
     Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.
     ``step(split, (rows, boxes_or_None, mix_or_None, aug))`` captures the jittered step (``train_step_resident(..., aug=)``): the
-    colour-jitter / erase table is copied per replay too, 64 bytes per sample.  ``label_smoothing`` is the steps' (all
+    colour-jitter / erase table is copied per replay too, 64 bytes per sample.  ``step(split, (rows, boxes_or_None, mix_or_None,
+    aug_or_None, keep_or_None, ra))`` captures the RandAugmented step (``train_step_resident(..., ra=)``): that table is one more
+    static input, 64 bytes per sample copied per replay.  ``label_smoothing`` is the steps' (all
     forms); it is part of every graph's key.  ``clip_grad`` likewise: the two launches of ``cara_grad_clip`` are captured with
     the step (``CaraEngine.train_step(..., clip_grad=)``).  An accumulation window (``accumulate`` with k > 1) spans several
     replays and is refused.  ``ema`` (``CaraEngine.make_ema(..., capturable=True)``): the average's launch is captured behind the
@@ -166,7 +168,8 @@ class GraphedTrainStep:
         ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table, or ``(split, (rows, boxes_or_None, mix))``:
         with a device int32 [batch, 8] mix table too, or ``(split, (rows, boxes_or_None, mix_or_None, aug))``: with a device int32
         [batch, 16] colour-jitter / erase table, or ``(split, (rows, boxes_or_None, mix_or_None, aug_or_None, keep))``: with a device
-        int32 [batch, K] patch-dropout table.  ``keep=`` hands that table to the ``(images, labels)`` and ``(split, rows)`` forms.
+        int32 [batch, K] patch-dropout table, or ``(split, (rows, boxes_or_None, mix_or_None, aug_or_None, keep_or_None, ra))``: with a
+        device int32 [batch, 16] RandAugment table.  ``keep=`` hands that table to the ``(images, labels)`` and ``(split, rows)`` forms.
         The table is one more static input, copied before every replay (4 K bytes per sample); its shape is part of the graph's key,
         so another K captures another graph."""
         from . import dist as cdist
@@ -174,9 +177,10 @@ class GraphedTrainStep:
         eng, model = self.eng, self.eng._model()
         resident = hasattr(x, "pixels")
         if resident and (isinstance(y, (tuple, list)) or keep is not None):
-            y = (*y, None, None, None, None)[:5] if isinstance(y, (tuple, list)) else (y, None, None, None, None)
+            y = (*y, None, None, None, None, None)[:6] if isinstance(y, (tuple, list)) else (y, None, None, None, None, None)
             kp = y[4] if y[4] is not None else keep
-            return self._call_tables(x, y[0], y[1], y[2], group, **({} if y[3] is None else {"aug": y[3]}), **({} if kp is None else {"keep": kp}))
+            return self._call_tables(x, y[0], y[1], y[2], group, **({} if y[3] is None else {"aug": y[3]}), **({} if kp is None else {"keep": kp}),
+                                     **({} if y[5] is None else {"ra": y[5]}))
         kw = self._kw()
         if keep is not None:   # (refused here, not inside a capture)
             if x.ndim != 4 or x.shape[2] != x.shape[3]:
@@ -221,28 +225,31 @@ class GraphedTrainStep:
         gr.replay()
         return loss
 
-    def _call_tables(self, split, rows, boxes, mix, group, aug=None, keep=None):
-        """the resident form through crop boxes and / or a mix table and / or an aug table and / or a keep table: warm, capture,
-        replay as above, with one to five static inputs"""
+    def _call_tables(self, split, rows, boxes, mix, group, aug=None, keep=None, ra=None):
+        """the resident form through crop boxes and / or a mix table and / or an aug table and / or a keep table and / or an ra table:
+        warm, capture, replay as above, with one to six static inputs"""
         from . import dist as cdist
         eng, model = self.eng, self.eng._model()
-        eng._resident_args(split, rows, boxes, mix, *(() if aug is None else (aug,)))     # (refused here, not inside a capture)
+        eng._resident_args(split, rows, boxes, mix, *(() if aug is None and ra is None else (aug,)),
+                           *(() if ra is None else (ra,)))                                 # (refused here, not inside a capture)
         if keep is not None:
             eng._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else eng._model_img(model), rows.device)
         self._advance()
-        tables = [t for t in (boxes, mix, aug, keep) if t is not None]
+        tables = [t for t in (boxes, mix, aug, keep, ra) if t is not None]
 
         def step(rs, ts):
             ts = list(ts)
             return eng.train_step_resident(split, rs, self.opt, group=group, boxes=ts.pop(0) if boxes is not None else None,
                                            **({"mix": ts.pop(0)} if mix is not None else {}),
                                            **({"aug": ts.pop(0)} if aug is not None else {}),
-                                           **({"keep": ts.pop(0)} if keep is not None else {}), **self._kw())
+                                           **({"keep": ts.pop(0)} if keep is not None else {}),
+                                           **({"ra": ts.pop(0)} if ra is not None else {}), **self._kw())
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(rows, tables)
         key = (("rows+boxes" if mix is None else "rows+boxes+mix", split, tuple(rows.shape), boxes is not None and tuple(boxes.shape),
                 mix is not None and tuple(mix.shape), *(() if aug is None else (("aug", tuple(aug.shape)),)),
-                *(() if keep is None else (("keep", tuple(keep.shape)),))), bool(model.training),
+                *(() if keep is None else (("keep", tuple(keep.shape)),)), *(() if ra is None else (("ra", tuple(ra.shape)),))),
+               bool(model.training),
                eng.precision, self.label_smoothing, self.clip_grad)
         ent = self._graphs.get(key)
         if ent is None:
@@ -305,6 +312,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     CutMix by index (``train_step_resident(..., mix=)``); a mix entry the kernel refuses is counted like a bad row too.
     One that yields ``(rows, boxes_or_None, mix_or_None, aug)`` (``train_rows(..., color=data.ColorJitterErase(...))``) trains with
     colour jitter and Random Erasing by index too (``train_step_resident(..., aug=)``).
+    One that yields ``(rows, boxes_or_None, mix_or_None, aug_or_None, keep_or_None, ra)`` (``train_rows(..., rand=data.RandAugment(...))``)
+    trains with RandAugment by index too (``train_step_resident(..., ra=)``); an ra entry the kernel refuses is counted like a bad row.
     ``label_smoothing`` in [0, 1): every step's loss is the smoothed cross-entropy (both feeds).
     ``clip_grad = max_norm``: every optimiser step clips the global gradient norm first (``train_step(..., clip_grad=)``; both
     feeds, eager and graphed).  ``accum_steps = k`` > 1: ``k`` consecutive batches of an epoch form a window -- one optimiser step,
@@ -367,6 +376,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
 
         def step(split, rows, opt, group=None, **win):
             if isinstance(rows, (tuple, list)):
+                if len(rows) > 5:   # (train_rows(..., rand=): None for the tables not asked for)
+                    rows, boxes, mix, aug, keep, ra = rows
+                    tables = {k: v for k, v in (("boxes", boxes), ("mix", mix), ("aug", aug), ("keep", keep), ("ra", ra)) if v is not None}
+                    return eng.train_step_resident(split, rows, opt, group=group, **tables, **smooth, **win)
                 if len(rows) > 4:   # (train_rows(..., patch_drop=): None for the tables not asked for)
                     rows, boxes, mix, aug, keep = rows
                     tables = {k: v for k, v in (("boxes", boxes), ("mix", mix), ("aug", aug), ("keep", keep)) if v is not None}
@@ -414,7 +427,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         if bad:
             raise CaraError(f"fit: {bad} row index(es) outside the training split (or crop boxes outside their image, or mix entries "
                             f"with a partner outside the batch, a rectangle outside the output or a weight outside [0, 1], or aug entries "
-                            f"data.check_aug refuses, or keep entries outside the patch grid) reached "
+                            f"data.check_aug refuses, or keep entries outside the patch grid, or ra entries data.check_ra refuses) reached "
                             f"the device up to epoch {upto}")
     for epoch in range(epochs):
         window = []

@@ -382,6 +382,36 @@ int cara_im2col_patches_u8_rows_keep(const unsigned char* pixels, int n_split, i
                                      const int* boxes, const int* mix, const int* aug, void* stat_scratch, const int* keep, int K,
                                      const float* mean, const float* std, void* patches, int* bad, int B, int C, int Hi, int Wi,
                                      int p, void* stream);
+/* RandAugment by index: cara_im2col_patches_u8_rows_keep / _aug with one more device table, ra int32 [B,16], row b =
+ *   (op0, arg0, op1, arg1, op2, arg2, m00, m01, m02, m10, m11, m12, fill, 0, 0, 0)
+ * op: a lookup slot on the quantised value q, applied in the order 0, 1, 2 -- 0 none (arg 0); 1 posterize, arg = bits kept 0..8:
+ * q & ~((1 << (8 - arg)) - 1); 2 solarize, arg = threshold 0..256: q < arg ? q : 255 - q; 3 solarize-add, arg 0..255: q < 128 ?
+ * min(q + arg, 255) : q; 4 invert: 255 - q (arg 0); 5 autocontrast, 6 equalize (arg 0; at most one of the two per row).  m..: the
+ * bits of six finite fp32 numbers of magnitude <= 32768, the output-to-input affine; fill = 0x00RRGGBB.  All of it in fp32, every
+ * product and sum one IEEE operation (no contraction).  Output pixel (ox, oy), x = ox + 0.5, y = oy + 0.5:
+ *   u = (m00 x + m01 y) + m02, v = (m10 x + m11 y) + m12; unless 0 <= u < Wi and 0 <= v < Hi the value is the channel's fill byte;
+ *   inside, the sample's box (w x h, flip) at the continuous position: uf = flip ? Wi - u : u, s = max(uf (w / Wi) - 0.5, 0), i0 =
+ *   min((int)s, w - 1), i1 = min(i0 + 1, w - 1), f = s - i0; the same for v with h / Hi and no flip; t + fy (b - t) of the two rows'
+ *   a + f (b - a).  A row whose matrix words are the bits of (1, 0, 0, 0, 1, 0) gives bit for bit the value of the call without ra.
+ *   With any lookup slot: q = (int)rintf(value) (half to even), the slots, (float)q -- the fill pixels too; without: no quantising.
+ *   Then the chain of the aug row (its contrast mean M_b is taken over these values), the mix (the partner's value after its own
+ *   ra row, tables and aug row), the normalisation, the erase and the one rounding, as in cara_im2col_patches_u8_rows_aug.
+ * Statistic slot: h_c[256] = the histogram of q as it stands before that slot over all Hi x Wi output pixels of channel c (fill
+ * pixels count; keep does not change it).  autocontrast: lo, hi = first / last non-zero bin; hi <= lo: identity; else lut[i] =
+ * clamp((255 (i - lo)) / (hi - lo), 0, 255), integer division, 0 below lo.  equalize: z = h[hi], step = (sum h - z) / 255; hi <= lo
+ * or step == 0: identity; else lut[i] = min(255, (step / 2 + sum_{j<i} h[j]) / step).  Pre-pass: 8 workgroups per sample count
+ * into LDS with integer atomics and store their partial histograms; one workgroup per (sample, channel) sums them and writes the
+ * table.  ra_scratch: cara_ra_stat_bytes(B) bytes, 4-byte aligned (uint8 lut [B][3][256], then int32 partial [B][8][3][256]); what
+ * it held before the call does not matter; a sample without a statistic slot loads no pixel in the pre-pass.
+ * Every table but rows may be NULL (keep NULL: all rows, K ignored).  ra NULL: the launches of _rows_keep / _rows_aug.  With ra, C
+ * must be 3 and ra_scratch present: CARA_E_ARG otherwise, nothing launched.  A sample gets zero patch rows and is counted once in
+ * *bad by the rules above and where its own OR ITS PARTNER's ra row has an op outside [0, 6], an argument outside its range, two
+ * statistic slots, a matrix word that is not finite or above 32768 in magnitude, a fill above 0xFFFFFF or a non-zero pad word.      */
+size_t cara_ra_stat_bytes(int B);
+int cara_im2col_patches_u8_rows_ra(const unsigned char* pixels, int n_split, int Hs, int Ws, const int64_t* rows, const int* boxes,
+                                   const int* mix, const int* aug, void* stat_scratch, const int* ra, void* ra_scratch,
+                                   const int* keep, int K, const float* mean, const float* std, void* patches, int* bad, int B,
+                                   int C, int Hi, int Wi, int p, void* stream);
 /* out[i] = labels[rows[i]] (device int64 [B] each; labels int64 [n_split]); a row outside [0, n_split) is not
  * dereferenced: it gives 0 and is counted in *bad (device int, may be NULL)                                    */
 int cara_gather_labels(const int64_t* labels, int n_split, const int64_t* rows, int64_t* out, int B, int* bad,
@@ -707,6 +737,13 @@ int cara_vit_forward_u8_rows_keep(const cara_geom* g, const cara_vit_shape* s, c
                                   const int64_t* rows, const int* boxes, const int* mix, const int* aug, void* stat_scratch,
                                   const int* keep, const float* mean, const float* std, const float* droppath, void* workspace,
                                   float* logits, int* bad, void* stream);
+/* cara_vit_forward_u8_rows_keep with the patch rows of cara_im2col_patches_u8_rows_ra: ra and ra_scratch (cara_ra_stat_bytes(B)
+ * bytes) are required, boxes / mix / aug / keep each NULL or not; without keep, tokens == (img/patch)^2 + 1.                       */
+int cara_vit_forward_u8_rows_ra(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w, const cara_cp* cp,
+                                const float* head_w, const float* head_b, const unsigned char* pixels, int n_split, int Hs, int Ws,
+                                const int64_t* rows, const int* boxes, const int* mix, const int* aug, void* stat_scratch,
+                                const int* ra, void* ra_scratch, const int* keep, const float* mean, const float* std,
+                                const float* droppath, void* workspace, float* logits, int* bad, void* stream);
 /* dlogits fp32 [B,classes] -> grads of the 12 CP tensors (overwritten), dhead_w, dhead_b.       */
 int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, const cara_vit_weights* w,
                       const cara_cp* cp, const float* head_w, const float* dlogits, const float* droppath,

@@ -23,7 +23,11 @@ CutMix table.
 
 --aug adds to the --mix legs: the mixed step with an all-zero colour table, with colour jitter alone and with jitter and Random
 Erasing (data.ColorJitterErase), and cara_im2col_patches_u8_rows_aug alone (its two pre-pass launches included) on an all-zero
-table, a jitter table and a jitter + erase table, each over the identity mix table."""
+table, a jitter table and a jitter + erase table, each over the identity mix table.
+
+--ra adds to the --aug legs: the cropped step with RandAugment tables (data.RandAugment) -- an identity table, geometric ops only,
+lookup ops only, equalize on every sample, and everything (all ops, Mixup / CutMix, Random Erasing) -- and
+cara_im2col_patches_u8_rows_ra alone on one drawn table of each kind (its pre-pass launches included, as the step runs them)."""
 import argparse
 import json
 import os
@@ -49,6 +53,7 @@ def main():
     ap.add_argument("--augment", action="store_true", help="time the augmented resident step and the two patch-row kernels instead")
     ap.add_argument("--mix", action="store_true", help="the --augment legs plus the mixed step and the mix kernel alone")
     ap.add_argument("--aug", action="store_true", help="the --mix legs plus the jittered / erased steps and the aug kernels alone")
+    ap.add_argument("--ra", action="store_true", help="the --aug legs plus the RandAugmented steps and the ra kernels alone")
     ap.add_argument("--source", type=int, default=256, help="--augment: side of the split the boxes are drawn on")
     ap.add_argument("--kernel-launches", type=int, default=200, help="--augment: launches per timed kernel window")
     args = ap.parse_args()
@@ -83,6 +88,8 @@ def main():
             yield from of_epoch(epoch)
             epoch += 1
 
+    if args.ra:
+        args.aug = True
     if args.aug:
         args.mix = True
     if args.augment or args.mix:
@@ -219,6 +226,39 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
                                                             L.ptr(stat), L.ptr(mean), L.ptr(std), L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st),
                         "cara_im2col_patches_u8_rows_aug")
             kernels[f"kernel/u8_rows_aug{S}/{name}"] = k_aug
+    if args.ra:
+        from cara_amd.data import ColorJitterErase, RandAugment, identity_ra
+        GEO, LOOK = ("Rotate", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel"), ("Posterize", "Solarize", "SolarizeAdd", "Invert")
+        ident_ra = type("IdentityRa", (), {"Hi": 224, "Wi": 224, "draw": staticmethod(
+            lambda B_, steps, generator: (identity_ra(B_, steps), torch.zeros(steps, B_, 6, dtype=torch.int32)))})()
+        kinds = (("ra0", ident_ra), ("geometry", RandAugment(224, prob=1.0, ops=GEO)), ("lookup", RandAugment(224, prob=1.0, ops=LOOK)),
+                 ("equalize", RandAugment(224, n=1, prob=1.0, ops=("Equalize",))))
+
+        def randaugmented(item):
+            opt.advance()
+            tables = {k: v for k, v in zip(("boxes", "mix", "aug", "keep", "ra"), item[1:]) if v is not None}
+            return eng.train_step_resident(big, item[0], opt, label_smoothing=0.1, **tables)
+        for name, r in kinds:
+            steps[f"eager/resident+crop{S}+{name}"] = (feeder(big.train_rows(B, augment=aug, rand=r)), randaugmented)
+        steps[f"eager/resident+crop{S}+mix+erase+ra"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224),
+                                                                               color=ColorJitterErase(224, 0.0, 0.0, 0.0), rand=RandAugment(224))),
+                                                         randaugmented)
+        ra_scratch = torch.empty(int(lib.cara_ra_stat_bytes(B)) // 4, dtype=torch.int32, device=dev)
+        stat_ra = torch.empty(int(lib.cara_aug_stat_bytes(B)) // 4, device=dev)
+        gr = torch.Generator().manual_seed(10)
+        for name, r in kinds + (("all", RandAugment(224)),):
+            t, slots = r.draw(B, 1, gr)
+            t = t[0].contiguous().to(dev)
+            a = identity_aug(B)
+            a[:, :6] = slots[0]
+            a = a.contiguous().to(dev) if name == "all" else None
+
+            def k_ra(t=t, a=a):
+                L.check(lib.cara_im2col_patches_u8_rows_ra(L.ptr(big.pixels), len(big), S, S, L.ptr(rows), L.ptr(boxes), None, L.ptr(a),
+                                                           L.ptr(stat_ra) if a is not None else None, L.ptr(t), L.ptr(ra_scratch), None, 0,
+                                                           L.ptr(mean), L.ptr(std), L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st),
+                        "cara_im2col_patches_u8_rows_ra")
+            kernels[f"kernel/u8_rows_ra{S}/{name}"] = k_ra
 
     def step_window(name, n):
         feed, step = steps[name]
