@@ -18,12 +18,13 @@ from __future__ import annotations
 import math
 import os
 from concurrent.futures import ThreadPoolExecutor
-from typing import Callable, Iterator, List, Optional, Sequence, Tuple
+from typing import Callable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import dist as D
+from .feed import Feed
 
 # vtab.py:9-31
 DATASET_NAMES = ("cifar", "caltech101", "dtd", "oxford_flowers102", "oxford_iiit_pet", "svhn", "sun397",
@@ -822,6 +823,35 @@ def keep_reference(tokens_or_rows: torch.Tensor, keep: torch.Tensor) -> torch.Te
     return tokens_or_rows[torch.arange(B, device=idx.device).reshape(B, 1).expand(B, K), idx]
 
 
+class _Drawer(NamedTuple):
+    """what ``ResidentSplit.train_rows`` knows of one of its table drawers"""
+    arg: str                    # train_rows' argument
+    field: str                  # the Feed field its table fills
+    attrs: Optional[tuple]      # the int attributes that, with a callable ``draw``, make an object such a drawer (None: not asked)
+    refusal: str                # ... and what anything else is told
+    seed: Callable              # (seed, epoch, rank) -> the seed of its generator: every drawer has a stream of its own
+    draw: Callable              # (drawer, Hs, Ws, steps, B, generator) -> its host table for an epoch of steps x B samples
+    width: object               # the columns of that int32 [steps, B, columns] table ("K": the drawer's own)
+    check: Callable             # (table, drawer, Hs, Ws, B): raises on an entry the kernel would refuse
+
+
+# in the order they draw
+_DRAWERS = (
+    _Drawer("patch_drop", "keep", ("grid",), "patch_drop must be a PatchDropout with its grid (PatchDropout(prob, size=, patch=) or grid=)",
+            keep_seed, lambda d, Hs, Ws, steps, B, g: d.draw(d.grid, B, steps, g), "K",
+            lambda t, d, Hs, Ws, B: check_keep(t, B, d.grid)),
+    _Drawer("augment", "boxes", None, "", box_seed, lambda d, Hs, Ws, steps, B, g: d.draw(Hs, Ws, steps * B, g).reshape(steps, B, 5), 5,
+            lambda t, d, Hs, Ws, B: check_boxes(t, Hs, Ws)),
+    _Drawer("mix", "mix", ("Hi", "Wi"), "mix must be a MixupCutmix (anything with draw(B, steps, generator), Hi and Wi)",
+            mix_seed, lambda d, Hs, Ws, steps, B, g: d.draw(B, steps, g), 8, lambda t, d, Hs, Ws, B: check_mix(t, B, d.Hi, d.Wi)),
+    _Drawer("color", "aug", ("Hi", "Wi"), "color must be a ColorJitterErase (anything with draw(B, steps, generator), Hi and Wi)",
+            aug_seed, lambda d, Hs, Ws, steps, B, g: d.draw(B, steps, g), 16, lambda t, d, Hs, Ws, B: check_aug(t, B, d.Hi, d.Wi)),
+    # (its draw gives a pair: the table and the int32 [steps, B, 6] jitter slots that replace aug's)
+    _Drawer("rand", "ra", ("Hi", "Wi"), "rand must be a RandAugment (anything with draw(B, steps, generator), Hi and Wi)",
+            ra_seed, lambda d, Hs, Ws, steps, B, g: d.draw(B, steps, g), 16, lambda t, d, Hs, Ws, B: check_ra(t, B)),
+)
+
+
 class ResidentSplit:
     """One file list decoded once and kept on ``device`` as the resized uint8 pixels ``pixels`` [N,3,size,size]
     (150 KB per image: the 73k-image dsprites test split is 11 GB, not 44) plus ``labels`` int64 [N]; a batch is
@@ -886,39 +916,26 @@ class ResidentSplit:
         (``dist.epoch_shard``), in the same order, for ``CaraEngine.train_step_resident`` -- which reads the uint8 pixels
         and the labels of those rows itself, so no fp32 batch is written.  An epoch's indices are range-checked on the host
         and uploaded once as one [steps, batch_size] tensor; every step gets a row view of it.
-        ``augment`` (a ``RandomResizedCropFlip``, or anything with its ``draw``): the iterator yields ``(rows, boxes)`` --
-        the same index vectors, each with an int32 [batch_size, 5] view of one [steps, batch_size, 5] box upload per epoch
-        (``train_step_resident(..., boxes=)``).  The boxes are drawn on the host from a generator seeded by (seed, epoch,
-        rank) and range-checked before the upload, like the indices.
-        ``mix`` (a ``MixupCutmix``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix)``
-        -- ``boxes`` is None without an ``augment`` -- each with an int32 [batch_size, 8] view of one [steps, batch_size, 8] upload
-        per epoch (``train_step_resident(..., mix=)``), drawn from a generator seeded by (seed, epoch, rank) on a stream of its
-        own (``mix_seed``) and range-checked (``check_mix``) before the upload.
-        ``color`` (a ``ColorJitterErase``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix,
-        aug)`` -- ``boxes`` and ``mix`` None where not asked for -- each with an int32 [batch_size, 16] view of one upload per epoch
-        (``train_step_resident(..., aug=)``), drawn on a third stream (``aug_seed``) and checked (``check_aug``) before the upload.
-        ``patch_drop`` (a ``PatchDropout`` that knows its ``grid``, or anything with its ``draw`` and ``grid``): the iterator yields
-        ``(rows, boxes, mix, aug, keep)`` -- None for the tables not asked for -- each with an int32 [batch_size, K] view of one
-        [steps, batch_size, K] upload per epoch (``train_step_resident(..., keep=)``), drawn on a fourth stream (``keep_seed``) and
-        checked (``check_keep``) before the upload.
-        ``rand`` (a ``RandAugment``, or anything with its ``draw``, ``Hi`` and ``Wi``): the iterator yields ``(rows, boxes, mix, aug, keep,
-        ra)`` -- None for the tables not asked for, except ``aug``, which carries the jitter slots ``rand`` drew -- each with an int32
-        [batch_size, 16] view of one upload per epoch (``train_step_resident(..., ra=)``), drawn on a fifth stream (``ra_seed``) and
-        checked (``check_ra``, ``check_aug``) before the upload.  With ``color`` too, ``color`` must only erase (its three jitters 0): as
-        in timm, auto-augment replaces colour jitter."""
-        if rand is not None and not (callable(getattr(rand, "draw", None)) and isinstance(getattr(rand, "Hi", None), int)
-                                     and isinstance(getattr(rand, "Wi", None), int)):
-            raise ValueError("rand must be a RandAugment (anything with draw(B, steps, generator), Hi and Wi)")
-        if rand is not None and color is not None and any(float(j) != 0.0 for j in getattr(color, "jitter", (1.0,))):
-            raise ValueError("rand replaces colour jitter: pass a color that only erases (brightness = contrast = saturation = 0)")
-        if patch_drop is not None and not (callable(getattr(patch_drop, "draw", None)) and isinstance(getattr(patch_drop, "grid", None), int)):
-            raise ValueError("patch_drop must be a PatchDropout with its grid (PatchDropout(prob, size=, patch=) or grid=)")
-        if color is not None and not (callable(getattr(color, "draw", None)) and isinstance(getattr(color, "Hi", None), int)
-                                      and isinstance(getattr(color, "Wi", None), int)):
-            raise ValueError("color must be a ColorJitterErase (anything with draw(B, steps, generator), Hi and Wi)")
-        if mix is not None and not (callable(getattr(mix, "draw", None)) and isinstance(getattr(mix, "Hi", None), int)
-                                    and isinstance(getattr(mix, "Wi", None), int)):
-            raise ValueError("mix must be a MixupCutmix (anything with draw(B, steps, generator), Hi and Wi)")
+        With a drawer, the iterator yields ``Feed(rows, boxes, mix, aug, keep, ra).item()`` instead: the tuple cut behind the last table
+        asked for, None for one in front of it that is not (``cara_amd.feed``).  Every table is an int32 [batch_size, columns] view of
+        one [steps, batch_size, columns] upload per epoch, drawn on the host from a generator seeded by (seed, epoch, rank) on a
+        stream of its drawer's own and checked before the upload, like the indices:
+        ``augment`` (a ``RandomResizedCropFlip``, or anything with its ``draw``) -> ``boxes``, 5 columns (``box_seed``, ``check_boxes``);
+        ``mix`` (a ``MixupCutmix``, or anything with its ``draw``, ``Hi`` and ``Wi``) -> ``mix``, 8 columns (``mix_seed``, ``check_mix``);
+        ``color`` (a ``ColorJitterErase``, or anything with its ``draw``, ``Hi`` and ``Wi``) -> ``aug``, 16 columns (``aug_seed``, ``check_aug``);
+        ``patch_drop`` (a ``PatchDropout`` that knows its ``grid``, or anything with its ``draw`` and ``grid``) -> ``keep``, K columns
+        (``keep_seed``, ``check_keep``);
+        ``rand`` (a ``RandAugment``, or anything with its ``draw``, ``Hi`` and ``Wi``) -> ``ra``, 16 columns (``ra_seed``, ``check_ra``), and
+        an ``aug`` that carries the jitter slots ``rand`` drew (``check_aug``).  With ``color`` too, ``color`` must only erase (its three
+        jitters 0): as in timm, auto-augment replaces colour jitter."""
+        drawers = {"augment": augment, "mix": mix, "color": color, "patch_drop": patch_drop, "rand": rand}
+        for s in sorted(_DRAWERS, key=lambda s: Feed._fields.index(s.field), reverse=True):   # (the last table's drawer first)
+            d = drawers[s.arg]
+            if d is not None and s.attrs is not None and not (callable(getattr(d, "draw", None))
+                                                              and all(isinstance(getattr(d, a, None), int) for a in s.attrs)):
+                raise ValueError(s.refusal)
+            if s.arg == "rand" and d is not None and color is not None and any(float(j) != 0.0 for j in getattr(color, "jitter", (1.0,))):
+                raise ValueError("rand replaces colour jitter: pass a color that only erases (brightness = contrast = saturation = 0)")
         rank = D.get_rank() if rank is None else rank
         world = D.world_size() if world is None else world
 
@@ -929,63 +946,30 @@ class ResidentSplit:
             table = torch.stack(idx)
             if int(table.min()) < 0 or int(table.max()) >= len(self):
                 raise ValueError(f"epoch {epoch}: a drawn index is outside [0, {len(self)})")
-            boxes = mixes = augs = keeps = None
-            if patch_drop is not None:
-                keeps = patch_drop.draw(patch_drop.grid, table.shape[1], table.shape[0],
-                                        torch.Generator().manual_seed(keep_seed(seed, epoch, rank)))
-                if not torch.is_tensor(keeps) or keeps.ndim != 3 or tuple(keeps.shape[:2]) != tuple(table.shape):
-                    raise ValueError(f"patch_drop.draw gave {tuple(keeps.shape) if torch.is_tensor(keeps) else type(keeps).__name__}, "
-                                     f"not an int32 {(*table.shape, 'K')} table")
-                check_keep(keeps, table.shape[1], patch_drop.grid)
-                keeps = keeps.contiguous().to(self.pixels.device)
-            if augment is not None:
-                Hs, Ws = self.pixels.shape[2:]
-                gen = torch.Generator().manual_seed(box_seed(seed, epoch, rank))
-                boxes = augment.draw(Hs, Ws, table.numel(), gen).reshape(*table.shape, 5)
-                check_boxes(boxes, Hs, Ws)
-                boxes = boxes.to(self.pixels.device)
-            if mix is not None:
-                mixes = mix.draw(table.shape[1], table.shape[0], torch.Generator().manual_seed(mix_seed(seed, epoch, rank)))
-                if not torch.is_tensor(mixes) or tuple(mixes.shape) != (*table.shape, 8):
-                    raise ValueError(f"mix.draw gave {tuple(mixes.shape) if torch.is_tensor(mixes) else type(mixes).__name__}, "
-                                     f"not an int32 {(*table.shape, 8)} table")
-                check_mix(mixes, table.shape[1], mix.Hi, mix.Wi)
-                mixes = mixes.contiguous().to(self.pixels.device)
-            if color is not None:
-                augs = color.draw(table.shape[1], table.shape[0], torch.Generator().manual_seed(aug_seed(seed, epoch, rank)))
-                if not torch.is_tensor(augs) or tuple(augs.shape) != (*table.shape, 16):
-                    raise ValueError(f"color.draw gave {tuple(augs.shape) if torch.is_tensor(augs) else type(augs).__name__}, "
-                                     f"not an int32 {(*table.shape, 16)} table")
-                check_aug(augs, table.shape[1], color.Hi, color.Wi)
-                augs = augs.contiguous().to(self.pixels.device)
-            ras = None
-            if rand is not None:
-                ras, slots = rand.draw(table.shape[1], table.shape[0], torch.Generator().manual_seed(ra_seed(seed, epoch, rank)))
-                if not torch.is_tensor(ras) or tuple(ras.shape) != (*table.shape, 16) or not torch.is_tensor(slots) \
-                        or tuple(slots.shape) != (*table.shape, 6):
-                    raise ValueError(f"rand.draw did not give an int32 {(*table.shape, 16)} table and int32 {(*table.shape, 6)} jitter slots")
-                check_ra(ras, table.shape[1])
-                ras = ras.contiguous().to(self.pixels.device)
-                host = identity_aug(table.shape[1], table.shape[0]) if augs is None else augs.cpu().clone()
-                host[..., :6] = slots
-                check_aug(host, table.shape[1], rand.Hi, rand.Wi)
-                augs = host.contiguous().to(self.pixels.device)
+            (steps, B), (Hs, Ws) = table.shape, self.pixels.shape[2:]
+            host = {}
+            for s in _DRAWERS:
+                d = drawers[s.arg]
+                if d is None:
+                    continue
+                t = s.draw(d, Hs, Ws, steps, B, torch.Generator().manual_seed(s.seed(seed, epoch, rank)))
+                t, slots = t if s.field == "ra" else (t, None)
+                if not torch.is_tensor(t) or t.ndim != 3 or tuple(t.shape[:2]) != (steps, B) or s.width not in ("K", t.shape[2]) \
+                        or (s.field == "ra" and (not torch.is_tensor(slots) or tuple(slots.shape) != (steps, B, 6))):
+                    raise ValueError(f"rand.draw did not give an int32 {(steps, B, 16)} table and int32 {(steps, B, 6)} jitter slots"
+                                     if s.field == "ra" else
+                                     f"{s.arg}.draw gave {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}, "
+                                     f"not an int32 {(steps, B, s.width)} table")
+                s.check(t, d, Hs, Ws, B)
+                host[s.field] = t
+                if slots is not None:   # (as in timm, auto-augment replaces colour jitter: aug keeps its erase columns only)
+                    host["aug"] = host["aug"].clone() if "aug" in host else identity_aug(B, steps)
+                    host["aug"][..., :6] = slots
+                    check_aug(host["aug"], B, d.Hi, d.Wi)
+            dev = {n: t.contiguous().to(self.pixels.device) for n, t in host.items()}
             table = table.to(self.pixels.device)
-            for step in range(table.shape[0]):
-                if ras is not None:
-                    yield (table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]), augs[step],
-                           (None if keeps is None else keeps[step]), ras[step])
-                elif keeps is not None:
-                    yield (table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]),
-                           (None if augs is None else augs[step]), keeps[step])
-                elif augs is not None:
-                    yield table[step], (None if boxes is None else boxes[step]), (None if mixes is None else mixes[step]), augs[step]
-                elif mixes is not None:
-                    yield table[step], (None if boxes is None else boxes[step]), mixes[step]
-                elif boxes is not None:
-                    yield table[step], boxes[step]
-                else:
-                    yield table[step]
+            for step in range(steps):
+                yield Feed(table[step], **{n: t[step] for n, t in dev.items()}).item()
         return epoch_iter
 
     def eval_batches(self, batch_size: int = 256) -> Callable[[], Iterator[Tuple[torch.Tensor, torch.Tensor]]]:
@@ -1028,10 +1012,7 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     ``augment`` / ``train_size`` (with ``resident_feed``): the training split is decoded at ``train_size`` (default 224, the
     model's size) and its ``train_rows`` yields ``(rows, boxes)`` drawn by ``augment`` -- "resize 256, random-resized-crop
     224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size.
-    ``mix`` (with ``resident_feed``; a ``MixupCutmix``): ``train_rows`` yields ``(rows, boxes or None, mix)``.
-    ``color`` (with ``resident_feed``; a ``ColorJitterErase``): ``train_rows`` yields ``(rows, boxes or None, mix or None, aug)``.
-    ``patch_drop`` (with ``resident_feed``; a ``PatchDropout`` with its grid): ``train_rows`` yields the 5-tuple ending in ``keep``.
-    ``rand`` (with ``resident_feed``; a ``RandAugment``): ``train_rows`` yields the 6-tuple ending in ``ra``."""
+    ``mix`` / ``color`` / ``patch_drop`` / ``rand`` (with ``resident_feed``): handed to ``train_rows``, which then yields tuples."""
     if (augment is not None or train_size is not None or mix is not None or color is not None or patch_drop is not None
             or rand is not None) and not resident_feed:
         raise ValueError("augment / train_size / mix / color / patch_drop / rand belong to the resident feed: pass resident_feed=True")
@@ -1042,10 +1023,7 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers, size=224 if train_size is None else train_size)
     test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
     if resident_feed:
-        feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix,
-                                        **({"color": color} if color is not None else {}),
-                                        **({"patch_drop": patch_drop} if patch_drop is not None else {}),
-                                        **({"rand": rand} if rand is not None else {})))
+        feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix, color=color, patch_drop=patch_drop, rand=rand))
     else:
         feed = train.train_batches(batch_size, seed=seed)
     return feed, (test if shard_eval else test.eval_batches(256))

@@ -16,10 +16,39 @@ import torch
 
 from . import _lib as L
 from ._lib import CaraError, check, ptr, stream
+from .feed import TABLES, Feed
 
 
 def _rp(rank: int) -> int:
     return 32 if rank <= 32 else 64
+
+
+_MODEL = ("g", "s", "w", "cp", "head_w", "head_b")          # what every cara_vit_forward* entry starts with (include/cara_hip.h)
+_RESULT = ("droppath", "workspace", "logits", "bad", "stream")   # ... and ends with
+
+
+def forward_call(tables, values):
+    """Which ``cara_vit_forward*`` entry a forward calls and with what: -> ``(entry, [(parameter, value), ...])``, the parameters
+    named and ordered as the entry's prototype in include/cara_hip.h.  ``tables``: {name: table} of the tables present
+    (``Feed.tables()``); ``values``: every other parameter by name -- with ``images`` an fp32 batch (``keep`` is then the only
+    table there is), with ``pixels`` the rows of a resident split.  The resident entry is the one named after the last table
+    present in Feed's order, each taking the tables in front of it too (NULL where not given); ``stat_scratch`` is NULL without
+    ``aug``.  Touches no tensor and no library."""
+    if "images" in values:
+        if set(tables) - {"keep"}:
+            raise CaraError(f"an fp32 batch takes a keep table only, not {sorted(tables)}")
+        entry = "cara_vit_forward_keep" if tables else "cara_vit_forward"
+        names = (*_MODEL, "images", *tables, *(n for n in _RESULT if tables or n != "bad"))
+    else:
+        level = max((Feed._fields.index(n) for n in tables), default=0)   # 0 rows, 1 boxes, 2 mix, 3 aug, 4 keep, 5 ra
+        entry = "cara_vit_forward_u8_rows" + ("", "_crop", "_mix", "_aug", "_keep", "_ra")[level]
+        names = (*_MODEL, "pixels", "n_split", *(("Hs", "Ws") if level else ()), "rows", *("boxes", "mix", "aug")[:level],
+                 *(("stat_scratch",) if level >= 3 else ()), *(("ra", "ra_scratch") if level == 5 else ()),
+                 *(("keep",) if level >= 4 else ()), "mean", "std", *_RESULT)
+    got = {**dict.fromkeys(TABLES), **values, **tables}
+    if "aug" not in tables:
+        got["stat_scratch"] = None
+    return entry, [(n, got[n]) for n in names]
 
 
 class _VitFn(torch.autograd.Function):
@@ -183,6 +212,13 @@ class CaraEngine:
         self._ingested = (t, w)
         self._ingest_sig = self._signature(model)
 
+    def _ensure_ingested(self, model, dev) -> bool:
+        """ingest when nothing is ingested yet, the signature moved or the model sits on another device; -> whether it did"""
+        if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
+            self._ingest(model, dev)
+            return True
+        return False
+
     # ------------------------------------------------------------------ per-shape state
     def _pos_rows(self, need, dev):
         """The token assembly adds row ``t`` of ``pos_embed`` to token ``t`` (row ``1 + keep[b][j]`` behind a patch dropout) and is not
@@ -205,8 +241,7 @@ class CaraEngine:
 
     def _state(self, model, B, img, dev, tokens=None):
         """``tokens``: 1 + K of a step behind a patch dropout; None = the grid's (img / patch)^2 + 1"""
-        if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
-            self._ingest(model, dev)
+        if self._ensure_ingested(model, dev):
             self._ws.clear()
         ncls = model.head.out_features
         exact = self.weight_dropout == "exact"
@@ -253,33 +288,35 @@ class CaraEngine:
         images = images.contiguous().float()
         dev = images.device
         with torch.cuda.device(dev):   # the library enqueues on the stream it is given and launches on the current device
-            return self._run_forward_on(model, images, droppath, head_w, head_b, cp, need_backward, dev, keep=keep)
+            return self._run_forward_on(model, images, Feed(None, keep=keep), droppath, head_w, head_b, cp, need_backward, dev)
 
-    def _check_keep(self, keep, B, img, dev):
-        """``keep`` of a patch dropout (``data.PatchDropout.draw``, one step's [batch, K] view), refused before anything is enqueued"""
-        model = self._model()
-        P = (img // model.patch_embed.proj.kernel_size[0]) ** 2
-        if not torch.is_tensor(keep) or keep.dtype != torch.int32 or keep.ndim != 2 or keep.shape[0] != B or not keep.is_contiguous() \
-                or keep.device != dev or not (1 <= keep.shape[1] <= P):
-            raise CaraError(f"keep must be a contiguous int32 [batch, K] tensor of patch indices on the model's device, 1 <= K <= {P} "
-                            "(data.PatchDropout.draw, data.check_keep)")
+    def _patches(self, img: int) -> int:
+        """P: the patches of the grid of an ``img`` x ``img`` input"""
+        return (img // self._model().patch_embed.proj.kernel_size[0]) ** 2
 
-    def _run_forward_on(self, model, images, droppath, head_w, head_b, cp, need_backward, dev, resident=None, keep=None):
-        """``resident = (split, rows[, boxes[, mix[, aug[, ra]]]])``: the images are rows of a resident uint8 split (``images`` is None
-        then), with ``boxes`` read through a crop box per sample at the model's own input size, with ``mix`` mixed by that table, with
-        ``aug`` colour-jittered and erased by that one, with ``ra`` RandAugmented by that one.  ``keep`` (device int32 [batch, K]): the patch tokens a patch dropout keeps;
-        the blocks then run on 1 + K tokens, on a workspace of that size"""
-        boxes = mix = aug = ra = None
-        if resident is None:
-            B, img = images.shape[0], images.shape[2]
+    @staticmethod
+    def _check_table(name, t, batch=None, dev=None, P=None):
+        """``t`` is the table ``name`` of ``feed.TABLES``: a contiguous int32 [*, columns] tensor (``keep``: 1 <= K <= ``P``) and, with
+        ``batch`` and ``dev``, one of ``batch`` rows on ``dev`` -- refused before anything is enqueued"""
+        width, msg = TABLES[name]
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.ndim != 2 or not t.is_contiguous() \
+                or (t.shape[1] != width if width else not (1 <= t.shape[1] <= P)) \
+                or (batch is not None and (t.device != dev or t.shape[0] != batch)):
+            raise CaraError(msg.format(P=P))
+
+    def _run_forward_on(self, model, source, feed, droppath, head_w, head_b, cp, need_backward, dev):
+        """``source``: an fp32 batch (``feed.rows`` is None and ``keep`` the only table there can be), or the resident uint8 split
+        whose images ``feed.rows`` the tables of ``feed`` shape (``train_step_resident``; with ``boxes`` at the model's own input
+        size).  Behind a ``keep`` the blocks run on 1 + K tokens, on a workspace of that size"""
+        resident, keep = feed.rows is not None, feed.keep
+        if resident:
+            B, img = feed.rows.shape[0], source.pixels.shape[2] if feed.boxes is None else self._model_img(model)
         else:
-            split, rows, boxes, mix, aug, ra = (*resident, None, None, None, None)[:6]
-            B, img = rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model)
-        # (keep was checked by the caller -- train_step, train_step_resident, forward_resident -- before anything was enqueued)
+            B, img = source.shape[0], source.shape[2]
+        # (the tables were checked by the caller -- train_step, train_step_resident, forward_resident -- before anything was enqueued)
         st = self._state(model, B, img, dev, None if keep is None else 1 + keep.shape[1])
-        if resident is not None:
-            if st["shape"].chans != 3:
-                raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
+        if resident and st["shape"].chans != 3:
+            raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
         # weight-space dropout is a train-mode thing (nn.Dropout is the identity in eval); the backward of this
         # forward reads the same struct, i.e. the same seed, and regenerates the masks
         use_exact = self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0
@@ -298,53 +335,23 @@ class CaraEngine:
         st["shape"].inference = 0 if need_backward else 1
         cps = self._cp_ptrs([t.detach().contiguous() for t in cp])
         logits = torch.empty_like(st["logits"])
-        args = (C.byref(st["geom"]), C.byref(st["shape"]), C.byref(self._ingested[1]), C.byref(cps),
-                ptr(head_w.detach().contiguous()), ptr(head_b.detach().contiguous()))
-        if keep is not None and resident is None:
-            check(self._lib().cara_vit_forward_keep(*args, ptr(images), ptr(keep), ptr(droppath), ptr(st["ws"]), ptr(logits),
-                                                    ptr(self._bad_rows(dev)), stream(dev)), "cara_vit_forward_keep")
-        elif ra is not None:
+        values = {"g": C.byref(st["geom"]), "s": C.byref(st["shape"]), "w": C.byref(self._ingested[1]), "cp": C.byref(cps),
+                  "head_w": head_w.detach().contiguous(), "head_b": head_b.detach().contiguous(), "droppath": droppath,
+                  "workspace": st["ws"], "logits": logits, "stream": stream(dev)}
+        if resident or keep is not None:   # (the entries that read indices count the bad ones)
+            values["bad"] = self._bad_rows(dev)
+        if resident:
+            px, rows = source.pixels, feed.rows
             mean, std = self._eval_norm(dev)
-            check(self._lib().cara_vit_forward_u8_rows_ra(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
-                                                          split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(aug),
-                                                          ptr(self._aug_stat(dev, rows.shape[0])) if aug is not None else None,
-                                                          ptr(ra), ptr(self._ra_stat(dev, rows.shape[0])), ptr(keep), ptr(mean), ptr(std),
-                                                          ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)), stream(dev)),
-                  "cara_vit_forward_u8_rows_ra")
-        elif keep is not None:
-            mean, std = self._eval_norm(dev)
-            check(self._lib().cara_vit_forward_u8_rows_keep(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
-                                                            split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(aug),
-                                                            ptr(self._aug_stat(dev, rows.shape[0])) if aug is not None else None,
-                                                            ptr(keep), ptr(mean), ptr(std), ptr(droppath), ptr(st["ws"]), ptr(logits),
-                                                            ptr(self._bad_rows(dev)), stream(dev)), "cara_vit_forward_u8_rows_keep")
-        elif resident is None:
-            check(self._lib().cara_vit_forward(*args, ptr(images), ptr(droppath), ptr(st["ws"]), ptr(logits), stream(dev)),
-                  "cara_vit_forward")
-        elif aug is not None:
-            mean, std = self._eval_norm(dev)
-            check(self._lib().cara_vit_forward_u8_rows_aug(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
-                                                           split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(aug),
-                                                           ptr(self._aug_stat(dev, rows.shape[0])), ptr(mean), ptr(std), ptr(droppath),
-                                                           ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)), stream(dev)),
-                  "cara_vit_forward_u8_rows_aug")
-        elif mix is not None:
-            mean, std = self._eval_norm(dev)
-            check(self._lib().cara_vit_forward_u8_rows_mix(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
-                                                           split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mix), ptr(mean), ptr(std),
-                                                           ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)),
-                                                           stream(dev)), "cara_vit_forward_u8_rows_mix")
-        elif boxes is not None:
-            mean, std = self._eval_norm(dev)
-            check(self._lib().cara_vit_forward_u8_rows_crop(*args, ptr(split.pixels), len(split), split.pixels.shape[2],
-                                                            split.pixels.shape[3], ptr(rows), ptr(boxes), ptr(mean), ptr(std),
-                                                            ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)),
-                                                            stream(dev)), "cara_vit_forward_u8_rows_crop")
+            values.update(pixels=px, n_split=len(source), Hs=px.shape[2], Ws=px.shape[3], rows=rows, mean=mean, std=std)
+            if feed.aug is not None:
+                values["stat_scratch"] = self._aug_stat(dev, B)
+            if feed.ra is not None:
+                values["ra_scratch"] = self._ra_stat(dev, B)
         else:
-            mean, std = self._eval_norm(dev)
-            check(self._lib().cara_vit_forward_u8_rows(*args, ptr(split.pixels), len(split), ptr(rows), ptr(mean), ptr(std),
-                                                       ptr(droppath), ptr(st["ws"]), ptr(logits), ptr(self._bad_rows(dev)),
-                                                       stream(dev)), "cara_vit_forward_u8_rows")
+            values["images"] = source
+        entry, params = forward_call(feed.tables(), values)
+        check(getattr(self._lib(), entry)(*[ptr(v) if v is None or torch.is_tensor(v) else v for _, v in params]), entry)
         self._fwd_serial += 1
         self._bwd_ready = self._fwd_serial if need_backward else -1
         return logits
@@ -597,14 +604,12 @@ class CaraEngine:
         if not flat.is_cuda:
             raise CaraError("clip_grad runs on the GPU only (no CPU path)")
         dev, n = flat.device, flat.numel() - 1
-        bufs = self.__dict__.setdefault("_clip_bufs", {})   # per (device, size), never replaced: a captured step holds the addresses
-        got = bufs.get((dev, n))
-        if got is None:
+        def make():
             nbytes = int(self._lib().cara_grad_clip_scratch_bytes(n))
             if nbytes == 0:
                 raise CaraError(f"cara_grad_clip takes 1 .. 2^31 elements, not {n}")
-            got = bufs[(dev, n)] = (torch.empty(nbytes // 4, device=dev), torch.zeros(2, device=dev))
-        scratch, out = got
+            return torch.empty(nbytes // 4, device=dev), torch.zeros(2, device=dev)
+        scratch, out = self._pinned("clip", dev, n, make)
         found = self._grad_views["_found_inf"] if self.precision == "fp16" else None
         with torch.cuda.device(dev):
             check(self._lib().cara_grad_clip(ptr(flat), n, max_norm, ptr(scratch), ptr(found), ptr(out), stream(dev)), "cara_grad_clip")
@@ -661,7 +666,7 @@ class CaraEngine:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
         if keep is not None:
-            self._check_keep(keep, images.shape[0], images.shape[-1], dev)
+            self._check_table("keep", keep, images.shape[0], dev, self._patches(images.shape[-1]))
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp, keep=keep),
@@ -748,45 +753,31 @@ class CaraEngine:
             raise CaraError("boxes need a model that states its input size (patch_embed.img_size)")
         return img
 
-    def _aug_stat(self, dev, B):
-        """the jitter kernels' statistic scratch (``cara_aug_stat_bytes``): one buffer per (device, batch size), never replaced -- a
-        captured step holds its address (68 bytes per sample)"""
-        bufs = self.__dict__.setdefault("_aug_stat_bufs", {})
-        buf = bufs.get((dev, B))
+    def _pinned(self, kind, dev, size, make):
+        """``make()`` once per (kind, device, size), and that buffer ever after, never replaced: a captured step holds its address,
+        and a step of another size in between must not free it"""
+        bufs = self.__dict__.setdefault("_pinned_bufs", {})
+        buf = bufs.get((kind, dev, size))
         if buf is None:
-            buf = bufs[(dev, B)] = torch.empty(int(self._lib().cara_aug_stat_bytes(B)) // 4, dtype=torch.float32, device=dev)
+            buf = bufs[(kind, dev, size)] = make()
         return buf
+
+    def _aug_stat(self, dev, B):
+        """the jitter kernels' statistic scratch (``cara_aug_stat_bytes``: 68 bytes per sample)"""
+        return self._pinned("aug_stat", dev, B, lambda: torch.empty(int(self._lib().cara_aug_stat_bytes(B)) // 4, dtype=torch.float32, device=dev))
 
     def _ra_stat(self, dev, B):
-        """the RandAugment pre-pass' scratch (``cara_ra_stat_bytes``: byte tables and partial histograms), kept like ``_aug_stat``'s"""
-        bufs = self.__dict__.setdefault("_ra_stat_bufs", {})
-        buf = bufs.get((dev, B))
-        if buf is None:
-            buf = bufs[(dev, B)] = torch.empty(int(self._lib().cara_ra_stat_bytes(B)) // 4, dtype=torch.int32, device=dev)
-        return buf
+        """the RandAugment pre-pass' scratch (``cara_ra_stat_bytes``: byte tables and partial histograms)"""
+        return self._pinned("ra_stat", dev, B, lambda: torch.empty(int(self._lib().cara_ra_stat_bytes(B)) // 4, dtype=torch.int32, device=dev))
 
-    def _resident_args(self, split, rows, boxes=None, mix=None, aug=None, ra=None):
+    def _resident_args(self, split, feed):
+        """``split`` and ``feed`` (a ``Feed``) are what ``train_step_resident`` takes, refused before anything is enqueued -- what a
+        table is before where it lives: a host-made table of the wrong type is refused as such; -> (model, device)"""
         model = self._model()
-        box_msg = "boxes must be a contiguous int32 [batch, 5] tensor (x0, y0, w, h, flip) on the model's device"
-        mix_msg = ("mix must be a contiguous int32 [batch, 8] tensor (partner, cx0, cy0, cw, ch, blend bits, target bits, 0) on the "
-                   "model's device")
-        # (what a box table is, before where it lives: a host-made table of the wrong type is refused as such)
-        if boxes is not None and (not torch.is_tensor(boxes) or boxes.dtype != torch.int32 or boxes.ndim != 2 or boxes.shape[1] != 5
-                                  or not boxes.is_contiguous()):
-            raise CaraError(box_msg)
-        if mix is not None and (not torch.is_tensor(mix) or mix.dtype != torch.int32 or mix.ndim != 2 or mix.shape[1] != 8
-                                or not mix.is_contiguous()):
-            raise CaraError(mix_msg)
-        aug_msg = ("aug must be a contiguous int32 [batch, 16] tensor (op0, f0, op1, f1, op2, f2, ex0, ey0, ew, eh, emode, eseed, 0, 0, 0, "
-                   "0) on the model's device")
-        if aug is not None and (not torch.is_tensor(aug) or aug.dtype != torch.int32 or aug.ndim != 2 or aug.shape[1] != 16
-                                or not aug.is_contiguous()):
-            raise CaraError(aug_msg)
-        ra_msg = ("ra must be a contiguous int32 [batch, 16] tensor (op0, arg0, op1, arg1, op2, arg2, m00, m01, m02, m10, m11, m12, fill, 0, "
-                  "0, 0) on the model's device")
-        if ra is not None and (not torch.is_tensor(ra) or ra.dtype != torch.int32 or ra.ndim != 2 or ra.shape[1] != 16
-                               or not ra.is_contiguous()):
-            raise CaraError(ra_msg)
+        rows, boxes = feed.rows, feed.boxes
+        tables = {n: t for n, t in feed.tables().items() if n != "keep"}   # (keep's columns need the grid: last)
+        for n, t in tables.items():
+            self._check_table(n, t)
         dev = model.head.weight.device if hasattr(model.head, "weight") else None
         if dev is None:
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
@@ -800,31 +791,15 @@ class CaraEngine:
         if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.device != dev or rows.ndim != 1 or rows.shape[0] == 0 \
                 or not rows.is_contiguous():
             raise CaraError("rows must be a contiguous int64 [batch] tensor on the model's device")
-        if boxes is not None and (boxes.device != dev or boxes.shape[0] != rows.shape[0]):
-            raise CaraError(box_msg)
-        if mix is not None and (mix.device != dev or mix.shape[0] != rows.shape[0]):
-            raise CaraError(mix_msg)
-        if aug is not None and (aug.device != dev or aug.shape[0] != rows.shape[0]):
-            raise CaraError(aug_msg)
-        if ra is not None and (ra.device != dev or ra.shape[0] != rows.shape[0]):
-            raise CaraError(ra_msg)
+        for n, t in tables.items():
+            self._check_table(n, t, rows.shape[0], dev)
+        if feed.keep is not None:
+            self._check_table("keep", feed.keep, rows.shape[0], dev, self._patches(px.shape[2] if boxes is None else self._model_img(model)))
         return model, dev
-
-    def _forward_rows(self, split, rows, droppath, hw, hb, cp, need_backward, boxes=None, mix=None, aug=None, keep=None, ra=None):
-        model = self._model()
-        dev = rows.device
-        with torch.cuda.device(dev):
-            return self._run_forward_on(model, None, droppath, hw, hb, cp, need_backward, dev, resident=(split, rows, boxes, mix, aug, ra),
-                                        keep=keep)
 
     def _gather_labels(self, split, rows):
         dev, B = rows.device, rows.shape[0]
-        # one buffer per (device, batch size), never replaced: a captured step holds its address, and a step of another batch
-        # size in between must not free it (8 bytes per sample)
-        bufs = self.__dict__.setdefault("_labels_bufs", {})
-        buf = bufs.get((dev, B))
-        if buf is None:
-            buf = bufs[(dev, B)] = torch.empty(B, dtype=torch.int64, device=dev)
+        buf = self._pinned("labels", dev, B, lambda: torch.empty(B, dtype=torch.int64, device=dev))   # (8 bytes per sample)
         check(self._lib().cara_gather_labels(ptr(split.labels.contiguous()), len(split), ptr(rows), ptr(buf), B, ptr(self._bad_rows(dev)),
                                              stream(dev)), "cara_gather_labels")
         return buf
@@ -858,32 +833,29 @@ class CaraEngine:
         A table entry the kernel refuses -- ``data.check_ra`` -- gives a zero image, counted like a bad row.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
-        model, dev = self._resident_args(split, rows, boxes, mix, aug, ra)
-        if keep is not None:
-            self._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
-        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._forward_rows(split, rows, dp, hw, hb, cp, True, boxes, mix, aug, keep, ra),
+        feed = Feed(rows, boxes, mix, aug, keep, ra)
+        model, dev = self._resident_args(split, feed)
+        return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._run_forward_on(model, split, feed, dp, hw, hb, cp, True, dev),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
                          keep=None, ra=None):
         """logits [batch, classes] of the images ``rows`` of a resident split, without autograd (tests and tools); ``boxes``,
         ``mix``, ``aug``, ``keep`` and ``ra`` as in ``train_step_resident`` (a centre-cropped evaluation by hand); ``weights`` as in ``evaluate``"""
-        model, dev = self._resident_args(split, rows, boxes, mix, aug, ra)
-        if keep is not None:
-            self._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else self._model_img(model), dev)
+        feed = Feed(rows, boxes, mix, aug, keep, ra)
+        model, dev = self._resident_args(split, feed)
         cp, hw, hb = self._forward_weights(model, dev, weights)
         self._refuse_fp16_unfactored()
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, rows.shape[0], dev)
-            return self._forward_rows(split, rows, droppath, hw, hb, cp, False, boxes, mix, aug, keep, ra)
+            return self._run_forward_on(model, split, feed, droppath, hw, hb, cp, False, dev)
 
     # ------------------------------------------------------------------ evaluation on the device
     def _eval_state(self, model, B, img, dev):
         """Workspace of the evaluation forwards: sized with cara_vit_shape::inference = 1 (two activation sets, nothing of the
         backward) and kept in ``_eval_ws``, beside the training workspaces of ``_ws``, which this never touches."""
-        if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
-            self._ingest(model, dev)
+        self._ensure_ingested(model, dev)
         ews = self.__dict__.setdefault("_eval_ws", {})
         self._pos_rows((img // model.patch_embed.proj.kernel_size[0]) ** 2 + 1, dev)
         ncls = model.head.out_features
@@ -993,8 +965,7 @@ class CaraEngine:
 
     # module-level entries (cara.cp_attn / cara.cp_mlp): the reference's patched forwards
     def _weights(self, model, dev):
-        if self._ingested is None or self._ingest_sig != self._signature(model) or self._ingested[0]["cls"].device != dev:
-            self._ingest(model, dev)
+        if self._ensure_ingested(model, dev):
             self._ws.clear()
         return self._ingested
 

@@ -18,6 +18,7 @@ from typing import Callable, Iterable, Optional
 import torch
 
 from ._lib import CaraError
+from .feed import Feed
 
 
 class CosineLRScheduler:
@@ -116,24 +117,19 @@ KEEP_AHEAD = 64   # steps of keep tables per draw of fit(patch_drop=)
 class GraphedTrainStep:
     """``CaraEngine.train_step`` captured into a hipGraph and replayed (``cara_vit_forward`` / ``cara_vit_backward`` only enqueue
     work on the caller's stream, include/cara_hip.h; the optimiser must be ``cara_amd.optim.AdamW(capturable=True)``: its step count
-    and learning rates live in device memory).  One graph per (batch shape, train / eval mode): the first call with a new key runs
-    eagerly (weights ingested, workspaces sized), the second captures, later ones copy the batch into the graph's input buffers,
-    upload { step, lr } and replay.  What a capture cannot hold runs eagerly, every time: more than one rank (the all-reduce) and the
-    exact weight-dropout mode (a fresh host-side seed per step).  Same switch as ``bench.py --graph``.
-    The resident form ``step(split, rows)`` captures ``train_step_resident``: one graph per (split, shape of ``rows``, mode), whose
-    only static input is the index vector -- 8 bytes per sample are copied per step, no image.  ``step(split, (rows, boxes))``
-    captures the augmented step (``train_step_resident(..., boxes=)``): one graph per (split, shapes, mode) again, whose static
-    inputs are the index vector and the box table -- both copied before every replay, 28 bytes per sample.
-    ``step(split, (rows, boxes_or_None, mix))`` captures the mixed step (``train_step_resident(..., mix=)``) the same way: the
-    Mixup / CutMix table is one more static input, 32 bytes per sample copied per replay.
-    ``step(split, (rows, boxes_or_None, mix_or_None, aug))`` captures the jittered step (``train_step_resident(..., aug=)``): the
-    colour-jitter / erase table is copied per replay too, 64 bytes per sample.  ``step(split, (rows, boxes_or_None, mix_or_None,
-    aug_or_None, keep_or_None, ra))`` captures the RandAugmented step (``train_step_resident(..., ra=)``): that table is one more
-    static input, 64 bytes per sample copied per replay.  ``label_smoothing`` is the steps' (all
-    forms); it is part of every graph's key.  ``clip_grad`` likewise: the two launches of ``cara_grad_clip`` are captured with
-    the step (``CaraEngine.train_step(..., clip_grad=)``).  An accumulation window (``accumulate`` with k > 1) spans several
-    replays and is refused.  ``ema`` (``CaraEngine.make_ema(..., capturable=True)``): the average's launch is captured behind the
-    optimiser's; its weight lives in device memory and ``ema.advance()`` runs before every step, as ``optimizer.advance()`` does."""
+    and learning rates live in device memory).  The first call with a new key runs eagerly (weights ingested, workspaces sized), the
+    second captures, later ones copy the inputs into the graph's static buffers, upload { step, lr } and replay.  What a capture
+    cannot hold runs eagerly, every time: more than one rank (the all-reduce) and the exact weight-dropout mode (a fresh host-side
+    seed per step).  Same switch as ``bench.py --graph``.
+    Two forms.  ``step(images, labels)`` captures ``train_step``: the batch and its labels are the static inputs.  ``step(split,
+    item)`` captures ``train_step_resident`` on a ``data.ResidentSplit``: ``item`` is what ``train_rows`` yields -- an index vector,
+    or a tuple of it and its tables (``feed.Feed``) -- and the static inputs are the index vector and the tables present, nothing
+    else: per sample and replay 8 bytes of ``rows``, 20 of ``boxes``, 32 of ``mix``, 64 of ``aug``, 4 K of ``keep``, 64 of ``ra``, no
+    image.  One graph per (form, split, which tables, every input's shape, train / eval mode, precision, smoothing, clip): another K
+    of ``keep`` captures another graph.  ``label_smoothing`` and ``clip_grad`` are the steps' (the two launches of ``cara_grad_clip``
+    are captured with the step).  An accumulation window (``accumulate`` with k > 1) spans several replays and is refused.
+    ``ema`` (``CaraEngine.make_ema(..., capturable=True)``): the average's launch is captured behind the optimiser's; its weight
+    lives in device memory and ``ema.advance()`` runs before every step, as ``optimizer.advance()`` does."""
 
     def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None):
         if not getattr(optimizer, "capturable", False):
@@ -143,7 +139,7 @@ class GraphedTrainStep:
         self.eng, self.opt, self.ema = engine, optimizer, ema
         self.label_smoothing = engine._smoothing(label_smoothing) if label_smoothing else 0.0
         self.clip_grad = engine._max_norm(clip_grad)
-        self._graphs = {}
+        self._graphs = {}   # key -> "warm", then (graph, source, static inputs, loss, held): source is the split, None for images
 
     def _kw(self):
         # (a step without smoothing, without a clip and without an average is called exactly as before)
@@ -154,53 +150,48 @@ class GraphedTrainStep:
             kw["ema"] = self.ema
         return kw
 
-    def _advance(self):
+    def __call__(self, x, y, group=None, accumulate=None, keep=None):
+        """``(images, labels)``, or ``(split, item)`` with ``item`` an index vector or a tuple of it and its tables in ``Feed``'s
+        order; ``keep=`` hands a patch-dropout table (device int32 [batch, K]) to the image form, and to a resident item without
+        one.  Everything is refused here, not inside a capture."""
+        if self.eng._window(accumulate)[1] > 1:
+            raise CaraError("GraphedTrainStep: accumulate with k > 1 is not supported (the window spans several graph replays)")
+        eng, kw = self.eng, self._kw()
+        if hasattr(x, "pixels"):
+            feed = Feed.of(y)
+            if feed.keep is None and keep is not None:
+                feed = feed._replace(keep=keep)
+            eng._resident_args(x, feed)
+            names = tuple(feed.tables())
+            # (the split itself is part of the key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
+            return self._run(lambda s: eng.train_step_resident(x, s[0], self.opt, group=group, **dict(zip(names, s[1:])), **kw),
+                             feed.static(), ("resident", x, names), group)
+        if keep is None:
+            return self._run(lambda s: eng.train_step(s[0], s[1], self.opt, group=group, **kw), (x, y), ("images", None, ()), group)
+        if x.ndim != 4 or x.shape[2] != x.shape[3]:
+            raise CaraError("images must be [B, C, H, H]")
+        eng._check_table("keep", keep, x.shape[0], x.device, eng._patches(x.shape[2]))
+        return self._run(lambda s: eng.train_step(s[0], s[1], self.opt, group=group, keep=s[2], **kw), (x, y, keep),
+                         ("images", None, ("keep",)), group)
+
+    def _run(self, step, live, key, group):
+        """warm, capture, replay: ``step(inputs)`` is the eager step on a tuple shaped like ``live``, this call's inputs;
+        ``key = (form, source, table names)`` is completed with the shapes and the settings that change the launches"""
+        from . import dist as cdist
+        eng, model = self.eng, self.eng._model()
         self.opt.advance()
         if self.ema is not None:
             self.ema.advance()
-
-    def _refuse_window(self, accumulate):
-        if self.eng._window(accumulate)[1] > 1:
-            raise CaraError("GraphedTrainStep: accumulate with k > 1 is not supported (the window spans several graph replays)")
-
-    def __call__(self, x, y, group=None, accumulate=None, keep=None):
-        """``(images, labels)``, or ``(split, rows)``: a ``data.ResidentSplit`` and a device int64 index vector, or
-        ``(split, (rows, boxes))``: the same with a device int32 [batch, 5] box table, or ``(split, (rows, boxes_or_None, mix))``:
-        with a device int32 [batch, 8] mix table too, or ``(split, (rows, boxes_or_None, mix_or_None, aug))``: with a device int32
-        [batch, 16] colour-jitter / erase table, or ``(split, (rows, boxes_or_None, mix_or_None, aug_or_None, keep))``: with a device
-        int32 [batch, K] patch-dropout table, or ``(split, (rows, boxes_or_None, mix_or_None, aug_or_None, keep_or_None, ra))``: with a
-        device int32 [batch, 16] RandAugment table.  ``keep=`` hands that table to the ``(images, labels)`` and ``(split, rows)`` forms.
-        The table is one more static input, copied before every replay (4 K bytes per sample); its shape is part of the graph's key,
-        so another K captures another graph."""
-        from . import dist as cdist
-        self._refuse_window(accumulate)
-        eng, model = self.eng, self.eng._model()
-        resident = hasattr(x, "pixels")
-        if resident and (isinstance(y, (tuple, list)) or keep is not None):
-            y = (*y, None, None, None, None, None)[:6] if isinstance(y, (tuple, list)) else (y, None, None, None, None, None)
-            kp = y[4] if y[4] is not None else keep
-            return self._call_tables(x, y[0], y[1], y[2], group, **({} if y[3] is None else {"aug": y[3]}), **({} if kp is None else {"keep": kp}),
-                                     **({} if y[5] is None else {"ra": y[5]}))
-        kw = self._kw()
-        if keep is not None:   # (refused here, not inside a capture)
-            if x.ndim != 4 or x.shape[2] != x.shape[3]:
-                raise CaraError("images must be [B, C, H, H]")
-            eng._check_keep(keep, x.shape[0], x.shape[2], x.device)
-        step = (lambda a, b, opt, group=None, k=None: eng.train_step_resident(a, b, opt, group=group, **kw)) if resident else \
-            (lambda a, b, opt, group=None, k=None: eng.train_step(a, b, opt, group=group, **kw, **({} if k is None else {"keep": k})))
-        self._advance()
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
-            return step(x, y, self.opt, group=group, k=keep)
-        # (the split itself is part of a resident key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
-        key = (("rows", x, tuple(y.shape)) if resident else tuple(x.shape), bool(model.training), eng.precision, self.label_smoothing,
-               self.clip_grad, *(() if keep is None else (("keep", tuple(keep.shape)),)))
+            return step(live)
+        key = (*key, tuple(tuple(t.shape) for t in live), bool(model.training), eng.precision, self.label_smoothing, self.clip_grad)
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
-            return step(x, y, self.opt, group=group, k=keep)
-        dev = y.device
+            return step(live)
+        dev = live[0].device
         if ent == "warm":
-            xs, ys, ks = (x if resident else x.clone()), y.clone(), (None if keep is None else keep.clone())
+            static = tuple(t.clone() for t in live)
             torch.cuda.synchronize(dev)
             gr = torch.cuda.CUDAGraph()
             gen = eng._device_generator(dev)
@@ -210,70 +201,15 @@ class GraphedTrainStep:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 with torch.cuda.graph(gr, stream=side):
-                    loss = step(xs, ys, self.opt, group=group, k=ks)
+                    loss = step(static)
             torch.cuda.current_stream(dev).wait_stream(side)
             # (the last element keeps what the engine would replace at an eager step of another batch size in between -- its dlogits
             # buffer and the workspace of this shape -- as ``loss`` keeps its loss buffer: the graph holds their addresses)
-            ent = self._graphs[key] = (gr, xs, ys, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]), ks)
+            ent = self._graphs[key] = (gr, key[1], static, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
             # (the capture itself ran nothing: fall through to the replay, which is this call's step)
-        gr, xs, ys, loss = ent[:4]
-        if not resident:
-            xs.copy_(x)
-        ys.copy_(y)
-        if keep is not None:
-            ent[5].copy_(keep)
-        gr.replay()
-        return loss
-
-    def _call_tables(self, split, rows, boxes, mix, group, aug=None, keep=None, ra=None):
-        """the resident form through crop boxes and / or a mix table and / or an aug table and / or a keep table and / or an ra table:
-        warm, capture, replay as above, with one to six static inputs"""
-        from . import dist as cdist
-        eng, model = self.eng, self.eng._model()
-        eng._resident_args(split, rows, boxes, mix, *(() if aug is None and ra is None else (aug,)),
-                           *(() if ra is None else (ra,)))                                 # (refused here, not inside a capture)
-        if keep is not None:
-            eng._check_keep(keep, rows.shape[0], split.pixels.shape[2] if boxes is None else eng._model_img(model), rows.device)
-        self._advance()
-        tables = [t for t in (boxes, mix, aug, keep, ra) if t is not None]
-
-        def step(rs, ts):
-            ts = list(ts)
-            return eng.train_step_resident(split, rs, self.opt, group=group, boxes=ts.pop(0) if boxes is not None else None,
-                                           **({"mix": ts.pop(0)} if mix is not None else {}),
-                                           **({"aug": ts.pop(0)} if aug is not None else {}),
-                                           **({"keep": ts.pop(0)} if keep is not None else {}),
-                                           **({"ra": ts.pop(0)} if ra is not None else {}), **self._kw())
-        if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
-            return step(rows, tables)
-        key = (("rows+boxes" if mix is None else "rows+boxes+mix", split, tuple(rows.shape), boxes is not None and tuple(boxes.shape),
-                mix is not None and tuple(mix.shape), *(() if aug is None else (("aug", tuple(aug.shape)),)),
-                *(() if keep is None else (("keep", tuple(keep.shape)),)), *(() if ra is None else (("ra", tuple(ra.shape)),))),
-               bool(model.training),
-               eng.precision, self.label_smoothing, self.clip_grad)
-        ent = self._graphs.get(key)
-        if ent is None:
-            self._graphs[key] = "warm"
-            return step(rows, tables)
-        dev = rows.device
-        if ent == "warm":
-            rs, bs = rows.clone(), tuple(t.clone() for t in tables)
-            torch.cuda.synchronize(dev)
-            gr = torch.cuda.CUDAGraph()
-            gen = eng._device_generator(dev)
-            if gen is not None:
-                gr.register_generator_state(gen)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                with torch.cuda.graph(gr, stream=side):
-                    loss = step(rs, bs)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            ent = self._graphs[key] = (gr, split, (rs, *bs), loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
-        gr, _, (rs, *bs), loss = ent[:4]
-        rs.copy_(rows)
-        for static, t in zip(bs, tables):
-            static.copy_(t)
+        gr, _, static, loss = ent[:4]
+        for s, t in zip(static, live):
+            s.copy_(t)
         gr.replay()
         return loss
 
@@ -306,14 +242,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     on an index vector: the same samples in the same order as ``split.train_batches(...)`` with the same seed, without the
     normalised fp32 batch.  An index outside the split is counted on the device, not read; the count is looked at where the
     evaluation epochs read from the device anyway and once more after the last epoch, and a non-zero one raises.
-    A ``rows_of`` that yields ``(rows, boxes)`` pairs (``train_rows(..., augment=data.RandomResizedCropFlip(...))``) trains
-    through a crop box per sample (``train_step_resident(..., boxes=)``); a box outside its image is counted like a bad row.
-    One that yields ``(rows, boxes_or_None, mix)`` triples (``train_rows(..., mix=data.MixupCutmix(...))``) trains with Mixup /
-    CutMix by index (``train_step_resident(..., mix=)``); a mix entry the kernel refuses is counted like a bad row too.
-    One that yields ``(rows, boxes_or_None, mix_or_None, aug)`` (``train_rows(..., color=data.ColorJitterErase(...))``) trains with
-    colour jitter and Random Erasing by index too (``train_step_resident(..., aug=)``).
-    One that yields ``(rows, boxes_or_None, mix_or_None, aug_or_None, keep_or_None, ra)`` (``train_rows(..., rand=data.RandAugment(...))``)
-    trains with RandAugment by index too (``train_step_resident(..., ra=)``); an ra entry the kernel refuses is counted like a bad row.
+    ``rows_of`` yields index vectors, or tuples of one and its tables in ``feed.Feed``'s order (``train_rows(..., augment=, mix=,
+    color=, patch_drop=, rand=)``: None for a table not asked for in front of one that is); the tables present are
+    ``train_step_resident``'s keyword arguments of those names.  A crop box outside its image, and an entry of ``mix``, ``aug``,
+    ``keep`` or ``ra`` that the kernel refuses (``data.check_mix`` ...), is counted like a bad row.
     ``label_smoothing`` in [0, 1): every step's loss is the smoothed cross-entropy (both feeds).
     ``clip_grad = max_norm``: every optimiser step clips the global gradient norm first (``train_step(..., clip_grad=)``; both
     feeds, eager and graphed).  ``accum_steps = k`` > 1: ``k`` consecutive batches of an epoch form a window -- one optimiser step,
@@ -374,26 +306,9 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         split, rows_of = train_batches
         train_batches = lambda epoch: ((split, rows) for rows in rows_of(epoch))   # noqa: E731
 
-        def step(split, rows, opt, group=None, **win):
-            if isinstance(rows, (tuple, list)):
-                if len(rows) > 5:   # (train_rows(..., rand=): None for the tables not asked for)
-                    rows, boxes, mix, aug, keep, ra = rows
-                    tables = {k: v for k, v in (("boxes", boxes), ("mix", mix), ("aug", aug), ("keep", keep), ("ra", ra)) if v is not None}
-                    return eng.train_step_resident(split, rows, opt, group=group, **tables, **smooth, **win)
-                if len(rows) > 4:   # (train_rows(..., patch_drop=): None for the tables not asked for)
-                    rows, boxes, mix, aug, keep = rows
-                    tables = {k: v for k, v in (("boxes", boxes), ("mix", mix), ("aug", aug), ("keep", keep)) if v is not None}
-                    return eng.train_step_resident(split, rows, opt, group=group, **tables, **smooth, **win)
-                if len(rows) > 3:
-                    rows, boxes, mix, aug = rows
-                    return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **({} if mix is None else {"mix": mix}), aug=aug,
-                                                   **smooth, **win)
-                if len(rows) > 2:
-                    rows, boxes, mix = rows
-                    return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, mix=mix, **smooth, **win)
-                rows, boxes = rows
-                return eng.train_step_resident(split, rows, opt, group=group, boxes=boxes, **smooth, **win)
-            return eng.train_step_resident(split, rows, opt, group=group, **smooth, **win)
+        def step(split, item, opt, group=None, **win):
+            f = Feed.of(item)
+            return eng.train_step_resident(split, f.rows, opt, group=group, **f.tables(), **smooth, **win)
     else:
         def step(x, y, opt, group=None, **win):
             return eng.train_step(x, y, opt, group=group, **smooth, **win)

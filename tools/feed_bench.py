@@ -157,6 +157,7 @@ def main():
 def augment_legs(args, eng, opt, split, feeder, dev, gd):
     from cara_amd import _lib as L
     from cara_amd.data import IMAGENET_MEAN, IMAGENET_STD, MixupCutmix, RandomResizedCropFlip, ResidentSplit, identity_mix
+    from cara_amd.feed import Feed
     S, B = args.source, args.batch
     big = ResidentSplit.from_tensors(torch.randint(0, 256, (args.images, 3, S, S), generator=gd, dtype=torch.uint8, device=dev), split.labels)
     aug = RandomResizedCropFlip(224)
@@ -165,11 +166,16 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
         opt.advance()
         return eng.train_step_resident(split, rows, opt)
 
-    def augmented(item):
+    def tabled(item, **kw):
+        """the step on whatever tables the feed's item carries"""
         opt.advance()
-        return eng.train_step_resident(big, item[0], opt, boxes=item[1])
+        f = Feed.of(item)
+        return eng.train_step_resident(big, f.rows, opt, **f.tables(), **kw)
+
+    def smoothed(item):
+        return tabled(item, label_smoothing=0.1)
     steps = {"eager/resident": (feeder(split.train_rows(B)), plain),
-             f"eager/resident+crop{S}": (feeder(big.train_rows(B, augment=aug)), augmented)}
+             f"eager/resident+crop{S}": (feeder(big.train_rows(B, augment=aug)), tabled)}
     # the kernels alone, on the rows and boxes of one drawn batch, into one patches buffer of the step's shape
     lib, dt = L.lib(args.precision), L.act_dtype(args.precision)
     rows, boxes = next(big.train_rows(B, augment=aug)(0))
@@ -187,10 +193,7 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
                                                      L.ptr(patches), L.ptr(bad), B, 3, 224, 224, 16, st), "cara_im2col_patches_u8_rows_crop")
     kernels = {"kernel/u8_rows": k_rows, f"kernel/u8_rows_crop{S}": k_crop}
     if args.mix:
-        def mixed(item):
-            opt.advance()
-            return eng.train_step_resident(big, item[0], opt, boxes=item[1], mix=item[2], label_smoothing=0.1)
-        steps[f"eager/resident+crop{S}+mix"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224))), mixed)
+        steps[f"eager/resident+crop{S}+mix"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224))), smoothed)
         rev = B - 1 - torch.arange(B, dtype=torch.int32)
         half = torch.tensor(0.5).view(torch.int32).item()
         mixup, cutmix = identity_mix(B), identity_mix(B)
@@ -210,11 +213,8 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
         zero_color = type("ZeroColor", (), {"Hi": 224, "Wi": 224, "draw": staticmethod(lambda B_, steps, generator: identity_aug(B_, steps))})()
         jitter, full = ColorJitterErase(224, erase_prob=0.0), ColorJitterErase(224)
 
-        def jittered(item):
-            opt.advance()
-            return eng.train_step_resident(big, item[0], opt, boxes=item[1], mix=item[2], aug=item[3], label_smoothing=0.1)
         for name, c in (("aug0", zero_color), ("jitter", jitter), ("jitter+erase", full)):
-            steps[f"eager/resident+crop{S}+mix+{name}"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224), color=c)), jittered)
+            steps[f"eager/resident+crop{S}+mix+{name}"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224), color=c)), smoothed)
         ident = identity_mix(B).to(dev)
         stat = torch.empty(int(lib.cara_aug_stat_bytes(B)) // 4, device=dev)
         gk = torch.Generator().manual_seed(9)
@@ -234,15 +234,11 @@ def augment_legs(args, eng, opt, split, feeder, dev, gd):
         kinds = (("ra0", ident_ra), ("geometry", RandAugment(224, prob=1.0, ops=GEO)), ("lookup", RandAugment(224, prob=1.0, ops=LOOK)),
                  ("equalize", RandAugment(224, n=1, prob=1.0, ops=("Equalize",))))
 
-        def randaugmented(item):
-            opt.advance()
-            tables = {k: v for k, v in zip(("boxes", "mix", "aug", "keep", "ra"), item[1:]) if v is not None}
-            return eng.train_step_resident(big, item[0], opt, label_smoothing=0.1, **tables)
         for name, r in kinds:
-            steps[f"eager/resident+crop{S}+{name}"] = (feeder(big.train_rows(B, augment=aug, rand=r)), randaugmented)
+            steps[f"eager/resident+crop{S}+{name}"] = (feeder(big.train_rows(B, augment=aug, rand=r)), smoothed)
         steps[f"eager/resident+crop{S}+mix+erase+ra"] = (feeder(big.train_rows(B, augment=aug, mix=MixupCutmix(224),
                                                                                color=ColorJitterErase(224, 0.0, 0.0, 0.0), rand=RandAugment(224))),
-                                                         randaugmented)
+                                                         smoothed)
         ra_scratch = torch.empty(int(lib.cara_ra_stat_bytes(B)) // 4, dtype=torch.int32, device=dev)
         stat_ra = torch.empty(int(lib.cara_aug_stat_bytes(B)) // 4, device=dev)
         gr = torch.Generator().manual_seed(10)
