@@ -16,26 +16,54 @@
 // One wave per row: pass 1 the row maximum, pass 2 (the row is in L2 by then: at most 87 KB) the exponentials and the
 // rank, 16-byte loads where the row is 16-byte aligned.  A workgroup of four waves walks rows with a grid stride, adds
 // its waves' partial sums in LDS and issues one atomicAdd per non-zero word.
+//
+// cara_eval_accumulate_report is the same kernel body with REPORT = true: the confusion matrix and the calibration bins of
+// include/cara_hip.h.  pass 2 also carries the lowest index whose logit equals the maximum (a wave-min reduction), the
+// confidence is the reciprocal of the sum the loss already forms.  The plain entry launches the REPORT = false instantiation.
 #include "common.h"
 
 namespace {
 
 constexpr int EVAL_WAVES = 4;
 
+// REPORT adds the lowest class index that holds the row maximum (the predicted class) to what a lane carries
+template <bool REPORT>
 struct RowAcc {
   float s;
   int rank;
 };
+template <>
+struct RowAcc<true> {
+  float s;
+  int rank;
+  int pred;
+};
 
-__device__ __forceinline__ void row_term(float x, int c, float m, float v, int y, RowAcc& a) {
+template <bool REPORT>
+__device__ __forceinline__ void row_term(float x, int c, float m, float v, int y, RowAcc<REPORT>& a) {
   a.s += expf(x - m);
   a.rank += (x > v || (x == v && c < y)) ? 1 : 0;
+  if constexpr (REPORT) a.pred = (x == m && c < a.pred) ? c : a.pred;
 }
 
+// REPORT = false: cara_eval_accumulate, `report` and `bins` unused.  REPORT = true: cara_eval_accumulate_report -- per row one
+// atomicAdd on the confusion cell (scattered: nothing to stage) and the three bin words of its confidence bin added up per
+// workgroup in LDS, published with one atomic per non-empty bin word.
+template <bool REPORT>
 __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const float* __restrict__ logits, int ldl,
                                                                           const int64_t* __restrict__ labels, int n_valid,
-                                                                          int C, unsigned long long* __restrict__ state) {
+                                                                          int C, unsigned long long* __restrict__ state,
+                                                                          unsigned long long* __restrict__ report, int bins) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ unsigned int sh_cnt[REPORT ? CARA_EVAL_REPORT_MAX_BINS : 1], sh_hit[REPORT ? CARA_EVAL_REPORT_MAX_BINS : 1];
+  __shared__ double sh_conf[REPORT ? CARA_EVAL_REPORT_MAX_BINS : 1];
+  if constexpr (REPORT) {
+    if ((int)threadIdx.x < bins) {
+      sh_cnt[threadIdx.x] = 0; sh_hit[threadIdx.x] = 0;
+      sh_conf[threadIdx.x] = 0.0;
+    }
+    __syncthreads();
+  }
   unsigned long long n = 0, t1 = 0, t5 = 0, bad = 0;
   double loss = 0.0;
   for (int b = blockIdx.x * EVAL_WAVES + wave; b < n_valid; b += gridDim.x * EVAL_WAVES) {
@@ -56,7 +84,10 @@ __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const 
     for (int c = C4 * 4 + lane; c < C; c += 64) m = fmaxf(m, lr[c]);
     m = wave_max(m);
     const float v = lr[y];
-    RowAcc a = {0.f, 0};
+    RowAcc<REPORT> a;
+    a.s = 0.f;
+    a.rank = 0;
+    if constexpr (REPORT) a.pred = C;
     for (int i = lane; i < C4; i += 64) {
       const float4 q = reinterpret_cast<const float4*>(lr)[i];
       row_term(q.x, 4 * i, m, v, y, a);
@@ -74,6 +105,22 @@ __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const 
     t1 += rank == 0 ? 1 : 0;
     t5 += rank < 5 ? 1 : 0;
     loss += (double)lse - (double)v;
+    if constexpr (REPORT) {
+      int pred = a.pred;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) pred = min(pred, __shfl_xor(pred, o, 64));
+      // a row without a finite maximum (NaN, or nothing above -3e38) matches no class: it is counted in column 0 / bin 0,
+      // never outside the buffer
+      pred = pred < C ? pred : 0;
+      const float conf = 1.0f / s, fb = conf * (float)bins;
+      const int bin = fb >= (float)(bins - 1) ? bins - 1 : (fb > 0.f ? (int)fb : 0);
+      if (lane == 0) {
+        atomicAdd(report + (size_t)y * C + pred, 1ull);
+        atomicAdd(&sh_cnt[bin], 1u);
+        if (rank == 0) atomicAdd(&sh_hit[bin], 1u);
+        atomicAdd(&sh_conf[bin], (double)conf);
+      }
+    }
   }
   // every lane of a wave holds the wave's totals: lane 0 of each wave publishes them, thread 0 adds the four
   __shared__ unsigned long long sh_i[EVAL_WAVES][4];
@@ -96,6 +143,28 @@ __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const 
     if (t5) atomicAdd(state + 2, t5);
     if (bad) atomicAdd(state + 4, bad);
   }
+  if constexpr (REPORT) {
+    // (the LDS adds above are ordered before this by the __syncthreads every wave has passed)
+    const int t = threadIdx.x;
+    if (t < bins && sh_cnt[t]) {
+      unsigned long long* bin_words = report + (size_t)C * C;
+      atomicAdd(bin_words + t, (unsigned long long)sh_cnt[t]);
+      if (sh_hit[t]) atomicAdd(bin_words + bins + t, (unsigned long long)sh_hit[t]);
+      atomicAdd(reinterpret_cast<double*>(bin_words + 2 * bins) + t, sh_conf[t]);
+    }
+  }
+}
+
+bool eval_args_ok(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes, void* state) {
+  if (!logits || !labels || !state || B <= 0 || n_valid < 0 || n_valid > B || classes < 1 || ldl < classes) return false;
+  if ((reinterpret_cast<uintptr_t>(state) & 7) || (reinterpret_cast<uintptr_t>(logits) & 3)) return false;
+  return true;
+}
+
+// at most 256 workgroups (one per CU): 1 280 atomics per launch at the worst, every row still read once
+int eval_grid(int n_valid) {
+  const int grid = (n_valid + EVAL_WAVES - 1) / EVAL_WAVES;
+  return grid > 256 ? 256 : grid;
 }
 
 }  // namespace
@@ -104,14 +173,28 @@ extern "C" size_t cara_eval_state_bytes(void) { return 5 * sizeof(unsigned long 
 
 extern "C" int cara_eval_accumulate(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
                                     void* state, void* stream) {
-  if (!logits || !labels || !state || B <= 0 || n_valid < 0 || n_valid > B || classes < 1 || ldl < classes) return CARA_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(state) & 7) || (reinterpret_cast<uintptr_t>(logits) & 3)) return CARA_E_ARG;
+  if (!eval_args_ok(logits, ldl, labels, B, n_valid, classes, state)) return CARA_E_ARG;
   if (n_valid == 0) return CARA_OK;
-  // at most 256 workgroups (one per CU): 1 280 atomics per launch at the worst, every row still read once
-  int grid = (n_valid + EVAL_WAVES - 1) / EVAL_WAVES;
-  grid = grid > 256 ? 256 : grid;
-  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(grid), dim3(EVAL_WAVES * 64), 0, static_cast<hipStream_t>(stream), logits, ldl,
-                     labels, n_valid, classes, static_cast<unsigned long long*>(state));
+  hipLaunchKernelGGL(eval_accumulate_kernel<false>, dim3(eval_grid(n_valid)), dim3(EVAL_WAVES * 64), 0, static_cast<hipStream_t>(stream),
+                     logits, ldl, labels, n_valid, classes, static_cast<unsigned long long*>(state),
+                     static_cast<unsigned long long*>(nullptr), 0);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" size_t cara_eval_report_bytes(int classes, int bins) {
+  if (classes < 1 || classes > CARA_EVAL_REPORT_MAX_CLASSES || bins < 1 || bins > CARA_EVAL_REPORT_MAX_BINS) return 0;
+  return ((size_t)classes * classes + 3 * (size_t)bins) * sizeof(unsigned long long);
+}
+
+extern "C" int cara_eval_accumulate_report(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
+                                           void* state, void* report, int bins, void* stream) {
+  if (!eval_args_ok(logits, ldl, labels, B, n_valid, classes, state)) return CARA_E_ARG;
+  if (cara_eval_report_bytes(classes, bins) == 0 || !report || (reinterpret_cast<uintptr_t>(report) & 7)) return CARA_E_ARG;
+  if (n_valid == 0) return CARA_OK;
+  hipLaunchKernelGGL(eval_accumulate_kernel<true>, dim3(eval_grid(n_valid)), dim3(EVAL_WAVES * 64), 0, static_cast<hipStream_t>(stream),
+                     logits, ldl, labels, n_valid, classes, static_cast<unsigned long long*>(state),
+                     static_cast<unsigned long long*>(report), bins);
   CARA_CHECK_LAUNCH();
   return CARA_OK;
 }

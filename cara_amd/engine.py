@@ -910,7 +910,8 @@ class CaraEngine:
                   "cara_vit_forward")
         return st["logits"]
 
-    def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None, weights=None) -> dict:
+    def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None, weights=None, report: bool = False,
+                 bins: int = 15) -> dict:
         """Top-1 / top-5 accuracy and mean cross-entropy of a whole split, on the device and sharded over the ranks of
         ``group``: ``test()`` of vit_cp.py:73-82 without its host read per batch.  -> ``dict(top1, top5, loss, n)``, the
         same on every rank; ``n`` is the number of images scored by all ranks together.
@@ -922,7 +923,13 @@ class CaraEngine:
         one SUM all-reduce of the state and one read-back.  Like the reference's ``test()`` it leaves the model in eval mode.
         ``debug_hook(logits, labels, n_valid)`` (tests) sees every batch's logits; they are overwritten by the next batch.
         ``weights`` (a ``ParamEma`` of ``make_ema``): the pass scores the averaged weights -- the same forward on the same workspace
-        is handed the shadow tensors as its CP and head pointers; nothing is copied and the model's parameters are not touched."""
+        is handed the shadow tensors as its CP and head pointers; nothing is copied and the model's parameters are not touched.
+        ``report = True``: every batch's launch is ``cara_eval_accumulate_report`` into one more zeroed device buffer, the confusion
+        matrix and ``bins`` equal-width confidence bins (include/cara_hip.h); state and report travel as ONE fp64 vector through the
+        same single all-reduce and host read.  The dict then also holds ``confusion`` (CPU int64 [C, C], row = label, column =
+        predicted class), ``support``, ``per_class`` (recall, NaN without support), ``precision`` (NaN for a class never
+        predicted), ``mean_per_class``, ``ece`` and ``calibration = {count, hits, confidence}`` (``evalcount.report_result``).
+        A head wider than ``CARA_EVAL_REPORT_MAX_CLASSES`` or a bin count the kernel refuses raises before the first forward."""
         from . import dist as cdist
         model = self._model()
         model.eval()
@@ -935,6 +942,14 @@ class CaraEngine:
         dev = model.head.weight.device
         if dev.type != "cuda":
             raise CaraError("cara_amd runs on the GPU only: move the model to a ROCm device (there is no CPU fallback)")
+        if report:
+            ncls = int(model.head.out_features)
+            if isinstance(bins, bool) or not isinstance(bins, int):
+                raise CaraError(f"evaluate: bins must be an integer, not {bins!r}")
+            report_bytes = int(self._lib().cara_eval_report_bytes(ncls, bins))
+            if report_bytes == 0:
+                raise CaraError(f"evaluate(report=True): {ncls} classes with {bins} bins is outside what cara_eval_accumulate_report "
+                                "takes (at most 4096 classes, 1 to 64 bins)")
         if hasattr(split_or_batches, "eval_shard"):
             batches = split_or_batches.eval_shard(batch_size, cdist.get_rank(group), cdist.world_size(group))
         else:
@@ -943,23 +958,40 @@ class CaraEngine:
         use = self._forward_weights(model, dev, weights)
         with torch.no_grad(), torch.cuda.device(dev):
             state = torch.zeros(int(lib.cara_eval_state_bytes()) // 8, dtype=torch.int64, device=dev)
+            rep = torch.zeros(report_bytes // 8, dtype=torch.int64, device=dev) if report else None
             for item in batches:
                 x, y = item[0], item[1]
                 n_valid = int(item[2]) if len(item) > 2 else y.shape[0]
                 if x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]:
                     raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
                 logits = self._eval_forward(model, x, dev, use)
-                check(lib.cara_eval_accumulate(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
-                                               logits.shape[1], ptr(state), stream(dev)), "cara_eval_accumulate")
+                if report:
+                    check(lib.cara_eval_accumulate_report(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
+                                                          logits.shape[1], ptr(state), ptr(rep), bins, stream(dev)),
+                          "cara_eval_accumulate_report")
+                else:
+                    check(lib.cara_eval_accumulate(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
+                                                   logits.shape[1], ptr(state), stream(dev)), "cara_eval_accumulate")
                 if debug_hook is not None:
                     debug_hook(logits, y, n_valid)
             # the five words as fp64 (counts are exact up to 2^53): ONE collective carries integers and the loss sum alike
             vec = state.to(torch.float64)
             vec[3] = state.view(torch.float64)[3]
-            cdist.allreduce_sum_(vec, group)
-            n, t1, t5, loss, bad = vec.tolist()   # the pass's only host read
+            if report:
+                # ... and the report's words behind them: the bin_conf region holds doubles, like the loss word
+                words = torch.cat([vec, rep.to(torch.float64)])
+                words[-bins:] = rep.view(torch.float64)[-bins:]
+                cdist.allreduce_sum_(words, group)
+                words = words.cpu()                # the pass's only host read
+                n, t1, t5, loss, bad = words[:5].tolist()
+            else:
+                cdist.allreduce_sum_(vec, group)
+                n, t1, t5, loss, bad = vec.tolist()   # the pass's only host read
         if bad:
             raise CaraError(f"evaluate: {int(bad)} label(s) outside [0, {model.head.out_features})")
+        if report:
+            from . import evalcount
+            return evalcount.report_result(words[:5], evalcount.report_from_vector(words[5:], ncls, bins))
         d = max(n, 1.0)
         return {"top1": t1 / d, "top5": t5 / d, "loss": loss / d, "n": int(n)}
 

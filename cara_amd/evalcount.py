@@ -52,3 +52,89 @@ def result(state) -> dict:
         raise ValueError(f"{int(bad)} label(s) outside [0, classes)")
     d = max(n, 1.0)
     return {"top1": t1 / d, "top5": t5 / d, "loss": loss / d, "n": int(n)}
+
+
+# ---- the evaluation report of ``cara_eval_accumulate_report``: confusion matrix and calibration bins ----------------------------
+# A report is four fp64 tensors, the kernel's regions in the kernel's order: ``confusion`` [classes, classes] (row = label, column =
+# predicted class), ``bin_count`` [bins], ``bin_hits`` [bins], ``bin_conf`` [bins].  ``pred`` = the lowest class index whose logit
+# equals the row maximum (the top-1 tie rule), ``conf`` = the top softmax probability, ``bin = min(bins - 1, floor(conf * bins))``.
+REPORT_KEYS = ("confusion", "bin_count", "bin_hits", "bin_conf")
+
+
+def report_words(classes: int, bins: int) -> int:
+    return int(classes) * int(classes) + 3 * int(bins)
+
+
+def new_report(classes: int, bins: int, device="cpu") -> dict:
+    if classes < 1 or bins < 1:
+        raise ValueError("a report needs at least one class and one bin")
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=device)   # noqa: E731
+    return {"confusion": z(classes, classes), "bin_count": z(bins), "bin_hits": z(bins), "bin_conf": z(bins)}
+
+
+def report_vector(report: dict) -> torch.Tensor:
+    """the report as one fp64 vector in the kernel's layout (what is all-reduced behind the five state words)"""
+    return torch.cat([report[k].reshape(-1).to(torch.float64) for k in REPORT_KEYS])
+
+
+def report_from_vector(vec, classes: int, bins: int) -> dict:
+    """``report_vector`` undone: views into ``vec`` (a tensor of ``report_words(classes, bins)`` fp64 words)"""
+    vec = torch.as_tensor(vec, dtype=torch.float64)
+    if vec.ndim != 1 or vec.shape[0] != report_words(classes, bins):
+        raise ValueError(f"a report of {classes} classes and {bins} bins holds {report_words(classes, bins)} words, not {tuple(vec.shape)}")
+    cc = classes * classes
+    return {"confusion": vec[:cc].view(classes, classes), "bin_count": vec[cc:cc + bins], "bin_hits": vec[cc + bins:cc + 2 * bins],
+            "bin_conf": vec[cc + 2 * bins:]}
+
+
+def accumulate_report(state: torch.Tensor, report: dict, logits: torch.Tensor, labels: torch.Tensor, n_valid: int = None):
+    """``accumulate`` into ``state`` and, for the same rows, the confusion cell and the confidence bin into ``report``
+    (``new_report(logits.shape[1], bins)``).  A row with a label outside ``[0, classes)`` touches nothing in ``report``.
+    Everything in fp64 from the fp32 logits: ``conf = exp(max - logsumexp)``.  -> (state, report)"""
+    accumulate(state, logits, labels, n_valid)
+    n_valid = logits.shape[0] if n_valid is None else int(n_valid)
+    classes, bins = logits.shape[1], report["bin_count"].shape[0]
+    if tuple(report["confusion"].shape) != (classes, classes):
+        raise ValueError(f"the report's confusion matrix is {tuple(report['confusion'].shape)}, the logits have {classes} classes")
+    l = logits[:n_valid].to(torch.float64)
+    y = labels[:n_valid].to(torch.int64)
+    ok = (y >= 0) & (y < classes)
+    l, y = l[ok], y[ok]
+    if l.shape[0] == 0:
+        return state, report
+    top = l.max(dim=1).values
+    cols = torch.arange(classes, device=l.device).view(1, -1).expand_as(l)
+    pred = torch.where(l == top.view(-1, 1), cols, torch.full_like(cols, classes)).min(dim=1).values   # lowest index on ties
+    conf = torch.exp(top - torch.logsumexp(l, dim=1))
+    which = torch.clamp(torch.floor(conf * bins).to(torch.int64), max=bins - 1)
+    ones = torch.ones_like(conf)
+    report["confusion"].view(-1).index_add_(0, y * classes + pred, ones)
+    report["bin_count"].index_add_(0, which, ones)
+    report["bin_hits"].index_add_(0, which, (pred == y).to(torch.float64))
+    report["bin_conf"].index_add_(0, which, conf)
+    return state, report
+
+
+def report_result(state, report: dict) -> dict:
+    """``result(state)`` plus what the report holds, the form ``CaraEngine.evaluate(report=True)`` returns (CPU tensors):
+    ``confusion`` int64 [C, C]; ``support`` int64 [C], the row sums; ``per_class`` fp64 [C], the recall ``diag / support`` (NaN
+    without support); ``precision`` fp64 [C], the diagonal over the column sums (NaN for a class never predicted);
+    ``mean_per_class``, the mean of ``per_class`` over the classes with support; ``ece = sum_b n_b / n |hits_b / n_b - conf_b / n_b|``
+    over the non-empty bins; ``calibration = {"count", "hits", "confidence"}``, each of length ``bins``, as accumulated."""
+    out = result(state)
+    confusion = report["confusion"].detach().cpu().round().to(torch.int64)
+    count = report["bin_count"].detach().cpu().round().to(torch.int64)
+    hits = report["bin_hits"].detach().cpu().round().to(torch.int64)
+    conf = report["bin_conf"].detach().cpu().to(torch.float64).clone()
+    support, predicted, diag = confusion.sum(1), confusion.sum(0), confusion.diagonal().to(torch.float64)
+    nan = torch.full_like(diag, float("nan"))
+    per_class = torch.where(support > 0, diag / support.clamp(min=1), nan)
+    precision = torch.where(predicted > 0, diag / predicted.clamp(min=1), nan)
+    seen, filled = support > 0, count > 0
+    gap = ((hits[filled].to(torch.float64) - conf[filled]) / count[filled]).abs()
+    ece = float((count[filled].to(torch.float64) / max(out["n"], 1) * gap).sum())
+    out.update(confusion=confusion, support=support, per_class=per_class, precision=precision,
+               mean_per_class=float(per_class[seen].mean()) if bool(seen.any()) else float("nan"), ece=ece,
+               calibration={"count": count, "hits": hits, "confidence": conf})
+    return out
+

@@ -218,7 +218,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         epochs: int = 100, lr: float = 1e-3, weight_decay: float = 1e-4, group=None, reference_eval_quirk: bool = True,
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
-        accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None):
+        accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
+        eval_metric: str = "top1"):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -265,7 +266,15 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     drawn ``KEEP_AHEAD`` steps at a time (the feed does not say how many batches an epoch has), checked (``data.check_keep``) and
     uploaded once per draw; each step gets a [batch, K] view (``train_step(..., keep=)``).  Every micro-batch of an accumulation
     window has its own rows, every rank its own stream, and the graphed step takes the table as a static input.  The evaluation
-    epochs see every patch.  The resident feed carries its table itself: ``train_rows(..., patch_drop=)``."""
+    epochs see every patch.  The resident feed carries its table itself: ``train_rows(..., patch_drop=)``.
+    ``eval_metric = "mean_per_class"`` (``eval_mode = "sharded"`` only): the evaluation epochs call
+    ``CaraEngine.evaluate(report=True)`` and the mean per-class accuracy (the mean recall over the classes the split holds) is the
+    number that is compared, returned, passed to ``on_eval`` and named in the ``save_best`` file -- with ``ema_decay`` for the raw
+    and the averaged pass alike.  ``"top1"`` (default): the top-1 accuracy, with the calls that were always made."""
+    if eval_metric not in ("top1", "mean_per_class"):
+        raise CaraError(f"eval_metric must be 'top1' or 'mean_per_class', not {eval_metric!r}")
+    if eval_metric == "mean_per_class" and eval_mode != "sharded":
+        raise CaraError("fit: eval_metric = 'mean_per_class' is computed by CaraEngine.evaluate(report=True): it needs eval_mode = 'sharded'")
     if patch_drop is not None and feed != "batches":
         raise CaraError("fit: patch_drop is the 'batches' feed's; the resident feed carries its table itself (train_rows(..., patch_drop=))")
     if patch_drop is not None and not callable(getattr(patch_drop, "draw", None)):
@@ -302,6 +311,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         smooth["ema"] = ema
     gstep = GraphedTrainStep(eng, opt, **smooth) if graph else None
     best = 0.0
+    scored = {"report": True} if eval_metric == "mean_per_class" else {}
     if feed == "resident":
         split, rows_of = train_batches
         train_batches = lambda epoch: ((split, rows) for rows in rows_of(epoch))   # noqa: E731
@@ -367,13 +377,13 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
             check_rows(epoch)
             if test_batches is not None:
                 if eval_mode == "sharded":
-                    acc = eng.evaluate(test_batches, group=group)["top1"]
+                    acc = eng.evaluate(test_batches, group=group, **scored)[eval_metric]
                 else:
                     acc = evaluate(model, test_batches())
                 raw = acc
                 if ema is not None:
                     if eval_mode == "sharded":
-                        acc = eng.evaluate(test_batches, group=group, weights=ema)["top1"]
+                        acc = eng.evaluate(test_batches, group=group, weights=ema, **scored)[eval_metric]
                     else:
                         with ema.swapped_in():
                             acc = evaluate(model, test_batches())

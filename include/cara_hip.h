@@ -460,6 +460,24 @@ int cara_cross_entropy_mix(const float* logits, const int64_t* labels, const int
 size_t cara_eval_state_bytes(void);
 int cara_eval_accumulate(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
                          void* state, void* stream);
+/* The same launch with an evaluation report: beside `state` (unchanged meaning, the same words) every scored row adds into
+ * `report`, device memory of 8-byte words (cara_eval_report_bytes(classes, bins) bytes, 8-byte aligned, zeroed by the
+ * caller before the first batch, accumulated across launches):
+ *   confusion int64 [classes][classes]  row = label, column = predicted class
+ *   bin_count int64 [bins]   bin_hits int64 [bins]   bin_conf double [bins]
+ * pred = the lowest class index whose logit equals the row maximum (the top-1 tie rule above: pred == label exactly when
+ * the row is a top-1 hit); conf = 1 / sum_c exp(l[c] - max), the top softmax probability, in fp32 from the sum the loss
+ * uses; bin = min(bins - 1, (int)(conf * bins)) in fp32.  The row adds 1 to confusion[label][pred] and to bin_count[bin],
+ * (pred == label) to bin_hits[bin] and conf to bin_conf[bin] (an fp64 sum whose order is not fixed).  A row whose label
+ * lies outside [0, classes) raises word 4 of `state` and touches nothing in `report`.  A row without a finite maximum
+ * (a NaN, or no logit above -3e38) is counted in column 0 / bin 0: every index stays inside the buffer.
+ * CARA_E_ARG with nothing launched: classes > CARA_EVAL_REPORT_MAX_CLASSES, bins outside [1, CARA_EVAL_REPORT_MAX_BINS],
+ * report NULL or not 8-byte aligned, and everything the plain entry refuses.  The byte count is 0 for a refused pair.   */
+#define CARA_EVAL_REPORT_MAX_CLASSES 4096
+#define CARA_EVAL_REPORT_MAX_BINS 64
+size_t cara_eval_report_bytes(int classes, int bins);
+int cara_eval_accumulate_report(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
+                                void* state, void* report, int bins, void* stream);
 /* bf16 <-> fp32 helpers (weight ingest)                                                        */
 int cara_f32_to_bf16(const float* src, void* dst, size_t n, void* stream);
 int cara_transpose_bf16(const void* src, void* dst, int rows, int cols, void* stream);

@@ -7,7 +7,9 @@
       kernel after every batch, one host read per pass;
 
 and print seconds per pass (median, min, max over --passes after one warm-up each), images/s and the workspace bytes of
-both.  Standalone: not part of bench.py.  --only a|b runs one leg (the leg (a) of an older build: CARA_LIB_PATH)."""
+both.  Standalone: not part of bench.py.  --only a|b runs one leg (the leg (a) of an older build: CARA_LIB_PATH).
+--report (with --only none to skip the legs above) times (b) against engine.evaluate(split, B, report=True): the same pass with
+cara_eval_accumulate_report instead of cara_eval_accumulate after every batch (docs/findings/eval_report.md)."""
 import argparse
 import ctypes as C
 import json
@@ -29,7 +31,10 @@ def main():
     ap.add_argument("--rank", type=int, default=16)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"])
-    ap.add_argument("--only", default="ab", choices=["a", "b", "ab"])
+    ap.add_argument("--only", default="ab", choices=["a", "b", "ab", "none"])
+    ap.add_argument("--report", action="store_true", help="time engine.evaluate with and without report=True, alternating")
+    ap.add_argument("--bins", type=int, default=15)
+    ap.add_argument("--rounds", type=int, default=2, help="--report: alternations of (plain passes, report passes)")
     args = ap.parse_args()
     from cara_amd import cara, create_model, recipe
     from cara_amd.data import ResidentSplit
@@ -76,7 +81,47 @@ def main():
         ts = timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch)))
         report("engine_evaluate", ts, eng.eval_workspace_bytes(), out[0]["top1"])
         res["engine_evaluate"].update(top5=out[0]["top5"], loss=out[0]["loss"], n=out[0]["n"])
+    if args.report:
+        # the plain pass and the report pass in turn, --rounds times, on the same box in one run: their ratio is the report's cost
+        plain, rep, out = [], [], [None]
+        for _ in range(args.rounds):
+            plain += timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch)))
+            rep += timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch, report=True, bins=args.bins)))
+        report("plain_pass", plain, eng.eval_workspace_bytes(), out[0]["top1"])
+        report("report_pass", rep, eng.eval_workspace_bytes(), out[0]["top1"])
+        res["report_pass"].update(bins=args.bins, mean_per_class=out[0]["mean_per_class"], ece=out[0]["ece"],
+                                  report_bytes=8 * (args.classes ** 2 + 3 * args.bins))
+        res["report_over_plain"] = round(res["report_pass"]["median_s"] / res["plain_pass"]["median_s"], 4)
+        res["counting_launch_us"] = _launch_us(eng, args, dev)
     print(json.dumps(res))
+
+
+def _launch_us(eng, args, dev, launches=200):
+    """device time of one counting launch on a [batch, classes] logit table, plain and with the report (events around `launches`
+    back-to-back launches, best of five after a warm-up)"""
+    from cara_amd._lib import check, ptr, stream
+    lib = eng._lib()
+    lg = torch.randn(args.batch, args.classes, device=dev) * 3.0
+    y = torch.randint(0, args.classes, (args.batch,), device=dev)
+    st = torch.zeros(5, dtype=torch.int64, device=dev)
+    rep = torch.zeros(args.classes ** 2 + 3 * args.bins, dtype=torch.int64, device=dev)
+    calls = {"plain": lambda: lib.cara_eval_accumulate(ptr(lg), args.classes, ptr(y), args.batch, args.batch, args.classes, ptr(st),
+                                                       stream(dev)),
+             "report": lambda: lib.cara_eval_accumulate_report(ptr(lg), args.classes, ptr(y), args.batch, args.batch, args.classes,
+                                                               ptr(st), ptr(rep), args.bins, stream(dev))}
+    out = {}
+    for name, call in calls.items():
+        best = float("inf")
+        for _ in range(6):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(launches):
+                check(call(), name)
+            t1.record()
+            torch.cuda.synchronize(dev)
+            best = min(best, t0.elapsed_time(t1) * 1e3 / launches)
+        out[name] = round(best, 3)
+    return out
 
 
 def _shape(eng, m, B):
