@@ -421,6 +421,61 @@ __global__ __launch_bounds__(64) void xent_mix_kernel(const float* __restrict__ 
     loss_per[b] = ok ? (lse - dot) * invB : qnan;
   }
 }
+// xent_mix_kernel with a weight per class and a bias on the logits (cw, cb fp32 [C]; NULL: all ones / all zeros):  z_c = l_c + cb_c
+// (the softmax, lse and p are of z),  W_b = sum_c cw_c q_c,  term_b = (W_b lse_b - sum_c cw_c q_c z_c) / B,  dlogits = (p_c W_b - cw_c q_c)
+// gsc: torch's cross_entropy(l + cb, q, weight=cw, reduction="sum") / B.  With q of xent_mix_kernel,  W_b = wa cw_ya + wb cw_yb + (eps / C)
+// sum_c cw_c  and  sum_c cw_c q_c z_c = wa cw_ya z_ya + wb cw_yb z_yb + (eps / C) sum_c cw_c z_c: two more wave reductions, gathered in the
+// pass that finds the maximum, and the two gathers of xent_mix_kernel; the eps / C terms are added only where they are not zero.
+// Guards as there; a guarded sample gathers class 0 of cw and cb, never a class its labels name.  The values of cw and cb are not
+// looked at: the caller keeps cw finite and >= 0 and cb finite.
+__global__ __launch_bounds__(64) void xent_bal_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                      const int* __restrict__ mix, float eps, const float* __restrict__ cw,
+                                                      const float* __restrict__ cb, float* __restrict__ loss_per,
+                                                      float* __restrict__ dlogits, int B, int C, float dscale,
+                                                      const float* __restrict__ loss_scale) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* lr = logits + (size_t)b * C;
+  float m = -3.0e38f, sw = 0.f, swz = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float z = cb ? lr[c] + cb[c] : lr[c], w = cw ? cw[c] : 1.f;
+    m = fmaxf(m, z);
+    sw += w;
+    swz += w * z;
+  }
+  m = wave_max(m);
+  sw = wave_sum(sw);
+  swz = wave_sum(swz);
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += __expf((cb ? lr[c] + cb[c] : lr[c]) - m);
+  s = wave_sum(s);
+  const float lse = m + __logf(s);
+  const int partner = mix ? mix[(size_t)b * 8] : b;
+  const float t = mix ? __int_as_float(mix[(size_t)b * 8 + 6]) : 0.f;
+  const int64_t yal = labels[b];
+  const bool pok = partner >= 0 && partner < B;
+  const int64_t ybl = pok ? labels[partner] : -1;
+  const bool ok = yal >= 0 && yal < C && ybl >= 0 && ybl < C && t >= 0.f && t <= 1.f;   // (wave-uniform)
+  const int ya = ok ? (int)yal : 0, yb = ok ? (int)ybl : 0;
+  const float wa = (1.f - eps) * (1.f - t), wb = (1.f - eps) * t, u = eps / (float)C;
+  const float ga = cw ? cw[ya] : 1.f, gb = cw ? cw[yb] : 1.f;
+  float W = wa * ga + wb * gb;
+  if (u != 0.f) W += u * sw;
+  const float qnan = __builtin_nanf("");
+  const float invB = 1.0f / B;
+  const float gsc = invB * dscale * (loss_scale ? *loss_scale : 1.f);   // (xent_kernel's)
+  if (dlogits)
+    for (int c = lane; c < C; c += 64) {
+      const float z = cb ? lr[c] + cb[c] : lr[c], w = cw ? cw[c] : 1.f;
+      const float q = (c == ya ? wa : 0.f) + (c == yb ? wb : 0.f) + u;
+      dlogits[(size_t)b * C + c] = ok ? (__expf(z - lse) * W - w * q) * gsc : qnan;
+    }
+  if (lane == 0) {
+    const float za = cb ? lr[ya] + cb[ya] : lr[ya], zb = cb ? lr[yb] + cb[yb] : lr[yb];
+    float dot = wa * (ga * za) + wb * (gb * zb);
+    if (u != 0.f) dot += u * swz;
+    loss_per[b] = ok ? (W * lse - dot) * invB : qnan;
+  }
+}
 __global__ __launch_bounds__(64) void xent_sum_kernel(const float* __restrict__ loss_per, float* __restrict__ loss, int B,
                                                       float* __restrict__ found_inf) {
   float s = 0.f;
@@ -675,6 +730,21 @@ extern "C" int cara_cross_entropy_mix(const float* logits, const int64_t* labels
   if (!logits || !labels || !loss || B <= 0 || C <= 0 || !(dscale > 0.f) || !(smoothing >= 0.f && smoothing < 1.f)) return CARA_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(xent_mix_kernel, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, loss + 1, dlogits, B, C, dscale, loss_scale);
+  CARA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+extern "C" int cara_cross_entropy_bal(const float* logits, const int64_t* labels, const int* mix, float smoothing,
+                                      const float* class_weight, const float* logit_bias, float* loss, float* dlogits, int B, int C,
+                                      float dscale, const float* loss_scale, float* found_inf, void* stream) {
+  // (without a weight and a bias this IS cara_cross_entropy_mix: the same launches, bit for bit)
+  if (!class_weight && !logit_bias)
+    return cara_cross_entropy_mix(logits, labels, mix, smoothing, loss, dlogits, B, C, dscale, loss_scale, found_inf, stream);
+  if (!logits || !labels || !loss || B <= 0 || C <= 0 || !(dscale > 0.f) || !(smoothing >= 0.f && smoothing < 1.f)) return CARA_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(xent_bal_kernel, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, class_weight, logit_bias, loss + 1,
+                     dlogits, B, C, dscale, loss_scale);
   CARA_CHECK_LAUNCH();
   hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
   CARA_CHECK_LAUNCH();

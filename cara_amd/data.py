@@ -302,6 +302,49 @@ def soft_target(labels: torch.Tensor, mix, classes: int, smoothing: float = 0.0)
     return (1.0 - smoothing) * ((1.0 - t) * eye[y] + t * eye[y[partner]]) + smoothing / classes
 
 
+def class_counts(split_or_labels, classes: int) -> torch.Tensor:
+    """Images per class, int64 [classes] on the host, of a ``ResidentSplit`` (its ``labels`` are read once) or a label tensor: what
+    ``balanced_class_weight`` and ``logit_prior`` are made from.  A label outside [0, classes) raises ``ValueError``."""
+    labels = getattr(split_or_labels, "labels", split_or_labels)
+    y = torch.as_tensor(labels).detach().cpu().reshape(-1).long()
+    if not isinstance(classes, int) or isinstance(classes, bool) or classes < 1:
+        raise ValueError(f"class_counts: classes must be an integer >= 1, not {classes!r}")
+    if y.numel() and (int(y.min()) < 0 or int(y.max()) >= classes):
+        raise ValueError(f"class_counts: labels span [{int(y.min())}, {int(y.max())}], outside [0, {classes})")
+    return torch.bincount(y, minlength=classes)
+
+
+def _counts64(counts, who: str) -> torch.Tensor:
+    n = torch.as_tensor(counts).detach().cpu().reshape(-1).double()
+    if n.numel() == 0 or not bool(torch.isfinite(n).all()) or bool((n < 0).any()) or not float(n.sum()) > 0:
+        raise ValueError(f"{who}: counts must be non-negative with a positive total")
+    return n
+
+
+def balanced_class_weight(counts, power: float = 1.0, dtype=torch.float32) -> torch.Tensor:
+    """Class weights for ``train_step(class_weight=)``, fp32 [classes]: ``w_c`` proportional to ``max(n_c, 1) ** -power`` and scaled
+    so that ``sum_c n_c w_c == sum_c n_c`` -- the mean weight over the training samples is 1, so the loss (a sum over the batch
+    divided by the batch size) keeps its scale.  ``power = 1`` is inverse frequency, ``0.5`` the usual softened form, ``0`` all
+    ones.  An absent class gets the weight of a class with one image.  Computed in float64 and rounded once to ``dtype`` (fp32 is
+    what the step takes: the identity then holds to that rounding, 2^-24 of the total).  Negative counts or a total that is not
+    positive raise ``ValueError``."""
+    n = _counts64(counts, "balanced_class_weight")
+    if isinstance(power, bool) or not isinstance(power, (int, float)) or not power >= 0.0 or power == float("inf"):
+        raise ValueError(f"balanced_class_weight: power must be a finite number >= 0, not {power!r}")
+    raw = n.clamp_min(1.0) ** -float(power)
+    return (raw * (n.sum() / (n * raw).sum())).to(dtype)
+
+
+def logit_prior(counts, tau: float = 1.0) -> torch.Tensor:
+    """The bias of logit-adjusted training (Menon et al., 2021) for ``train_step(logit_bias=)``, fp32 [classes]:
+    ``tau * log((n_c + 1) / (N + classes))`` -- the add-one smoothing keeps the bias of an absent class finite.  Negative counts
+    or a total that is not positive raise ``ValueError``."""
+    n = _counts64(counts, "logit_prior")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not abs(tau) < float("inf"):
+        raise ValueError(f"logit_prior: tau must be a finite number, not {tau!r}")
+    return (float(tau) * torch.log((n + 1.0) / (n.sum() + n.numel()))).float()
+
+
 def aug_seed(seed: int, epoch: int, rank: int) -> int:
     """``box_seed`` of the stream that draws the colour-jitter / erase tables (a third constant)"""
     return box_seed(seed, epoch, rank, stream=0x2545F491)

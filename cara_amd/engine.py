@@ -638,7 +638,8 @@ class CaraEngine:
             return self._clip_flat(max_norm)
 
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
-                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, keep=None):
+                   label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, keep=None, class_weight=None,
+                   logit_bias=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -660,7 +661,14 @@ class CaraEngine:
         window, at its last micro-step only.  A step skipped for an fp16 overflow updates the average too (cara_amd/ema.py).
         ``keep`` (device int32 [batch, K], e.g. one step of ``data.PatchDropout.draw``): patch dropout -- sample ``i`` trains on
         its cls token and the K patch tokens ``keep[i]``, each with its own row of the position embedding
-        (``cara_vit_forward_keep``); the blocks run on 1 + K tokens.  None runs the step it was."""
+        (``cara_vit_forward_keep``); the blocks run on 1 + K tokens.  None runs the step it was.
+        ``class_weight`` / ``logit_bias`` (fp32 [classes] on the images' device, e.g. ``data.balanced_class_weight`` and
+        ``data.logit_prior``): the loss is ``torch.nn.functional.cross_entropy(logits + logit_bias, q, weight=class_weight,
+        reduction="sum") / batch`` on the step's soft target ``q`` (``cara_cross_entropy_bal``) -- divided by the batch size, not by
+        the batch's weight mass, so windows, ranks and the all-reduce work as before.  The bias enters the loss only (logit-adjusted
+        training): the model's logits and ``evaluate`` are untouched.  A negative or non-finite weight and a non-finite bias are
+        refused; the values are read on the host once per tensor and version (an in-place change is checked again at the next
+        step).  Both None: the loss launches are the ones they were."""
         eps = self._smoothing(label_smoothing)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
@@ -670,13 +678,33 @@ class CaraEngine:
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp, keep=keep),
-                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema)
+                          lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema,
+                          class_weight, logit_bias)
+
+    def _class_vectors(self, class_weight, logit_bias, ncls, dev):
+        """``class_weight`` / ``logit_bias`` of a step, refused here -- before anything is launched -- unless each is None or a
+        contiguous fp32 [ncls] tensor on ``dev`` with finite values (weights >= 0 as well).  The values cost a host read: one per
+        tensor, remembered by (address, version), so a steady step reads nothing."""
+        seen = self.__dict__.setdefault("_class_vec_ok", {})
+        for name, t, floor in (("class_weight", class_weight, True), ("logit_bias", logit_bias, False)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.ndim != 1 or t.shape[0] != ncls or t.device != dev \
+                    or not t.is_contiguous():
+                raise CaraError(f"{name} must be a contiguous fp32 [{ncls}] tensor -- one entry per class of the head -- on the model's device")
+            key = (t.data_ptr(), t._version)
+            if seen.get(name) != key:
+                bad = ~torch.isfinite(t) | (t < 0) if floor else ~torch.isfinite(t)
+                if bool(bad.any()):
+                    raise CaraError(f"{name} must be finite{' and >= 0' if floor else ''} in every class")
+                seen[name] = key
 
     def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None,
-              ema=None):
+              ema=None, class_weight=None, logit_bias=None):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
-        (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one.
+        (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one, with a
+        ``class_weight`` or a ``logit_bias`` the weighted, logit-adjusted one on that target.
         ``accumulate``, ``clip_grad`` and ``ema`` as in ``train_step``."""
         model = self._model()
         self._check_ema(ema, dev, "ema")
@@ -691,6 +719,7 @@ class CaraEngine:
         if hw.device != dev or any(t.device != dev for t in cp):
             raise CaraError("model parameters and images must be on the same device")
         self._refuse_fp16_unfactored()
+        self._class_vectors(class_weight, logit_bias, hw.shape[0], dev)
         self._enter_window(win_i, win_k, B)
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
@@ -711,7 +740,11 @@ class CaraEngine:
             gv = self._grad_buffers(model, dev)
             tail = (B, ncls, C.c_float(1.0 / (world_size(group) * win_k)), ptr(self._amp(dev)) if fp16 else None,
                     ptr(gv["_found_inf"]) if fp16 else None, stream(dev))
-            if mix is None and smoothing == 0.0:
+            if class_weight is not None or logit_bias is not None:
+                check(self._lib().cara_cross_entropy_bal(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(class_weight),
+                                                         ptr(logit_bias), ptr(self._loss_buf), ptr(self._dlogits), *tail),
+                      "cara_cross_entropy_bal")
+            elif mix is None and smoothing == 0.0:
                 check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(self._loss_buf), ptr(self._dlogits), *tail),
                       "cara_cross_entropy_ex")
             else:
@@ -805,7 +838,8 @@ class CaraEngine:
         return buf
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
-                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None, ra=None):
+                            mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None, ra=None,
+                            class_weight=None, logit_bias=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -831,12 +865,14 @@ class CaraEngine:
         its 2x3 affine with a fill colour and passes its lookup slots (posterize, solarize, solarize-add, invert, autocontrast,
         equalize) before the jitter chain, the mix and the rest (``cara_vit_forward_u8_rows_ra``; with or without the other tables).
         A table entry the kernel refuses -- ``data.check_ra`` -- gives a zero image, counted like a bad row.
+        ``class_weight`` / ``logit_bias`` as in ``train_step``: on the soft target of both labels where there is a ``mix`` table.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
         feed = Feed(rows, boxes, mix, aug, keep, ra)
         model, dev = self._resident_args(split, feed)
         return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._run_forward_on(model, split, feed, dp, hw, hb, cp, True, dev),
-                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema)
+                          lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema,
+                          class_weight, logit_bias)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
                          keep=None, ra=None):

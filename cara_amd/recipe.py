@@ -129,9 +129,12 @@ class GraphedTrainStep:
     of ``keep`` captures another graph.  ``label_smoothing`` and ``clip_grad`` are the steps' (the two launches of ``cara_grad_clip``
     are captured with the step).  An accumulation window (``accumulate`` with k > 1) spans several replays and is refused.
     ``ema`` (``CaraEngine.make_ema(..., capturable=True)``): the average's launch is captured behind the optimiser's; its weight
-    lives in device memory and ``ema.advance()`` runs before every step, as ``optimizer.advance()`` does."""
+    lives in device memory and ``ema.advance()`` runs before every step, as ``optimizer.advance()`` does.
+    ``class_weight`` / ``logit_bias`` (``train_step``'s): the graph captures the two tensors' addresses, so they are held here and in
+    every entry and their identity is part of the key; a replay re-reads their contents, as it re-reads a mix table -- an in-place
+    change takes effect at the next call (and is checked there, on the host, before the replay)."""
 
-    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None):
+    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None, class_weight=None, logit_bias=None):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
         if ema is not None and not getattr(ema, "capturable", False):
@@ -139,6 +142,7 @@ class GraphedTrainStep:
         self.eng, self.opt, self.ema = engine, optimizer, ema
         self.label_smoothing = engine._smoothing(label_smoothing) if label_smoothing else 0.0
         self.clip_grad = engine._max_norm(clip_grad)
+        self.class_weight, self.logit_bias = class_weight, logit_bias
         self._graphs = {}   # key -> "warm", then (graph, source, static inputs, loss, held): source is the split, None for images
 
     def _kw(self):
@@ -148,6 +152,10 @@ class GraphedTrainStep:
             kw["clip_grad"] = self.clip_grad
         if self.ema is not None:
             kw["ema"] = self.ema
+        if self.class_weight is not None:
+            kw["class_weight"] = self.class_weight
+        if self.logit_bias is not None:
+            kw["logit_bias"] = self.logit_bias
         return kw
 
     def __call__(self, x, y, group=None, accumulate=None, keep=None):
@@ -157,6 +165,11 @@ class GraphedTrainStep:
         if self.eng._window(accumulate)[1] > 1:
             raise CaraError("GraphedTrainStep: accumulate with k > 1 is not supported (the window spans several graph replays)")
         eng, kw = self.eng, self._kw()
+        if self.class_weight is not None or self.logit_bias is not None:
+            head = eng._model().head
+            if not hasattr(head, "weight"):
+                raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+            eng._class_vectors(self.class_weight, self.logit_bias, head.weight.shape[0], head.weight.device)
         if hasattr(x, "pixels"):
             feed = Feed.of(y)
             if feed.keep is None and keep is not None:
@@ -185,6 +198,8 @@ class GraphedTrainStep:
         if cdist.world_size(group) > 1 or (eng.weight_dropout == "exact" and model.training):
             return step(live)
         key = (*key, tuple(tuple(t.shape) for t in live), bool(model.training), eng.precision, self.label_smoothing, self.clip_grad)
+        if self.class_weight is not None or self.logit_bias is not None:
+            key = (*key, id(self.class_weight), id(self.logit_bias))
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -205,7 +220,7 @@ class GraphedTrainStep:
             torch.cuda.current_stream(dev).wait_stream(side)
             # (the last element keeps what the engine would replace at an eager step of another batch size in between -- its dlogits
             # buffer and the workspace of this shape -- as ``loss`` keeps its loss buffer: the graph holds their addresses)
-            ent = self._graphs[key] = (gr, key[1], static, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"]))
+            ent = self._graphs[key] = (gr, key[1], static, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"], self.class_weight, self.logit_bias))
             # (the capture itself ran nothing: fall through to the replay, which is this call's step)
         gr, _, static, loss = ent[:4]
         for s, t in zip(static, live):
@@ -219,7 +234,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
         accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
-        eval_metric: str = "top1"):
+        eval_metric: str = "top1", class_weight=None, logit_bias=None):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -270,7 +285,11 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``eval_metric = "mean_per_class"`` (``eval_mode = "sharded"`` only): the evaluation epochs call
     ``CaraEngine.evaluate(report=True)`` and the mean per-class accuracy (the mean recall over the classes the split holds) is the
     number that is compared, returned, passed to ``on_eval`` and named in the ``save_best`` file -- with ``ema_decay`` for the raw
-    and the averaged pass alike.  ``"top1"`` (default): the top-1 accuracy, with the calls that were always made."""
+    and the averaged pass alike.  ``"top1"`` (default): the top-1 accuracy, with the calls that were always made.
+    ``class_weight`` / ``logit_bias`` (fp32 [classes], host or device, e.g. ``data.balanced_class_weight`` / ``data.logit_prior`` of
+    ``data.class_counts(split, classes)``): moved to the model's device once, and every training step of either feed, eager or
+    graphed, runs the weighted, logit-adjusted loss (``train_step(..., class_weight=, logit_bias=)``).  The evaluation epochs are
+    unchanged: they score the raw logits."""
     if eval_metric not in ("top1", "mean_per_class"):
         raise CaraError(f"eval_metric must be 'top1' or 'mean_per_class', not {eval_metric!r}")
     if eval_metric == "mean_per_class" and eval_mode != "sharded":
@@ -292,6 +311,17 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     smooth = {"label_smoothing": eng._smoothing(label_smoothing)} if label_smoothing else {}
     if clip_grad is not None:
         smooth["clip_grad"] = eng._max_norm(clip_grad)
+    if class_weight is not None or logit_bias is not None:
+        if not hasattr(model.head, "weight"):
+            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+        hdev = model.head.weight.device
+        for name, t in (("class_weight", class_weight), ("logit_bias", logit_bias)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t):
+                raise CaraError(f"fit: {name} must be an fp32 [classes] tensor, not {type(t).__name__}")
+            smooth[name] = t.detach().to(hdev).contiguous()
+        eng._class_vectors(smooth.get("class_weight"), smooth.get("logit_bias"), model.head.weight.shape[0], hdev)
     model.train()
     params = trainable_parameters(model)
     if cdist.world_size(group) > 1:

@@ -448,6 +448,20 @@ int cara_cross_entropy_ex(const float* logits, const int64_t* labels, float* los
  * loss[0] are NaN, the other samples unaffected.  smoothing outside [0, 1): CARA_E_ARG, nothing launched.  found_inf is cleared. */
 int cara_cross_entropy_mix(const float* logits, const int64_t* labels, const int* mix, float smoothing, float* loss,
                            float* dlogits, int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream);
+/* cara_cross_entropy_mix with a weight per class and a bias on the logits: class_weight, logit_bias = device fp32 [C], either may
+ * be NULL (all ones / all zeros).  With q, ya, yb and t of cara_cross_entropy_mix, all in fp32:
+ *   z_c = logits[b][c] + logit_bias[c] (softmax, lse and p are of z),  W_b = sum_c class_weight[c] q_c,
+ *   loss[1 + b] = (W_b lse_b - sum_c class_weight[c] q_c z_c) / B,  loss[0] = their sum (unscaled),
+ *   dlogits[b][c] = (p_c W_b - class_weight[c] q_c) / B * dscale * loss scale
+ * -- torch's cross_entropy(logits + bias, q, weight = class_weight, reduction = "sum") / B.  The divisor is B, not the weight mass
+ * of the batch: the loss stays linear in the samples, so dscale and a SUM all-reduce mean what they mean above (weights whose mean
+ * over the training samples is 1 keep the loss scale).  The bias enters the loss only (logit-adjusted training): logits is not
+ * written.  Both vectors NULL: the launches of cara_cross_entropy_mix, bit for bit.  The guards, the NaNs and the refusals are
+ * cara_cross_entropy_mix's; a refused sample reads no class of either vector that its labels name.  The VALUES of the two vectors are
+ * not looked at: the caller keeps class_weight finite and >= 0 and logit_bias finite.  found_inf is cleared.                     */
+int cara_cross_entropy_bal(const float* logits, const int64_t* labels, const int* mix, float smoothing, const float* class_weight,
+                           const float* logit_bias, float* loss, float* dlogits, int B, int C, float dscale,
+                           const float* loss_scale, float* found_inf, void* stream);
 /* Scoring on the device (test() of vit_cp.py:73-82 without its per-batch host read): for the first n_valid <= B rows of
  * logits fp32 [B,classes] (row stride ldl floats) and labels int64 [B], ADD into `state`, five 64-bit words
  * (cara_eval_state_bytes() = 40 bytes, 8-byte aligned, zeroed by the caller before the first batch):
