@@ -167,7 +167,105 @@ int eval_grid(int n_valid) {
   return grid > 256 ? 256 : grid;
 }
 
+// ---- cara_eval_combine_views: the V views' logits of a sample -> one row that the two kernels above score unchanged ----------
+// One wave per sample.  Pass 1 walks the V rows (V <= 16) as the accumulate kernel walks one: row maximum, then lse_v = m_v +
+// logf(sum expf(l - m_v)); lane v keeps lse_v and pass 2 reads it with v_readlane (v is wave-uniform; the read does not depend on
+// which lanes are active) -- no LDS, no barrier: the waves of a workgroup run different trip counts.  Pass 2 is over the classes:
+// per class the V values are read twice (L1 / L2: a sample is at most 64 KB at 1000 classes), once for M = max_v a_v and once for
+// the sum of expf(a_v - M) in view order.  16-byte loads when every row of the sample is 16-byte aligned, the output row stored
+// 16 bytes at a time when it is too.
+__device__ __forceinline__ float lane_value(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
+
+template <int MODE>
+__device__ __forceinline__ float combine_one(const float* __restrict__ col, int ldl, int V, float my_lse, float logV, float fV) {
+  if constexpr (MODE == CARA_EVAL_COMBINE_LOGIT) {
+    float acc = col[0];
+    for (int v = 1; v < V; ++v) acc += col[(size_t)v * ldl];
+    return acc / fV;
+  } else {
+    float M = -INFINITY;
+    for (int v = 0; v < V; ++v) M = fmaxf(M, col[(size_t)v * ldl] - lane_value(my_lse, v));
+    float t = 0.f;
+    for (int v = 0; v < V; ++v) t += expf((col[(size_t)v * ldl] - lane_value(my_lse, v)) - M);
+    // M = -inf: the class has probability zero in every view (t is NaN there: -inf - -inf)
+    return M == -INFINITY ? M : (M + logf(t)) - logV;
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(EVAL_WAVES * 64) void eval_combine_kernel(const float* __restrict__ logits, int ldl, int S, int V, int C,
+                                                                       float* __restrict__ out, int ldo) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float fV = (float)V, logV = logf(fV);
+  for (int s = blockIdx.x * EVAL_WAVES + wave; s < S; s += gridDim.x * EVAL_WAVES) {
+    const float* base = logits + (size_t)s * V * ldl;
+    float* orow = out + (size_t)s * ldo;
+    // every row of the sample starts on 16 bytes: the first does and the stride keeps it (one view: no stride to keep)
+    const bool vec = ((reinterpret_cast<uintptr_t>(base) & 15) == 0) && (V == 1 || (ldl & 3) == 0);
+    const bool vec_out = (reinterpret_cast<uintptr_t>(orow) & 15) == 0;
+    const int C4 = vec ? C >> 2 : 0;
+    float my_lse = 0.f;
+    if constexpr (MODE == CARA_EVAL_COMBINE_PROB) {
+      for (int v = 0; v < V; ++v) {
+        const float* lr = base + (size_t)v * ldl;
+        float m = -INFINITY;
+        for (int i = lane; i < C4; i += 64) {
+          const float4 q = reinterpret_cast<const float4*>(lr)[i];
+          m = fmaxf(fmaxf(m, q.x), fmaxf(q.y, fmaxf(q.z, q.w)));
+        }
+        for (int c = C4 * 4 + lane; c < C; c += 64) m = fmaxf(m, lr[c]);
+        m = wave_max(m);
+        float sum = 0.f;
+        for (int i = lane; i < C4; i += 64) {
+          const float4 q = reinterpret_cast<const float4*>(lr)[i];
+          sum += expf(q.x - m);
+          sum += expf(q.y - m);
+          sum += expf(q.z - m);
+          sum += expf(q.w - m);
+        }
+        for (int c = C4 * 4 + lane; c < C; c += 64) sum += expf(lr[c] - m);
+        const float lse = m + logf(wave_sum(sum));   // (the same value in every lane)
+        my_lse = lane == v ? lse : my_lse;
+      }
+    }
+    for (int i = lane; i < C4; i += 64) {
+      float4 o;
+      o.x = combine_one<MODE>(base + 4 * i, ldl, V, my_lse, logV, fV);
+      o.y = combine_one<MODE>(base + 4 * i + 1, ldl, V, my_lse, logV, fV);
+      o.z = combine_one<MODE>(base + 4 * i + 2, ldl, V, my_lse, logV, fV);
+      o.w = combine_one<MODE>(base + 4 * i + 3, ldl, V, my_lse, logV, fV);
+      if (vec_out) {
+        reinterpret_cast<float4*>(orow)[i] = o;
+      } else {
+        orow[4 * i] = o.x; orow[4 * i + 1] = o.y; orow[4 * i + 2] = o.z; orow[4 * i + 3] = o.w;
+      }
+    }
+    for (int c = C4 * 4 + lane; c < C; c += 64) orow[c] = combine_one<MODE>(base + c, ldl, V, my_lse, logV, fV);
+  }
+}
+
 }  // namespace
+
+extern "C" int cara_eval_combine_views(const float* logits, int ldl, int S, int V, int classes, int mode, float* out, int ldo,
+                                       void* stream) {
+  if (!logits || !out || S < 1 || V < 1 || V > CARA_EVAL_MAX_VIEWS || classes < 1 || ldl < classes || ldo < classes) return CARA_E_ARG;
+  if (mode != CARA_EVAL_COMBINE_PROB && mode != CARA_EVAL_COMBINE_LOGIT) return CARA_E_ARG;
+  const uintptr_t lo_l = reinterpret_cast<uintptr_t>(logits), lo_o = reinterpret_cast<uintptr_t>(out);
+  if ((lo_l & 3) || (lo_o & 3)) return CARA_E_ARG;
+  // the bytes the launch reads and the bytes it writes (the last row of each ends behind its `classes` columns)
+  const uintptr_t hi_l = lo_l + (((size_t)S * V - 1) * (size_t)ldl + classes) * sizeof(float);
+  const uintptr_t hi_o = lo_o + (((size_t)S - 1) * (size_t)ldo + classes) * sizeof(float);
+  if (lo_o < hi_l && lo_l < hi_o) return CARA_E_ARG;
+  const dim3 grid(eval_grid(S)), block(EVAL_WAVES * 64);
+  if (mode == CARA_EVAL_COMBINE_PROB)
+    hipLaunchKernelGGL(eval_combine_kernel<CARA_EVAL_COMBINE_PROB>, grid, block, 0, static_cast<hipStream_t>(stream), logits, ldl, S, V,
+                       classes, out, ldo);
+  else
+    hipLaunchKernelGGL(eval_combine_kernel<CARA_EVAL_COMBINE_LOGIT>, grid, block, 0, static_cast<hipStream_t>(stream), logits, ldl, S, V,
+                       classes, out, ldo);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
 
 extern "C" size_t cara_eval_state_bytes(void) { return 5 * sizeof(unsigned long long); }
 

@@ -136,6 +136,88 @@ def check_boxes(boxes: torch.Tensor, Hs: int, Ws: int) -> None:
         raise ValueError(f"{int(bad.sum())} crop box(es) outside the {Hs} x {Ws} source, the first: {boxes.reshape(-1, 5)[int(bad.to(torch.int64).argmax())].tolist()}")
 
 
+EVAL_MAX_VIEWS = 16   # CARA_EVAL_MAX_VIEWS of include/cara_hip.h: the views cara_eval_combine_views takes per sample
+
+
+class EvalViews:
+    """The views every test image is scored through (``CaraEngine.evaluate(views=)``): a host int32 [V, 5] table of
+    ``(x0, y0, w, h, flip)`` boxes in source pixels, the same for every sample, made for a source size by ``table(Hs, Ws)``.
+    ``size`` is the side every view is resized to, the model's input.  The resampling is the crop kernel's
+    (``cara_im2col_patches_u8_rows_crop``, ``resized_crop_reference``): bilinear with half-pixel centres and NO antialias filter --
+    a strong downscale aliases where PIL's or torchvision's antialiased resize would not -- and a box of side ``size`` is the
+    source's exact bytes.
+    ``resize(size)``: the whole image (the identity on a split of ``size``).  ``center(size, crop_pct)``: the centred square of
+    side ``round(min(Hs, Ws) * crop_pct)``, timm's resize / centre-crop protocol when the split was decoded at ``size / crop_pct``
+    (256 -> ``(16, 16, 224, 224, 0)``).  ``flip=True`` on either adds the mirrored view behind it.  ``five_crop``: the four corners
+    (top-left, top-right, bottom-left, bottom-right) and the centre at that side; ``ten_crop``: those and then their mirror images.
+    ``EvalViews(table)``: a hand-made table."""
+
+    def __init__(self, table, size: Optional[int] = None):
+        t = torch.as_tensor(table)
+        if t.dtype not in (torch.int32, torch.int64) or t.ndim != 2 or t.shape[1] != 5 or t.shape[0] < 1:
+            raise ValueError("EvalViews takes an integer [V, 5] table (x0, y0, w, h, flip), V >= 1")
+        self.size = None if size is None else int(size)
+        self._fixed, self._make, self.V = t.to(torch.int32).cpu().contiguous(), None, int(t.shape[0])
+
+    @classmethod
+    def _of(cls, size, V, make) -> "EvalViews":
+        if int(size) <= 0:
+            raise ValueError("EvalViews: size > 0")
+        self = cls.__new__(cls)
+        self.size, self._fixed, self._make, self.V = int(size), None, make, V
+        return self
+
+    @staticmethod
+    def _side(Hs, Ws, crop_pct):
+        if not 0.0 < float(crop_pct) <= 1.0:
+            raise ValueError("EvalViews: 0 < crop_pct <= 1")
+        return max(1, int(math.floor(min(Hs, Ws) * float(crop_pct) + 0.5)))
+
+    @staticmethod
+    def _with_flips(boxes, flip):
+        return boxes + [(x0, y0, w, h, 1) for x0, y0, w, h, _ in boxes] if flip else boxes
+
+    @classmethod
+    def resize(cls, size: int, flip: bool = False) -> "EvalViews":
+        return cls._of(size, 2 if flip else 1, lambda Hs, Ws: cls._with_flips([(0, 0, Ws, Hs, 0)], flip))
+
+    @classmethod
+    def center(cls, size: int, crop_pct: float = 0.875, flip: bool = False) -> "EvalViews":
+        def make(Hs, Ws):
+            s = cls._side(Hs, Ws, crop_pct)
+            return cls._with_flips([((Ws - s) // 2, (Hs - s) // 2, s, s, 0)], flip)
+        cls._side(1, 1, crop_pct)
+        return cls._of(size, 2 if flip else 1, make)
+
+    @classmethod
+    def five_crop(cls, size: int, crop_pct: float = 0.875, _flip: bool = False) -> "EvalViews":
+        def make(Hs, Ws):
+            s = cls._side(Hs, Ws, crop_pct)
+            return cls._with_flips([(0, 0, s, s, 0), (Ws - s, 0, s, s, 0), (0, Hs - s, s, s, 0), (Ws - s, Hs - s, s, s, 0),
+                                    ((Ws - s) // 2, (Hs - s) // 2, s, s, 0)], _flip)
+        cls._side(1, 1, crop_pct)
+        return cls._of(size, 10 if _flip else 5, make)
+
+    @classmethod
+    def ten_crop(cls, size: int, crop_pct: float = 0.875) -> "EvalViews":
+        return cls.five_crop(size, crop_pct, _flip=True)
+
+    def table(self, Hs: int, Ws: int) -> torch.Tensor:
+        """host int32 [V, 5] for an ``Hs`` x ``Ws`` source; ValueError for a box outside it or more than ``EVAL_MAX_VIEWS`` views"""
+        t = self._fixed if self._make is None else torch.tensor(self._make(int(Hs), int(Ws)), dtype=torch.int32)
+        check_views(t, Hs, Ws)
+        return t.contiguous()
+
+
+def check_views(table: torch.Tensor, Hs: int, Ws: int) -> None:
+    """ValueError unless ``table`` is an int32 [V, 5] table of 1 <= V <= ``EVAL_MAX_VIEWS`` boxes inside an ``Hs`` x ``Ws`` image"""
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.ndim != 2 or table.shape[1] != 5 or table.shape[0] < 1:
+        raise ValueError("a view table is an int32 [V, 5] tensor (x0, y0, w, h, flip), V >= 1")
+    if table.shape[0] > EVAL_MAX_VIEWS:
+        raise ValueError(f"{table.shape[0]} views: cara_eval_combine_views takes at most {EVAL_MAX_VIEWS} per sample")
+    check_boxes(table, Hs, Ws)
+
+
 def resized_crop_reference(pixels_u8: torch.Tensor, rows, boxes, size, dtype=torch.float64) -> torch.Tensor:
     """What ``cara_im2col_patches_u8_rows_crop`` samples, before normalisation, in torch ops on the CPU: [B,C,Hi,Wi] of
     ``dtype`` with ``size`` = Hi or (Hi, Wi).  Output pixel (oy, ox) of sample b: ``ox' = flip ? Wi-1-ox : ox``,
@@ -1040,11 +1122,39 @@ class ResidentSplit:
                 y = torch.cat([y, y[:1].expand(pad)])
             yield px, y, j - i
 
+    def eval_view_shard(self, views_table: torch.Tensor, batch_size: int = 256, rank: Optional[int] = None,
+                        world: Optional[int] = None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]]:
+        """This rank's part of the split (``dist.eval_shard``) seen through the V views of ``views_table`` (host int32 [V, 5],
+        ``EvalViews.table``), by index: ``(rows int64 [S*V], boxes int32 [S*V, 5], labels int64 [S], n_valid_samples)`` with
+        ``S = batch_size // V`` whole samples per batch and view ``v`` of sample ``s`` in row ``s*V + v`` -- what
+        ``cara_vit_forward_u8_rows_crop`` and ``cara_eval_combine_views`` read.  Every batch has the same shape: the last one of a
+        shard is padded with copies of its first sample and says so in ``n_valid``.  ``rows`` and ``labels`` are built on the
+        device, ``boxes`` is ONE device tensor uploaded before the first batch and yielded every time: no host upload per batch.
+        The table is checked against the split's size, and ``V <= batch_size``, here -- before the first batch exists."""
+        check_views(views_table, *self.pixels.shape[2:])
+        V = int(views_table.shape[0])
+        S = int(batch_size) // V
+        if S < 1:
+            raise ValueError(f"batch_size {batch_size} holds no whole sample of {V} views")
+        rank = D.get_rank() if rank is None else rank
+        world = D.world_size() if world is None else world
+        mine = D.eval_shard(len(self), rank, world, S)
+        dev = self.pixels.device
+
+        def batches():
+            boxes = views_table.repeat(S, 1).contiguous().to(dev)
+            for i in range(mine.start, mine.stop, S):
+                j = min(i + S, mine.stop)
+                idx = torch.arange(i, i + S, dtype=torch.int64, device=dev)
+                if j - i < S:
+                    idx = torch.where(idx < j, idx, torch.full_like(idx, i))
+                yield idx.repeat_interleave(V), boxes, self.labels.index_select(0, idx), j - i
+        return batches()
 
 
 def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optional[str] = None, device="cuda",
              seed: int = 0, workers: int = 8, shard_eval: bool = False, resident_feed: bool = False, augment=None,
-             train_size: Optional[int] = None, mix=None, color=None, patch_drop=None, rand=None):
+             train_size: Optional[int] = None, mix=None, color=None, patch_drop=None, rand=None, test_size: Optional[int] = None):
     """Drop-in for ``vtab.get_data`` (vtab.py:88-107): the same split files -- ``train800val200.txt`` /
     ``test.txt`` when ``evaluate`` else ``train800.txt`` / ``val200.txt`` -- under ``./data/vtab-1k/<name>``.
     Returns (train_batches, test_batches) in the form ``recipe.fit`` takes instead of two DataLoaders.
@@ -1054,17 +1164,22 @@ def get_data(name: str, evaluate: bool = True, batch_size: int = 64, root: Optio
     ``fit(feed="resident")`` takes: the steps read the split's uint8 pixels by index instead of a normalised fp32 batch.
     ``augment`` / ``train_size`` (with ``resident_feed``): the training split is decoded at ``train_size`` (default 224, the
     model's size) and its ``train_rows`` yields ``(rows, boxes)`` drawn by ``augment`` -- "resize 256, random-resized-crop
-    224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.  The test split keeps the model's size.
+    224" is ``train_size=256, augment=RandomResizedCropFlip(224)``.
+    ``test_size`` (with ``shard_eval``): the test split is decoded at that size instead of the model's and read through the crop
+    boxes of an ``EvalViews`` -- "resize 256, centre-crop 224" is ``test_size=256`` and ``fit(..., eval_views=EvalViews.center(224))``.
     ``mix`` / ``color`` / ``patch_drop`` / ``rand`` (with ``resident_feed``): handed to ``train_rows``, which then yields tuples."""
     if (augment is not None or train_size is not None or mix is not None or color is not None or patch_drop is not None
             or rand is not None) and not resident_feed:
         raise ValueError("augment / train_size / mix / color / patch_drop / rand belong to the resident feed: pass resident_feed=True")
     if train_size is not None and train_size != 224 and augment is None:
         raise ValueError("a training split of another size than the model's is read through crop boxes: pass augment")
+    if test_size is not None and test_size != 224 and not shard_eval:
+        raise ValueError("a test split of another size than the model's is read through view boxes: pass shard_eval=True and "
+                         "evaluate with views")
     root = root if root is not None else "./data/vtab-1k/" + name
     tr, te = ("train800val200.txt", "test.txt") if evaluate else ("train800.txt", "val200.txt")
     train = ResidentSplit(root, os.path.join(root, tr), device=device, workers=workers, size=224 if train_size is None else train_size)
-    test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers)
+    test = ResidentSplit(root, os.path.join(root, te), device=device, workers=workers, size=224 if test_size is None else test_size)
     if resident_feed:
         feed = (train, train.train_rows(batch_size, seed=seed, augment=augment, mix=mix, color=color, patch_drop=patch_drop, rand=rand))
     else:

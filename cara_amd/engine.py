@@ -946,8 +946,27 @@ class CaraEngine:
                   "cara_vit_forward")
         return st["logits"]
 
+    def _eval_forward_views(self, model, split, rows, boxes, dev, weights):
+        """logits [S*V, classes] of the images ``rows`` of a resident split through the crop boxes ``boxes``:
+        cara_vit_forward_u8_rows_crop on the inference-sized workspace of that row count.  The returned tensor is the workspace
+        entry's own, as in ``_eval_forward``."""
+        st = self._eval_state(model, rows.shape[0], self._model_img(model), dev)
+        if st["shape"].chans != 3:
+            raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
+        cp, hw, hb = weights
+        cps = self._cp_ptrs([t.detach().contiguous() for t in cp])
+        mean, std = self._eval_norm(dev)
+        px = split.pixels
+        values = {"g": C.byref(st["geom"]), "s": C.byref(st["shape"]), "w": C.byref(self._ingested[1]), "cp": C.byref(cps),
+                  "head_w": hw.detach().contiguous(), "head_b": hb.detach().contiguous(), "droppath": None, "workspace": st["ws"],
+                  "logits": st["logits"], "bad": self._bad_rows(dev), "stream": stream(dev), "pixels": px, "n_split": len(split),
+                  "Hs": px.shape[2], "Ws": px.shape[3], "rows": rows, "mean": mean, "std": std}
+        entry, params = forward_call({"boxes": boxes}, values)
+        check(getattr(self._lib(), entry)(*[ptr(v) if v is None or torch.is_tensor(v) else v for _, v in params]), entry)
+        return st, st["logits"]
+
     def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None, weights=None, report: bool = False,
-                 bins: int = 15) -> dict:
+                 bins: int = 15, views=None, combine: str = "prob") -> dict:
         """Top-1 / top-5 accuracy and mean cross-entropy of a whole split, on the device and sharded over the ranks of
         ``group``: ``test()`` of vit_cp.py:73-82 without its host read per batch.  -> ``dict(top1, top5, loss, n)``, the
         same on every rank; ``n`` is the number of images scored by all ranks together.
@@ -965,10 +984,30 @@ class CaraEngine:
         same single all-reduce and host read.  The dict then also holds ``confusion`` (CPU int64 [C, C], row = label, column =
         predicted class), ``support``, ``per_class`` (recall, NaN without support), ``precision`` (NaN for a class never
         predicted), ``mean_per_class``, ``ece`` and ``calibration = {count, hits, confidence}`` (``evalcount.report_result``).
-        A head wider than ``CARA_EVAL_REPORT_MAX_CLASSES`` or a bin count the kernel refuses raises before the first forward."""
+        A head wider than ``CARA_EVAL_REPORT_MAX_CLASSES`` or a bin count the kernel refuses raises before the first forward.
+        ``views`` (a ``data.EvalViews``; the source must be a ``ResidentSplit``, of any stored size): every image is scored through
+        the V crop boxes of ``views.table(Hs, Ws)`` -- centre crop, flips, five / ten crops.  A batch is ``S = batch_size // V`` whole
+        samples (``ResidentSplit.eval_view_shard``): one ``cara_vit_forward_u8_rows_crop`` of ``S*V`` rows, one
+        ``cara_eval_combine_views`` into a ``[S, classes]`` buffer kept with the workspace, and the accumulate launch of above on
+        the combined rows.  ``combine = "prob"``: the mean of the views' softmax probabilities, as its logarithm (loss
+        ``-log pbar[y]``, confidence ``max pbar``); ``"logit"``: the mean of the views' logits.  One view: no combine launch in
+        either mode -- its log-softmax scores exactly as its logits do -- and ``combined`` below is the view's logits themselves.
+        ``n`` counts samples, not views; ``debug_hook(logits, labels, n_valid, combined)`` then sees the per-view logits
+        ``[S*V, classes]`` and the combined rows.  Resampling is bilinear without an antialias filter (``data.EvalViews``).
+        Views on another source, a table that leaves the split, more views than ``batch_size`` or an unknown ``combine`` raise
+        before the first forward.  Without ``views`` the pass issues the launches it always did."""
         from . import dist as cdist
         model = self._model()
         model.eval()
+        if combine not in L.EVAL_COMBINE:
+            raise CaraError(f"evaluate: combine must be one of {tuple(L.EVAL_COMBINE)}, not {combine!r}")
+        if views is not None:   # (what the arguments are before where anything lives)
+            from .data import EvalViews
+            split = split_or_batches
+            if not isinstance(views, EvalViews):
+                raise CaraError("evaluate: views must be a data.EvalViews")
+            if not hasattr(split, "eval_view_shard") or getattr(split, "pixels", None) is None:
+                raise CaraError("evaluate(views=) reads a data.ResidentSplit by index: batches and callables carry no views")
         if not hasattr(model.head, "weight"):
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")
         if self.precision not in ("bf16", "fp16"):
@@ -986,7 +1025,16 @@ class CaraEngine:
             if report_bytes == 0:
                 raise CaraError(f"evaluate(report=True): {ncls} classes with {bins} bins is outside what cara_eval_accumulate_report "
                                 "takes (at most 4096 classes, 1 to 64 bins)")
-        if hasattr(split_or_batches, "eval_shard"):
+        if views is not None:
+            if views.size is not None and views.size != self._model_img(model):
+                raise CaraError(f"evaluate: the views are made for a {views.size}-pixel input, the model takes {self._model_img(model)}")
+            try:
+                batches = split.eval_view_shard(views.table(*split.pixels.shape[2:]), batch_size, cdist.get_rank(group),
+                                                cdist.world_size(group))
+            except ValueError as e:
+                raise CaraError(f"evaluate: {e}") from None
+            V, mode = views.V, L.EVAL_COMBINE[combine]
+        elif hasattr(split_or_batches, "eval_shard"):
             batches = split_or_batches.eval_shard(batch_size, cdist.get_rank(group), cdist.world_size(group))
         else:
             batches = split_or_batches() if callable(split_or_batches) else split_or_batches
@@ -996,11 +1044,27 @@ class CaraEngine:
             state = torch.zeros(int(lib.cara_eval_state_bytes()) // 8, dtype=torch.int64, device=dev)
             rep = torch.zeros(report_bytes // 8, dtype=torch.int64, device=dev) if report else None
             for item in batches:
-                x, y = item[0], item[1]
-                n_valid = int(item[2]) if len(item) > 2 else y.shape[0]
-                if x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]:
-                    raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
-                logits = self._eval_forward(model, x, dev, use)
+                per_view = None
+                if views is not None:
+                    rows, boxes, y, n_valid = item
+                    self._resident_args(split, Feed(rows, boxes))
+                    st, per_view = self._eval_forward_views(model, split, rows, boxes, dev, use)
+                    logits = per_view
+                    # one view: its mean logit is its logit, and its log-softmax is scored exactly as its logits are (loss, confidence
+                    # and ranks do not see a shift of the whole row) -- no combine launch, the pass is bit for bit the plain one
+                    if V > 1:
+                        S = y.shape[0]
+                        logits = st.setdefault("combined", {}).get(S)
+                        if logits is None:
+                            logits = st["combined"][S] = torch.empty(S, per_view.shape[1], device=dev)
+                        check(lib.cara_eval_combine_views(ptr(per_view), per_view.shape[1], S, V, per_view.shape[1], mode, ptr(logits),
+                                                          logits.shape[1], stream(dev)), "cara_eval_combine_views")
+                else:
+                    x, y = item[0], item[1]
+                    n_valid = int(item[2]) if len(item) > 2 else y.shape[0]
+                    if x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]:
+                        raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
+                    logits = self._eval_forward(model, x, dev, use)
                 if report:
                     check(lib.cara_eval_accumulate_report(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
                                                           logits.shape[1], ptr(state), ptr(rep), bins, stream(dev)),
@@ -1009,7 +1073,7 @@ class CaraEngine:
                     check(lib.cara_eval_accumulate(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
                                                    logits.shape[1], ptr(state), stream(dev)), "cara_eval_accumulate")
                 if debug_hook is not None:
-                    debug_hook(logits, y, n_valid)
+                    debug_hook(logits, y, n_valid) if views is None else debug_hook(per_view, y, n_valid, logits)
             # the five words as fp64 (counts are exact up to 2^53): ONE collective carries integers and the loss sum alike
             vec = state.to(torch.float64)
             vec[3] = state.view(torch.float64)[3]

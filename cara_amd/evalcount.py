@@ -12,6 +12,8 @@ State: ``float64 [5] = (n, top1, top5, loss_sum, bad_labels)``, the kernel's fiv
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 STATE_WORDS = 5
@@ -43,6 +45,29 @@ def accumulate(state: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, 
     state[TOP5] += float((rank < 5).sum())
     state[LOSS] += (torch.logsumexp(l, dim=1) - v.view(-1)).sum()
     return state
+
+
+COMBINE_MODES = ("prob", "logit")
+
+
+def combine_views(logits: torch.Tensor, V: int, mode: str = "prob") -> torch.Tensor:
+    """The V views' logits of every sample as one row: ``cara_eval_combine_views`` in plain torch, fp64 from the fp32 logits.
+    ``logits`` [S*V, classes], the views of sample ``s`` in rows ``s*V .. s*V+V-1`` -> fp64 [S, classes], which ``accumulate`` /
+    ``accumulate_report`` then score.  ``"prob"``: ``log(mean_v softmax(l_v))`` -- the loss of the row is ``-log pbar[y]``, its
+    confidence ``max pbar``; a class with probability zero in every view gives ``-inf``, not NaN.  ``"logit"``: ``mean_v l_v``."""
+    V = int(V)
+    if mode not in COMBINE_MODES:
+        raise ValueError(f"combine must be one of {COMBINE_MODES}, not {mode!r}")
+    if logits.ndim != 2 or V < 1 or logits.shape[0] % V:
+        raise ValueError("combine_views takes logits [S*V, classes] with V >= 1")
+    l = logits.to(torch.float64).view(logits.shape[0] // V, V, logits.shape[1])
+    if mode == "logit":
+        return l.mean(dim=1)
+    logp = torch.log_softmax(l, dim=2)
+    top = logp.max(dim=1, keepdim=True).values
+    # (where every view says -inf the shift would be inf - inf: shift by 0 there, the sum of the exponentials is 0, its log -inf)
+    shift = torch.where(torch.isinf(top), torch.zeros_like(top), top)
+    return (shift + torch.log(torch.exp(logp - shift).sum(dim=1, keepdim=True))).squeeze(1) - math.log(V)
 
 
 def result(state) -> dict:

@@ -234,7 +234,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
         accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
-        eval_metric: str = "top1", class_weight=None, logit_bias=None):
+        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob"):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -289,7 +289,13 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``class_weight`` / ``logit_bias`` (fp32 [classes], host or device, e.g. ``data.balanced_class_weight`` / ``data.logit_prior`` of
     ``data.class_counts(split, classes)``): moved to the model's device once, and every training step of either feed, eager or
     graphed, runs the weighted, logit-adjusted loss (``train_step(..., class_weight=, logit_bias=)``).  The evaluation epochs are
-    unchanged: they score the raw logits."""
+    unchanged: they score the raw logits.
+    ``eval_views`` (a ``data.EvalViews``; ``eval_mode = "sharded"`` only, ``test_batches`` a ``ResidentSplit`` of any stored size) and
+    ``eval_combine`` (``"prob"`` / ``"logit"``): the evaluation epochs score every test image through those views
+    (``CaraEngine.evaluate(views=, combine=)``: centre crop, flips, five / ten crops) -- the raw and the averaged pass alike, with
+    either ``eval_metric``.  None (default): the calls that were always made."""
+    if eval_views is not None and eval_mode != "sharded":
+        raise CaraError("fit: eval_views are read by CaraEngine.evaluate(views=): they need eval_mode = 'sharded'")
     if eval_metric not in ("top1", "mean_per_class"):
         raise CaraError(f"eval_metric must be 'top1' or 'mean_per_class', not {eval_metric!r}")
     if eval_metric == "mean_per_class" and eval_mode != "sharded":
@@ -342,6 +348,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     gstep = GraphedTrainStep(eng, opt, **smooth) if graph else None
     best = 0.0
     scored = {"report": True} if eval_metric == "mean_per_class" else {}
+    if eval_views is not None:
+        scored.update(views=eval_views, combine=eval_combine)
     if feed == "resident":
         split, rows_of = train_batches
         train_batches = lambda epoch: ((split, rows) for rows in rows_of(epoch))   # noqa: E731

@@ -492,6 +492,22 @@ int cara_eval_accumulate(const float* logits, int ldl, const int64_t* labels, in
 size_t cara_eval_report_bytes(int classes, int bins);
 int cara_eval_accumulate_report(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes,
                                 void* state, void* report, int bins, void* stream);
+/* Multi-view evaluation (centre crop + flip, five / ten crops): the V views' logits of every sample -> ONE row per sample, in a
+ * form the two entries above score unchanged.  logits fp32 [S*V, classes] (row stride ldl floats), the views of sample s in
+ * rows s*V .. s*V+V-1; out fp32 [S, classes] (row stride ldo floats).  All in fp32 with the accurate expf / logf:
+ *   CARA_EVAL_COMBINE_PROB   out[s][c] = log((1/V) sum_v softmax(l_{s,v})[c]), formed in the log domain:
+ *                            lse_v = m_v + logf(sum_c expf(l_v[c] - m_v)),  a_v = l_v[c] - lse_v,  M = max_v a_v,
+ *                            out = M + logf(sum_v expf(a_v - M)) - logf(V), views summed in index order; -inf (not NaN) where M
+ *                            is -inf, i.e. the class has probability zero in every view.  The accumulate entries then give
+ *                            loss = -log pbar[y], confidence = max pbar, and their rank and tie rules on pbar.
+ *   CARA_EVAL_COMBINE_LOGIT  out[s][c] = (sum_v l_{s,v}[c]) / V, summed in view order, the division correctly rounded.
+ * V = 1 is legal: log_softmax and a copy.  One launch, one wave per sample; columns >= classes of out are never written.
+ * CARA_E_ARG with nothing launched: a NULL pointer, S < 1, V outside [1, CARA_EVAL_MAX_VIEWS], classes < 1, ldl or ldo < classes,
+ * an unknown mode, logits or out not 4-byte aligned, out overlapping logits.                                                     */
+#define CARA_EVAL_MAX_VIEWS 16
+#define CARA_EVAL_COMBINE_PROB 0
+#define CARA_EVAL_COMBINE_LOGIT 1
+int cara_eval_combine_views(const float* logits, int ldl, int S, int V, int classes, int mode, float* out, int ldo, void* stream);
 /* bf16 <-> fp32 helpers (weight ingest)                                                        */
 int cara_f32_to_bf16(const float* src, void* dst, size_t n, void* stream);
 int cara_transpose_bf16(const void* src, void* dst, int rows, int cols, void* stream);

@@ -9,7 +9,10 @@
 and print seconds per pass (median, min, max over --passes after one warm-up each), images/s and the workspace bytes of
 both.  Standalone: not part of bench.py.  --only a|b runs one leg (the leg (a) of an older build: CARA_LIB_PATH).
 --report (with --only none to skip the legs above) times (b) against engine.evaluate(split, B, report=True): the same pass with
-cara_eval_accumulate_report instead of cara_eval_accumulate after every batch (docs/findings/eval_report.md)."""
+cara_eval_accumulate_report instead of cara_eval_accumulate after every batch (docs/findings/eval_report.md).
+--views center|flip|five|ten times (b) against engine.evaluate(split, B, views=...) on the same split, alternating: 1, 2, 5 or 10
+forwards per image in batches of B // V whole samples, and the device time of one cara_eval_combine_views launch on such a batch
+as a share of the pass (docs/findings/eval_views.md).  --combine prob|logit."""
 import argparse
 import ctypes as C
 import json
@@ -34,7 +37,10 @@ def main():
     ap.add_argument("--only", default="ab", choices=["a", "b", "ab", "none"])
     ap.add_argument("--report", action="store_true", help="time engine.evaluate with and without report=True, alternating")
     ap.add_argument("--bins", type=int, default=15)
-    ap.add_argument("--rounds", type=int, default=2, help="--report: alternations of (plain passes, report passes)")
+    ap.add_argument("--rounds", type=int, default=2, help="--report / --views: alternations of (plain passes, other passes)")
+    ap.add_argument("--views", default=None, choices=["center", "flip", "five", "ten"],
+                    help="time engine.evaluate with and without these views (centre crop, centre crop + flip, five crops, ten crops)")
+    ap.add_argument("--combine", default="prob", choices=["prob", "logit"])
     args = ap.parse_args()
     from cara_amd import cara, create_model, recipe
     from cara_amd.data import ResidentSplit
@@ -93,7 +99,44 @@ def main():
                                   report_bytes=8 * (args.classes ** 2 + 3 * args.bins))
         res["report_over_plain"] = round(res["report_pass"]["median_s"] / res["plain_pass"]["median_s"], 4)
         res["counting_launch_us"] = _launch_us(eng, args, dev)
+    if args.views:
+        from cara_amd.data import EvalViews
+        views = {"center": EvalViews.center(224), "flip": EvalViews.center(224, flip=True), "five": EvalViews.five_crop(224),
+                 "ten": EvalViews.ten_crop(224)}[args.views]
+        plain, multi, out = [], [], [None]
+        for _ in range(args.rounds):
+            plain += timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch)))
+            multi += timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch, views=views, combine=args.combine)))
+        report("plain_pass", plain, eng.eval_workspace_bytes(), None)
+        report("views_pass", multi, eng.eval_workspace_bytes(), out[0]["top1"])
+        S = args.batch // views.V
+        batches = -(-args.images // S)
+        us = _combine_us(eng, args, dev, S, views.V) if views.V > 1 else 0.0     # (one view: no combine launch)
+        res["views_pass"].update(views=args.views, V=views.V, combine=args.combine, samples_per_batch=S, batches=batches, n=out[0]["n"],
+                                 loss=out[0]["loss"], combine_launch_us=us,
+                                 combine_share_pct=round(100 * us * 1e-6 * batches / res["views_pass"]["median_s"], 4))
+        res["views_over_plain"] = round(res["views_pass"]["median_s"] / res["plain_pass"]["median_s"], 4)
     print(json.dumps(res))
+
+
+def _combine_us(eng, args, dev, S, V, launches=200):
+    """device time of one cara_eval_combine_views launch on a [S*V, classes] logit table (events around `launches` back-to-back
+    launches, best of six after a warm-up)"""
+    from cara_amd import _lib as L
+    lib = eng._lib()
+    lg = torch.randn(S * V, args.classes, device=dev) * 3.0
+    out = torch.empty(S, args.classes, device=dev)
+    best = float("inf")
+    for _ in range(7):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(launches):
+            L.check(lib.cara_eval_combine_views(L.ptr(lg), args.classes, S, V, args.classes, L.EVAL_COMBINE[args.combine], L.ptr(out),
+                                                args.classes, L.stream(dev)), "cara_eval_combine_views")
+        t1.record()
+        torch.cuda.synchronize(dev)
+        best = min(best, t0.elapsed_time(t1) * 1e3 / launches)
+    return round(best, 3)
 
 
 def _launch_us(eng, args, dev, launches=200):
