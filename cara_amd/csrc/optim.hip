@@ -11,7 +11,8 @@
 // memory, nothing to upload when a learning rate changes.
 // Beside it: the loss-scale update of the IEEE-half build, and gradient accumulation and global-norm clipping over the step's one
 // flat gradient buffer (cara_grad_accumulate, cara_grad_clip), and the moving average of the trainable tensors, AdamW's scheme again
-// (cara_ema_update).
+// (cara_ema_update), and the two launches of sharpness-aware minimisation around a step's second pass (cara_sam_perturb,
+// cara_sam_restore).
 #include "common.h"
 
 namespace {
@@ -251,7 +252,173 @@ __global__ __launch_bounds__(256) void ema_kernel(const ema_table a) {
   }
 }
 
+// ---- sharpness-aware minimisation: the move to w + rho g / |g| and the way back (cara_hip.h: cara_sam_perturb, cara_sam_restore) ----
+// ema_kernel's scheme a third time: pointers and sizes of up to 32 tensors BY VALUE in the kernel arguments (1064 bytes), a prefix walk,
+// 1024-element chunks -- one launch over the 14 tensors of a step.  Both launches move 0.5 MB at rank 16: their cost is the launch.
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+struct sam_table {
+  float* p[CARA_ADAMW_MAX_TENSORS];
+  const float* g[CARA_ADAMW_MAX_TENSORS];   // (restore: unused)
+  float* b[CARA_ADAMW_MAX_TENSORS];         // perturb writes the backup, restore reads it
+  size_t n[CARA_ADAMW_MAX_TENSORS];
+  int ntensors;
+  float rho;
+  const float* norm;
+  const float* found_inf_in;                // perturb: the carry it reads (or NULL)
+  float* found_inf_out;                     // restore: the word the carry is added to (or NULL)
+  float* state;
+};
+
+// one fp32 multiply, then one fp32 add: tests/sam_model.py restates exactly this (no fma: see the clip kernels above)
+__device__ __forceinline__ float sam_move(float p, float g, float scale) {
+#pragma clang fp contract(off)
+  const float s = scale * g;
+  return p + s;
+}
+
+// -> the tensor of this workgroup and the first element of its chunk, or -1 past the last tensor (uniform)
+__device__ __forceinline__ int sam_locate(const sam_table& a, size_t* base) {
+  int t = 0, first = 0;
+  for (; t < a.ntensors && t < CARA_ADAMW_MAX_TENSORS; ++t) {
+    const int nchunk = (int)((a.n[t] + ADAMW_CHUNK - 1) / ADAMW_CHUNK);
+    if ((int)blockIdx.x < first + nchunk) break;
+    first += nchunk;
+  }
+  if (t >= a.ntensors || t >= CARA_ADAMW_MAX_TENSORS) return -1;
+  *base = (size_t)((int)blockIdx.x - first) * ADAMW_CHUNK;
+  return t;
+}
+
+__global__ __launch_bounds__(256) void sam_perturb_kernel(const sam_table a) {
+#pragma clang fp contract(off)
+  size_t base = 0;
+  const int t = sam_locate(a, &base);
+  if (t < 0) return;
+  // every thread forms the same scale from the same two device floats: two IEEE operations
+  const float carry = a.found_inf_in ? *a.found_inf_in : 0.f;
+  const float norm = *a.norm;
+  const bool move = !(carry != 0.f) && __builtin_isfinite(norm);   // an overflowed first pass, or a norm that is none: only the backup
+  const float den = norm + 1e-12f;
+  const float scale = move ? a.rho / den : 0.f;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.state[0] = carry;
+    a.state[1] = norm;
+    a.state[2] = scale;
+    a.state[3] = 0.f;
+  }
+  float* p = a.p[t];
+  const float* g = a.g[t];
+  float* b = a.b[t];
+  const size_t n = a.n[t];
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)b) & 15) == 0) {   // all three 16-byte aligned: one float4 per thread
+    const size_t i = base + 4 * (size_t)threadIdx.x;
+    if (i + 4 <= n) {
+      f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+      *reinterpret_cast<f32x4*>(b + i) = pv;
+      if (move) {
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) pv[c] = sam_move(pv[c], gv[c], scale);
+        *reinterpret_cast<f32x4*>(p + i) = pv;
+      }
+    } else {
+      for (size_t k = i; k < n; ++k) {   // the tensor's last 1 .. 3 elements
+        const float pk = p[k];
+        b[k] = pk;
+        if (move) p[k] = sam_move(pk, g[k], scale);
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const size_t i = base + (size_t)j * 256 + threadIdx.x;
+    if (i < n) {
+      const float pi = p[i];
+      b[i] = pi;
+      if (move) p[i] = sam_move(pi, g[i], scale);
+    }
+  }
+}
+
+// p = backup: a copy of the bits (dwords moved, never an arithmetic operation: -0, subnormals and NaN payloads come back)
+__global__ __launch_bounds__(256) void sam_restore_kernel(const sam_table a) {
+  size_t base = 0;
+  const int t = sam_locate(a, &base);
+  if (t < 0) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && a.found_inf_out) *a.found_inf_out += a.state[0];   // the first pass's overflow, once
+  unsigned* p = reinterpret_cast<unsigned*>(a.p[t]);
+  const unsigned* b = reinterpret_cast<const unsigned*>(a.b[t]);
+  const size_t n = a.n[t];
+  if ((((uintptr_t)p | (uintptr_t)b) & 15) == 0) {
+    const size_t i = base + 4 * (size_t)threadIdx.x;
+    if (i + 4 <= n) {
+      *reinterpret_cast<u32x4*>(p + i) = *reinterpret_cast<const u32x4*>(b + i);
+    } else {
+      for (size_t k = i; k < n; ++k) p[k] = b[k];
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const size_t i = base + (size_t)j * 256 + threadIdx.x;
+    if (i < n) p[i] = b[i];
+  }
+}
+
+// the checks the two entries share -> the launch's workgroups, 0 for CARA_E_ARG
+size_t sam_fill(sam_table& a, int ntensors, float* const* param, const float* const* grad, float* const* backup, const size_t* n) {
+  if (!param || !backup || !n || ntensors < 1 || ntensors > CARA_ADAMW_MAX_TENSORS) return 0;
+  size_t chunks = 0;
+  for (int t = 0; t < ntensors; ++t) {
+    const float* g = grad ? grad[t] : nullptr;
+    if (!param[t] || !backup[t] || (grad && !g) || n[t] == 0 || ((uintptr_t)param[t] | (uintptr_t)backup[t] | (uintptr_t)g) % 4 != 0) return 0;
+    if (n[t] > (size_t)0x7fffffffu * ADAMW_CHUNK) return 0;
+    // backup[t] overlapping param[t] or grad[t] anywhere in its n[t] elements (pointer equality is the common mistake)
+    const uintptr_t lo = (uintptr_t)backup[t], bytes = n[t] * sizeof(float), pp = (uintptr_t)param[t], gg = (uintptr_t)g;
+    if ((lo < pp + bytes && pp < lo + bytes) || (gg && lo < gg + bytes && gg < lo + bytes)) return 0;
+    a.p[t] = param[t];
+    a.g[t] = g;
+    a.b[t] = backup[t];
+    a.n[t] = n[t];
+    chunks += (n[t] + ADAMW_CHUNK - 1) / ADAMW_CHUNK;
+  }
+  if (chunks > 0x7fffffffu) return 0;
+  a.ntensors = ntensors;
+  return chunks;
+}
+
 }  // namespace
+
+extern "C" int cara_sam_perturb(int ntensors, float* const* param, const float* const* grad, float* const* backup, const size_t* n,
+                                float rho, const float* norm, const float* found_inf, float* state, void* stream) {
+  if (!grad || !norm || !state || !(rho >= 0.f) || !__builtin_isfinite(rho)) return CARA_E_ARG;   // (a NaN fails the comparison)
+  if (((uintptr_t)norm | (uintptr_t)found_inf | (uintptr_t)state) % 4 != 0) return CARA_E_ARG;
+  sam_table a = {};
+  const size_t chunks = sam_fill(a, ntensors, param, grad, backup, n);
+  if (chunks == 0) return CARA_E_ARG;
+  a.rho = rho;
+  a.norm = norm;
+  a.found_inf_in = found_inf;
+  a.state = state;
+  hipLaunchKernelGGL(sam_perturb_kernel, dim3((unsigned)chunks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+
+extern "C" int cara_sam_restore(int ntensors, float* const* param, const float* const* backup, const size_t* n, const float* state,
+                                float* found_inf, void* stream) {
+  if (!state || ((uintptr_t)state | (uintptr_t)found_inf) % 4 != 0) return CARA_E_ARG;
+  sam_table a = {};
+  const size_t chunks = sam_fill(a, ntensors, param, nullptr, const_cast<float* const*>(backup), n);
+  if (chunks == 0) return CARA_E_ARG;
+  a.found_inf_out = found_inf;
+  a.state = const_cast<float*>(state);
+  hipLaunchKernelGGL(sam_restore_kernel, dim3((unsigned)chunks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
 
 extern "C" int cara_ema_update(int ntensors, float* const* ema, const float* const* param, const size_t* n, float weight,
                                const float* weight_dev, void* stream) {

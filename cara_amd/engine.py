@@ -639,7 +639,7 @@ class CaraEngine:
 
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
                    label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, keep=None, class_weight=None,
-                   logit_bias=None):
+                   logit_bias=None, sam_rho=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -668,8 +668,24 @@ class CaraEngine:
         the batch's weight mass, so windows, ranks and the all-reduce work as before.  The bias enters the loss only (logit-adjusted
         training): the model's logits and ``evaluate`` are untouched.  A negative or non-finite weight and a non-finite bias are
         refused; the values are read on the host once per tensor and version (an in-place change is checked again at the next
-        step).  Both None: the loss launches are the ones they were."""
+        step).  Both None: the loss launches are the ones they were.
+        ``sam_rho`` (None, or a number >= 0): sharpness-aware minimisation (Foret et al.) -- every micro-step runs forward, loss and
+        backward TWICE on the same input with the same DropPath multipliers: once at the weights w, which gives g1 and the returned
+        loss, and once at w + e, e = sam_rho g1 / (||g1|| + 1e-12) over all trainable tensors, which gives the gradient g2 that the
+        unchanged remainder of the step works on (accumulate, all-reduce, clip, loss scale, optimiser, ``ema``).  Between the passes:
+        ``cara_grad_clip`` with max_norm = inf measures ||g1|| into buffers of SAM's own, ``cara_sam_perturb`` keeps a backup and moves
+        the weights; behind the second backward ``cara_sam_restore`` copies the backup back bit for bit -- three small launches, no
+        host read.  ``sam_loss`` is the second pass's loss (device scalar), ``sam_norm`` the device float [4] (carry, ||g1||, scale
+        applied, 0).  In a window the perturbation comes from each micro-batch's own gradient.  Data parallel: the perturbation uses
+        the rank's LOCAL gradient (m-sharpness with m = the per-rank batch: the direction g / ||g|| depends neither on the
+        1 / world and 1 / k pre-division nor on the fp16 loss scale, which is divided out already); there is still one all-reduce
+        per optimiser step, and the bitwise restore keeps the replicas identical.  fp16: an overflow in the first pass leaves the
+        weights alone and is carried into the found-inf word behind the second pass -- the step is skipped and the scale backed
+        off once.  ``sam_rho = 0.0`` runs both passes and leaves the gradients of the plain step, bit for bit.  Refused with
+        ``weight_dropout = "exact"`` in train mode: that mode draws a fresh mask seed per forward, so the two passes would not see
+        the same masks.  None: the launches are the ones they were."""
         eps = self._smoothing(label_smoothing)
+        self._sam_rho(sam_rho)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
@@ -679,7 +695,7 @@ class CaraEngine:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp, keep=keep),
                           lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema,
-                          class_weight, logit_bias)
+                          class_weight, logit_bias, sam_rho)
 
     def _class_vectors(self, class_weight, logit_bias, ncls, dev):
         """``class_weight`` / ``logit_bias`` of a step, refused here -- before anything is launched -- unless each is None or a
@@ -700,13 +716,17 @@ class CaraEngine:
                 seen[name] = key
 
     def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None,
-              ema=None, class_weight=None, logit_bias=None):
+              ema=None, class_weight=None, logit_bias=None, sam_rho=None):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
         (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one, with a
         ``class_weight`` or a ``logit_bias`` the weighted, logit-adjusted one on that target.
-        ``accumulate``, ``clip_grad`` and ``ema`` as in ``train_step``."""
+        ``accumulate``, ``clip_grad``, ``ema`` and ``sam_rho`` as in ``train_step``."""
         model = self._model()
+        rho = self._sam_rho(sam_rho)
+        if rho is not None and self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0:
+            raise CaraError("sam_rho cannot run with weight_dropout = 'exact' in train mode: that mode draws a fresh mask seed per "
+                            "forward, so the two passes of a SAM step would see different masks")
         self._check_ema(ema, dev, "ema")
         if ema is not None and not ema.capturable and torch.cuda.is_current_stream_capturing():
             raise CaraError("a captured step needs make_ema(..., capturable=True): the weight would be frozen into the graph")
@@ -740,17 +760,26 @@ class CaraEngine:
             gv = self._grad_buffers(model, dev)
             tail = (B, ncls, C.c_float(1.0 / (world_size(group) * win_k)), ptr(self._amp(dev)) if fp16 else None,
                     ptr(gv["_found_inf"]) if fp16 else None, stream(dev))
-            if class_weight is not None or logit_bias is not None:
-                check(self._lib().cara_cross_entropy_bal(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(class_weight),
-                                                         ptr(logit_bias), ptr(self._loss_buf), ptr(self._dlogits), *tail),
-                      "cara_cross_entropy_bal")
-            elif mix is None and smoothing == 0.0:
-                check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(self._loss_buf), ptr(self._dlogits), *tail),
-                      "cara_cross_entropy_ex")
-            else:
-                check(self._lib().cara_cross_entropy_mix(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(self._loss_buf),
-                                                         ptr(self._dlogits), *tail), "cara_cross_entropy_mix")
-            self._run_backward(self._dlogits, droppath, hw, cp, prescaled=True)
+
+            def loss_and_backward(logits, loss_buf):
+                if class_weight is not None or logit_bias is not None:
+                    check(self._lib().cara_cross_entropy_bal(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(class_weight),
+                                                             ptr(logit_bias), ptr(loss_buf), ptr(self._dlogits), *tail),
+                          "cara_cross_entropy_bal")
+                elif mix is None and smoothing == 0.0:
+                    check(self._lib().cara_cross_entropy_ex(ptr(logits), ptr(labels), ptr(loss_buf), ptr(self._dlogits), *tail),
+                          "cara_cross_entropy_ex")
+                else:
+                    check(self._lib().cara_cross_entropy_mix(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(loss_buf),
+                                                             ptr(self._dlogits), *tail), "cara_cross_entropy_mix")
+                self._run_backward(self._dlogits, droppath, hw, cp, prescaled=True)
+            loss_and_backward(logits, self._loss_buf)
+            if rho is not None:
+                # the gradient at w + rho g1 / |g1| in g1's place: measure, move, the same forward / loss / backward again, move back
+                # -- before the accumulate and the tail, which then work on g2 as they did on g1
+                sam = self._sam_perturb(model, dev, B, rho)
+                loss_and_backward(forward(droppath, hw, hb, cp), sam["loss"])
+                self._sam_restore(sam, dev)
             if win_k > 1:
                 self._accumulate_flat(win_i, win_k, dev)
             if win_i == win_k - 1:
@@ -758,6 +787,66 @@ class CaraEngine:
                 if ema is not None:
                     ema.update()
         return self._loss_buf[0]
+
+    # ------------------------------------------------------------------ sharpness-aware minimisation
+    sam_loss = None   # device scalar: the loss of the last SAM step's second pass (at the perturbed weights)
+    sam_norm = None   # device float [4] of the last SAM step: (found-inf carried over, |g1|, scale applied -- 0: weights left alone, 0)
+
+    @staticmethod
+    def _sam_rho(sam_rho) -> Optional[float]:
+        """``sam_rho``: None (the plain step) or the radius of SAM's L2 ball, a finite number >= 0"""
+        if sam_rho is None:
+            return None
+        if isinstance(sam_rho, bool) or not isinstance(sam_rho, (int, float)) or not (0.0 <= sam_rho < float("inf")):   # (a NaN fails the comparison)
+            raise CaraError(f"sam_rho must be None or a finite number >= 0, not {sam_rho!r}")
+        return float(sam_rho)
+
+    def _sam_perturb(self, model, dev, B, rho):
+        """between the two passes of a SAM step: |g1| over the gradient elements of the flat buffer (``cara_grad_clip`` with
+        max_norm = inf writes no gradient; scratch and result are SAM's own, ``grad_norm`` stays the clip's), then
+        ``cara_sam_perturb`` over the trainable tensors -- the backups live in one flat buffer with the gradient buffer's layout.
+        -> the step's SAM buffers.  Nothing is read on the host."""
+        flat, views = self._flat_grad, self._grad_views
+        params = self.trainable_parameters()
+        n = flat.numel() - 1
+
+        def make():
+            from .dist import flat_views
+            nbytes = int(self._lib().cara_grad_clip_scratch_bytes(n))
+            if nbytes == 0:
+                raise CaraError(f"cara_grad_clip takes 1 .. 2^31 elements, not {n}")
+            names = list(self.cp_fields) + ["head_w", "head_b"]
+            backup, bviews = flat_views([(nm, views[nm].shape) for nm in names], dev)
+            return {"scratch": torch.empty(nbytes // 4, device=dev), "norm": torch.zeros(2, device=dev), "state": torch.zeros(4, device=dev),
+                    "backup": backup, "views": [bviews[nm] for nm in names], "grads": [views[nm] for nm in names], "plan": None}
+        sam = self._pinned("sam", dev, (n, flat.data_ptr()), make)
+        loss = self._pinned("sam_loss", dev, B, lambda: torch.empty(1 + B, device=dev))
+        key = tuple(p.data_ptr() for p in params)
+        if sam["plan"] is None or sam["plan"][0] != key:   # (the host arrays are kept while no parameter moves, as ParamEma's)
+            k = len(params)
+            if k > L.ADAMW_MAX_TENSORS:
+                raise CaraError(f"sam_rho: {k} trainable tensors, one launch carries {L.ADAMW_MAX_TENSORS}")
+            for p, g in zip(params, sam["grads"]):
+                if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or p.numel() != g.numel():
+                    raise CaraError("sam_rho moves the trainable tensors in place: contiguous fp32 parameters on the step's device")
+            arr = lambda ts: (C.c_void_p * k)(*[t.data_ptr() for t in ts])   # noqa: E731
+            sam["plan"] = (key, k, arr(params), arr(sam["grads"]), arr(sam["views"]), (C.c_size_t * k)(*[p.numel() for p in params]))
+        found = views["_found_inf"] if self.precision == "fp16" else None
+        _, k, parr, garr, barr, narr = sam["plan"]
+        lib = self._lib()
+        check(lib.cara_grad_clip(ptr(flat), n, float("inf"), ptr(sam["scratch"]), ptr(found), ptr(sam["norm"]), stream(dev)), "cara_grad_clip")
+        check(lib.cara_sam_perturb(k, parr, garr, barr, narr, rho, ptr(sam["norm"]), ptr(found), ptr(sam["state"]), stream(dev)),
+              "cara_sam_perturb")
+        sam["loss"] = loss
+        self.sam_loss, self.sam_norm = loss[0], sam["state"]
+        return sam
+
+    def _sam_restore(self, sam, dev):
+        """behind the second backward: the weights back from the backup, bit for bit, and the first pass's found-inf word added to
+        the one the second pass's loss launch cleared"""
+        _, k, parr, _, barr, narr = sam["plan"]
+        found = self._grad_views["_found_inf"] if self.precision == "fp16" else None
+        check(self._lib().cara_sam_restore(k, parr, barr, narr, ptr(sam["state"]), ptr(found), stream(dev)), "cara_sam_restore")
 
     # ------------------------------------------------------------------ training from a resident uint8 split
     def _bad_rows(self, dev):
@@ -839,7 +928,7 @@ class CaraEngine:
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
                             mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None, ra=None,
-                            class_weight=None, logit_bias=None):
+                            class_weight=None, logit_bias=None, sam_rho=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -866,13 +955,16 @@ class CaraEngine:
         equalize) before the jitter chain, the mix and the rest (``cara_vit_forward_u8_rows_ra``; with or without the other tables).
         A table entry the kernel refuses -- ``data.check_ra`` -- gives a zero image, counted like a bad row.
         ``class_weight`` / ``logit_bias`` as in ``train_step``: on the soft target of both labels where there is a ``mix`` table.
+        ``sam_rho`` as in ``train_step``: the second pass reads the same rows through the same tables -- the feed is deterministic, erase
+        noise included, so its input is bit for bit the first pass's.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
+        self._sam_rho(sam_rho)
         feed = Feed(rows, boxes, mix, aug, keep, ra)
         model, dev = self._resident_args(split, feed)
         return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._run_forward_on(model, split, feed, dp, hw, hb, cp, True, dev),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema,
-                          class_weight, logit_bias)
+                          class_weight, logit_bias, sam_rho)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
                          keep=None, ra=None):

@@ -132,9 +132,13 @@ class GraphedTrainStep:
     lives in device memory and ``ema.advance()`` runs before every step, as ``optimizer.advance()`` does.
     ``class_weight`` / ``logit_bias`` (``train_step``'s): the graph captures the two tensors' addresses, so they are held here and in
     every entry and their identity is part of the key; a replay re-reads their contents, as it re-reads a mix table -- an in-place
-    change takes effect at the next call (and is checked there, on the host, before the replay)."""
+    change takes effect at the next call (and is checked there, on the host, before the replay).
+    ``sam_rho`` (``train_step``'s): both passes of the SAM step, the measuring launches and the two launches that move the weights and
+    put them back are captured in the ONE graph; the value is part of the key (``("sam_rho", rho)``), and the engine's SAM buffers
+    are never replaced, so the graph's addresses stay good."""
 
-    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None, class_weight=None, logit_bias=None):
+    def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None, class_weight=None, logit_bias=None,
+                 sam_rho=None):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
         if ema is not None and not getattr(ema, "capturable", False):
@@ -143,6 +147,7 @@ class GraphedTrainStep:
         self.label_smoothing = engine._smoothing(label_smoothing) if label_smoothing else 0.0
         self.clip_grad = engine._max_norm(clip_grad)
         self.class_weight, self.logit_bias = class_weight, logit_bias
+        self.sam_rho = engine._sam_rho(sam_rho)
         self._graphs = {}   # key -> "warm", then (graph, source, static inputs, loss, held): source is the split, None for images
 
     def _kw(self):
@@ -156,6 +161,8 @@ class GraphedTrainStep:
             kw["class_weight"] = self.class_weight
         if self.logit_bias is not None:
             kw["logit_bias"] = self.logit_bias
+        if self.sam_rho is not None:
+            kw["sam_rho"] = self.sam_rho
         return kw
 
     def __call__(self, x, y, group=None, accumulate=None, keep=None):
@@ -200,6 +207,8 @@ class GraphedTrainStep:
         key = (*key, tuple(tuple(t.shape) for t in live), bool(model.training), eng.precision, self.label_smoothing, self.clip_grad)
         if self.class_weight is not None or self.logit_bias is not None:
             key = (*key, id(self.class_weight), id(self.logit_bias))
+        if self.sam_rho is not None:
+            key = (*key, ("sam_rho", self.sam_rho))
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -234,7 +243,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
         accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
-        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob"):
+        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob", sam_rho=None):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -293,7 +302,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``eval_views`` (a ``data.EvalViews``; ``eval_mode = "sharded"`` only, ``test_batches`` a ``ResidentSplit`` of any stored size) and
     ``eval_combine`` (``"prob"`` / ``"logit"``): the evaluation epochs score every test image through those views
     (``CaraEngine.evaluate(views=, combine=)``: centre crop, flips, five / ten crops) -- the raw and the averaged pass alike, with
-    either ``eval_metric``.  None (default): the calls that were always made."""
+    either ``eval_metric``.  None (default): the calls that were always made.
+    ``sam_rho`` (a number >= 0): every training step of either feed is a sharpness-aware one (``train_step(..., sam_rho=)``: two
+    forward/backward passes per micro-step, the optimiser steps on the gradient at the perturbed weights) -- with ``accum_steps``,
+    ``clip_grad`` and ``ema_decay``, eager or graphed (both passes in the one graph).  Not with ``weight_dropout = "exact"``."""
     if eval_views is not None and eval_mode != "sharded":
         raise CaraError("fit: eval_views are read by CaraEngine.evaluate(views=): they need eval_mode = 'sharded'")
     if eval_metric not in ("top1", "mean_per_class"):
@@ -317,6 +329,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     smooth = {"label_smoothing": eng._smoothing(label_smoothing)} if label_smoothing else {}
     if clip_grad is not None:
         smooth["clip_grad"] = eng._max_norm(clip_grad)
+    if sam_rho is not None:
+        smooth["sam_rho"] = eng._sam_rho(sam_rho)
     if class_weight is not None or logit_bias is not None:
         if not hasattr(model.head, "weight"):
             raise CaraError("the classifier head must be a Linear (num_classes > 0)")

@@ -654,6 +654,26 @@ int cara_grad_clip(float* g, size_t n, float max_norm, float* scratch, const flo
  * writes nothing.  Only enqueues.                                                                                              */
 int cara_ema_update(int ntensors, float* const* ema, const float* const* param, const size_t* n, float weight,
                     const float* weight_dev, void* stream);
+/* Sharpness-aware minimisation (Foret et al.) around the second pass of a step, cara_ema_update's scheme: param, grad, backup and n
+ * are HOST arrays of ntensors entries (1 <= ntensors <= CARA_ADAMW_MAX_TENSORS), carried by value in the kernel arguments; ONE launch
+ * each; 16-byte accesses for a tensor whose pointers are all 16-byte aligned, dword accesses otherwise: the same bits.
+ * cara_sam_perturb: backup[i][j] = param[i][j] (bitwise) for every element, then, with norm a device float holding the global L2 norm
+ * of all grad tensors (out[0] of a measuring cara_grad_clip),
+ *   scale = rho / (norm + 1e-12f)          two IEEE fp32 operations, the same in every thread (1e-12: the published implementation's)
+ *   param = param + scale * grad           one fp32 multiply, then one fp32 add -- no fma
+ * found_inf (device float or NULL) != 0, or a norm that is not finite: the backup is written all the same and param is left untouched.
+ * Workgroup 0 writes state (device float[4]) = { carry, norm read, scale applied, 0 }: carry = *found_inf (0 for NULL), and the scale
+ * applied is 0 where param was left untouched.  grad is never written.
+ * cara_sam_restore: param[i][j] = backup[i][j], a copy of the bits (-0, subnormals and NaN payloads come back: never param - e), and,
+ * where found_inf is given, one thread does *found_inf += state[0] -- the cross-entropy launch of the second pass has cleared the
+ * word, and an overflow of the first pass must still skip the step and back the loss scale off, once.
+ * CARA_E_ARG, nothing launched: a null array or entry, n[i] == 0, ntensors out of range, a pointer that is not 4-byte aligned,
+ * backup[i] overlapping param[i] or grad[i], rho < 0 or not finite, a null norm or state.  Both only enqueue and capture into a
+ * hipGraph.                                                                                                                        */
+int cara_sam_perturb(int ntensors, float* const* param, const float* const* grad, float* const* backup, const size_t* n, float rho,
+                     const float* norm, const float* found_inf, float* state, void* stream);
+int cara_sam_restore(int ntensors, float* const* param, const float* const* backup, const size_t* n, const float* state,
+                     float* found_inf, void* stream);
 
 /* ---- exact weight-space dropout mode (the reference's train-mode arithmetic, cara.py:35,57,81,92) ---- */
 /* keep(o,i) of linear `linear_id` = (cara_weight_dropout_hash(o*in + i, seed, linear_id) >> 8) >= p * 2^24
