@@ -75,7 +75,7 @@ template <int RP>
 __global__ __launch_bounds__(256) void contract_tile_kernel(const float* __restrict__ dW, int nslab, size_t slab_stride,
                                                             const bf16* __restrict__ U, const bf16* __restrict__ Vs,
                                                             float* __restrict__ pV, float* __restrict__ pU, int out, int in,
-                                                            unsigned seed, unsigned lin, unsigned thresh, float inv_keep) {
+                                                            unsigned seed, unsigned lin, unsigned thresh, float inv_keep, bool vec4) {
   __shared__ float g[64][65];
   __shared__ __attribute__((aligned(16))) float us[64][RP + 4];
   __shared__ __attribute__((aligned(16))) float vs[64][RP + 4];
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void contract_tile_kernel(const float* __restr
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (o < out) {
       const size_t e = (size_t)o * in + i;
-      if (i + 4 <= in && (in & 3) == 0) {
+      if (vec4 && i + 4 <= in) {   // (vec4: decided by the entry point -- in % 4, slab_stride % 4 and dW's address)
         f32x4 a = *reinterpret_cast<const f32x4*>(dW + e);
         for (int sidx = 1; sidx < nslab; ++sidx) a += *reinterpret_cast<const f32x4*>(dW + e + sidx * slab_stride);
 #pragma unroll
@@ -170,14 +170,14 @@ __global__ __launch_bounds__(256) void reduce_chunks_kernel(const float* __restr
 // reads 256 columns of two rows per instruction (16 bytes per lane: lanes 0..31 one row, 32..63 the next); the two row
 // halves and the workgroup's four waves are summed in fixed order into scratch [chunk][N]; reduce_chunks_kernel
 // finishes.  (The first form read two bytes per lane: 32 us for 19 - 77 MB.)
-__global__ __launch_bounds__(256) void colsum_kernel(const bf16* __restrict__ X, int ld, int M, int N, float* __restrict__ scratch) {
+__global__ __launch_bounds__(256) void colsum_kernel(const bf16* __restrict__ X, int ld, int M, int N, float* __restrict__ scratch, bool vec8) {
   __shared__ float part[4][2][256];   // [wave][row of the instruction's pair][column]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cl = (lane & 31) * 8, rp = lane >> 5;           // 32 lanes x 8 columns = 256 columns; two rows per instruction
   const int c0 = blockIdx.x * 256 + cl;
   const int per = (M + gridDim.y - 1) / gridDim.y, m_begin = blockIdx.y * per, m_end = min(M, m_begin + per);
   float s[8] = {};
-  const bool vec = c0 + 8 <= N && (ld & 7) == 0;
+  const bool vec = vec8 && c0 + 8 <= N;   // (vec8: decided by the entry point -- ld % 8 and X's address)
   for (int m = m_begin + wave * 2 + rp; m < m_end; m += 8) {
     if (vec) {
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(X + (size_t)m * ld + c0);
@@ -250,10 +250,13 @@ extern "C" int cara_dropout_grad_contract(const float* dW, int nslab, size_t sla
   float* pV = static_cast<float*>(scratch);               // [ti][out][Rp]
   float* pU = pV + (size_t)ti * out * Rp;                  // [to][in][Rp]
   const dim3 grid(ti, to);
+  // the 16-byte loads of a row of four are legal only where every slab's every row starts on a 16-byte boundary; anything else
+  // takes the scalar path, which adds the slabs in the same order (the same bits)
+  const bool vec4 = (in & 3) == 0 && (reinterpret_cast<uintptr_t>(dW) & 15) == 0 && (nslab == 1 || (slab_stride & 3) == 0);
   if (Rp == 32)
-    hipLaunchKernelGGL(contract_tile_kernel<32>, grid, dim3(256), 0, st, dW, nslab, slab_stride, (const bf16*)U, (const bf16*)Vs, pV, pU, out, in, seed, linear_id, thresh, inv_keep);
+    hipLaunchKernelGGL(contract_tile_kernel<32>, grid, dim3(256), 0, st, dW, nslab, slab_stride, (const bf16*)U, (const bf16*)Vs, pV, pU, out, in, seed, linear_id, thresh, inv_keep, vec4);
   else
-    hipLaunchKernelGGL(contract_tile_kernel<64>, grid, dim3(256), 0, st, dW, nslab, slab_stride, (const bf16*)U, (const bf16*)Vs, pV, pU, out, in, seed, linear_id, thresh, inv_keep);
+    hipLaunchKernelGGL(contract_tile_kernel<64>, grid, dim3(256), 0, st, dW, nslab, slab_stride, (const bf16*)U, (const bf16*)Vs, pV, pU, out, in, seed, linear_id, thresh, inv_keep, vec4);
   const size_t nv = (size_t)out * Rp, nu = (size_t)in * Rp;
   hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, pV, ti, nv, dVs);
   hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, st, pU, to, nu, dU);
@@ -270,7 +273,9 @@ extern "C" int cara_colsum_bf16(const void* X, int ld, int M, int N, float* out,
   int chunks = M >= 256 ? (512 * 256 + N - 1) / N : 1;
   chunks = chunks > 256 ? 256 : chunks;
   while (chunks > 1 && M / chunks < 16) chunks >>= 1;
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 255) / 256, chunks), dim3(256), 0, st, (const bf16*)X, ld, M, N, static_cast<float*>(scratch));
+  // 16-byte loads need ld % 8 == 0 and a 16-byte aligned X; anything else takes the scalar path (the same order, the same bits)
+  const bool vec8 = (ld & 7) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  hipLaunchKernelGGL(colsum_kernel, dim3((N + 255) / 256, chunks), dim3(256), 0, st, (const bf16*)X, ld, M, N, static_cast<float*>(scratch), vec8);
   hipLaunchKernelGGL(reduce_chunks_kernel, dim3((N + 255) / 256), dim3(256), 0, st, static_cast<const float*>(scratch), chunks, (size_t)N, out);
   CARA_CHECK_LAUNCH();
   return CARA_OK;

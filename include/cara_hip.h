@@ -688,13 +688,17 @@ int cara_materialize_merge(const void* W, const void* U, const void* Vs, int Rp,
 /* From the dense weight gradient dW (= dY^T X, given as `nslab` split-K partial slabs of fp32 [out,in], slab_stride
  * floats apart, summed on the fly) to the skinny quantities cara_factor_grad_reduce takes:
  * dVs[o,r] = sum_i keep/(1-p) dW[o,i] U[i,r], dU[i,r] = sum_o keep/(1-p) dW[o,i] Vs[o,r] (fp32 [out,Rp] / [in,Rp],
- * overwritten, fixed summation order; ONE pass over dW for both).  scratch: cara_dropout_grad_scratch_bytes(out, in, Rp). */
+ * overwritten, fixed summation order; ONE pass over dW for both).  scratch: cara_dropout_grad_scratch_bytes(out, in, Rp).
+ * dW needs only the alignment of a float and slab_stride may be any number of floats: the entry point reads dW sixteen bytes at
+ * a time where in % 4 == 0, dW is 16-byte aligned and (nslab == 1 or slab_stride % 4 == 0), and element by element otherwise --
+ * the same sums in the same order, the same bits.  U and Vs are rows of Rp 16-bit values, 16-byte aligned (the operand pack's). */
 size_t cara_dropout_grad_scratch_bytes(int out, int in, int Rp);
 int cara_dropout_grad_contract(const float* dW, int nslab, size_t slab_stride, const void* U, const void* Vs, int Rp,
                                int out, int in, float p, unsigned seed, unsigned linear_id, float* dU, float* dVs,
                                void* scratch, void* stream);
 /* out fp32 [N] = column sums of a bf16 [M, ld] matrix (dc = sum_m dY), fixed order; scratch:
- * cara_colsum_scratch_bytes(N).                                                                               */
+ * cara_colsum_scratch_bytes(N).  X needs only the alignment of its elements and ld >= N: rows are read sixteen bytes at a time
+ * where ld % 8 == 0 and X is 16-byte aligned, element by element otherwise (the same order, the same bits).       */
 size_t cara_colsum_scratch_bytes(int N);
 int cara_colsum_bf16(const void* X, int ld, int M, int N, float* out, void* scratch, void* stream);
 

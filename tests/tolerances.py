@@ -66,3 +66,15 @@ GEMM_CAPS = {"bf16": 0.005, "gelu_h": 0.01, "gelu_u": 0.005, "gelu_dg": 0.005, "
 # all eight geometries, both draws and both builds (fp16: Vs_qkv of the order-5 geometry (5, 40, 5, 17); bf16: Vs_fc2 of the order-2
 # geometry; every other matrix 0.0001 or none), a hundredth of it; never fitted to a device.
 ADAPTER_CAPS = {"pack": 0.02}
+
+# The exact-dropout and order-2 kernels (oracle/exact_modes_model.py), per 16-bit output kind, under the same rule as GEMM_CAPS (the
+# share is taken over the elements whose derived term is below a quarter of their own 16-bit step; one neighbour case never breaks a
+# cap; a tensor with no capped element fails).  Chosen as there: the fp32 other-order restatement's largest share over all host
+# cases and both builds (tests/test_exact_modes_model.py, `python -m tests.test_exact_modes_model`; table in
+# docs/findings/exact_modes_contract.md section 3), doubled and rounded up to the next of 0.5 %, 1 %, 2 %; never fitted to a device.
+# Measured: merge_Weff 0.0008 (fp16, Gaussian; outlier 0.0005; bf16 none) -> 0.5 %; merge_Dm 0.0005 (fp16 Gaussian and bf16 early
+# training; outlier 0.0003) -> 0.5 %; dd_Dm 0.0003 (fp16; bf16 none) -> 0.5 %.  The early-training family of merge_Weff (Vs at 1e-6
+# next to W at 2e-2): the delta is far below W's step, almost every element is simply W, and the restatement has NO neighbour case
+# in either build; its derived term gamma(Rp + 2) (|W| + |delta|) stays below a quarter step, so the same cap is in force there, and
+# where a term is not below a quarter step no cap applies (the interval alone, as for the offset LayerNorm rows).
+EXACT_CAPS = {"merge_Weff": 0.005, "merge_Dm": 0.005, "dd_Dm": 0.005}
