@@ -476,6 +476,88 @@ __global__ __launch_bounds__(64) void xent_bal_kernel(const float* __restrict__ 
     loss_per[b] = ok ? (W * lse - dot) * invB : qnan;
   }
 }
+// The sigmoid family on xent_mix_kernel's soft target: per element (b, c), z = logits[b][c], q = q_c of xent_mix_kernel (the same
+// wa, wb, u and guards), with a threshold thr >= 0 replaced by (q > thr ? 1 : 0) -- timm's target.gt(thr), decided on the fp32 q.
+// Everything comes from ONE exponential that cannot overflow, e = __expf(-|z|) in [0, 1], and w = 1 + e in [1, 2]:
+//   L = log1p(e) = __logf(w) (e / (w - 1)), or e where w == 1: w - 1 is exact, and log(w) / (w - 1) barely moves when 1 + e rounds to
+//   w, so L keeps its RELATIVE accuracy down to the smallest e -- __logf(1 + e) alone is off by u absolutely, 1e-3 of L at |z| = 9,
+//   which the focal loss multiplies into the gradient of every easy negative;
+//   sp(z) = max(z, 0) + L,  sp(-z) = max(-z, 0) + L  (softplus; -log sigma(-z) and -log sigma(z)),
+//   r = 1 / w,  sigma(|z|) = r,  sigma(-|z|) = e r:  s+ = sigma(z) and s- = sigma(-z) are these two in the order of z's sign --
+// neither is formed as 1 - the other.  The difference s+ - q is formed as (1 - q) s+ - q s- (s+ + s- = 1), a difference of two
+// non-negative products of which one is zero for a hard target: no cancellation at a saturated logit.
+// BCE (FOCAL = false):  l = (pw q) sp(-z) + (1 - q) sp(z),  dl/dz = (1 - q) s+ - (pw q) s-  [= s+ (1 - q + pw q) - pw q];  pw =
+//   pos_weight[c] or 1 -- torch's binary_cross_entropy_with_logits(z, q, pos_weight = pw).  A product with 1.f is exact: a vector of
+//   ones gives the bits of no vector.
+// Focal (FOCAL = true; torchvision's sigmoid_focal_loss on a soft q):  ce = q sp(-z) + (1 - q) sp(z),  m = q s- + (1 - q) s+ (a sum
+//   of non-negative terms),  a = alpha q + (1 - alpha)(1 - q) or 1,  l = a m^g ce,
+//   dl/dz = a [((1 - q) s+ - q s-) m^g + g ce m^(g - 1) s+ s- (1 - 2 q)].   m^(g - 1) is 1 at g == 1, m at g == 2 and
+//   __expf((g - 1) __logf(m)) for another g > 1 (0 at m == 0);  m^g = m^(g - 1) m;  g == 0 takes m^g = 1 and no second term.
+// term_b = (sum_c l) invBD,  invBD = the fp32 nearest to 1 / (B D), D = C (the mean over the classes) or 1 (their sum);
+// dlogits = dl/dz gsc,  gsc = invBD dscale loss scale.  One wave per sample, classes lane-strided, one pass; the loss does not depend
+// on whether dlogits is written.  Plain operators, no contraction: the bound of tests/sigmoid_loss_model.py counts every rounding.
+// Guards as in xent_mix_kernel; pos_weight is read by class index c only, never through a label.
+template <bool FOCAL>
+__global__ __launch_bounds__(64) void sigmoid_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                          const int* __restrict__ mix, float eps, float thr, float fg, float alpha,
+                                                          const float* __restrict__ pw, float* __restrict__ loss_per,
+                                                          float* __restrict__ dlogits, int B, int C, float invBD, float dscale,
+                                                          const float* __restrict__ loss_scale) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* lr = logits + (size_t)b * C;
+  const int partner = mix ? mix[(size_t)b * 8] : b;
+  const float t = mix ? __int_as_float(mix[(size_t)b * 8 + 6]) : 0.f;
+  const int64_t yal = labels[b];
+  const bool pok = partner >= 0 && partner < B;
+  const int64_t ybl = pok ? labels[partner] : -1;
+  const bool ok = yal >= 0 && yal < C && ybl >= 0 && ybl < C && t >= 0.f && t <= 1.f;   // (wave-uniform)
+  const int ya = ok ? (int)yal : 0, yb = ok ? (int)ybl : 0;
+  const float wa = (1.f - eps) * (1.f - t), wb = (1.f - eps) * t, u = eps / (float)C;   // (xent_mix_kernel's)
+  const float qnan = __builtin_nanf("");
+  const float gsc = invBD * dscale * (loss_scale ? *loss_scale : 1.f);
+  const float g1 = fg - 1.f, oma = 1.f - alpha;
+  float sl = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float z = lr[c];
+    float q = (c == ya ? wa : 0.f) + (c == yb ? wb : 0.f) + u;
+    if (thr >= 0.f) q = q > thr ? 1.f : 0.f;
+    const float omq = 1.f - q;
+    const float e = __expf(-fabsf(z)), w = 1.f + e, r = 1.f / w, er = e * r;
+    const float L = w == 1.f ? e : __logf(w) * (e / (w - 1.f));
+    const bool pos = z >= 0.f;
+    const float sp = pos ? r : er, sm = pos ? er : r;                 // sigma(z), sigma(-z)
+    const float spz = fmaxf(z, 0.f) + L, spn = fmaxf(-z, 0.f) + L;    // softplus(z), softplus(-z)
+    float l, g;
+    if (!FOCAL) {
+      const float pq = (pw ? pw[c] : 1.f) * q;
+      l = pq * spn + omq * spz;
+      g = omq * sp - pq * sm;
+    } else {
+      const float ce = q * spn + omq * spz;
+      const float m = q * sm + omq * sp;
+      const float d0 = omq * sp - q * sm;
+      if (fg == 0.f) {
+        l = ce;
+        g = d0;
+      } else {
+        const float mg1 = fg == 1.f ? 1.f : fg == 2.f ? m : __expf(g1 * __logf(m));
+        const float mg = mg1 * m;
+        l = mg * ce;
+        g = d0 * mg + fg * ce * mg1 * (sp * sm) * (1.f - 2.f * q);
+      }
+      if (alpha >= 0.f) {
+        const float a = alpha * q + oma * omq;
+        l = a * l;
+        g = a * g;
+      }
+    }
+    sl += l;
+    if (dlogits) dlogits[(size_t)b * C + c] = ok ? g * gsc : qnan;
+  }
+  sl = wave_sum(sl);
+  if (lane == 0) loss_per[b] = ok ? sl * invBD : qnan;
+}
 __global__ __launch_bounds__(64) void xent_sum_kernel(const float* __restrict__ loss_per, float* __restrict__ loss, int B,
                                                       float* __restrict__ found_inf) {
   float s = 0.f;
@@ -745,6 +827,29 @@ extern "C" int cara_cross_entropy_bal(const float* logits, const int64_t* labels
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(xent_bal_kernel, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, class_weight, logit_bias, loss + 1,
                      dlogits, B, C, dscale, loss_scale);
+  CARA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+extern "C" int cara_sigmoid_loss(const float* logits, const int64_t* labels, const int* mix, float smoothing, float target_threshold,
+                                 float gamma, float alpha, const float* pos_weight, int sum_classes, float* loss, float* dlogits,
+                                 int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream) {
+  if (!logits || !labels || !loss || B <= 0 || C <= 0 || !(dscale > 0.f) || !(smoothing >= 0.f && smoothing < 1.f)) return CARA_E_ARG;
+  // (every comparison is written so that a NaN fails it)
+  if (!(target_threshold < 1.f) || !(alpha <= 1.f) || (sum_classes != 0 && sum_classes != 1)) return CARA_E_ARG;
+  if (!(gamma == 0.f || (gamma >= 1.f && gamma <= 3.0e38f))) return CARA_E_ARG;
+  const bool focal = gamma > 0.f || alpha >= 0.f;
+  if (focal && pos_weight) return CARA_E_ARG;
+  const float thr = target_threshold < 0.f ? -1.f : target_threshold, al = alpha < 0.f ? -1.f : alpha;
+  const float invBD = (float)(1.0 / ((double)B * (double)(sum_classes ? 1 : C)));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (focal)
+    hipLaunchKernelGGL(sigmoid_loss_kernel<true>, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, thr, gamma, al, nullptr,
+                       loss + 1, dlogits, B, C, invBD, dscale, loss_scale);
+  else
+    hipLaunchKernelGGL(sigmoid_loss_kernel<false>, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, thr, 0.f, -1.f, pos_weight,
+                       loss + 1, dlogits, B, C, invBD, dscale, loss_scale);
   CARA_CHECK_LAUNCH();
   hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
   CARA_CHECK_LAUNCH();

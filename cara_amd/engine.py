@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 from ._lib import CaraError, check, ptr, stream
 from .feed import TABLES, Feed
+from .loss import check_loss
 
 
 def _rp(rank: int) -> int:
@@ -639,7 +640,7 @@ class CaraEngine:
 
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
                    label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, keep=None, class_weight=None,
-                   logit_bias=None, sam_rho=None):
+                   logit_bias=None, sam_rho=None, loss=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -683,9 +684,15 @@ class CaraEngine:
         weights alone and is carried into the found-inf word behind the second pass -- the step is skipped and the scale backed
         off once.  ``sam_rho = 0.0`` runs both passes and leaves the gradients of the plain step, bit for bit.  Refused with
         ``weight_dropout = "exact"`` in train mode: that mode draws a fresh mask seed per forward, so the two passes would not see
-        the same masks.  None: the launches are the ones they were."""
+        the same masks.  None: the launches are the ones they were.
+        ``loss`` (None, a ``cara_amd.loss.BCE`` or a ``cara_amd.loss.Focal``): a sigmoid loss in the cross-entropy's place
+        (``cara_sigmoid_loss``) on the same soft target -- labels, ``mix`` table and ``label_smoothing`` -- with the same pre-divided,
+        loss-scaled ``dlogits``; it runs in both passes of a SAM step and composes with everything above.  Refused beside
+        ``class_weight`` / ``logit_bias``, which are the softmax loss's.  A BCE's ``pos_weight`` is checked like ``class_weight``.
+        None: the launches are the ones they were."""
         eps = self._smoothing(label_smoothing)
         self._sam_rho(sam_rho)
+        check_loss(loss, class_weight, logit_bias)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
@@ -695,7 +702,7 @@ class CaraEngine:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp, keep=keep),
                           lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema,
-                          class_weight, logit_bias, sam_rho)
+                          class_weight, logit_bias, sam_rho, loss)
 
     def _class_vectors(self, class_weight, logit_bias, ncls, dev):
         """``class_weight`` / ``logit_bias`` of a step, refused here -- before anything is launched -- unless each is None or a
@@ -716,14 +723,16 @@ class CaraEngine:
                 seen[name] = key
 
     def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None,
-              ema=None, class_weight=None, logit_bias=None, sam_rho=None):
+              ema=None, class_weight=None, logit_bias=None, sam_rho=None, loss=None):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
         (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one, with a
-        ``class_weight`` or a ``logit_bias`` the weighted, logit-adjusted one on that target.
+        ``class_weight`` or a ``logit_bias`` the weighted, logit-adjusted one on that target, with a ``loss`` object the sigmoid loss
+        it describes on that target.
         ``accumulate``, ``clip_grad``, ``ema`` and ``sam_rho`` as in ``train_step``."""
         model = self._model()
         rho = self._sam_rho(sam_rho)
+        check_loss(loss, class_weight, logit_bias)
         if rho is not None and self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0:
             raise CaraError("sam_rho cannot run with weight_dropout = 'exact' in train mode: that mode draws a fresh mask seed per "
                             "forward, so the two passes of a SAM step would see different masks")
@@ -740,6 +749,8 @@ class CaraEngine:
             raise CaraError("model parameters and images must be on the same device")
         self._refuse_fp16_unfactored()
         self._class_vectors(class_weight, logit_bias, hw.shape[0], dev)
+        if loss is not None:
+            loss.check_pos_weight(hw.shape[0], dev, self.__dict__.setdefault("_class_vec_ok", {}))
         self._enter_window(win_i, win_k, B)
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
@@ -762,7 +773,12 @@ class CaraEngine:
                     ptr(gv["_found_inf"]) if fp16 else None, stream(dev))
 
             def loss_and_backward(logits, loss_buf):
-                if class_weight is not None or logit_bias is not None:
+                if loss is not None:
+                    thr, fgamma, alpha = loss.c_args()
+                    check(self._lib().cara_sigmoid_loss(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), C.c_float(thr),
+                                                        C.c_float(fgamma), C.c_float(alpha), ptr(loss.pos_weight), int(loss.sum_classes),
+                                                        ptr(loss_buf), ptr(self._dlogits), *tail), "cara_sigmoid_loss")
+                elif class_weight is not None or logit_bias is not None:
                     check(self._lib().cara_cross_entropy_bal(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), ptr(class_weight),
                                                              ptr(logit_bias), ptr(loss_buf), ptr(self._dlogits), *tail),
                           "cara_cross_entropy_bal")
@@ -928,7 +944,7 @@ class CaraEngine:
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
                             mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None, ra=None,
-                            class_weight=None, logit_bias=None, sam_rho=None):
+                            class_weight=None, logit_bias=None, sam_rho=None, loss=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -957,14 +973,16 @@ class CaraEngine:
         ``class_weight`` / ``logit_bias`` as in ``train_step``: on the soft target of both labels where there is a ``mix`` table.
         ``sam_rho`` as in ``train_step``: the second pass reads the same rows through the same tables -- the feed is deterministic, erase
         noise included, so its input is bit for bit the first pass's.
+        ``loss`` as in ``train_step``: on the soft target of both labels where there is a ``mix`` table.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
         self._sam_rho(sam_rho)
+        check_loss(loss, class_weight, logit_bias)
         feed = Feed(rows, boxes, mix, aug, keep, ra)
         model, dev = self._resident_args(split, feed)
         return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._run_forward_on(model, split, feed, dp, hw, hb, cp, True, dev),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema,
-                          class_weight, logit_bias, sam_rho)
+                          class_weight, logit_bias, sam_rho, loss)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
                          keep=None, ra=None):

@@ -19,6 +19,7 @@ import torch
 
 from ._lib import CaraError
 from .feed import Feed
+from .loss import BCE, check_loss
 
 
 class CosineLRScheduler:
@@ -135,10 +136,13 @@ class GraphedTrainStep:
     change takes effect at the next call (and is checked there, on the host, before the replay).
     ``sam_rho`` (``train_step``'s): both passes of the SAM step, the measuring launches and the two launches that move the weights and
     put them back are captured in the ONE graph; the value is part of the key (``("sam_rho", rho)``), and the engine's SAM buffers
-    are never replaced, so the graph's addresses stay good."""
+    are never replaced, so the graph's addresses stay good.
+    ``loss`` (``train_step``'s: a ``loss.BCE`` or ``loss.Focal``): the object -- and with it a BCE's ``pos_weight`` tensor, whose address
+    the graph captures -- is held here and in every entry; its settings and that tensor's identity are part of the key, and a replay
+    re-reads the tensor's contents as it re-reads ``class_weight`` (checked on the host before the replay)."""
 
     def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None, class_weight=None, logit_bias=None,
-                 sam_rho=None):
+                 sam_rho=None, loss=None):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
         if ema is not None and not getattr(ema, "capturable", False):
@@ -148,6 +152,7 @@ class GraphedTrainStep:
         self.clip_grad = engine._max_norm(clip_grad)
         self.class_weight, self.logit_bias = class_weight, logit_bias
         self.sam_rho = engine._sam_rho(sam_rho)
+        self.loss = check_loss(loss, class_weight, logit_bias)
         self._graphs = {}   # key -> "warm", then (graph, source, static inputs, loss, held): source is the split, None for images
 
     def _kw(self):
@@ -163,6 +168,8 @@ class GraphedTrainStep:
             kw["logit_bias"] = self.logit_bias
         if self.sam_rho is not None:
             kw["sam_rho"] = self.sam_rho
+        if self.loss is not None:
+            kw["loss"] = self.loss
         return kw
 
     def __call__(self, x, y, group=None, accumulate=None, keep=None):
@@ -172,11 +179,13 @@ class GraphedTrainStep:
         if self.eng._window(accumulate)[1] > 1:
             raise CaraError("GraphedTrainStep: accumulate with k > 1 is not supported (the window spans several graph replays)")
         eng, kw = self.eng, self._kw()
-        if self.class_weight is not None or self.logit_bias is not None:
+        if self.class_weight is not None or self.logit_bias is not None or self.loss is not None:
             head = eng._model().head
             if not hasattr(head, "weight"):
                 raise CaraError("the classifier head must be a Linear (num_classes > 0)")
             eng._class_vectors(self.class_weight, self.logit_bias, head.weight.shape[0], head.weight.device)
+            if self.loss is not None:
+                self.loss.check_pos_weight(head.weight.shape[0], head.weight.device, eng.__dict__.setdefault("_class_vec_ok", {}))
         if hasattr(x, "pixels"):
             feed = Feed.of(y)
             if feed.keep is None and keep is not None:
@@ -209,6 +218,8 @@ class GraphedTrainStep:
             key = (*key, id(self.class_weight), id(self.logit_bias))
         if self.sam_rho is not None:
             key = (*key, ("sam_rho", self.sam_rho))
+        if self.loss is not None:
+            key = (*key, ("loss", *self.loss.key()))
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -229,7 +240,8 @@ class GraphedTrainStep:
             torch.cuda.current_stream(dev).wait_stream(side)
             # (the last element keeps what the engine would replace at an eager step of another batch size in between -- its dlogits
             # buffer and the workspace of this shape -- as ``loss`` keeps its loss buffer: the graph holds their addresses)
-            ent = self._graphs[key] = (gr, key[1], static, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"], self.class_weight, self.logit_bias))
+            ent = self._graphs[key] = (gr, key[1], static, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"], self.class_weight, self.logit_bias,
+                                                                   self.loss, getattr(self.loss, "pos_weight", None)))
             # (the capture itself ran nothing: fall through to the replay, which is this call's step)
         gr, _, static, loss = ent[:4]
         for s, t in zip(static, live):
@@ -243,7 +255,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
         accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
-        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob", sam_rho=None):
+        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob", sam_rho=None, loss=None):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -305,7 +317,12 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     either ``eval_metric``.  None (default): the calls that were always made.
     ``sam_rho`` (a number >= 0): every training step of either feed is a sharpness-aware one (``train_step(..., sam_rho=)``: two
     forward/backward passes per micro-step, the optimiser steps on the gradient at the perturbed weights) -- with ``accum_steps``,
-    ``clip_grad`` and ``ema_decay``, eager or graphed (both passes in the one graph).  Not with ``weight_dropout = "exact"``."""
+    ``clip_grad`` and ``ema_decay``, eager or graphed (both passes in the one graph).  Not with ``weight_dropout = "exact"``.
+    ``loss`` (a ``loss.BCE`` or ``loss.Focal``): every training step of either feed, eager or graphed, trains on that sigmoid loss
+    (``train_step(..., loss=)``); a BCE's ``pos_weight`` (host or device) is moved to the model's device once.  Not beside
+    ``class_weight`` / ``logit_bias``.  ``evaluate`` is untouched: the evaluation epochs score the raw logits, and the loss they
+    report stays the softmax cross-entropy, whatever the training loss is."""
+    check_loss(loss, class_weight, logit_bias)
     if eval_views is not None and eval_mode != "sharded":
         raise CaraError("fit: eval_views are read by CaraEngine.evaluate(views=): they need eval_mode = 'sharded'")
     if eval_metric not in ("top1", "mean_per_class"):
@@ -342,6 +359,14 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
                 raise CaraError(f"fit: {name} must be an fp32 [classes] tensor, not {type(t).__name__}")
             smooth[name] = t.detach().to(hdev).contiguous()
         eng._class_vectors(smooth.get("class_weight"), smooth.get("logit_bias"), model.head.weight.shape[0], hdev)
+    if loss is not None:
+        if not hasattr(model.head, "weight"):
+            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+        hdev = model.head.weight.device
+        if loss.pos_weight is not None and loss.pos_weight.device != hdev:
+            loss = BCE(loss.target_threshold, loss.pos_weight.detach().to(hdev).contiguous(), loss.sum_classes)
+        loss.check_pos_weight(model.head.weight.shape[0], hdev, eng.__dict__.setdefault("_class_vec_ok", {}))
+        smooth["loss"] = loss
     model.train()
     params = trainable_parameters(model)
     if cdist.world_size(group) > 1:

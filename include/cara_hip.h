@@ -462,6 +462,29 @@ int cara_cross_entropy_mix(const float* logits, const int64_t* labels, const int
 int cara_cross_entropy_bal(const float* logits, const int64_t* labels, const int* mix, float smoothing, const float* class_weight,
                            const float* logit_bias, float* loss, float* dlogits, int B, int C, float dscale,
                            const float* loss_scale, float* found_inf, void* stream);
+/* The sigmoid losses on cara_cross_entropy_mix's soft target: binary cross-entropy (timm's BinaryCrossEntropy, torch's
+ * binary_cross_entropy_with_logits) and the focal loss (torchvision's sigmoid_focal_loss, extended to a soft target).  The tail
+ * arguments from loss on, the labels, mix and smoothing are cara_cross_entropy_mix's.  All in fp32, per element, z = logits[b][c]:
+ *   q_c = the soft target there (same ya, yb, t, eps);  target_threshold >= 0:  q_c <- (q_c > target_threshold) ? 1 : 0
+ *         (timm's target.gt(thr), decided on the fp32 q_c);  target_threshold < 0: none.
+ *   sp(z) = max(z, 0) + log1p(exp(-|z|)),  s+ = sigma(z),  s- = sigma(-z), all from the one exp(-|z|): nothing overflows, and
+ *         neither sigmoid is formed as one minus the other.
+ *   BCE (gamma == 0 and alpha < 0):  l = pw_c q sp(-z) + (1 - q) sp(z),  dl/dz = s+ (1 - q + pw_c q) - pw_c q, evaluated as
+ *         (1 - q) s+ - pw_c q s-;  pw_c = pos_weight[c] (device fp32 [C]) or 1 where pos_weight is NULL.
+ *   focal (gamma > 0 or alpha >= 0; pos_weight must be NULL):  ce = q sp(-z) + (1 - q) sp(z),  m = q s- + (1 - q) s+,
+ *         a = alpha q + (1 - alpha)(1 - q) (alpha < 0: none, a = 1),  l = a m^gamma ce,
+ *         dl/dz = a [(s+ - q) m^gamma + gamma ce m^(gamma - 1) s+ s- (1 - 2 q)].   gamma is 0 or >= 1.
+ *   loss[1 + b] = sum_c l / (B D),  D = C (the "mean" of torch and timm) or 1 with sum_classes = 1 (timm's sum_classes);
+ *   loss[0] = their sum through the fixed tree (unscaled);  dlogits[b][c] = dl/dz / (B D) * dscale * loss scale.
+ * The loss is linear in the samples: dscale, accumulation windows and a SUM all-reduce mean what they mean above.
+ * Bit for bit: pos_weight of all ones == pos_weight NULL; dlogits NULL gives the same loss.  The guards and NaNs are
+ * cara_cross_entropy_mix's (a refused sample indexes nothing through a label; pos_weight is read by class index only).
+ * CARA_E_ARG, nothing launched: smoothing outside [0, 1); target_threshold >= 1 or NaN; gamma negative, in (0, 1) or not finite;
+ * alpha > 1 or NaN; pos_weight with a focal parameter; sum_classes outside {0, 1}; NULL logits, labels or loss; B <= 0, C <= 0;
+ * dscale not > 0.  The VALUES of pos_weight are not looked at: the caller keeps them finite and >= 0.  found_inf is cleared.   */
+int cara_sigmoid_loss(const float* logits, const int64_t* labels, const int* mix, float smoothing, float target_threshold,
+                      float gamma, float alpha, const float* pos_weight, int sum_classes, float* loss, float* dlogits,
+                      int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream);
 /* Scoring on the device (test() of vit_cp.py:73-82 without its per-batch host read): for the first n_valid <= B rows of
  * logits fp32 [B,classes] (row stride ldl floats) and labels int64 [B], ADD into `state`, five 64-bit words
  * (cara_eval_state_bytes() = 40 bytes, 8-byte aligned, zeroed by the caller before the first batch):
