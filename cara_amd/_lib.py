@@ -27,13 +27,15 @@ SYMBOLS = (
     "cara_grad_accumulate", "cara_grad_clip_scratch_bytes", "cara_grad_clip", "cara_ema_update", "cara_sam_perturb", "cara_sam_restore",
     "cara_weight_dropout_hash", "cara_materialize_merge", "cara_dropout_grad_scratch_bytes", "cara_dropout_grad_contract", "cara_colsum_scratch_bytes", "cara_colsum_bf16", "cara_factor_prep", "cara_factor_grad_scratch_bytes", "cara_factor_grad_reduce", "cara_vit_workspace_bytes", "cara_vit_forward",
     "cara_vit_backward", "cara_head_backward", "cara_im2col_patches_u8", "cara_vit_forward_u8", "cara_im2col_patches_u8_rows", "cara_gather_labels", "cara_vit_forward_u8_rows", "cara_im2col_patches_u8_rows_crop", "cara_vit_forward_u8_rows_crop", "cara_im2col_patches_u8_rows_mix", "cara_vit_forward_u8_rows_mix", "cara_cross_entropy_mix", "cara_cross_entropy_bal", "cara_sigmoid_loss", "cara_aug_stat_bytes", "cara_im2col_patches_u8_rows_aug", "cara_vit_forward_u8_rows_aug",
-    "cara_im2col_patches_keep", "cara_im2col_patches_u8_rows_keep", "cara_assemble_tokens_keep", "cara_vit_forward_keep", "cara_vit_forward_u8_rows_keep", "cara_ra_stat_bytes", "cara_im2col_patches_u8_rows_ra", "cara_vit_forward_u8_rows_ra", "cara_eval_accumulate", "cara_eval_state_bytes", "cara_eval_report_bytes", "cara_eval_accumulate_report", "cara_eval_combine_views", "cara_sizeof_struct", "cara_sizeof_gemm_args", "cara_profile_sites", "cara_profile_site_read", "cara_debug_tr_probe", "cara_debug_tr_frag",
+    "cara_im2col_patches_keep", "cara_im2col_patches_u8_rows_keep", "cara_assemble_tokens_keep", "cara_vit_forward_keep", "cara_vit_forward_u8_rows_keep", "cara_ra_stat_bytes", "cara_im2col_patches_u8_rows_ra", "cara_vit_forward_u8_rows_ra", "cara_eval_accumulate", "cara_eval_state_bytes", "cara_eval_report_bytes", "cara_eval_accumulate_report", "cara_eval_combine_views", "cara_eval_predict", "cara_sizeof_struct", "cara_sizeof_gemm_args", "cara_profile_sites", "cara_profile_site_read", "cara_debug_tr_probe", "cara_debug_tr_frag",
 )
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_DG, EPI_MULH = range(7)
 # cara_eval_combine_views: CARA_EVAL_MAX_VIEWS and the two CARA_EVAL_COMBINE_* modes of include/cara_hip.h
 EVAL_MAX_VIEWS = 16
 EVAL_COMBINE = {"prob": 0, "logit": 1}
+# cara_eval_predict: CARA_EVAL_PREDICT_MAX_K, the most top-k slots a table row holds
+PREDICT_MAX_K = 16
 
 
 class GemmArgs(C.Structure):
@@ -211,6 +213,9 @@ def lib(operands: str = None) -> C.CDLL:
     if hasattr(_lib, "cara_eval_combine_views"):       # the views' logits of a sample -> one row (ints between pointers)
         P, I = C.c_void_p, C.c_int
         _lib.cara_eval_combine_views.argtypes = [P, I, I, I, I, I, P, I, P]
+    if hasattr(_lib, "cara_eval_predict"):             # per-sample records: two 64-bit row numbers between ints and pointers
+        P, I, Q = C.c_void_p, C.c_int, C.c_int64
+        _lib.cara_eval_predict.argtypes = [P, I, P, I, I, I, I, Q, Q, P, P, P, P, P]
     if hasattr(_lib, "cara_vit_forward_u8_rows"):
         # the indexed feed: n_split is an int between pointers, so the argument types are stated
         P, I = C.c_void_p, C.c_int

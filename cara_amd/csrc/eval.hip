@@ -46,6 +46,46 @@ __device__ __forceinline__ void row_term(float x, int c, float m, float v, int y
   if constexpr (REPORT) a.pred = (x == m && c < a.pred) ? c : a.pred;
 }
 
+// The walk over one row that every scoring kernel of this file shares (the accumulate kernel, its report form and the predict
+// kernel): the SAME loads in the SAME order, so the three form the same maximum and, bit for bit, the same sum.  16-byte loads over
+// the first 4 * C4 classes when the row starts on 16 bytes (C4 = 0 otherwise), a scalar tail, lane-strided.
+__device__ __forceinline__ int row_vec4(const float* lr, int C) { return (reinterpret_cast<uintptr_t>(lr) & 15) == 0 ? C >> 2 : 0; }
+
+// pass 1: the row maximum, in every lane (never below -3e38: a row without a finite maximum keeps that value)
+__device__ __forceinline__ float row_max(const float* __restrict__ lr, int C, int C4, int lane) {
+  float m = -3.0e38f;
+  for (int i = lane; i < C4; i += 64) {
+    const float4 q = reinterpret_cast<const float4*>(lr)[i];
+    m = fmaxf(fmaxf(m, q.x), fmaxf(q.y, fmaxf(q.z, q.w)));
+  }
+  for (int c = C4 * 4 + lane; c < C; c += 64) m = fmaxf(m, lr[c]);
+  return wave_max(m);
+}
+
+// pass 2: this lane's part of sum expf(l - m) and of the rank of (v, y) -- the caller reduces both over the wave
+template <bool REPORT>
+__device__ __forceinline__ RowAcc<REPORT> row_walk(const float* __restrict__ lr, int C, int C4, int lane, float m, float v, int y) {
+  RowAcc<REPORT> a;
+  a.s = 0.f;
+  a.rank = 0;
+  if constexpr (REPORT) a.pred = C;
+  for (int i = lane; i < C4; i += 64) {
+    const float4 q = reinterpret_cast<const float4*>(lr)[i];
+    row_term(q.x, 4 * i, m, v, y, a);
+    row_term(q.y, 4 * i + 1, m, v, y, a);
+    row_term(q.z, 4 * i + 2, m, v, y, a);
+    row_term(q.w, 4 * i + 3, m, v, y, a);
+  }
+  for (int c = C4 * 4 + lane; c < C; c += 64) row_term(lr[c], c, m, v, y, a);
+  return a;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // REPORT = false: cara_eval_accumulate, `report` and `bins` unused.  REPORT = true: cara_eval_accumulate_report -- per row one
 // atomicAdd on the confusion cell (scattered: nothing to stage) and the three bin words of its confidence bin added up per
 // workgroup in LDS, published with one atomic per non-empty bin word.
@@ -74,32 +114,12 @@ __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const 
     }
     const int y = (int)y64;
     const float* lr = logits + (size_t)b * ldl;
-    const bool vec = ((reinterpret_cast<uintptr_t>(lr) & 15) == 0);
-    const int C4 = vec ? C >> 2 : 0;
-    float m = -3.0e38f;
-    for (int i = lane; i < C4; i += 64) {
-      const float4 q = reinterpret_cast<const float4*>(lr)[i];
-      m = fmaxf(fmaxf(m, q.x), fmaxf(q.y, fmaxf(q.z, q.w)));
-    }
-    for (int c = C4 * 4 + lane; c < C; c += 64) m = fmaxf(m, lr[c]);
-    m = wave_max(m);
+    const int C4 = row_vec4(lr, C);
+    const float m = row_max(lr, C, C4, lane);
     const float v = lr[y];
-    RowAcc<REPORT> a;
-    a.s = 0.f;
-    a.rank = 0;
-    if constexpr (REPORT) a.pred = C;
-    for (int i = lane; i < C4; i += 64) {
-      const float4 q = reinterpret_cast<const float4*>(lr)[i];
-      row_term(q.x, 4 * i, m, v, y, a);
-      row_term(q.y, 4 * i + 1, m, v, y, a);
-      row_term(q.z, 4 * i + 2, m, v, y, a);
-      row_term(q.w, 4 * i + 3, m, v, y, a);
-    }
-    for (int c = C4 * 4 + lane; c < C; c += 64) row_term(lr[c], c, m, v, y, a);
+    const RowAcc<REPORT> a = row_walk<REPORT>(lr, C, C4, lane, m, v, y);
     const float s = wave_sum(a.s);
-    int rank = a.rank;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+    const int rank = wave_sum_int(a.rank);
     const float lse = m + logf(s);
     ++n;
     t1 += rank == 0 ? 1 : 0;
@@ -155,10 +175,15 @@ __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_accumulate_kernel(const 
   }
 }
 
+// what every scoring entry asks of the logit table (cara_eval_predict takes its labels as optional and has no state)
+bool eval_table_ok(const float* logits, int ldl, int B, int n_valid, int classes) {
+  if (!logits || B <= 0 || n_valid < 0 || n_valid > B || classes < 1 || ldl < classes) return false;
+  return (reinterpret_cast<uintptr_t>(logits) & 3) == 0;
+}
+
 bool eval_args_ok(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes, void* state) {
-  if (!logits || !labels || !state || B <= 0 || n_valid < 0 || n_valid > B || classes < 1 || ldl < classes) return false;
-  if ((reinterpret_cast<uintptr_t>(state) & 7) || (reinterpret_cast<uintptr_t>(logits) & 3)) return false;
-  return true;
+  if (!eval_table_ok(logits, ldl, B, n_valid, classes) || !labels || !state) return false;
+  return (reinterpret_cast<uintptr_t>(state) & 7) == 0;
 }
 
 // at most 256 workgroups (one per CU): 1 280 atomics per launch at the worst, every row still read once
@@ -244,7 +269,120 @@ __global__ __launch_bounds__(EVAL_WAVES * 64) void eval_combine_kernel(const flo
   }
 }
 
+// ---- cara_eval_predict: a batch of logit rows -> per-sample records in a device table (include/cara_hip.h) ---------------------
+// One wave per row, rows walked with the accumulate kernel's grid stride.  Passes 1 and 2 are row_max / row_walk above, so m, s and
+// the rank are the accumulate kernel's own.  Then k selection rounds over the row (L1 / L2 by now: at most 16 KB at 4096 classes):
+// a lane keeps the best (value, index) pair of its classes among those that sort AFTER the previous pick in the stable descending
+// order -- value below it, or equal with a higher index --, a six-stage xor butterfly over the pairs leaves the wave's best in every
+// lane, and lane j keeps round j's.  Comparisons only: a NaN is never picked, -inf is picked like any value.  No LDS, no barrier
+// (the waves of a workgroup run different trip counts), no atomics: lanes 0..k-1 store the k indices and the k probabilities of the
+// row as two coalesced stores, lane 0 its loss and rank.
+struct Pick {
+  float x;
+  int c;
+};
+
+// (x, c) sorts before (bx, bc) in the stable descending order
+__device__ __forceinline__ bool sorts_before(float x, int c, float bx, int bc) { return x > bx || (x == bx && c < bc); }
+
+__device__ __forceinline__ void pick_term(float x, int c, const Pick& prev, Pick& best) {
+  const bool open = sorts_before(prev.x, prev.c, x, c);           // behind the previous pick
+  if (open && sorts_before(x, c, best.x, best.c)) {
+    best.x = x;
+    best.c = c;
+  }
+}
+
+// `none` = classes: no class is left (or the rest are NaN).  -inf with index `none` loses against every real candidate.
+__device__ __forceinline__ Pick next_pick(const float* __restrict__ lr, int C, int C4, int lane, const Pick& prev) {
+  Pick best = {-INFINITY, C};
+  for (int i = lane; i < C4; i += 64) {
+    const float4 q = reinterpret_cast<const float4*>(lr)[i];
+    pick_term(q.x, 4 * i, prev, best);
+    pick_term(q.y, 4 * i + 1, prev, best);
+    pick_term(q.z, 4 * i + 2, prev, best);
+    pick_term(q.w, 4 * i + 3, prev, best);
+  }
+  for (int c = C4 * 4 + lane; c < C; c += 64) pick_term(lr[c], c, prev, best);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ox = __shfl_xor(best.x, o, 64);
+    const int oc = __shfl_xor(best.c, o, 64);
+    if (sorts_before(ox, oc, best.x, best.c)) {
+      best.x = ox;
+      best.c = oc;
+    }
+  }
+  return best;
+}
+
+__global__ __launch_bounds__(EVAL_WAVES * 64) void eval_predict_kernel(const float* __restrict__ logits, int ldl,
+                                                                       const int64_t* __restrict__ labels, int n_valid, int C, int k,
+                                                                       int64_t first, int32_t* __restrict__ topk_idx,
+                                                                       float* __restrict__ topk_prob, float* __restrict__ loss_out,
+                                                                       int32_t* __restrict__ rank_out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int b = blockIdx.x * EVAL_WAVES + wave; b < n_valid; b += gridDim.x * EVAL_WAVES) {
+    const float* lr = logits + (size_t)b * ldl;
+    const int C4 = row_vec4(lr, C);
+    const float m = row_max(lr, C, C4, lane);
+    // no labels, or a label outside [0, classes): v = NaN compares false with everything, the walk still forms the same sum
+    bool labelled = false;
+    int y = 0;
+    if (labels) {
+      const int64_t y64 = labels[b];   // (wave-uniform: one row per wave)
+      labelled = y64 >= 0 && y64 < C;
+      y = labelled ? (int)y64 : 0;
+    }
+    const float v = labelled ? lr[y] : __int_as_float(0x7fc00000);
+    const RowAcc<false> a = row_walk<false>(lr, C, C4, lane, m, v, y);
+    const float s = wave_sum(a.s);
+    const int rank = wave_sum_int(a.rank);
+    Pick prev = {INFINITY, -1}, mine = {-INFINITY, C};
+    bool finite_max = false;
+    for (int j = 0; j < k; ++j) {
+      const Pick p = next_pick(lr, C, C4, lane, prev);
+      if (j == 0) finite_max = p.c < C && p.x == m;   // the report kernel's rule: some class holds the maximum
+      if (lane == j) mine = p;
+      if (p.c >= C) break;                            // nothing is left: the later slots keep index -1
+      prev = p;
+    }
+    const size_t row = (size_t)(first + b);
+    if (lane < k) {
+      int idx = mine.c < C ? mine.c : -1;
+      float prob = mine.c < C ? expf(mine.x - m) / s : 0.f;
+      if (!finite_max) {
+        idx = lane == 0 ? 0 : -1;
+        prob = __int_as_float(0x7fc00000);
+      }
+      topk_idx[row * k + lane] = idx;
+      topk_prob[row * k + lane] = prob;
+    }
+    if (labels && lane == 0) {
+      const float nan = __int_as_float(0x7fc00000);
+      loss_out[row] = labelled && finite_max ? (float)((double)(m + logf(s)) - (double)v) : nan;
+      rank_out[row] = labelled ? rank : -1;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int cara_eval_predict(const float* logits, int ldl, const int64_t* labels, int B, int n_valid, int classes, int k,
+                                 int64_t first, int64_t n_rows, int32_t* topk_idx, float* topk_prob, float* loss, int32_t* rank,
+                                 void* stream) {
+  if (!eval_table_ok(logits, ldl, B, n_valid, classes) || !topk_idx || !topk_prob) return CARA_E_ARG;
+  if ((labels != nullptr) != (loss != nullptr) || (labels != nullptr) != (rank != nullptr)) return CARA_E_ARG;
+  if (k < 1 || k > CARA_EVAL_PREDICT_MAX_K || first < 0 || n_rows < 0 || first > n_rows - n_valid) return CARA_E_ARG;
+  const uintptr_t four = reinterpret_cast<uintptr_t>(topk_idx) | reinterpret_cast<uintptr_t>(topk_prob) |
+                         reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(rank);
+  if ((four & 3) || (reinterpret_cast<uintptr_t>(labels) & 7)) return CARA_E_ARG;
+  if (n_valid == 0) return CARA_OK;
+  hipLaunchKernelGGL(eval_predict_kernel, dim3(eval_grid(n_valid)), dim3(EVAL_WAVES * 64), 0, static_cast<hipStream_t>(stream), logits,
+                     ldl, labels, n_valid, classes, k, first, topk_idx, topk_prob, loss, rank);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
 
 extern "C" int cara_eval_combine_views(const float* logits, int ldl, int S, int V, int classes, int mode, float* out, int ldo,
                                        void* stream) {

@@ -1075,6 +1075,88 @@ class CaraEngine:
         check(getattr(self._lib(), entry)(*[ptr(v) if v is None or torch.is_tensor(v) else v for _, v in params]), entry)
         return st, st["logits"]
 
+    def _eval_setup(self, what, split_or_batches, views, combine):
+        """what ``evaluate`` and ``predict`` check before anything is sized: the arguments, the head, the precision, the device.
+        Leaves the model in eval mode -> (model, device)"""
+        model = self._model()
+        model.eval()
+        if combine not in L.EVAL_COMBINE:
+            raise CaraError(f"{what}: combine must be one of {tuple(L.EVAL_COMBINE)}, not {combine!r}")
+        if views is not None:   # (what the arguments are before where anything lives)
+            from .data import EvalViews
+            split = split_or_batches
+            if not isinstance(views, EvalViews):
+                raise CaraError(f"{what}: views must be a data.EvalViews")
+            if not hasattr(split, "eval_view_shard") or getattr(split, "pixels", None) is None:
+                raise CaraError(f"{what}(views=) reads a data.ResidentSplit by index: batches and callables carry no views")
+        if not hasattr(model.head, "weight"):
+            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+        if self.precision not in ("bf16", "fp16"):
+            raise CaraError(f"precision must be 'bf16' or 'fp16', not {self.precision!r}")
+        if self.precision == "fp16" and self.cp_length == 2:
+            raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
+        dev = model.head.weight.device
+        if dev.type != "cuda":
+            raise CaraError("cara_amd runs on the GPU only: move the model to a ROCm device (there is no CPU fallback)")
+        return model, dev
+
+    def _eval_source(self, what, model, split_or_batches, batch_size, group, views):
+        """this rank's batches of an evaluation pass -> (batches, shard): ``shard`` is the ``range`` of sample indices they cover
+        when the source is a ``ResidentSplit`` (``dist.eval_shard``: contiguous, file order), None for batches that are this rank's
+        part already.  With ``views`` a batch is ``(rows, boxes, labels, n_valid)`` of ``batch_size // V`` whole samples."""
+        from . import dist as cdist
+        rank, world = cdist.get_rank(group), cdist.world_size(group)
+        if views is not None:
+            split = split_or_batches
+            if views.size is not None and views.size != self._model_img(model):
+                raise CaraError(f"{what}: the views are made for a {views.size}-pixel input, the model takes {self._model_img(model)}")
+            try:
+                batches = split.eval_view_shard(views.table(*split.pixels.shape[2:]), batch_size, rank, world)
+            except ValueError as e:
+                raise CaraError(f"{what}: {e}") from None
+            return batches, cdist.eval_shard(len(split), rank, world, int(batch_size) // views.V)
+        if hasattr(split_or_batches, "eval_shard"):
+            return split_or_batches.eval_shard(batch_size, rank, world), cdist.eval_shard(len(split_or_batches), rank, world, batch_size)
+        return (split_or_batches() if callable(split_or_batches) else split_or_batches), None
+
+    def _eval_logits(self, what, model, dev, split, batches, use, views, combine, labels_optional=False):
+        """The loop ``evaluate`` and ``predict`` share: per batch the forward on the inference-sized workspace and, with more than
+        one view, the combine launch -> yields ``(logits, per_view, labels, n_valid)``: the rows to score (the workspace's own
+        tensor, or its ``combined`` buffer: valid until the next batch) and, with views, the per-view logits.  The caller holds
+        ``torch.no_grad()`` and the device; nothing here reads the device.  ``labels_optional``: a batch may be the images alone
+        or carry None as its labels."""
+        lib = self._lib()
+        if views is not None:
+            V, mode = views.V, L.EVAL_COMBINE[combine]
+        for item in batches:
+            per_view = None
+            if views is not None:
+                rows, boxes, y, n_valid = item
+                self._resident_args(split, Feed(rows, boxes))
+                st, per_view = self._eval_forward_views(model, split, rows, boxes, dev, use)
+                logits = per_view
+                # one view: its mean logit is its logit, and its log-softmax is scored exactly as its logits are (loss, confidence
+                # and ranks do not see a shift of the whole row) -- no combine launch, the pass is bit for bit the plain one
+                if V > 1:
+                    S = y.shape[0]
+                    logits = st.setdefault("combined", {}).get(S)
+                    if logits is None:
+                        logits = st["combined"][S] = torch.empty(S, per_view.shape[1], device=dev)
+                    check(lib.cara_eval_combine_views(ptr(per_view), per_view.shape[1], S, V, per_view.shape[1], mode, ptr(logits),
+                                                      logits.shape[1], stream(dev)), "cara_eval_combine_views")
+            else:
+                if labels_optional and torch.is_tensor(item):
+                    item = (item, None)
+                x, y = item[0], item[1]
+                n_valid = int(item[2]) if len(item) > 2 else x.shape[0]
+                if not (labels_optional and y is None) and (
+                        x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]):
+                    raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
+                if x.device != dev:
+                    raise CaraError("a batch is (images or uint8 pixels[, labels[, n_valid]]) on the model's device")
+                logits = self._eval_forward(model, x, dev, use)
+            yield logits, per_view, y, n_valid
+
     def evaluate(self, split_or_batches, batch_size: int = 256, group=None, debug_hook=None, weights=None, report: bool = False,
                  bins: int = 15, views=None, combine: str = "prob") -> dict:
         """Top-1 / top-5 accuracy and mean cross-entropy of a whole split, on the device and sharded over the ranks of
@@ -1106,27 +1188,7 @@ class CaraEngine:
         ``[S*V, classes]`` and the combined rows.  Resampling is bilinear without an antialias filter (``data.EvalViews``).
         Views on another source, a table that leaves the split, more views than ``batch_size`` or an unknown ``combine`` raise
         before the first forward.  Without ``views`` the pass issues the launches it always did."""
-        from . import dist as cdist
-        model = self._model()
-        model.eval()
-        if combine not in L.EVAL_COMBINE:
-            raise CaraError(f"evaluate: combine must be one of {tuple(L.EVAL_COMBINE)}, not {combine!r}")
-        if views is not None:   # (what the arguments are before where anything lives)
-            from .data import EvalViews
-            split = split_or_batches
-            if not isinstance(views, EvalViews):
-                raise CaraError("evaluate: views must be a data.EvalViews")
-            if not hasattr(split, "eval_view_shard") or getattr(split, "pixels", None) is None:
-                raise CaraError("evaluate(views=) reads a data.ResidentSplit by index: batches and callables carry no views")
-        if not hasattr(model.head, "weight"):
-            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
-        if self.precision not in ("bf16", "fp16"):
-            raise CaraError(f"precision must be 'bf16' or 'fp16', not {self.precision!r}")
-        if self.precision == "fp16" and self.cp_length == 2:
-            raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
-        dev = model.head.weight.device
-        if dev.type != "cuda":
-            raise CaraError("cara_amd runs on the GPU only: move the model to a ROCm device (there is no CPU fallback)")
+        model, dev = self._eval_setup("evaluate", split_or_batches, views, combine)
         if report:
             ncls = int(model.head.out_features)
             if isinstance(bins, bool) or not isinstance(bins, int):
@@ -1135,46 +1197,14 @@ class CaraEngine:
             if report_bytes == 0:
                 raise CaraError(f"evaluate(report=True): {ncls} classes with {bins} bins is outside what cara_eval_accumulate_report "
                                 "takes (at most 4096 classes, 1 to 64 bins)")
-        if views is not None:
-            if views.size is not None and views.size != self._model_img(model):
-                raise CaraError(f"evaluate: the views are made for a {views.size}-pixel input, the model takes {self._model_img(model)}")
-            try:
-                batches = split.eval_view_shard(views.table(*split.pixels.shape[2:]), batch_size, cdist.get_rank(group),
-                                                cdist.world_size(group))
-            except ValueError as e:
-                raise CaraError(f"evaluate: {e}") from None
-            V, mode = views.V, L.EVAL_COMBINE[combine]
-        elif hasattr(split_or_batches, "eval_shard"):
-            batches = split_or_batches.eval_shard(batch_size, cdist.get_rank(group), cdist.world_size(group))
-        else:
-            batches = split_or_batches() if callable(split_or_batches) else split_or_batches
+        from . import dist as cdist
+        batches, _ = self._eval_source("evaluate", model, split_or_batches, batch_size, group, views)
         lib = self._lib()
         use = self._forward_weights(model, dev, weights)
         with torch.no_grad(), torch.cuda.device(dev):
             state = torch.zeros(int(lib.cara_eval_state_bytes()) // 8, dtype=torch.int64, device=dev)
             rep = torch.zeros(report_bytes // 8, dtype=torch.int64, device=dev) if report else None
-            for item in batches:
-                per_view = None
-                if views is not None:
-                    rows, boxes, y, n_valid = item
-                    self._resident_args(split, Feed(rows, boxes))
-                    st, per_view = self._eval_forward_views(model, split, rows, boxes, dev, use)
-                    logits = per_view
-                    # one view: its mean logit is its logit, and its log-softmax is scored exactly as its logits are (loss, confidence
-                    # and ranks do not see a shift of the whole row) -- no combine launch, the pass is bit for bit the plain one
-                    if V > 1:
-                        S = y.shape[0]
-                        logits = st.setdefault("combined", {}).get(S)
-                        if logits is None:
-                            logits = st["combined"][S] = torch.empty(S, per_view.shape[1], device=dev)
-                        check(lib.cara_eval_combine_views(ptr(per_view), per_view.shape[1], S, V, per_view.shape[1], mode, ptr(logits),
-                                                          logits.shape[1], stream(dev)), "cara_eval_combine_views")
-                else:
-                    x, y = item[0], item[1]
-                    n_valid = int(item[2]) if len(item) > 2 else y.shape[0]
-                    if x.device != dev or y.device != dev or y.dtype != torch.int64 or y.ndim != 1 or y.shape[0] != x.shape[0]:
-                        raise CaraError("a batch is (images or uint8 pixels, int64 [batch] labels[, n_valid]) on the model's device")
-                    logits = self._eval_forward(model, x, dev, use)
+            for logits, per_view, y, n_valid in self._eval_logits("evaluate", model, dev, split_or_batches, batches, use, views, combine):
                 if report:
                     check(lib.cara_eval_accumulate_report(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
                                                           logits.shape[1], ptr(state), ptr(rep), bins, stream(dev)),
@@ -1204,6 +1234,66 @@ class CaraEngine:
             return evalcount.report_result(words[:5], evalcount.report_from_vector(words[5:], ncls, bins))
         d = max(n, 1.0)
         return {"top1": t1 / d, "top5": t5 / d, "loss": loss / d, "n": int(n)}
+
+    def predict(self, split_or_batches, k: int = 5, batch_size: int = 256, group=None, weights=None, views=None,
+                combine: str = "prob"):
+        """The model's answer for every image of a split, on the device: the pass of ``evaluate`` -- the same sources, checks,
+        inference-sized workspace, ``weights=`` and ``views=`` / ``combine=`` -- with ONE ``cara_eval_predict`` launch per batch
+        (on the combined rows with more than one view) instead of the counting launch, and no host read anywhere.
+        -> ``evalcount.Predictions``: device tensors ``topk`` int32 [N, k] (the ``k`` best classes, best first, ties to the lowest
+        class index), ``prob`` fp32 [N, k] (their softmax probabilities), ``loss`` fp32 [N] (the per-sample cross-entropy), ``rank``
+        int32 [N] (the label's position in the sorted row: 0 = a top-1 hit, ``< 5`` = a top-5 hit, -1 = a label outside the
+        classes) and ``labels``; include/cara_hip.h has the rules.  ``1 <= k <= 16``; slots beyond the class count hold -1 / 0.
+
+        A ``ResidentSplit``: ``N = len(split)`` and row ``i`` is sample ``i`` in file order.  Every rank of ``group`` fills the
+        rows of its (contiguous) shard in one zeroed table -- padded rows are never written -- and ONE integer SUM all-reduce of
+        the table's 32-bit words (the floats as their bits: ``x + 0`` is exact on integers) leaves the whole table on every
+        rank, bit for bit the one a single rank fills.  An iterable, or a callable returning one, of ``(pixels_u8 or images,
+        labels[, n_valid])`` batches: the table holds this rank's valid rows in arrival order and there is no collective; a
+        batch may be the images alone or carry None as its labels (every batch alike), then ``loss``, ``rank`` and ``labels``
+        are None.  ``Predictions.counts()`` gives ``evaluate``'s dict, ``confusion`` / ``errors`` / ``confident`` / ``save`` the
+        per-sample views, each with one host read."""
+        from . import dist as cdist
+        from .evalcount import Predictions
+        model, dev = self._eval_setup("predict", split_or_batches, views, combine)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= L.PREDICT_MAX_K:
+            raise CaraError(f"predict: k must be an integer in [1, {L.PREDICT_MAX_K}], not {k!r}")
+        batches, shard = self._eval_source("predict", model, split_or_batches, batch_size, group, views)
+        lib = self._lib()
+        use = self._forward_weights(model, dev, weights)
+        with torch.no_grad(), torch.cuda.device(dev):
+            if shard is not None:
+                # the whole table as ONE buffer of 32-bit words: [N, k] indices, [N, k] probabilities, [N] losses, [N] ranks
+                N = len(split_or_batches)
+                words = torch.zeros(N * (2 * k + 2), dtype=torch.int32, device=dev)
+                topk, prob = words[:N * k].view(N, k), words[N * k:2 * N * k].view(torch.float32).view(N, k)
+                loss, rank = words[2 * N * k:2 * N * k + N].view(torch.float32), words[2 * N * k + N:]
+                done = shard.start
+                for logits, _, y, n_valid in self._eval_logits("predict", model, dev, split_or_batches, batches, use, views, combine):
+                    check(lib.cara_eval_predict(ptr(logits), logits.shape[1], ptr(y.contiguous()), logits.shape[0], n_valid,
+                                                logits.shape[1], k, done, N, ptr(topk), ptr(prob), ptr(loss), ptr(rank), stream(dev)),
+                          "cara_eval_predict")
+                    done += n_valid
+                cdist.allreduce_sum_(words, group)
+                return Predictions(topk, prob, loss, rank, split_or_batches.labels)
+            # batches of unknown number: a table per batch, its valid rows joined behind the loop (on the device)
+            parts, labelled = [], None
+            for logits, _, y, n_valid in self._eval_logits("predict", model, dev, split_or_batches, batches, use, views, combine,
+                                                           labels_optional=True):
+                if labelled is None:
+                    labelled = y is not None
+                if labelled != (y is not None):
+                    raise CaraError("predict: either every batch carries labels or none does")
+                B = logits.shape[0]
+                t = (torch.empty(B, k, dtype=torch.int32, device=dev), torch.empty(B, k, device=dev),
+                     torch.empty(B, device=dev) if labelled else None, torch.empty(B, dtype=torch.int32, device=dev) if labelled else None,
+                     y.contiguous() if labelled else None)
+                check(lib.cara_eval_predict(ptr(logits), logits.shape[1], ptr(t[4]), B, n_valid, logits.shape[1], k, 0, B,
+                                            ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), stream(dev)), "cara_eval_predict")
+                parts.append([c[:n_valid] if c is not None else None for c in t])
+            if not parts:
+                return Predictions(torch.empty(0, k, dtype=torch.int32, device=dev), torch.empty(0, k, device=dev))
+            return Predictions(*[torch.cat(c) if c[0] is not None else None for c in zip(*parts)])
 
     # module-level entries (cara.cp_attn / cara.cp_mlp): the reference's patched forwards
     def _weights(self, model, dev):

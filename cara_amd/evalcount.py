@@ -163,3 +163,151 @@ def report_result(state, report: dict) -> dict:
                calibration={"count": count, "hits": hits, "confidence": conf})
     return out
 
+
+
+# ---- per-sample records of ``cara_eval_predict``: top-k classes and probabilities, loss and rank of every row ---------------------
+# The contract of include/cara_hip.h taken literally, in fp64 from the fp32 logits; the ordering is a stable sort of ``-x``.
+NO_FINITE_MAX = -3.0e38   # the kernels' floor of a row maximum (as the fp32 value nearest to it): below it a row matches no class
+
+
+def predict_rows(logits: torch.Tensor, labels, k: int):
+    """``logits`` [B, classes] (fp32 values), ``labels`` int64 [B] or None, ``k`` >= 1 -> ``(idx int32 [B, k], prob fp64 [B, k],
+    loss fp64 [B], rank int32 [B])``, the last two None without labels.  ``idx[:, j]`` = the class at position ``j`` of the stable
+    descending sort of the row (ties to the lowest index, ``-inf`` last in index order); slots ``j >= classes``: index -1,
+    probability 0.  ``prob = exp(l[idx] - m) / sum exp(l - m)``; ``loss = m + log(sum) - l[label]``; ``rank`` as in ``accumulate``.
+    A label outside ``[0, classes)``: rank -1, loss NaN.  A row without a finite maximum (nothing at or above the fp32 -3e38, or a
+    NaN): index 0 then -1, every probability and the loss NaN."""
+    k = int(k)
+    if logits.ndim != 2 or logits.shape[1] < 1 or k < 1:
+        raise ValueError("predict_rows takes logits [B, classes >= 1] and k >= 1")
+    l = logits.detach().to(torch.float64).cpu()
+    B, classes = l.shape
+    kk = min(k, classes)
+    order = torch.argsort(-l, dim=1, stable=True)[:, :kk]
+    m = l.max(dim=1, keepdim=True).values
+    floor = float(torch.tensor(NO_FINITE_MAX, dtype=torch.float32))
+    degenerate = ~(m[:, 0] >= floor)                                   # (a NaN maximum compares false: degenerate)
+    # (the kernels' maximum never falls below the floor; where the row has a class at or above it, it is the row's own maximum)
+    shift = torch.where(degenerate.view(-1, 1), torch.zeros_like(m), m)
+    s = torch.exp(l - shift).sum(dim=1, keepdim=True)
+    idx = torch.full((B, k), -1, dtype=torch.int32)
+    prob = torch.zeros(B, k, dtype=torch.float64)
+    idx[:, :kk] = order.to(torch.int32)
+    prob[:, :kk] = torch.exp(l.gather(1, order) - shift) / s
+    idx[degenerate, 0] = 0
+    idx[degenerate, 1:] = -1
+    prob[degenerate] = float("nan")
+    if labels is None:
+        return idx, prob, None, None
+    y = labels.detach().to(torch.int64).cpu()
+    if y.shape != (B,):
+        raise ValueError("labels must hold one entry per row")
+    ok = (y >= 0) & (y < classes)
+    ys = torch.where(ok, y, torch.zeros_like(y)).view(-1, 1)
+    v = l.gather(1, ys)
+    cols = torch.arange(classes).view(1, -1)
+    rank = ((l > v).sum(1) + ((l == v) & (cols < ys)).sum(1)).to(torch.int32)
+    loss = (shift + torch.log(s) - v)[:, 0]
+    rank[~ok] = -1
+    loss[~ok | degenerate] = float("nan")
+    return idx, prob, loss, rank
+
+
+class Predictions:
+    """The table a ``CaraEngine.predict`` pass fills: ``topk`` int32 [N, k] and ``prob`` fp32 [N, k] (``cara_eval_predict``'s
+    top-k classes and their softmax probabilities, best first), ``loss`` fp32 [N] and ``rank`` int32 [N] (None for a pass without
+    labels), ``labels`` int64 [N] (the labels the pass read, None without) -- tensors on the device of the pass (or on the CPU:
+    ``load``).  Row ``i`` of a ``ResidentSplit`` is sample ``i`` in file order.  Every helper below makes at most ONE host read."""
+
+    def __init__(self, topk, prob, loss=None, rank=None, labels=None):
+        if topk.ndim != 2 or prob.shape != topk.shape or (loss is None) != (rank is None):
+            raise ValueError("Predictions: topk and prob are [N, k], loss and rank come together")
+        self.topk, self.prob, self.loss, self.rank, self.labels = topk, prob, loss, rank, labels
+
+    def __len__(self) -> int:
+        return int(self.topk.shape[0])
+
+    @property
+    def k(self) -> int:
+        return int(self.topk.shape[1])
+
+    def _need_labels(self, what):
+        from ._lib import CaraError
+        if self.rank is None:
+            raise CaraError(f"Predictions.{what}: the pass had no labels")
+
+    def counts(self) -> dict:
+        """``dict(top1, top5, loss, n)``, the form and -- in its integers -- the values of ``CaraEngine.evaluate`` on the same pass;
+        the loss is the fp64 sum of the fp32 per-row terms.  A row with ``rank == -1`` (a label outside the classes) raises."""
+        from ._lib import CaraError
+        self._need_labels("counts")
+        r = self.rank
+        good = r >= 0
+        words = torch.stack([good.sum().double(), (r == 0).sum().double(), (good & (r < 5)).sum().double(),
+                             torch.where(good, self.loss.double(), torch.zeros((), dtype=torch.float64, device=r.device)).sum(),
+                             (~good).sum().double()]).tolist()          # the only host read
+        n, t1, t5, loss, bad = words
+        if bad:
+            raise CaraError(f"predict: {int(bad)} label(s) outside the classes of the head")
+        d = max(n, 1.0)
+        return {"top1": t1 / d, "top5": t5 / d, "loss": loss / d, "n": int(n)}
+
+    def confusion(self, classes: int) -> torch.Tensor:
+        """CPU int64 [classes, classes], row = label, column = ``topk[:, 0]``: ``evaluate(report=True)["confusion"]``"""
+        self._need_labels("confusion")
+        classes = int(classes)
+        y, p = self.labels.to(torch.int64), self.topk[:, 0].to(torch.int64)
+        ok = (y >= 0) & (y < classes) & (p >= 0) & (p < classes)
+        cell = torch.where(ok, y * classes + p, torch.full_like(y, classes * classes))
+        return torch.bincount(cell, minlength=classes * classes + 1)[:classes * classes].view(classes, classes).cpu()
+
+    def errors(self) -> torch.Tensor:
+        """CPU int64: the indices of the samples whose label is not the first slot (``rank != 0``), ascending"""
+        self._need_labels("errors")
+        return (self.rank != 0).cpu().nonzero()[:, 0]
+
+    def confident(self, threshold: float):
+        """``(indices, classes)``, CPU int64: the samples whose top probability is at least ``threshold`` and the class they are
+        given -- pseudo-labels"""
+        both = torch.stack([(self.prob[:, 0] >= float(threshold)).to(torch.int32), self.topk[:, 0]]).cpu()
+        keep = both[0].nonzero()[:, 0]
+        return keep, both[1][keep].to(torch.int64)
+
+    def _words(self):
+        """every column as int32 words of ONE [N, W] tensor (floats and int64 labels as their bits) and the column ranges"""
+        cols = [("topk", self.topk.view(len(self), -1)), ("prob", self.prob.view(torch.int32))]
+        if self.rank is not None:
+            cols += [("loss", self.loss.view(torch.int32).view(-1, 1)), ("rank", self.rank.view(-1, 1))]
+        if self.labels is not None:
+            cols.append(("labels", self.labels.to(torch.int64).contiguous().view(torch.int32).view(-1, 2)))
+        return torch.cat([c for _, c in cols], dim=1), [(n, c.shape[1]) for n, c in cols]
+
+    def save(self, path: str, names=None) -> str:
+        """write the table as an ``.npz`` (``topk``, ``prob`` and, when the pass had labels, ``loss``, ``rank``, ``labels``;
+        ``names``: one string per row, or ``ResidentSplit.imlist``'s ``(path, label)`` pairs, stored as ``names``) -> the file name"""
+        import numpy as np
+        if names is not None and len(names) != len(self):
+            raise ValueError(f"save: {len(names)} names for {len(self)} rows")
+        words, cols = self._words()
+        words = words.cpu().numpy()                                       # the only host read
+        out, at = {}, 0
+        kinds = {"prob": np.float32, "loss": np.float32, "labels": np.int64}
+        for name, width in cols:
+            a = np.ascontiguousarray(words[:, at:at + width]).view(kinds.get(name, np.int32))
+            out[name] = a if name in ("topk", "prob") else a.reshape(-1)
+            at += width
+        if names is not None:
+            out["names"] = np.array([n if isinstance(n, str) else n[0] for n in names], dtype=str)
+        path = path if path.endswith(".npz") else path + ".npz"
+        with open(path, "wb") as fh:
+            np.savez(fh, **out)
+        return path
+
+    @classmethod
+    def load(cls, path: str):
+        """-> ``(Predictions on the CPU, names or None)`` of a file ``save`` wrote"""
+        import numpy as np
+        with np.load(path) as z:
+            t = {n: torch.from_numpy(z[n]) for n in z.files if n != "names"}
+            names = [str(n) for n in z["names"]] if "names" in z.files else None
+        return cls(t["topk"], t["prob"], t.get("loss"), t.get("rank"), t.get("labels")), names

@@ -255,7 +255,8 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         on_eval: Optional[Callable[..., None]] = None, save_best: Optional[dict] = None, seed: Optional[int] = None,
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
         accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
-        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob", sam_rho=None, loss=None):
+        eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob", sam_rho=None, loss=None,
+        save_predictions: Optional[str] = None):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -321,8 +322,15 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``loss`` (a ``loss.BCE`` or ``loss.Focal``): every training step of either feed, eager or graphed, trains on that sigmoid loss
     (``train_step(..., loss=)``); a BCE's ``pos_weight`` (host or device) is moved to the model's device once.  Not beside
     ``class_weight`` / ``logit_bias``.  ``evaluate`` is untouched: the evaluation epochs score the raw logits, and the loss they
-    report stays the softmax cross-entropy, whatever the training loss is."""
+    report stays the softmax cross-entropy, whatever the training loss is.
+    ``save_predictions`` (a file name; ``eval_mode = "sharded"`` only): every evaluation that becomes the best so far -- the one
+    ``save_best`` keeps the weights of -- is followed by one ``CaraEngine.predict`` pass with the same ``eval_views`` /
+    ``eval_combine`` and the same weights (the average with ``ema_decay``), and rank 0 writes its table there
+    (``evalcount.Predictions.save``, with the split's file names when the source is a ``ResidentSplit``): when ``fit`` returns
+    the file holds the per-sample predictions of the returned best pass."""
     check_loss(loss, class_weight, logit_bias)
+    if save_predictions is not None and eval_mode != "sharded":
+        raise CaraError("fit: save_predictions is written by CaraEngine.predict: it needs eval_mode = 'sharded'")
     if eval_views is not None and eval_mode != "sharded":
         raise CaraError("fit: eval_views are read by CaraEngine.evaluate(views=): they need eval_mode = 'sharded'")
     if eval_metric not in ("top1", "mean_per_class"):
@@ -472,6 +480,12 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
                     save_best["path"] = checkpoint_name(save_best.get("dataset", "task"), acc, save_best.get("seed", seed),
                                                         save_best.get("dir", "."))
                     save_checkpoint(model, save_best["path"], weights=ema)
+                if acc > best and save_predictions is not None:
+                    # (every rank takes part in the pass's all-reduce; the pass that was just scored: views and weights alike)
+                    table = eng.predict(test_batches, group=group, weights=ema,
+                                        **({"views": eval_views, "combine": eval_combine} if eval_views is not None else {}))
+                    if cdist.get_rank(group) == 0:
+                        table.save(save_predictions, names=getattr(test_batches, "imlist", None))
                 best = max(best, acc)
                 if on_eval:
                     on_eval(epoch, acc) if ema is None else on_eval(epoch, raw, acc)

@@ -531,6 +531,36 @@ int cara_eval_accumulate_report(const float* logits, int ldl, const int64_t* lab
 #define CARA_EVAL_COMBINE_PROB 0
 #define CARA_EVAL_COMBINE_LOGIT 1
 int cara_eval_combine_views(const float* logits, int ldl, int S, int V, int classes, int mode, float* out, int ldo, void* stream);
+/* Per-sample predictions: for every batch row b < n_valid of logits fp32 [B,classes] (row stride ldl floats; the rows the two
+ * accumulate entries score, cara_eval_combine_views' output included) WRITE row first + b, and only that row, of a device table
+ * of n_rows rows: topk_idx int32 [n_rows][k], topk_prob fp32 [n_rows][k] and, with labels int64 [B], loss fp32 [n_rows] and
+ * rank int32 [n_rows].  labels NULL: no loss, no rank (both NULL then, and only then).  With l the row, fp32 throughout:
+ *   topk_idx[j]   the class at position j of the STABLE DESCENDING sort of the row: ties go to the lowest class index, the rule of
+ *                 cara_eval_accumulate.  So topk_idx[0] is the `pred` of cara_eval_accumulate_report, rank == 0 exactly when
+ *                 topk_idx[0] == label, and rank < 5 exactly when the label is among the first five slots.  -inf logits (what
+ *                 cara_eval_combine_views writes for a class of probability zero) are ordinary values: they sort last, in index
+ *                 order.  Slots j >= classes hold index -1 and probability 0.
+ *   topk_prob[j]  expf(l[idx_j] - m) / s with m the row maximum and s = sum_c expf(l[c] - m), formed by the same walk over the
+ *                 row, in the same order, as the accumulate entries form it (one device function): topk_prob[0] is, bit for bit,
+ *                 the `conf` the report bins.  The accurate expf / logf, the division correctly rounded.
+ *   loss          (float)((double)(m + logf(s)) - (double)l[label]): the term cara_eval_accumulate adds, rounded once to fp32.
+ *   rank          #{c : l[c] > v} + #{c < label : l[c] == v}, v = l[label]: the label's position in that sort.
+ * A label outside [0, classes): rank = -1 and loss = NaN; the row's top-k slots are written as for any row.  A row without a
+ * finite maximum (the report's case: no logit above -3e38, or only NaN): topk_idx[0] = 0, the other indices -1, all k
+ * probabilities and the loss NaN; rank as defined.  A row that holds a NaN beside finite values may give any values.  In every
+ * case each index lies in [-1, classes) and nothing outside the row's own slots is written.  Plain stores, no atomics: the same
+ * inputs give the same bits, and rows of one table may be filled by launches in any order (and by several processes whose
+ * tables are then added as integer words: an unwritten row of a zeroed table adds nothing).
+ * One wave per row: the two passes of the accumulate kernel, then k selection rounds over the (cache-resident) row.  Any B, any
+ * class count.  CARA_E_ARG with nothing launched: logits, topk_idx or topk_prob NULL; loss / rank not NULL exactly when labels
+ * is; k outside [1, CARA_EVAL_PREDICT_MAX_K]; first < 0, n_rows < 0 or first + n_valid > n_rows; logits, topk_idx, topk_prob,
+ * loss or rank not 4-byte aligned, labels not 8-byte aligned; B <= 0, n_valid outside [0, B], classes < 1, ldl < classes.   */
+#define CARA_EVAL_PREDICT_MAX_K 16
+int cara_eval_predict(const float* logits, int ldl, const int64_t* labels /* may be NULL */, int B, int n_valid, int classes,
+                      int k, int64_t first, int64_t n_rows,
+                      int32_t* topk_idx /* [n_rows][k] */, float* topk_prob /* [n_rows][k] */,
+                      float* loss /* [n_rows], NULL iff labels NULL */, int32_t* rank /* [n_rows], NULL iff labels NULL */,
+                      void* stream);
 /* bf16 <-> fp32 helpers (weight ingest)                                                        */
 int cara_f32_to_bf16(const float* src, void* dst, size_t n, void* stream);
 int cara_transpose_bf16(const void* src, void* dst, int rows, int cols, void* stream);

@@ -12,7 +12,10 @@ both.  Standalone: not part of bench.py.  --only a|b runs one leg (the leg (a) o
 cara_eval_accumulate_report instead of cara_eval_accumulate after every batch (docs/findings/eval_report.md).
 --views center|flip|five|ten times (b) against engine.evaluate(split, B, views=...) on the same split, alternating: 1, 2, 5 or 10
 forwards per image in batches of B // V whole samples, and the device time of one cara_eval_combine_views launch on such a batch
-as a share of the pass (docs/findings/eval_views.md).  --combine prob|logit."""
+as a share of the pass (docs/findings/eval_views.md).  --combine prob|logit.
+--predict times (b) against engine.predict(split, k, B) on the same split, alternating: the same forwards with one
+cara_eval_predict launch per batch instead of the counting launch, and the device time of that launch beside the counting launches'
+(docs/findings/eval_predict.md).  --k."""
 import argparse
 import ctypes as C
 import json
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--views", default=None, choices=["center", "flip", "five", "ten"],
                     help="time engine.evaluate with and without these views (centre crop, centre crop + flip, five crops, ten crops)")
     ap.add_argument("--combine", default="prob", choices=["prob", "logit"])
+    ap.add_argument("--predict", action="store_true", help="time engine.evaluate against engine.predict, alternating")
+    ap.add_argument("--k", type=int, default=5, help="--predict: top-k slots per sample")
     args = ap.parse_args()
     from cara_amd import cara, create_model, recipe
     from cara_amd.data import ResidentSplit
@@ -116,6 +121,19 @@ def main():
                                  loss=out[0]["loss"], combine_launch_us=us,
                                  combine_share_pct=round(100 * us * 1e-6 * batches / res["views_pass"]["median_s"], 4))
         res["views_over_plain"] = round(res["views_pass"]["median_s"] / res["plain_pass"]["median_s"], 4)
+    if args.predict:
+        # the plain pass and the predict pass in turn, --rounds times, on the same box in one run: their ratio is the table's cost
+        plain, pred, out, tab = [], [], [None], [None]
+        for _ in range(args.rounds):
+            plain += timed(lambda: out.__setitem__(0, eng.evaluate(split, args.batch)))
+            pred += timed(lambda: tab.__setitem__(0, eng.predict(split, args.k, args.batch)))
+        counts = tab[0].counts()
+        report("plain_pass", plain, eng.eval_workspace_bytes(), out[0]["top1"])
+        report("predict_pass", pred, eng.eval_workspace_bytes(), counts["top1"])
+        res["predict_pass"].update(k=args.k, n=counts["n"], loss=counts["loss"], table_bytes=4 * args.images * (2 * args.k + 2),
+                                   same_counts=[counts[key] == out[0][key] for key in ("n", "top1", "top5")])
+        res["predict_over_plain"] = round(res["predict_pass"]["median_s"] / res["plain_pass"]["median_s"], 4)
+        res["counting_launch_us"] = _launch_us(eng, args, dev)
     print(json.dumps(res))
 
 
@@ -140,7 +158,7 @@ def _combine_us(eng, args, dev, S, V, launches=200):
 
 
 def _launch_us(eng, args, dev, launches=200):
-    """device time of one counting launch on a [batch, classes] logit table, plain and with the report (events around `launches`
+    """device time of one counting launch on a [batch, classes] logit table, plain, with the report and as cara_eval_predict (events around `launches`
     back-to-back launches, best of five after a warm-up)"""
     from cara_amd._lib import check, ptr, stream
     lib = eng._lib()
@@ -148,10 +166,15 @@ def _launch_us(eng, args, dev, launches=200):
     y = torch.randint(0, args.classes, (args.batch,), device=dev)
     st = torch.zeros(5, dtype=torch.int64, device=dev)
     rep = torch.zeros(args.classes ** 2 + 3 * args.bins, dtype=torch.int64, device=dev)
+    k = getattr(args, "k", 5)
+    tab = (torch.zeros(args.batch, k, dtype=torch.int32, device=dev), torch.zeros(args.batch, k, device=dev),
+           torch.zeros(args.batch, device=dev), torch.zeros(args.batch, dtype=torch.int32, device=dev))
     calls = {"plain": lambda: lib.cara_eval_accumulate(ptr(lg), args.classes, ptr(y), args.batch, args.batch, args.classes, ptr(st),
                                                        stream(dev)),
              "report": lambda: lib.cara_eval_accumulate_report(ptr(lg), args.classes, ptr(y), args.batch, args.batch, args.classes,
-                                                               ptr(st), ptr(rep), args.bins, stream(dev))}
+                                                               ptr(st), ptr(rep), args.bins, stream(dev)),
+             "predict": lambda: lib.cara_eval_predict(ptr(lg), args.classes, ptr(y), args.batch, args.batch, args.classes, k, 0, args.batch,
+                                                      ptr(tab[0]), ptr(tab[1]), ptr(tab[2]), ptr(tab[3]), stream(dev))}
     out = {}
     for name, call in calls.items():
         best = float("inf")
