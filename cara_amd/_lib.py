@@ -26,7 +26,7 @@ SYMBOLS = (
     "cara_dense_delta_materialize", "cara_dense_delta_grad_scratch_bytes", "cara_dense_delta_grad", "cara_sum_slabs_f32", "cara_adamw_step",
     "cara_grad_accumulate", "cara_grad_clip_scratch_bytes", "cara_grad_clip", "cara_ema_update", "cara_sam_perturb", "cara_sam_restore",
     "cara_weight_dropout_hash", "cara_materialize_merge", "cara_dropout_grad_scratch_bytes", "cara_dropout_grad_contract", "cara_colsum_scratch_bytes", "cara_colsum_bf16", "cara_factor_prep", "cara_factor_grad_scratch_bytes", "cara_factor_grad_reduce", "cara_vit_workspace_bytes", "cara_vit_forward",
-    "cara_vit_backward", "cara_head_backward", "cara_im2col_patches_u8", "cara_vit_forward_u8", "cara_im2col_patches_u8_rows", "cara_gather_labels", "cara_vit_forward_u8_rows", "cara_im2col_patches_u8_rows_crop", "cara_vit_forward_u8_rows_crop", "cara_im2col_patches_u8_rows_mix", "cara_vit_forward_u8_rows_mix", "cara_cross_entropy_mix", "cara_cross_entropy_bal", "cara_sigmoid_loss", "cara_aug_stat_bytes", "cara_im2col_patches_u8_rows_aug", "cara_vit_forward_u8_rows_aug",
+    "cara_vit_backward", "cara_head_backward", "cara_im2col_patches_u8", "cara_vit_forward_u8", "cara_im2col_patches_u8_rows", "cara_gather_labels", "cara_vit_forward_u8_rows", "cara_im2col_patches_u8_rows_crop", "cara_vit_forward_u8_rows_crop", "cara_im2col_patches_u8_rows_mix", "cara_vit_forward_u8_rows_mix", "cara_cross_entropy_mix", "cara_cross_entropy_bal", "cara_sigmoid_loss", "cara_distill_loss", "cara_aug_stat_bytes", "cara_im2col_patches_u8_rows_aug", "cara_vit_forward_u8_rows_aug",
     "cara_im2col_patches_keep", "cara_im2col_patches_u8_rows_keep", "cara_assemble_tokens_keep", "cara_vit_forward_keep", "cara_vit_forward_u8_rows_keep", "cara_ra_stat_bytes", "cara_im2col_patches_u8_rows_ra", "cara_vit_forward_u8_rows_ra", "cara_eval_accumulate", "cara_eval_state_bytes", "cara_eval_report_bytes", "cara_eval_accumulate_report", "cara_eval_combine_views", "cara_eval_predict", "cara_sizeof_struct", "cara_sizeof_gemm_args", "cara_profile_sites", "cara_profile_site_read", "cara_debug_tr_probe", "cara_debug_tr_frag",
 )
 
@@ -237,6 +237,9 @@ def lib(operands: str = None) -> C.CDLL:
     if hasattr(_lib, "cara_sigmoid_loss"):               # the sigmoid family on the same target: four floats, a vector and a flag in front
         P, I, F = C.c_void_p, C.c_int, C.c_float
         _lib.cara_sigmoid_loss.argtypes = [P, P, P, F, F, F, F, P, I, P, P, I, I, F, P, P, P]
+    if hasattr(_lib, "cara_distill_loss"):               # distillation: a teacher's logits behind the student's; alpha, T and a flag
+        P, I, F = C.c_void_p, C.c_int, C.c_float
+        _lib.cara_distill_loss.argtypes = [P, P, P, P, F, F, F, I, P, P, I, I, F, P, P, P]
     if hasattr(_lib, "cara_vit_forward_u8_rows_aug"):    # ... and a colour-jitter / erase table with its statistic scratch
         P, I = C.c_void_p, C.c_int
         _lib.cara_aug_stat_bytes.argtypes = [I]

@@ -558,6 +558,105 @@ __global__ __launch_bounds__(64) void sigmoid_loss_kernel(const float* __restric
   sl = wave_sum(sl);
   if (lane == 0) loss_per[b] = ok ? sl * invBD : qnan;
 }
+// Knowledge distillation on xent_mix_kernel's soft target q (the same wa, wb, u and guards): z = the student's row, t = the teacher's
+// row (fp32, no gradient), a = alpha in (0, 1], T = temperature.  invT = 1 / T is formed once and every tempered logit is x invT.
+// tempered_lse(x, invT) = m + __logf(sum_c __expf(x_c invT - m)), m = max_c x_c invT, is the ONE device function behind the three
+// log-sum-exps -- lse(z) (invT = 1: a product with 1.f is exact), lse(z / T) and lse(t / T) -- so that the student's and the
+// teacher's tempered log-probabilities  lz_c = z_c invT - lse(z / T),  lt_c = t_c invT - lse(t / T)  are the same operations on
+// either row:  pT = __expf(lz), r = __expf(lt), and a teacher row equal to the student's gives pT - r == 0 and lt - lz == 0 exactly.
+// soft (HARD = false):  kl = sum_c r_c (lt_c - lz_c) -- the log-ratio form: shift-invariant in either row, its error scales with the
+//   teacher's entropy and cross-entropy and not with the size of the logits, and it reuses lz and lt, which the gradient exponentiates
+//   anyway;  term_b = ((1 - a) (lse - dot) + (a T T) kl) invB,  dlogits = ((1 - a) (p - q) + (a T) (pT - r)) gsc,  p = __expf(z - lse);
+//   dot = sum_c q_c z_c as xent_mix_kernel forms it.
+// hard (HARD = true; DeiT):  yt = the LOWEST class that attains the teacher row's maximum (cara_eval_accumulate's tie rule),
+//   q' = (1 - a) q + a [c == yt]:  term_b = (lse - ((1 - a) dot + a z_yt)) invB,  dlogits = (p - q') gsc;  T is not read.
+// A teacher row with any non-finite value (found by |t_c| <= FLT_MAX, which a NaN fails, before anything else looks at the row)
+// joins the label guards: the term and the dlogits row are NaN and yt is 0, never an index formed from such a row.  The loss does
+// not depend on whether dlogits is written.  Plain operators, no contraction: the bound of tests/distill_model.py counts every rounding.
+__device__ __forceinline__ float tempered_lse(const float* __restrict__ row, int C, int lane, float invT) {
+#pragma clang fp contract(off)
+  float m = -3.0e38f;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c] * invT);
+  m = wave_max(m);
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += __expf(row[c] * invT - m);
+  s = wave_sum(s);
+  return m + __logf(s);
+}
+template <bool HARD>
+__global__ __launch_bounds__(64) void distill_kernel(const float* __restrict__ logits, const float* __restrict__ teacher,
+                                                     const int64_t* __restrict__ labels, const int* __restrict__ mix, float eps,
+                                                     float alpha, float T, float* __restrict__ loss_per, float* __restrict__ dlogits,
+                                                     int B, int C, float dscale, const float* __restrict__ loss_scale) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* lr = logits + (size_t)b * C;
+  const float* tr = teacher + (size_t)b * C;
+  float sl = 0.f, tbad = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    sl += lr[c];
+    if (!(fabsf(tr[c]) <= 3.4028235e38f)) tbad = 1.f;
+  }
+  sl = wave_sum(sl);
+  tbad = wave_max(tbad);
+  const float lse = tempered_lse(lr, C, lane, 1.f);
+  const int partner = mix ? mix[(size_t)b * 8] : b;
+  const float t = mix ? __int_as_float(mix[(size_t)b * 8 + 6]) : 0.f;
+  const int64_t yal = labels[b];
+  const bool pok = partner >= 0 && partner < B;
+  const int64_t ybl = pok ? labels[partner] : -1;
+  const bool ok = yal >= 0 && yal < C && ybl >= 0 && ybl < C && t >= 0.f && t <= 1.f && tbad == 0.f;   // (wave-uniform)
+  const int ya = ok ? (int)yal : 0, yb = ok ? (int)ybl : 0;
+  const float wa = (1.f - eps) * (1.f - t), wb = (1.f - eps) * t, u = eps / (float)C;   // (xent_mix_kernel's)
+  const float qnan = __builtin_nanf("");
+  const float invB = 1.0f / B;
+  const float gsc = invB * dscale * (loss_scale ? *loss_scale : 1.f);
+  const float oma = 1.f - alpha;
+  const float la = lr[ya];
+  float dot = (1.f - eps) * (la + t * (lr[yb] - la));
+  if (u != 0.f) dot += u * sl;
+  if (HARD) {
+    float bx = -INFINITY;
+    int bc = C;   // (-inf at index C loses against every class of a finite row)
+    for (int c = lane; c < C; c += 64)
+      if (tr[c] > bx) {
+        bx = tr[c];
+        bc = c;
+      }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ox = __shfl_xor(bx, o, 64);
+      const int oc = __shfl_xor(bc, o, 64);
+      if (ox > bx || (ox == bx && oc < bc)) {
+        bx = ox;
+        bc = oc;
+      }
+    }
+    const int yt = ok ? bc : 0;
+    if (dlogits)
+      for (int c = lane; c < C; c += 64) {
+        const float q = (c == ya ? wa : 0.f) + (c == yb ? wb : 0.f) + u;
+        const float qd = oma * q + (c == yt ? alpha : 0.f);
+        dlogits[(size_t)b * C + c] = ok ? (__expf(lr[c] - lse) - qd) * gsc : qnan;
+      }
+    if (lane == 0) loss_per[b] = ok ? (lse - (oma * dot + alpha * lr[yt])) * invB : qnan;
+  } else {
+    const float invT = 1.f / T, aT = alpha * T, aT2 = aT * T;
+    const float lseZ = tempered_lse(lr, C, lane, invT), lseT = tempered_lse(tr, C, lane, invT);
+    float kl = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float lz = lr[c] * invT - lseZ, lt = tr[c] * invT - lseT;
+      const float pT = __expf(lz), r = __expf(lt);
+      kl += r * (lt - lz);
+      if (dlogits) {
+        const float q = (c == ya ? wa : 0.f) + (c == yb ? wb : 0.f) + u;
+        dlogits[(size_t)b * C + c] = ok ? (oma * (__expf(lr[c] - lse) - q) + aT * (pT - r)) * gsc : qnan;
+      }
+    }
+    kl = wave_sum(kl);
+    if (lane == 0) loss_per[b] = ok ? (oma * (lse - dot) + aT2 * kl) * invB : qnan;
+  }
+}
 __global__ __launch_bounds__(64) void xent_sum_kernel(const float* __restrict__ loss_per, float* __restrict__ loss, int B,
                                                       float* __restrict__ found_inf) {
   float s = 0.f;
@@ -850,6 +949,28 @@ extern "C" int cara_sigmoid_loss(const float* logits, const int64_t* labels, con
   else
     hipLaunchKernelGGL(sigmoid_loss_kernel<false>, dim3(B), dim3(64), 0, st, logits, labels, mix, smoothing, thr, 0.f, -1.f, pos_weight,
                        loss + 1, dlogits, B, C, invBD, dscale, loss_scale);
+  CARA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
+  CARA_CHECK_LAUNCH();
+  return CARA_OK;
+}
+extern "C" int cara_distill_loss(const float* logits, const float* teacher, const int64_t* labels, const int* mix, float smoothing,
+                                 float alpha, float temperature, int hard, float* loss, float* dlogits, int B, int C, float dscale,
+                                 const float* loss_scale, float* found_inf, void* stream) {
+  // (every comparison is written so that a NaN fails it)
+  if (!(alpha >= 0.f && alpha <= 1.f) || (hard != 0 && hard != 1)) return CARA_E_ARG;
+  // (without a teacher's share this IS cara_cross_entropy_mix: the same launches, bit for bit; the teacher is not read)
+  if (alpha == 0.f) return cara_cross_entropy_mix(logits, labels, mix, smoothing, loss, dlogits, B, C, dscale, loss_scale, found_inf, stream);
+  if (!logits || !labels || !loss || B <= 0 || C <= 0 || !(dscale > 0.f) || !(smoothing >= 0.f && smoothing < 1.f)) return CARA_E_ARG;
+  // (a temperature so small that the fp32 1 / T is infinite would turn every tempered logit into inf or NaN: refused like T <= 0)
+  if (!teacher || (!hard && !(temperature > 0.f && temperature <= 3.4028235e38f && 1.f / temperature <= 3.4028235e38f))) return CARA_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hard)
+    hipLaunchKernelGGL(distill_kernel<true>, dim3(B), dim3(64), 0, st, logits, teacher, labels, mix, smoothing, alpha, 1.f, loss + 1, dlogits,
+                       B, C, dscale, loss_scale);
+  else
+    hipLaunchKernelGGL(distill_kernel<false>, dim3(B), dim3(64), 0, st, logits, teacher, labels, mix, smoothing, alpha, temperature, loss + 1,
+                       dlogits, B, C, dscale, loss_scale);
   CARA_CHECK_LAUNCH();
   hipLaunchKernelGGL(xent_sum_kernel, dim3(1), dim3(64), 0, st, loss + 1, loss, B, found_inf);
   CARA_CHECK_LAUNCH();

@@ -17,7 +17,7 @@ import torch
 from . import _lib as L
 from ._lib import CaraError, check, ptr, stream
 from .feed import TABLES, Feed
-from .loss import check_loss
+from .loss import check_distill, check_loss
 
 
 def _rp(rank: int) -> int:
@@ -305,10 +305,12 @@ class CaraEngine:
                 or (batch is not None and (t.device != dev or t.shape[0] != batch)):
             raise CaraError(msg.format(P=P))
 
-    def _run_forward_on(self, model, source, feed, droppath, head_w, head_b, cp, need_backward, dev):
+    def _run_forward_on(self, model, source, feed, droppath, head_w, head_b, cp, need_backward, dev, teacher=False, bad=None):
         """``source``: an fp32 batch (``feed.rows`` is None and ``keep`` the only table there can be), or the resident uint8 split
         whose images ``feed.rows`` the tables of ``feed`` shape (``train_step_resident``; with ``boxes`` at the model's own input
-        size).  Behind a ``keep`` the blocks run on 1 + K tokens, on a workspace of that size"""
+        size).  Behind a ``keep`` the blocks run on 1 + K tokens, on a workspace of that size.  ``teacher``: the teacher pass of a
+        distillation step -- eval semantics whatever ``model.training`` says (no weight dropout; the caller passes no DropPath);
+        ``bad``: the counter of refused indices to use in this engine's own place (a model teacher counts into the student's)"""
         resident, keep = feed.rows is not None, feed.keep
         if resident:
             B, img = feed.rows.shape[0], source.pixels.shape[2] if feed.boxes is None else self._model_img(model)
@@ -320,8 +322,8 @@ class CaraEngine:
             raise CaraError("uint8 pixels are normalised with the three ImageNet channel statistics: chans must be 3")
         # weight-space dropout is a train-mode thing (nn.Dropout is the identity in eval); the backward of this
         # forward reads the same struct, i.e. the same seed, and regenerates the masks
-        use_exact = self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0
-        if model.training and not use_exact and not self._warned_wd:
+        use_exact = self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0 and not teacher
+        if model.training and not use_exact and not self._warned_wd and not teacher:
             self._warned_wd = True
             import warnings
             warnings.warn("cara_amd: train-mode forwards run the FACTORED adapters without the reference's Dropout(0.1) on the "
@@ -340,7 +342,7 @@ class CaraEngine:
                   "head_w": head_w.detach().contiguous(), "head_b": head_b.detach().contiguous(), "droppath": droppath,
                   "workspace": st["ws"], "logits": logits, "stream": stream(dev)}
         if resident or keep is not None:   # (the entries that read indices count the bad ones)
-            values["bad"] = self._bad_rows(dev)
+            values["bad"] = self._bad_rows(dev) if bad is None else bad
         if resident:
             px, rows = source.pixels, feed.rows
             mean, std = self._eval_norm(dev)
@@ -640,7 +642,7 @@ class CaraEngine:
 
     def train_step(self, images, labels, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None,
                    label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, keep=None, class_weight=None,
-                   logit_bias=None, sam_rho=None, loss=None):
+                   logit_bias=None, sam_rho=None, loss=None, distill=None):
         """One fine-tuning step of vit_cp.py:45-50 without autograd bookkeeping:
         forward -> mean cross-entropy -> backward straight into ONE flat fp32 gradient buffer
         (12 CP tensors + head) -> a single all-reduce of that buffer when ``group``/the default
@@ -689,10 +691,20 @@ class CaraEngine:
         (``cara_sigmoid_loss``) on the same soft target -- labels, ``mix`` table and ``label_smoothing`` -- with the same pre-divided,
         loss-scaled ``dlogits``; it runs in both passes of a SAM step and composes with everything above.  Refused beside
         ``class_weight`` / ``logit_bias``, which are the softmax loss's.  A BCE's ``pos_weight`` is checked like ``class_weight``.
+        None: the launches are the ones they were.
+        ``distill`` (None or a ``cara_amd.loss.Distill``): knowledge distillation -- every micro-step first runs the TEACHER's forward on
+        the same batch and ``keep`` table in eval semantics (no DropPath, no weight dropout, nothing kept for a backward:
+        ``cara_vit_shape::inference``), copies its logits into ``teacher_logits``, and the loss launch is ``cara_distill_loss`` on the
+        step's labels and ``label_smoothing``: the blended loss is what is returned.  The teacher is a ``ParamEma`` of this engine
+        (the mean teacher: the update still runs last, so step n learns from the average after step n - 1), another ``cara()`` model
+        (through its own engine and precision; a ``keep`` table needs the same patch grid) or a device fp32 [batch, classes] tensor
+        (no pass).  Both passes of a SAM step read the one buffer.  The accumulate step, the all-reduce, the clip, the loss scale,
+        the optimiser and the EMA update are untouched.  Refused beside ``loss=``, ``class_weight`` and ``logit_bias``.
         None: the launches are the ones they were."""
         eps = self._smoothing(label_smoothing)
         self._sam_rho(sam_rho)
         check_loss(loss, class_weight, logit_bias)
+        check_distill(distill, loss, class_weight, logit_bias)
         if not images.is_cuda:
             raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
         dev = images.device
@@ -700,9 +712,18 @@ class CaraEngine:
             self._check_table("keep", keep, images.shape[0], dev, self._patches(images.shape[-1]))
         if labels.dtype != torch.int64 or labels.device != dev or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
             raise CaraError("labels must be an int64 [batch] tensor on the images' device (the kernel reads 8-byte class indices)")
+        teach = None
+        if distill is not None:
+            self._teacher_of(distill, dev, images.shape[0], keep=keep)
+            if images.ndim != 4 or images.shape[2] != images.shape[3]:
+                raise CaraError("images must be [B, C, H, H]")
+            x32, bad = images.contiguous().float(), self._bad_rows(dev)
+            # (the teacher's engine -- this one for an EMA teacher -- on the same batch and keep table, in eval semantics)
+            teach = lambda eng, tm, hw, hb, cp: eng._run_forward_on(tm, x32, Feed(None, keep=keep), None, hw, hb, cp, False, dev,   # noqa: E731
+                                                                    teacher=True, bad=bad)
         return self._step(dev, images.shape[0], lambda dp, hw, hb, cp: self._run_forward(images, dp, hw, hb, cp, keep=keep),
                           lambda: labels.contiguous(), optimizer, group, droppath, None, eps, accumulate, clip_grad, ema,
-                          class_weight, logit_bias, sam_rho, loss)
+                          class_weight, logit_bias, sam_rho, loss, distill, teach)
 
     def _class_vectors(self, class_weight, logit_bias, ncls, dev):
         """``class_weight`` / ``logit_bias`` of a step, refused here -- before anything is launched -- unless each is None or a
@@ -723,16 +744,18 @@ class CaraEngine:
                 seen[name] = key
 
     def _step(self, dev, B, forward, labels_of, optimizer, group, droppath, mix=None, smoothing=0.0, accumulate=None, clip_grad=None,
-              ema=None, class_weight=None, logit_bias=None, sam_rho=None, loss=None):
+              ema=None, class_weight=None, logit_bias=None, sam_rho=None, loss=None, distill=None, teach=None):
         """What train_step and train_step_resident share -- everything but the image source: ``forward(droppath, head_w,
         head_b, cp)`` -> logits of the ``B`` samples with the backward's activations kept; ``labels_of()`` -> their int64 labels
         (called inside the step, on ``dev``).  With a ``mix`` table or a ``smoothing`` the loss is the soft-target one, with a
         ``class_weight`` or a ``logit_bias`` the weighted, logit-adjusted one on that target, with a ``loss`` object the sigmoid loss
-        it describes on that target.
+        it describes on that target.  With a ``distill`` object, ``teach(engine, model, head_w, head_b, cp)`` -> the logits of the SAME
+        input through the teacher's engine and weights in eval semantics; it runs before ``forward`` (a tensor teacher needs none).
         ``accumulate``, ``clip_grad``, ``ema`` and ``sam_rho`` as in ``train_step``."""
         model = self._model()
         rho = self._sam_rho(sam_rho)
         check_loss(loss, class_weight, logit_bias)
+        plan = self._teacher_of(distill, dev, B, loss, class_weight, logit_bias)
         if rho is not None and self.weight_dropout == "exact" and model.training and self.weight_dropout_p > 0:
             raise CaraError("sam_rho cannot run with weight_dropout = 'exact' in train mode: that mode draws a fresh mask seed per "
                             "forward, so the two passes of a SAM step would see different masks")
@@ -755,6 +778,18 @@ class CaraEngine:
         with torch.no_grad(), torch.cuda.device(dev):
             if droppath is None:
                 droppath = self.draw_droppath(model, B, dev)
+            if plan is not None:
+                # ONE teacher pass per micro-step, before the student's forward (an EMA teacher runs on the student's workspace, which
+                # an inference forward leaves free for it); both passes of a SAM step read its buffer
+                kind, teng, tmodel = plan
+                if kind == "tensor":
+                    tlogits = distill.teacher
+                else:
+                    tcp, thw, thb = teng._forward_weights(tmodel, dev, distill.teacher if kind == "ema" else None)
+                    tshape = (B, thw.shape[0])
+                    tlogits = self._pinned("teacher_logits", dev, tshape, lambda: torch.empty(*tshape, device=dev))
+                    tlogits.copy_(teach(teng, tmodel, thw, thb, tcp))
+                self.teacher_logits = tlogits
             logits = forward(droppath, hw, hb, cp)
             labels = labels_of()
             B, ncls = logits.shape
@@ -773,7 +808,12 @@ class CaraEngine:
                     ptr(gv["_found_inf"]) if fp16 else None, stream(dev))
 
             def loss_and_backward(logits, loss_buf):
-                if loss is not None:
+                if plan is not None:
+                    alpha, temperature, hard = distill.c_args()
+                    check(self._lib().cara_distill_loss(ptr(logits), ptr(tlogits), ptr(labels), ptr(mix), C.c_float(smoothing),
+                                                        C.c_float(alpha), C.c_float(temperature), hard, ptr(loss_buf), ptr(self._dlogits),
+                                                        *tail), "cara_distill_loss")
+                elif loss is not None:
                     thr, fgamma, alpha = loss.c_args()
                     check(self._lib().cara_sigmoid_loss(ptr(logits), ptr(labels), ptr(mix), C.c_float(smoothing), C.c_float(thr),
                                                         C.c_float(fgamma), C.c_float(alpha), ptr(loss.pos_weight), int(loss.sum_classes),
@@ -803,6 +843,49 @@ class CaraEngine:
                 if ema is not None:
                     ema.update()
         return self._loss_buf[0]
+
+    # ------------------------------------------------------------------ knowledge distillation
+    teacher_logits = None   # device fp32 [batch, classes]: what the last distilled micro-step's loss read as the teacher's logits
+
+    @staticmethod
+    def _img_of(model):
+        img = getattr(model.patch_embed, "img_size", None)
+        return tuple(img) if isinstance(img, (tuple, list)) else (img, img)
+
+    def _teacher_of(self, distill, dev, B, loss=None, class_weight=None, logit_bias=None, keep=None):
+        """``distill=`` of a step of ``B`` samples on ``dev``, refused here -- before anything is launched -- unless it is None or a
+        ``loss.Distill`` this step can run; -> None, or (kind, the engine the teacher pass runs through, the model it runs on):
+        ("tensor", None, None), ("ema", self, the model) or ("model", the teacher's engine, the teacher)."""
+        d = check_distill(distill, loss, class_weight, logit_bias)
+        if d is None:
+            return None
+        model = self._model()
+        if not hasattr(model.head, "weight"):
+            raise CaraError("the classifier head must be a Linear (num_classes > 0)")
+        ncls, kind, t = model.head.weight.shape[0], d.kind(), d.teacher
+        if kind == "fit":
+            raise CaraError("Distill('ema') is resolved by recipe.fit(ema_decay=...): hand a step the ParamEma itself")
+        if kind == "tensor":
+            if t.dtype != torch.float32 or tuple(t.shape) != (B, ncls) or t.device != dev or not t.is_contiguous():
+                raise CaraError(f"a tensor teacher must be a contiguous fp32 [{B}, {ncls}] tensor -- the batch's logits, one column per "
+                                f"class of the head -- on the step's device, not {t.dtype} {tuple(t.shape)} on {t.device}")
+            return kind, None, None
+        if kind == "ema":
+            self._check_ema(t, dev, "the distillation teacher")
+            return kind, self, model
+        teng = t._cara_engine
+        if not hasattr(t.head, "weight") or t.head.weight.device != dev or getattr(t, "CP_" + teng.cp_fields[0]).device != dev:
+            raise CaraError("the teacher model must sit on the step's device (and have a Linear head)")
+        if t.head.weight.shape[0] != ncls:
+            raise CaraError(f"the teacher model has {t.head.weight.shape[0]} classes, the student {ncls}")
+        if self._img_of(t) != self._img_of(model):
+            raise CaraError(f"the teacher model's image size {self._img_of(t)} is not the student's {self._img_of(model)}")
+        if keep is not None and tuple(t.patch_embed.proj.kernel_size) != tuple(model.patch_embed.proj.kernel_size):
+            raise CaraError("keep with a model teacher needs the same patch grid: the table names the student's patches")
+        if teng.precision not in ("bf16", "fp16"):
+            raise CaraError(f"precision must be 'bf16' or 'fp16', not {teng.precision!r}")
+        teng._refuse_fp16_unfactored()
+        return kind, teng, t
 
     # ------------------------------------------------------------------ sharpness-aware minimisation
     sam_loss = None   # device scalar: the loss of the last SAM step's second pass (at the perturbed weights)
@@ -944,7 +1027,7 @@ class CaraEngine:
 
     def train_step_resident(self, split, rows, optimizer=None, group=None, droppath: Optional[torch.Tensor] = None, boxes=None,
                             mix=None, label_smoothing: float = 0.0, accumulate=None, clip_grad=None, ema=None, aug=None, keep=None, ra=None,
-                            class_weight=None, logit_bias=None, sam_rho=None, loss=None):
+                            class_weight=None, logit_bias=None, sam_rho=None, loss=None, distill=None):
         """``train_step`` on the images ``rows`` (device int64 [batch], any order, duplicates allowed) of a
         ``data.ResidentSplit`` on the model's device: the patch rows are built straight from the split's uint8 pixels
         (``cara_vit_forward_u8_rows``: no fp32 batch is written) and the labels gathered by ``cara_gather_labels``; everything
@@ -974,15 +1057,26 @@ class CaraEngine:
         ``sam_rho`` as in ``train_step``: the second pass reads the same rows through the same tables -- the feed is deterministic, erase
         noise included, so its input is bit for bit the first pass's.
         ``loss`` as in ``train_step``: on the soft target of both labels where there is a ``mix`` table.
+        ``distill`` as in ``train_step``: the teacher reads the same split, rows and tables (``boxes``, ``mix``, ``aug``, ``ra``, ``keep``) --
+        the feed is deterministic, so its input is bit for bit the student's -- and the loss is on the soft target of both labels.
         Without any of them, the step is the one it was."""
         eps = self._smoothing(label_smoothing)
         self._sam_rho(sam_rho)
         check_loss(loss, class_weight, logit_bias)
+        check_distill(distill, loss, class_weight, logit_bias)
         feed = Feed(rows, boxes, mix, aug, keep, ra)
         model, dev = self._resident_args(split, feed)
+        teach = None
+        if distill is not None:
+            self._teacher_of(distill, dev, rows.shape[0], keep=keep)
+            # (every index the teacher pass refuses is counted into THIS engine's counter, whichever engine runs the pass: a bad row
+            # then counts once more per teacher pass, and resident_bad_rows() of the training engine sees all of them)
+            bad = self._bad_rows(dev)
+            teach = lambda eng, tm, hw, hb, cp: eng._run_forward_on(tm, split, feed, None, hw, hb, cp, False, dev, teacher=True,   # noqa: E731
+                                                                    bad=bad)
         return self._step(dev, rows.shape[0], lambda dp, hw, hb, cp: self._run_forward_on(model, split, feed, dp, hw, hb, cp, True, dev),
                           lambda: self._gather_labels(split, rows), optimizer, group, droppath, mix, eps, accumulate, clip_grad, ema,
-                          class_weight, logit_bias, sam_rho, loss)
+                          class_weight, logit_bias, sam_rho, loss, distill, teach)
 
     def forward_resident(self, split, rows, droppath: Optional[torch.Tensor] = None, boxes=None, mix=None, weights=None, aug=None,
                          keep=None, ra=None):

@@ -1,7 +1,8 @@
 """The sigmoid losses of the fused train step (``cara_sigmoid_loss``, include/cara_hip.h): small value objects handed to
 ``CaraEngine.train_step(..., loss=)``, ``train_step_resident``, ``recipe.GraphedTrainStep`` and ``recipe.fit``.  They hold settings
 only; the arithmetic is the kernel's.  Every value the C entry refuses is refused here first, on the host, before a step launches
-anything.  ``loss=None`` is the softmax cross-entropy the step always ran."""
+anything.  ``loss=None`` is the softmax cross-entropy the step always ran.  ``Distill`` is the value object of ``distill=``: knowledge
+distillation on that softmax cross-entropy (``cara_distill_loss``) against a teacher whose forward the step runs itself."""
 from __future__ import annotations
 
 import math
@@ -97,6 +98,63 @@ class Focal(SigmoidLoss):
 
     def __repr__(self):
         return f"Focal(gamma={self.gamma!r}, alpha={self.alpha!r}, sum_classes={self.sum_classes})"
+
+
+class Distill:
+    """Knowledge distillation in the fused step (``cara_distill_loss``): handed to ``train_step(..., distill=)``,
+    ``train_step_resident``, ``recipe.GraphedTrainStep`` and ``recipe.fit``.  On the step's soft target ``q`` and with the teacher's
+    logits ``t`` of the same input:
+    soft (``hard=False``): ``(1 - alpha) * cross_entropy(z, q) + alpha * T**2 * kl_div(log_softmax(z / T), softmax(t / T),
+    reduction="batchmean")`` (Hinton et al.);  hard (``hard=True``, DeiT): the cross-entropy on ``(1 - alpha) q + alpha
+    onehot(argmax t)``, ties to the lowest class; ``temperature`` is then not read.
+    ``teacher`` is one of
+    * a ``ParamEma`` of the training engine (``CaraEngine.make_ema``) -- the mean teacher: the step's own forward on the average;
+    * another ``cara()`` model on the same device with the same image size and class count -- its rank, ``cp_length``, depth, dim and
+      precision are its own: the pass runs through its engine, in eval semantics whatever its ``training`` flag says;
+    * a device fp32 [batch, classes] tensor of recorded logits (contiguous, on the step's device): no teacher pass;
+    * the string ``"ema"``, for ``recipe.fit(ema_decay=...)`` alone, which puts the average it trains with in its place.
+    ``alpha`` in [0, 1], ``temperature`` finite and > 0 (and not below 2.94e-39, where the fp32 1 / T overflows).  The teacher gets no
+    gradient and its pass runs before the student's."""
+
+    def __init__(self, teacher, alpha=0.5, temperature=1.0, hard=False):
+        alpha, temperature = _number("alpha", alpha), _number("temperature", temperature)
+        if not (0.0 <= alpha <= 1.0):                                        # (a NaN fails the comparison)
+            raise CaraError(f"alpha must be a number in [0, 1], not {alpha!r}")
+        hard = _flag("hard", hard)
+        # (the kernel multiplies by the fp32 1 / T: a T whose reciprocal overflows there would make every tempered logit inf or NaN)
+        t32 = torch.tensor(temperature, dtype=torch.float32)    # (what the entry gets)
+        if not hard and not (0.0 < temperature < math.inf and bool(torch.isfinite(t32)) and bool(torch.isfinite(1.0 / t32))):
+            raise CaraError(f"temperature must be a number > 0 that is finite in fp32 and whose fp32 reciprocal is finite, not {temperature!r}")
+        from .ema import ParamEma
+        if not (torch.is_tensor(teacher) or isinstance(teacher, ParamEma) or getattr(teacher, "_cara_engine", None) is not None
+                or (isinstance(teacher, str) and teacher == "ema")):
+            raise CaraError("teacher must be a ParamEma of the engine, a cara() model, an fp32 [batch, classes] tensor of logits or, "
+                            f"for recipe.fit, the string 'ema', not {teacher!r}")
+        self.teacher, self.alpha, self.temperature, self.hard = teacher, alpha, temperature, hard
+
+    def kind(self):
+        """"tensor", "ema", "model" or "fit" (the unresolved string)"""
+        from .ema import ParamEma
+        t = self.teacher
+        return "tensor" if torch.is_tensor(t) else "ema" if isinstance(t, ParamEma) else "fit" if isinstance(t, str) else "model"
+
+    def c_args(self):
+        """(alpha, temperature, hard) as the C entry takes them"""
+        return self.alpha, self.temperature, int(self.hard)
+
+    def __repr__(self):
+        return f"Distill({self.kind()} teacher, alpha={self.alpha!r}, temperature={self.temperature!r}, hard={self.hard})"
+
+
+def check_distill(distill, loss=None, class_weight=None, logit_bias=None):
+    """``distill=`` of a step: None or a ``Distill``; not beside ``loss=`` (the sigmoid losses) or ``class_weight`` / ``logit_bias``"""
+    if distill is None:
+        return None
+    if not isinstance(distill, Distill):
+        raise CaraError(f"distill must be None or a cara_amd.loss.Distill, not {distill!r}")
+    if loss is not None or class_weight is not None or logit_bias is not None:
+        raise CaraError("distill= cannot run beside loss=, class_weight or logit_bias: the distilled loss is the softmax cross-entropy's")
+    return distill
 
 
 def check_loss(loss, class_weight=None, logit_bias=None):

@@ -19,7 +19,7 @@ import torch
 
 from ._lib import CaraError
 from .feed import Feed
-from .loss import BCE, check_loss
+from .loss import BCE, Distill, check_distill, check_loss
 
 
 class CosineLRScheduler:
@@ -139,10 +139,15 @@ class GraphedTrainStep:
     are never replaced, so the graph's addresses stay good.
     ``loss`` (``train_step``'s: a ``loss.BCE`` or ``loss.Focal``): the object -- and with it a BCE's ``pos_weight`` tensor, whose address
     the graph captures -- is held here and in every entry; its settings and that tensor's identity are part of the key, and a replay
-    re-reads the tensor's contents as it re-reads ``class_weight`` (checked on the host before the replay)."""
+    re-reads the tensor's contents as it re-reads ``class_weight`` (checked on the host before the replay).
+    ``distill`` (``train_step``'s: a ``loss.Distill``): the teacher pass is captured with the rest of the step.  What keeps the
+    graph's addresses good is that every entry HOLDS the object (and with it a tensor teacher or the teacher model),
+    ``engine.teacher_logits`` and a model teacher's workspace.  The object's identity is also named in the key; since the object
+    is fixed for the life of this ``GraphedTrainStep`` that only labels the entry, it tells no two entries apart.  A tensor teacher is
+    a static input of the caller's: the graph holds its address and every replay re-reads its contents."""
 
     def __init__(self, engine, optimizer, label_smoothing: float = 0.0, clip_grad=None, ema=None, class_weight=None, logit_bias=None,
-                 sam_rho=None, loss=None):
+                 sam_rho=None, loss=None, distill=None):
         if not getattr(optimizer, "capturable", False):
             raise CaraError("GraphedTrainStep needs cara_amd.optim.AdamW(capturable=True)")
         if ema is not None and not getattr(ema, "capturable", False):
@@ -153,6 +158,7 @@ class GraphedTrainStep:
         self.class_weight, self.logit_bias = class_weight, logit_bias
         self.sam_rho = engine._sam_rho(sam_rho)
         self.loss = check_loss(loss, class_weight, logit_bias)
+        self.distill = check_distill(distill, loss, class_weight, logit_bias)
         self._graphs = {}   # key -> "warm", then (graph, source, static inputs, loss, held): source is the split, None for images
 
     def _kw(self):
@@ -170,6 +176,8 @@ class GraphedTrainStep:
             kw["sam_rho"] = self.sam_rho
         if self.loss is not None:
             kw["loss"] = self.loss
+        if self.distill is not None:
+            kw["distill"] = self.distill
         return kw
 
     def __call__(self, x, y, group=None, accumulate=None, keep=None):
@@ -190,11 +198,14 @@ class GraphedTrainStep:
             feed = Feed.of(y)
             if feed.keep is None and keep is not None:
                 feed = feed._replace(keep=keep)
-            eng._resident_args(x, feed)
+            _, dev = eng._resident_args(x, feed)
+            eng._teacher_of(self.distill, dev, feed.rows.shape[0], keep=feed.keep)
             names = tuple(feed.tables())
             # (the split itself is part of the key, not its id(): the entry then keeps it -- and the address the graph reads -- alive)
             return self._run(lambda s: eng.train_step_resident(x, s[0], self.opt, group=group, **dict(zip(names, s[1:])), **kw),
                              feed.static(), ("resident", x, names), group)
+        if self.distill is not None:
+            eng._teacher_of(self.distill, x.device, x.shape[0], keep=keep)
         if keep is None:
             return self._run(lambda s: eng.train_step(s[0], s[1], self.opt, group=group, **kw), (x, y), ("images", None, ()), group)
         if x.ndim != 4 or x.shape[2] != x.shape[3]:
@@ -202,6 +213,15 @@ class GraphedTrainStep:
         eng._check_table("keep", keep, x.shape[0], x.device, eng._patches(x.shape[2]))
         return self._run(lambda s: eng.train_step(s[0], s[1], self.opt, group=group, keep=s[2], **kw), (x, y, keep),
                          ("images", None, ("keep",)), group)
+
+    def _distill_held(self):
+        """what a captured distilled step reads besides the engine's own buffers: the object (its tensor teacher or the teacher model),
+        the engine's teacher-logits buffer and a model teacher's workspace of the captured shape"""
+        d = self.distill
+        if d is None:
+            return None
+        teng = getattr(d.teacher, "_cara_engine", None)
+        return (d, self.eng.teacher_logits, None if teng is None else teng._ws[teng._last_key]["ws"])
 
     def _run(self, step, live, key, group):
         """warm, capture, replay: ``step(inputs)`` is the eager step on a tuple shaped like ``live``, this call's inputs;
@@ -220,6 +240,8 @@ class GraphedTrainStep:
             key = (*key, ("sam_rho", self.sam_rho))
         if self.loss is not None:
             key = (*key, ("loss", *self.loss.key()))
+        if self.distill is not None:
+            key = (*key, ("distill", id(self.distill)))
         ent = self._graphs.get(key)
         if ent is None:
             self._graphs[key] = "warm"
@@ -241,7 +263,7 @@ class GraphedTrainStep:
             # (the last element keeps what the engine would replace at an eager step of another batch size in between -- its dlogits
             # buffer and the workspace of this shape -- as ``loss`` keeps its loss buffer: the graph holds their addresses)
             ent = self._graphs[key] = (gr, key[1], static, loss, (eng._dlogits, eng._ws[eng._last_key]["ws"], self.class_weight, self.logit_bias,
-                                                                   self.loss, getattr(self.loss, "pos_weight", None)))
+                                                                   self.loss, getattr(self.loss, "pos_weight", None), self._distill_held()))
             # (the capture itself ran nothing: fall through to the replay, which is this call's step)
         gr, _, static, loss = ent[:4]
         for s, t in zip(static, live):
@@ -256,7 +278,7 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
         graph: bool = False, eval_mode: str = "reference", feed: str = "batches", label_smoothing: float = 0.0, clip_grad=None,
         accum_steps: int = 1, ema_decay: Optional[float] = None, ema_warmup: bool = False, patch_drop=None,
         eval_metric: str = "top1", class_weight=None, logit_bias=None, eval_views=None, eval_combine: str = "prob", sam_rho=None, loss=None,
-        save_predictions: Optional[str] = None):
+        save_predictions: Optional[str] = None, distill=None):
     """``train_batches(epoch)`` yields (images, labels) already on the device (per-rank shard under
     data parallelism).  Returns (best accuracy, optimizer).
 
@@ -327,8 +349,14 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     ``save_best`` keeps the weights of -- is followed by one ``CaraEngine.predict`` pass with the same ``eval_views`` /
     ``eval_combine`` and the same weights (the average with ``ema_decay``), and rank 0 writes its table there
     (``evalcount.Predictions.save``, with the split's file names when the source is a ``ResidentSplit``): when ``fit`` returns
-    the file holds the per-sample predictions of the returned best pass."""
+    the file holds the per-sample predictions of the returned best pass.
+    ``distill`` (a ``loss.Distill``): every training step of either feed, eager or graphed, is a distilled one (``train_step(...,
+    distill=)``).  ``Distill("ema", ...)`` with ``ema_decay = d`` is the mean teacher: the string is replaced by the average this
+    call trains with.  Not beside ``loss``, ``class_weight`` or ``logit_bias``.  The evaluation epochs are untouched."""
     check_loss(loss, class_weight, logit_bias)
+    check_distill(distill, loss, class_weight, logit_bias)
+    if distill is not None and distill.kind() == "fit" and ema_decay is None:
+        raise CaraError("fit: Distill('ema') names the average fit trains with: it needs ema_decay")
     if save_predictions is not None and eval_mode != "sharded":
         raise CaraError("fit: save_predictions is written by CaraEngine.predict: it needs eval_mode = 'sharded'")
     if eval_views is not None and eval_mode != "sharded":
@@ -392,6 +420,10 @@ def fit(model, train_batches: Callable[[int], Iterable], test_batches: Optional[
     if ema_decay is not None:
         ema = eng.ema = eng.make_ema(ema_decay, warmup=ema_warmup, capturable=graph)
         smooth["ema"] = ema
+    if distill is not None:
+        if distill.kind() == "fit":
+            distill = Distill(ema, distill.alpha, distill.temperature, distill.hard)
+        smooth["distill"] = distill
     gstep = GraphedTrainStep(eng, opt, **smooth) if graph else None
     best = 0.0
     scored = {"report": True} if eval_metric == "mean_per_class" else {}

@@ -485,6 +485,31 @@ int cara_cross_entropy_bal(const float* logits, const int64_t* labels, const int
 int cara_sigmoid_loss(const float* logits, const int64_t* labels, const int* mix, float smoothing, float target_threshold,
                       float gamma, float alpha, const float* pos_weight, int sum_classes, float* loss, float* dlogits,
                       int B, int C, float dscale, const float* loss_scale, float* found_inf, void* stream);
+/* Knowledge distillation on cara_cross_entropy_mix's soft target (Hinton et al.; DeiT's hard variant): teacher = device fp32 [B,C],
+ * dense, the logits of a teacher for the same samples -- it gets no gradient.  labels, mix, smoothing and the tail arguments from
+ * loss on are cara_cross_entropy_mix's, q its soft target, z = logits[b], t = teacher[b], a = alpha in [0, 1], T = temperature.
+ * All in fp32, one wave per sample:
+ *   soft (hard == 0):  p = softmax(z),  pT = softmax(z / T),  r = softmax(t / T),
+ *     loss[1 + b] = [(1 - a)(lse(z) - sum_c q_c z_c) + a T^2 sum_c r_c (log r_c - log pT_c)] / B,
+ *     dlogits[b][c] = [(1 - a)(p_c - q_c) + a T (pT_c - r_c)] / B * dscale * loss scale
+ *     -- (1 - a) cross_entropy(z, q) + a T^2 kl_div(log_softmax(z / T), softmax(t / T), reduction = "batchmean") and its gradient.
+ *     log r_c and log pT_c are x_c (1 / T) - lse(x / T) from ONE function applied to either row, and the sum is taken over their
+ *     differences: teacher == logits (the same values) with a == 1 gives a dlogits of exact zeros.
+ *   hard (hard == 1):  yt = the lowest class index that attains the maximum of t (cara_eval_accumulate's tie rule),
+ *     q' = (1 - a) q + a onehot(yt),  loss[1 + b] = (lse(z) - sum_c q'_c z_c) / B,  dlogits = (p - q') / B * dscale * loss scale;
+ *     temperature is not read.
+ *   loss[0] = the sum of the terms through the fixed tree (unscaled).  The loss is linear in the samples: dscale, accumulation
+ *   windows and a SUM all-reduce mean what they mean above.
+ * Bit for bit: alpha == 0 is cara_cross_entropy_mix (the same launches; teacher is not read and may be NULL); dlogits NULL gives the
+ * same loss.  The label and mix guards are cara_cross_entropy_mix's.  With alpha > 0 a teacher row that holds a NaN, +inf or -inf
+ * makes that sample's term, its dlogits row and loss[0] NaN and is never turned into a class index; every other sample's outputs
+ * are the bits they are without it.
+ * CARA_E_ARG, nothing launched: alpha outside [0, 1] or NaN; hard outside {0, 1}; with alpha > 0: teacher NULL, and in soft mode a
+ * temperature that is not finite, not > 0, or so small that the fp32 1 / temperature is not finite (below about 2.94e-39);
+ * everything cara_cross_entropy_mix refuses.  found_inf is cleared.                                                            */
+int cara_distill_loss(const float* logits, const float* teacher, const int64_t* labels, const int* mix, float smoothing,
+                      float alpha, float temperature, int hard, float* loss, float* dlogits, int B, int C, float dscale,
+                      const float* loss_scale, float* found_inf, void* stream);
 /* Scoring on the device (test() of vit_cp.py:73-82 without its per-batch host read): for the first n_valid <= B rows of
  * logits fp32 [B,classes] (row stride ldl floats) and labels int64 [B], ADD into `state`, five 64-bit words
  * (cara_eval_state_bytes() = 40 bytes, 8-byte aligned, zeroed by the caller before the first batch):
