@@ -317,7 +317,8 @@ extern "C" int cara_skinny_xu(const void* X, int ldx, const void* Ut, void* T, v
 extern "C" int cara_skinny_xu_r(const void* X, int ldx, const void* Ut, void* T, void* Tt, int ldt,
                                 int M, int K, int Rp, int rank, void* stream) {
   if (!X || !Ut || !T || M <= 0 || K <= 0 || (K & 31) || rank <= 0 || rank > Rp) return CARA_E_ARG;
-  // ldx < 0: X is K-panel-major with -ldx >= M rows per panel (sliced kernel only)
+  if (!(Rp == 32 || Rp == 64)) return CARA_E_ARG;   // (before the memset below: a refusal writes nothing)
+  // ldx < 0: X is K-panel-major with -ldx >= M rows per panel (both kernels)
   const bool xpanels = ldx < 0;
   if (xpanels ? -ldx < M : ((ldx & 7) || ldx < K)) return CARA_E_ARG;
   if (Tt && (ldt < M || (ldt & 7))) return CARA_E_ARG;

@@ -367,6 +367,14 @@ def test_tskinny(M, K1, Rp):
     L().tskinny_xtg(X, Gt, D, cs)
     close(D, X.double().t() @ G.double(), 1e-4, 2e-3 * math.sqrt(M / 100), "tskinny D")
     close(cs, X.double().sum(0), 1e-4, 2e-3 * math.sqrt(M / 100), "tskinny colsum")
+    # ... and the bound derived from the launch's own chunk and step counts (oracle/skinny_model.py; M = 12608: waves of 4 and 5 steps,
+    # which the shapes of tests/test_skinny_contract_gpu.py do not reach)
+    from oracle import skinny_model
+    o = skinny_model.xtg(X, Gt, M, K1, Rp, Rp)
+    for name, got in (("D", D), ("colsum", cs)):
+        ok, ratio = _K().hold_f32(got, *o[name])
+        print(f"tskinny {M} {K1} {Rp} {name}: worst/bound {ratio:.3f}, steps per wave {sorted(skinny_model.ts_wave_steps(M, K1))}")
+        assert bool(ok.all()), (name, ratio)
     D2 = torch.empty_like(D)
     L().tskinny_xtg(X, Gt, D2, None)
     assert torch.equal(D, D2), "tskinny must be bitwise reproducible (fixed-order slab sum)"

@@ -78,3 +78,12 @@ ADAPTER_CAPS = {"pack": 0.02}
 # in either build; its derived term gamma(Rp + 2) (|W| + |delta|) stays below a quarter step, so the same cap is in force there, and
 # where a term is not below a quarter step no cap applies (the interval alone, as for the offset LayerNorm rows).
 EXACT_CAPS = {"merge_Weff": 0.005, "merge_Dm": 0.005, "dd_Dm": 0.005}
+
+# The skinny products as stand-alone launches (oracle/skinny_model.py): T = X U, its transpose and G' = dY Vs, one kind "T", under
+# the same rule as GEMM_CAPS (the share is taken over the elements whose derived term is below a quarter of their own 16-bit step; one
+# neighbour case never breaks a cap).  Started from GEMM_CAPS["T"] and kept there: the fp32 other-order restatement
+# (tests/test_skinny_model.py, `python -m tests.test_skinny_model`; table in docs/findings/skinny_contract.md section 3) has at most
+# ONE neighbour case per tensor on every host case and in both builds, a share of at most 0.0003 (fp16; bf16 none): an eighth of half
+# the cap.  A tensor of fewer than 400 elements (M = 1: 32) cannot express half the cap -- one element of it is
+# more -- and is held to "at most one neighbour case", as check_16 holds it.  Never fitted to a device.
+SKINNY_CAPS = {"T": GEMM_CAPS["T"]}
