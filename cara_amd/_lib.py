@@ -27,7 +27,7 @@ SYMBOLS = (
     "cara_grad_accumulate", "cara_grad_clip_scratch_bytes", "cara_grad_clip", "cara_ema_update", "cara_sam_perturb", "cara_sam_restore",
     "cara_weight_dropout_hash", "cara_materialize_merge", "cara_dropout_grad_scratch_bytes", "cara_dropout_grad_contract", "cara_colsum_scratch_bytes", "cara_colsum_bf16", "cara_factor_prep", "cara_factor_grad_scratch_bytes", "cara_factor_grad_reduce", "cara_vit_workspace_bytes", "cara_vit_forward",
     "cara_vit_backward", "cara_head_backward", "cara_im2col_patches_u8", "cara_vit_forward_u8", "cara_im2col_patches_u8_rows", "cara_gather_labels", "cara_vit_forward_u8_rows", "cara_im2col_patches_u8_rows_crop", "cara_vit_forward_u8_rows_crop", "cara_im2col_patches_u8_rows_mix", "cara_vit_forward_u8_rows_mix", "cara_cross_entropy_mix", "cara_cross_entropy_bal", "cara_sigmoid_loss", "cara_distill_loss", "cara_aug_stat_bytes", "cara_im2col_patches_u8_rows_aug", "cara_vit_forward_u8_rows_aug",
-    "cara_im2col_patches_keep", "cara_im2col_patches_u8_rows_keep", "cara_assemble_tokens_keep", "cara_vit_forward_keep", "cara_vit_forward_u8_rows_keep", "cara_ra_stat_bytes", "cara_im2col_patches_u8_rows_ra", "cara_vit_forward_u8_rows_ra", "cara_eval_accumulate", "cara_eval_state_bytes", "cara_eval_report_bytes", "cara_eval_accumulate_report", "cara_eval_combine_views", "cara_eval_predict", "cara_sizeof_struct", "cara_sizeof_gemm_args", "cara_profile_sites", "cara_profile_site_read", "cara_debug_tr_probe", "cara_debug_tr_frag",
+    "cara_im2col_patches_keep", "cara_im2col_patches_u8_rows_keep", "cara_assemble_tokens_keep", "cara_vit_forward_keep", "cara_vit_forward_u8_rows_keep", "cara_ra_stat_bytes", "cara_im2col_patches_u8_rows_ra", "cara_vit_forward_u8_rows_ra", "cara_eval_accumulate", "cara_eval_state_bytes", "cara_eval_report_bytes", "cara_eval_accumulate_report", "cara_eval_combine_views", "cara_eval_predict", "cara_token_mean", "cara_token_mean_bwd", "cara_sizeof_struct", "cara_sizeof_gemm_args", "cara_profile_sites", "cara_profile_site_read", "cara_debug_tr_probe", "cara_debug_tr_frag",
 )
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_GELU_DG, EPI_MULH = range(7)
@@ -110,7 +110,7 @@ class VitShape(C.Structure):
     _fields_ = [("B", C.c_int), ("img", C.c_int), ("patch", C.c_int), ("chans", C.c_int),
                 ("tokens", C.c_int), ("num_classes", C.c_int), ("eps", C.c_float),
                 ("wd_exact", C.c_int), ("wd_p", C.c_float), ("wd_seed", C.c_uint), ("inference", C.c_int),
-                ("loss_scale", C.c_void_p), ("found_inf", C.c_void_p)]
+                ("loss_scale", C.c_void_p), ("found_inf", C.c_void_p), ("pool", C.c_int)]
 
 
 class TsReduce(C.Structure):
@@ -259,6 +259,10 @@ def lib(operands: str = None) -> C.CDLL:
         _lib.cara_ra_stat_bytes.restype = C.c_size_t
         _lib.cara_im2col_patches_u8_rows_ra.argtypes = [P, I, I, I, P, P, P, P, P, P, P, P, I, P, P, P, P, I, I, I, I, I, P]
         _lib.cara_vit_forward_u8_rows_ra.argtypes = [P, P, P, P, P, P, P, I, I, I] + [P] * 15
+    if hasattr(_lib, "cara_token_mean"):   # the pooled readout: ints between pointers
+        P, I = C.c_void_p, C.c_int
+        _lib.cara_token_mean.argtypes = [P, I, I, I, I, P, P]
+        _lib.cara_token_mean_bwd.argtypes = [P, P, I, I, I, I, P, P, I, P]
     if hasattr(_lib, "cara_grad_clip"):   # accumulation and clipping over the flat gradient buffer (a size_t and a float between pointers)
         P, Z, F = C.c_void_p, C.c_size_t, C.c_float
         _lib.cara_grad_accumulate.argtypes = [P, P, P, Z, P]

@@ -69,6 +69,16 @@ _STRUCTURE = {
 }
 
 
+def pooled_readout(model) -> bool:
+    """Is this the mean-pooled readout the fused path computes -- ``global_pool == "avg"``, ``norm`` an Identity and ``fc_norm`` an
+    affine ``LayerNorm(embed_dim)``: ``head(fc_norm(x[:, 1:].mean(1)))``?  (Anything else with a pool or an fc_norm is refused by
+    ``_check_vit``.)"""
+    fc = getattr(model, "fc_norm", None)
+    return getattr(model, "global_pool", "token") == "avg" and isinstance(getattr(model, "norm", None), nn.Identity) and \
+        isinstance(fc, nn.LayerNorm) and fc.weight is not None and fc.bias is not None and \
+        tuple(fc.normalized_shape) == (model.embed_dim,)
+
+
 def _check_vit(model) -> None:
     """What the HIP path supports of a timm-shaped ViT (the reference's configuration, vit_cp.py:155): say so up
     front instead of computing something else."""
@@ -119,12 +129,19 @@ def _check_vit(model) -> None:
 
     def drop_p(m):
         return float(getattr(m, "p", getattr(m, "prob", 0.0)) or 0.0)
+    # The one readout besides the cls token: the mean of the patch tokens through fc_norm (timm's global_pool = "avg" with its default
+    # fc_norm: norm an Identity, fc_norm an affine LayerNorm).  Every other mix of the three is another function.
+    pooled = pooled_readout(model)
     for name in ("fc_norm", "norm_pre", "patch_drop", "attn_pool"):
         m = getattr(model, name, None)
-        if live(m) and not (name == "patch_drop" and drop_p(m) == 0.0):
-            bad(f"{name} is not supported (timm 0.4.12's VisionTransformer has none)")
-    if getattr(model, "global_pool", "token") not in ("token", "", None):
-        bad(f"global_pool = {model.global_pool!r}: only the cls-token readout is supported")
+        if live(m) and not (name == "patch_drop" and drop_p(m) == 0.0) and not (name == "fc_norm" and pooled):
+            bad(f"{name} is not supported (timm 0.4.12's VisionTransformer has none)" if name != "fc_norm" else
+                "fc_norm is supported behind global_pool = 'avg' with norm = Identity only (the cls-token readout has none)")
+    if not pooled and getattr(model, "global_pool", "token") not in ("token", "", None):
+        bad(f"global_pool = {model.global_pool!r}: only the cls-token readout and 'avg' with norm = Identity and fc_norm = LayerNorm(embed_dim) "
+            "(the mean of the patch tokens through fc_norm) are supported")
+    if not pooled and (not isinstance(model.norm, nn.LayerNorm) or model.norm.weight is None):
+        bad("norm must be an affine LayerNorm (the cls-token readout)")
     if int(getattr(model, "num_prefix_tokens", 1)) != 1 or getattr(model, "no_embed_class", False) or \
             getattr(model, "reg_token", None) is not None:
         bad("exactly one prefix token (cls, with its own position embedding) is supported")
@@ -249,6 +266,8 @@ def cara(config: Dict[str, Any]) -> th.nn.Module:
         raise CaraError("cp_length must be 2, 3, 4 or 5")
     if cp_length == 2 and config.get("weight_dropout", "off") == "exact":
         raise CaraError("cp_length 2 (dense QKV deltas) runs with weight_dropout = 'off' only")
+    if pooled_readout(model) and config.get("weight_dropout", "off") == "exact":
+        raise CaraError("a mean-pooled readout (global_pool = 'avg') runs with weight_dropout = 'off' only")
     if cp_length == 2 and getattr(model, "embed_dim", 128) % 128:
         raise CaraError("cp_length 2 (dense QKV deltas) needs embed_dim % 128 == 0 (its backward forms the dense x^T dY in 128 x 128 tiles)")
     global global_model

@@ -49,8 +49,19 @@ def resize_pos_embed(posemb: torch.Tensor, posemb_new: torch.Tensor, num_tokens:
     return torch.cat([tok, grid], dim=1)
 
 
+def _refuse_pooled(model, what: str) -> None:
+    """The Google/JAX ViT applies ``encoder_norm`` to the tokens BEFORE its readout; a mean-pooled model here carries ``fc_norm``
+    BEHIND the pool and no ``norm``: the same numbers under the other name would be a different function."""
+    from ._lib import CaraError
+    from .cara import pooled_readout
+    if pooled_readout(model) or (hasattr(model, "fc_norm") and not hasattr(getattr(model, "norm", None), "weight")):
+        raise CaraError(f"{what}: the JAX layout has encoder_norm in front of the readout; a mean-pooled model (global_pool = 'avg', "
+                        "fc_norm behind the pool) has no counterpart of it -- load and save such a model through its state dict")
+
+
 def jax_to_state_dict(w: Dict[str, np.ndarray], model) -> Dict[str, torch.Tensor]:
     """timm-0.4.12-keyed tensors for every backbone parameter of ``model`` found in the JAX dict."""
+    _refuse_pooled(model, "jax_to_state_dict")
     prefix = "opt/target/" if "opt/target/embedding/kernel" in w else ""
     sd: Dict[str, torch.Tensor] = {}
     sd["patch_embed.proj.weight"] = _n2p(w[f"{prefix}embedding/kernel"])
@@ -86,6 +97,7 @@ def jax_to_state_dict(w: Dict[str, np.ndarray], model) -> Dict[str, torch.Tensor
 
 def state_dict_to_jax(model) -> Dict[str, np.ndarray]:
     """Inverse mapping (export in the Google layout); used by the round-trip test."""
+    _refuse_pooled(model, "state_dict_to_jax")
     sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     D = model.embed_dim
     H = model.blocks[0].attn.num_heads
@@ -120,6 +132,7 @@ def state_dict_to_jax(model) -> Dict[str, np.ndarray]:
 
 def load_jax_npz(model, path: str) -> None:
     """``create_model(..., checkpoint_path=path)`` of the reference (vit_cp.py:155)."""
+    _refuse_pooled(model, "load_jax_npz")   # (before the file is opened)
     w = np.load(path)
     sd = jax_to_state_dict({k: w[k] for k in w.files}, model)
     missing, unexpected = model.load_state_dict(sd, strict=False)

@@ -5,7 +5,7 @@
 #   build.sh all    -> both
 set -euo pipefail
 cd "$(dirname "$0")"
-SRCS="lib.hip gemm.hip gemm8.hip skinny.hip norm_misc.hip feed.hip attention.hip factors.hip dropout_exact.hip dense_delta.hip optim.hip linear.hip eval.hip"
+SRCS="lib.hip gemm.hip gemm8.hip skinny.hip norm_misc.hip pool.hip feed.hip attention.hip factors.hip dropout_exact.hip dense_delta.hip optim.hip linear.hip eval.hip"
 [ -f vit.hip ] && SRCS="$SRCS vit.hip"
 build_one() {   # $1 = object dir, $2 = output, $3.. = extra flags
   local dir=$1 out=$2; shift 2

@@ -31,6 +31,8 @@ struct LayerWs {
 
 struct Ws {
   size_t pack, patches, emb, head_wb, clsn, meanF, rstdF, x_last;
+  bool pool;                // cara_vit_shape::pool = 1: the mean-pooled readout
+  size_t pooled, dpooled;   // ... then only: the mean of the patch rows of x_last [B, D] fp32, and its gradient
   LayerWs layer[64];
   // backward
   size_t dx, dXn, dAO, dclsn, gscratch, gemm_scratch;
@@ -84,6 +86,7 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
   // `tokens`; which entries take fewer tokens than the grid has is theirs to say, vit_forward_body)
   if (s->img % s->patch || s->tokens > (s->img / s->patch) * (s->img / s->patch) + 1) return false;
   if ((s->chans * s->patch * s->patch) % 64 || g->dim % 256) return false;
+  if (!(s->pool == 0 || s->pool == 1) || (s->pool && s->wd_exact)) return false;   // (the pooled readout: not with exact weight dropout)
   const size_t D = g->dim, M = (size_t)s->B * s->tokens, Rp = g->Rp;
   const size_t ldt = (M + 31) / 32 * 32;
   w->M = (int)M;
@@ -111,6 +114,10 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
     w->ddt = c.take((size_t)g->depth * 3 * D * D * 2);
   }
   w->x_last = c.take(M * D * 4);
+  // (the pooled readout's rows, only where it is asked for: with pool = 0 no offset and no size moves)
+  w->pool = s->pool == 1;
+  w->pooled = w->dpooled = 0;
+  if (w->pool) w->pooled = c.take((size_t)s->B * D * 4);
   // cara_vit_shape::inference (as cara_vit_forward reads it: never with the exact weight-dropout mode): two activation
   // sets, which the blocks take in turn -- block l reads the residual stream from set l % 2 and leaves it in the other
   // set's x_in -- and nothing of the backward: no gradient stream, no dY / G' set, no slabs, no dense gradients.  Being a
@@ -159,6 +166,7 @@ bool layout(const cara_geom* g, const cara_vit_shape* s, Ws* w) {
     }
   }
   w->dclsn = c.take((size_t)s->B * D * 2);
+  if (w->pool) w->dpooled = c.take((size_t)s->B * D * 4);
   w->gscratch = c.take(cara_factor_grad_scratch_bytes(g));
   const size_t ins[4] = {D, D, D, 4 * D}, outs[4] = {3 * D, D, 4 * D, D};
   const Placements can = placements(g, s, (int)M);
@@ -777,7 +785,7 @@ BlockPlan plan_block(const cara_geom* g, const cara_vit_shape* s, int M, int l) 
   p.exact = s->wd_exact != 0;
   p.dense_qkv = g->cp_length == 2;
   p.inference = s->inference != 0 && !p.exact;
-  p.cls_only = last && cls_shortcut_enabled() && !p.exact;
+  p.cls_only = last && cls_shortcut_enabled() && !p.exact && s->pool == 0;   // (a pooled readout reads every patch row of the last block)
   p.cls_attn = p.cls_only && cls_attention_enabled();
   const int Mr = p.Mr = p.cls_only ? s->B : M;
   p.ldr = p.cls_only ? N * D : D;
@@ -1075,6 +1083,12 @@ static int vit_forward_body(const cara_geom* g, const cara_vit_shape* s, const c
 #endif
     TRY(linear(3, sv.h, e, cx));
   }
+  if (W.pool) {
+    // pooled readout: mean of the patch rows (no LayerNorm in front) -> fc_norm (norm_g / norm_b carry it) -> head, the same fp32 launch
+    TRY(cara_token_mean(px.f32(W.x_last), B, N, 1, D, px.f32(W.pooled), stream));
+    return cara_head_forward(px.f32(W.pooled), (long)D, w->norm_g, w->norm_b, head_w, head_b, ws + W.clsn, px.f32(W.meanF), px.f32(W.rstdF), logits, B,
+                             s->num_classes, D, s->eps, stream);
+  }
   // norm -> cls token -> head  (LayerNorm is per token, so only the cls rows are normalised)
   // ... all in fp32, one launch (cara_head_forward): the 16-bit xn and the row statistics are kept for the backward
   return cara_head_forward(px.f32(W.x_last), (long)N * D, w->norm_g, w->norm_b, head_w, head_b, ws + W.clsn, px.f32(W.meanF), px.f32(W.rstdF), logits, B,
@@ -1203,13 +1217,21 @@ extern "C" int cara_vit_backward(const cara_geom* g, const cara_vit_shape* s, co
   const Ws::Bwd& R = W.bwd;
   TRY(head_backward_scaled(dlogits, ws + W.clsn, head_w, dhead_w, dhead_b, ws + W.dclsn, B, s->num_classes, D, s->loss_scale,
                            s->found_inf, stream));
-  if (!last.dx_on_cls) {   // (the last block reads every row of dx and of its dyb: zeros outside the cls rows)
-    if (hipMemsetAsync(dx, 0, (size_t)M * D * 4, hs) != hipSuccess) return CARA_E_LAUNCH;
-    if (hipMemsetAsync(ws + R.dyb_fc2, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
-  }
   const float* dp_last = droppath ? droppath + (size_t)(2 * (g->depth - 1) + 1) * B : nullptr;
-  TRY(cara_layernorm_bwd(ws + W.dclsn, px.f32(W.x_last), (long)N * D, w->norm_g, px.f32(W.meanF), px.f32(W.rstdF), nullptr, dx, ws + R.dyb_fc2, dp_last, 1, B,
-                         D, stream));
+  if (W.pool) {
+    // pooled readout: fc_norm's backward on the B pooled rows, then the pooled gradient spread over the patch rows -- every element of
+    // dx and of the last block's dyb is written once (zeros on the cls rows), in the memsets' place
+    TRY(cara_layernorm_bwd(ws + W.dclsn, px.f32(W.pooled), (long)D, w->norm_g, px.f32(W.meanF), px.f32(W.rstdF), nullptr, px.f32(W.dpooled), nullptr, nullptr, 1,
+                           B, D, stream));
+    TRY(cara_token_mean_bwd(px.f32(W.dpooled), dp_last, B, N, 1, D, dx, ws + R.dyb_fc2, last.dyb_in, stream));
+  } else {
+    if (!last.dx_on_cls) {   // (the last block reads every row of dx and of its dyb: zeros outside the cls rows)
+      if (hipMemsetAsync(dx, 0, (size_t)M * D * 4, hs) != hipSuccess) return CARA_E_LAUNCH;
+      if (hipMemsetAsync(ws + R.dyb_fc2, 0, (size_t)M * D * 2, hs) != hipSuccess) return CARA_E_LAUNCH;
+    }
+    TRY(cara_layernorm_bwd(ws + W.dclsn, px.f32(W.x_last), (long)N * D, w->norm_g, px.f32(W.meanF), px.f32(W.rstdF), nullptr, dx, ws + R.dyb_fc2, dp_last, 1, B,
+                           D, stream));
+  }
   bool have_G_fc2 = false;   // G' of this block's fc2 was left by the LayerNorm backward of the block above
   for (int l = g->depth - 1; l >= 0; --l) {
     const BlockPlan& p = plans[l];

@@ -154,6 +154,22 @@ class CaraEngine:
         if self.precision == "fp16" and (self.weight_dropout == "exact" or self.cp_length == 2):
             raise CaraError("precision = 'fp16' runs the factored adapters (weight_dropout = 'off', cp_length 3 / 4 / 5)")
 
+    # ------------------------------------------------------------------ the readout
+    @staticmethod
+    def _pool(model) -> int:
+        """cara_vit_shape::pool of this model: 1 = the mean of the patch tokens through fc_norm, 0 = the cls token through norm"""
+        from .cara import pooled_readout
+        return 1 if pooled_readout(model) else 0
+
+    @classmethod
+    def _readout_norm(cls, model):
+        """the LayerNorm in front of the head (cara_vit_weights::norm_g / norm_b): fc_norm of a pooled model, else norm"""
+        return model.fc_norm if cls._pool(model) else model.norm
+
+    def _refuse_pooled_exact(self, model):
+        if self.weight_dropout == "exact" and self._pool(model):
+            raise CaraError("a mean-pooled readout (global_pool = 'avg') runs with weight_dropout = 'off' only")
+
     # ------------------------------------------------------------------ frozen weights -> HBM layout
     def _backbone_params(self, model):
         return [p for n, p in model.named_parameters() if not n.startswith("CP_") and not n.startswith("head.")]
@@ -207,8 +223,9 @@ class CaraEngine:
         t["proj_b"] = f32([b.attn.proj.bias for b in blocks])
         t["fc1_b"] = f32([b.mlp.fc1.bias for b in blocks])
         t["fc2_b"] = f32([b.mlp.fc2.bias for b in blocks])
-        t["norm_g"] = model.norm.weight.detach().to(dev, torch.float32).contiguous()
-        t["norm_b"] = model.norm.bias.detach().to(dev, torch.float32).contiguous()
+        readout = self._readout_norm(model)   # (fc_norm's parameters are backbone parameters too: _signature sees them change)
+        t["norm_g"] = readout.weight.detach().to(dev, torch.float32).contiguous()
+        t["norm_b"] = readout.bias.detach().to(dev, torch.float32).contiguous()
         w = L.VitWeights(**{n: ptr(t[n]) for n, _ in L.VitWeights._fields_})
         self._ingested = (t, w)
         self._ingest_sig = self._signature(model)
@@ -242,6 +259,7 @@ class CaraEngine:
 
     def _state(self, model, B, img, dev, tokens=None):
         """``tokens``: 1 + K of a step behind a patch dropout; None = the grid's (img / patch)^2 + 1"""
+        self._refuse_pooled_exact(model)   # (before anything is ingested, sized or launched)
         if self._ensure_ingested(model, dev):
             self._ws.clear()
         ncls = model.head.out_features
@@ -255,7 +273,8 @@ class CaraEngine:
         if tokens is None:
             tokens = (img // pe.proj.kernel_size[0]) ** 2 + 1
         # (the token count is part of the key: a kept step and a full step of the same batch have workspaces of their own)
-        key = (B, img, ncls, str(dev), exact, self._operands(), self._slot, tokens)
+        pool = self._pool(model)
+        key = (B, img, ncls, str(dev), exact, self._operands(), self._slot, tokens) + ((pool,) if pool else ())
         st = self._ws.get(key)
         if st is None:
             geom = L.Geom(len(model.blocks), model.embed_dim, model.blocks[0].attn.num_heads, self.rank, self.Rp, self.scale,
@@ -264,7 +283,7 @@ class CaraEngine:
             # workspace -- eval -- simply does not touch them)
             patch = pe.proj.kernel_size[0]
             shape = L.VitShape(B, img, patch, pe.proj.in_channels, tokens, ncls,
-                               float(model.norm.eps), 1 if exact else 0, float(self.weight_dropout_p), 0)
+                               float(self._readout_norm(model).eps), 1 if exact else 0, float(self.weight_dropout_p), 0, pool=pool)
             nbytes = self._lib().cara_vit_workspace_bytes(C.byref(geom), C.byref(shape))
             if nbytes == 0:
                 raise CaraError(f"unsupported geometry for the HIP path: {geom.depth=} {geom.dim=} {geom.heads=} "
@@ -1099,15 +1118,16 @@ class CaraEngine:
         ews = self.__dict__.setdefault("_eval_ws", {})
         self._pos_rows((img // model.patch_embed.proj.kernel_size[0]) ** 2 + 1, dev)
         ncls = model.head.out_features
-        key = (B, img, ncls, str(dev), self._operands())
+        pool = self._pool(model)
+        key = (B, img, ncls, str(dev), self._operands()) + ((pool,) if pool else ())
         st = ews.get(key)
         if st is None:
             pe = model.patch_embed
             geom = L.Geom(len(model.blocks), model.embed_dim, model.blocks[0].attn.num_heads, self.rank, self.Rp, self.scale,
                           self.cp_length)
             patch = pe.proj.kernel_size[0]
-            shape = L.VitShape(B, img, patch, pe.proj.in_channels, (img // patch) ** 2 + 1, ncls, float(model.norm.eps),
-                               0, float(self.weight_dropout_p), 0, 1)
+            shape = L.VitShape(B, img, patch, pe.proj.in_channels, (img // patch) ** 2 + 1, ncls, float(self._readout_norm(model).eps),
+                               0, float(self.weight_dropout_p), 0, 1, pool=pool)
             nbytes = self._lib().cara_vit_workspace_bytes(C.byref(geom), C.byref(shape))
             if nbytes == 0:
                 raise CaraError(f"unsupported geometry for the HIP path: {geom.depth=} {geom.dim=} {geom.heads=} {shape.tokens=}")

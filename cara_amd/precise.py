@@ -78,6 +78,8 @@ def forward(model, images: torch.Tensor) -> torch.Tensor:
         raise CaraError("precise.forward needs a model adapted by cara_amd.cara()")
     if eng.cp_length != 4:
         raise CaraError("the bf16x3 parity instrument covers the default tensorisation (cp_length 4)")
+    if eng._pool(model):
+        raise CaraError("the bf16x3 parity instrument covers the cls-token readout only")
     if not images.is_cuda:
         raise CaraError("cara_amd runs on the GPU only (no CPU fallback)")
     if images.ndim != 4 or images.shape[2] != images.shape[3]:

@@ -95,8 +95,14 @@ class PatchEmbed(_NoEagerForward):
 
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
-                 num_heads=12, mlp_ratio=4.0, qkv_bias=True, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0):
+                 num_heads=12, mlp_ratio=4.0, qkv_bias=True, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0,
+                 global_pool="token", fc_norm=None):
         super().__init__()
+        if global_pool not in ("token", "avg"):
+            raise CaraError(f"cara_amd supports global_pool 'token' (the cls readout) and 'avg' (mean of the patch tokens), not {global_pool!r}")
+        # timm's rule (newer releases): the readout norm moves behind the pool whenever the pool is the mean, unless told otherwise
+        use_fc_norm = (global_pool == "avg") if fc_norm is None else bool(fc_norm)
+        self.global_pool = global_pool
         if drop_rate != 0.0 or attn_drop_rate != 0.0:
             raise CaraError("cara_amd supports drop_rate = attn_drop_rate = 0 (the reference's configuration)")
         if mlp_ratio != 4.0 or not qkv_bias:
@@ -114,7 +120,11 @@ class VisionTransformer(nn.Module):
         self.blocks = nn.Sequential(*[
             Block(embed_dim, num_heads, mlp_ratio, qkv_bias, drop_rate, attn_drop_rate, dpr[i], nn.GELU, norm_layer)
             for i in range(depth)])
-        self.norm = norm_layer(embed_dim)
+        # state-dict keys: norm.{weight, bias} -- or, with fc_norm, fc_norm.{weight, bias} and no norm.* at all (timm's layout; a
+        # model without fc_norm has no such attribute, like timm 0.4.12's)
+        self.norm = nn.Identity() if use_fc_norm else norm_layer(embed_dim)
+        if use_fc_norm:
+            self.fc_norm = norm_layer(embed_dim)
         self.pre_logits = nn.Identity()
         self.head = nn.Linear(self.num_features, num_classes) if num_classes > 0 else nn.Identity()
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
@@ -133,6 +143,9 @@ class VisionTransformer(nn.Module):
 
     def reset_classifier(self, num_classes, global_pool=""):
         """vit_cp.py:166 calls this AFTER cara(); the engine re-reads ``self.head`` every step."""
+        if global_pool not in ("", None, getattr(self, "global_pool", "token")):
+            raise CaraError(f"reset_classifier(global_pool={global_pool!r}): the readout of this model is {getattr(self, 'global_pool', 'token')!r} and "
+                            "cannot be changed here (the norm sits on the other side of the pool: build the model with the pool it needs)")
         self.num_classes = num_classes
         dev = self.cls_token.device
         self.head = (nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()).to(dev)

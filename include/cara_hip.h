@@ -823,6 +823,13 @@ typedef struct {
    * cara_cross_entropy_ex) is set to 1 when a written gradient is not finite.                                           */
   const float* loss_scale;
   float* found_inf;
+  /* The readout.  0: the final LayerNorm on the cls row, then the head (timm's global_pool = "token").  1: the mean of the patch
+   * tokens (rows 1 .. tokens - 1 of the last block's output, no LayerNorm in front), then LayerNorm with cara_vit_weights::norm_g /
+   * norm_b -- which carry fc_norm's parameters in this mode -- then the head (global_pool = "avg" with fc_norm).  The last block then
+   * runs on all its rows, the workspace holds two more fp32 [B,dim] rows (cara_vit_workspace_bytes sees the field; with 0 every size
+   * is what it was), and the backward spreads the pooled gradient over the patch rows.  Not with wd_exact; any other value:
+   * CARA_E_ARG.                                                                                                                */
+  int pool;
 } cara_vit_shape;
 size_t cara_vit_workspace_bytes(const cara_geom* g, const cara_vit_shape* s);
 /* Both calls are stateless (everything lives in the caller's workspace and runs in order on the caller's stream):
@@ -909,6 +916,20 @@ int cara_head_backward(const float* dlogits, const void* xn_bf16, const float* h
 int cara_head_forward(const float* x, long ldx, const float* gamma, const float* beta, const float* head_w,
                       const float* head_b, void* xn_16, float* mean, float* rstd, float* logits, int B, int classes,
                       int D, float eps, void* stream);
+/* The mean-pooled readout (timm's global_pool = "avg" behind fc_norm; cara_vit_shape::pool = 1), both HBM-bound, no atomics:
+ * the same input gives the same bits on every run.  x fp32 [B,tokens,D], out fp32 [B,D]:
+ *   out[b,:] = mean over t in [first, tokens) of x[b,t,:]
+ * in fp32, in a fixed order; rows below `first` (the cls token: first = 1) are never read, and with one token the row goes
+ * through bit for bit.  CARA_E_ARG, nothing launched: a NULL pointer, B <= 0, first < 0, tokens <= first, D <= 0, D % 4 != 0.  */
+int cara_token_mean(const float* x, int B, int tokens, int first, int D, float* out, void* stream);
+/* Its backward, into the residual-stream gradient of the last block and the dY of that block's fc2:
+ *   dx fp32 [B,tokens,D]: dx[b,t,:] = dpool[b,:] / (tokens - first) for t >= first, exactly 0 below;
+ *   dyb bf16: the 16-bit values of rowscale[b] * dx (rowscale fp32 [B], NULL = 1), row-major [B*tokens, D], or K-panel-major
+ *   [D/32][dyb_panels][32] when dyb_panels > 0 (>= B*tokens rows per panel, D % 32 == 0): cara_layernorm_bwd_ex's layout rule.
+ * Every element of both outputs is written (no memset in front).  dpool stays in whatever scale it has: nothing is unscaled or
+ * tested for inf here.  Refusals as above.                                                                                    */
+int cara_token_mean_bwd(const float* dpool, const float* rowscale, int B, int tokens, int first, int D, float* dx, void* dyb,
+                        int dyb_panels, void* stream);
 
 /* ---- ABI self-description ------------------------------------------------------------------- */
 /* sizeof() of the structs above as THIS library was compiled, so that a binding can assert that its own mirror of a

@@ -7,7 +7,8 @@
 // printed, and (library entries) forwarded to the library's own function for its return value and its own launches; the HIP
 // stand-ins launch nothing.  All device pointers are made-up addresses that nothing dereferences.  The switches (CARA_*) are read
 // once per process by the library: one run per setting.  HOST_TRACE_SITES=1 turns every site bracket on (cara_profile_sites), so the
-// event records show the brackets' scopes.
+// event records show the brackets' scopes.  HOST_TRACE_POOL=1 traces the pooled-readout shapes (cara_vit_shape::pool = 1) INSTEAD of the
+// token-readout ones, so that the traces of the other settings stay comparable across that feature.
 #include <dlfcn.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -158,6 +159,10 @@ ENTRY(int, cara_layernorm_bwd_ex,
       (const void* dy, const float* x, long ldx, const float* gamma, const float* mean, const float* rstd, const float* dx_in, float* dx_out, void* dyb,
        const float* rowscale, int rows_per_sample, int M, int C, const void* Vst, int rank, int Rp, void* G, void* Gt, int ldt, int dyb_panels, void* stream),
       dy, x, ldx, gamma, mean, rstd, dx_in, dx_out, dyb, rowscale, rows_per_sample, M, C, Vst, rank, Rp, G, Gt, ldt, dyb_panels, stream)
+ENTRY(int, cara_token_mean, (const float* x, int B, int tokens, int first, int D, float* out, void* stream), x, B, tokens, first, D, out, stream)
+ENTRY(int, cara_token_mean_bwd,
+      (const float* dpool, const float* rowscale, int B, int tokens, int first, int D, float* dx, void* dyb, int dyb_panels, void* stream),
+      dpool, rowscale, B, tokens, first, D, dx, dyb, dyb_panels, stream)
 ENTRY(int, cara_attention_fwd, (const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream), qkv, out, lse, B, N, H, scale, stream)
 ENTRY(int, cara_attention_cls_fwd, (const void* qkv, void* out, float* lse, int B, int N, int H, float scale, void* stream), qkv, out, lse, B, N, H, scale, stream)
 ENTRY(int, cara_attention_bwd, (const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N, int H, float scale, void* stream),
@@ -245,6 +250,17 @@ const Shape SHAPES[] = {
     {"exact weight dropout", 2, 768, 16, 32, 32, 224, 4, 1},
     {"depth 1", 1, 768, 16, 32, 64, 224, 4, 0},
 };
+// HOST_TRACE_POOL=1: the mean-pooled readout (the last block on all its rows, the pool and its backward in the memsets' place), at the
+// regimes above that differ in the last block; with exact weight dropout both entries refuse
+const Shape POOLED[] = {
+    {"pooled, depth 3, 96 px, batch 28 (M = 1036)", 3, 768, 16, 32, 28, 96, 4, 0},
+    {"pooled, depth 12, 224 px, batch 64", 12, 768, 16, 32, 64, 224, 4, 0},
+    {"pooled, rank 64", 2, 768, 64, 64, 64, 224, 4, 0},
+    {"pooled, batch 4", 2, 768, 16, 32, 4, 224, 4, 0},
+    {"pooled, order 2", 2, 768, 16, 32, 32, 224, 2, 0},
+    {"pooled, exact weight dropout (refused)", 2, 768, 16, 32, 32, 224, 4, 1},
+    {"pooled, depth 1", 1, 768, 16, 32, 64, 224, 4, 0},
+};
 
 template <class T>
 T* fake(int i) { return reinterpret_cast<T*>((uintptr_t)0x100000000000ull + (uintptr_t)i * 0x1000000000ull); }
@@ -277,9 +293,14 @@ int main() {
   const int* boxes = fake<int>(n++);
   int* bad = fake<int>(n++);
 
-  for (const Shape& sh : SHAPES) {
+  const bool pooled = getenv("HOST_TRACE_POOL") != nullptr;
+  const Shape* shapes = pooled ? POOLED : SHAPES;
+  const size_t nshapes = pooled ? sizeof(POOLED) / sizeof(POOLED[0]) : sizeof(SHAPES) / sizeof(SHAPES[0]);
+  for (size_t i = 0; i < nshapes; ++i) {
+    const Shape& sh = shapes[i];
     cara_geom g = {sh.depth, sh.dim, sh.dim / 64, sh.rank, sh.Rp, 0.1f, sh.order};
     cara_vit_shape s = {};
+    s.pool = pooled ? 1 : 0;
     s.B = sh.B; s.img = sh.img; s.patch = 16; s.chans = 3; s.tokens = (sh.img / 16) * (sh.img / 16) + 1; s.num_classes = 100;
     s.eps = 1e-6f; s.wd_exact = sh.exact; s.wd_p = 0.1f; s.wd_seed = 1234u;
     printf("==== %s: depth %d dim %d rank %d Rp %d B %d img %d order %d exact %d\n", sh.what, sh.depth, sh.dim, sh.rank, sh.Rp, sh.B, sh.img, sh.order, sh.exact);

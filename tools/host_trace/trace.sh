@@ -2,8 +2,12 @@
 # Build host_trace.cpp against a given libcara_hip.so and write one trace per setting of the switches into a directory.
 #   tools/host_trace/trace.sh <path/to/libcara_hip.so> <out_dir>
 # Run it on the library before a change and after it, then `diff -r` the two directories: a refactor of vit.hip's host code leaves
-# every file byte-identical.  No GPU is needed (nothing is launched).  Every run covers the 16 shapes of host_trace.cpp, each with
-# inference 0 and 1: the workspace size, the four forward entries and the backward.
+# every file byte-identical.  No GPU is needed (nothing is launched).  50 settings below, one .trace file each:
+#   * 45 without HOST_TRACE_POOL: the 16 token-readout shapes of host_trace.cpp (SHAPES), each with inference 0 and 1: the workspace
+#     size, the four forward entries and the backward.  These files hold token-readout shapes only and are the ones to compare across
+#     a change that must leave the token path alone.
+#   * 5 with HOST_TRACE_POOL=1: the 7 shapes of the mean-pooled readout (POOLED, cara_vit_shape::pool = 1) in SHAPES' place, the same
+#     entries; one of the 7 asks for exact weight dropout, which the pooled readout refuses: workspace size 0 and status 1 from every entry.
 set -euo pipefail
 LIB=$(realpath "$1")
 OUT=$2
@@ -61,6 +65,11 @@ HOST_TRACE_SITES=1
 HOST_TRACE_SITES=1 CARA_EPI_RIDERS=1
 HOST_TRACE_SITES=1 CARA_FC1_SIDE=1
 HOST_TRACE_SITES=1 CARA_CLS_SHORTCUT=0
+HOST_TRACE_POOL=1
+HOST_TRACE_POOL=1 CARA_PANEL_ACTS=0
+HOST_TRACE_POOL=1 CARA_PANEL_ACTS=7
+HOST_TRACE_POOL=1 CARA_EPI_RIDERS=1
+HOST_TRACE_POOL=1 HOST_TRACE_SITES=1
 EOF
 )
 while IFS= read -r setting; do
